@@ -1,13 +1,18 @@
 #!/usr/bin/env python3
 """Benchmark of the Gibbs-sweep hot path on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload NAME]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload NAME] [--dump-outputs DIR]
 
 A "step" is one sweep of the hot path over every variable of the workload graph (one epoch of
 gibbsthread, numbskull/inference.py:10-33; for the *_learn workloads one epoch of learnthread,
 learning.py:12-125).  The default workload is the one BASELINE.json's metric is quoted on: the
 2500x4000 (10M-variable) 2D Ising grid of ising/ising.cpp:134-199, binary variables, EQUAL
 factors, one fixed weight 0.1, inference only, inputs resident in HBM before the timed region.
+
+The timed region is ONE call of the hot path with exactly K steps.  In front of it run one untimed
+call of the same K steps -- a handle builds what a call of a given length needs on its first such
+call (captured sweep sequences, learning launch plans) -- and W burn-in sweeps (at least 10 in all).
+--dump-outputs DIR writes what the timed call left to its caller as DIR/<name>.npy (dump_outputs).
 
 Prints ONE JSON line (rank 0): metric = variable-updates/sec over all GPUs, plus
   roofline     bytes one launch must move in the compiled device layout (nsk_compile.cpp "layout
@@ -236,7 +241,54 @@ def state_checks(fg, info, tallied_sweeps, grid, learning):
     return out
 
 
-REPEATS = 5      # timed blocks of K steps each; the line's value is the MEDIAN block
+REPEATS = 5      # side_run: timed blocks of its steps each; its value is the MEDIAN block
+
+DUMP_SAMPLE = 1 << 21     # --dump-outputs: an output longer than this is written at a seeded sample of its positions
+DUMP_SEED = 20240604
+
+
+def dump_positions(n):
+    """Sorted positions of an n-element output that --dump-outputs writes (None: all of them).  A function of n
+    alone, so that two runs with the same arguments write the same elements."""
+    if n <= DUMP_SAMPLE:
+        return None
+    return np.unique(np.random.default_rng(DUMP_SEED).integers(0, n, DUMP_SAMPLE))
+
+
+def dump_outputs(directory, fg, learning, tallied_sweeps, dist, rank, world):
+    """What the timed call of the hot path left to its caller, as DIR/<name>.npy: the values of the variables
+    (var_value, float32) and, for inference, the marginals (count / tallied sweeps, float64: one slot per binary
+    variable, `cardinality` slots otherwise, factorgraph.py inference()); for learning the evidence chain's values
+    (var_value_evid, float32) and the weights (weight_value, float64).  An output of more than DUMP_SAMPLE elements
+    is written at dump_positions() of it (at most 32 MB in all).  N ranks: the owned variables of every rank in
+    rank order (= global id order of the range partition); the weights, which every rank holds, from rank 0.
+    Collective when world > 1; reads the host arrays state_checks() downloaded."""
+    lo, hi = fg.own_range if fg.own_range is not None else (0, len(fg.variable))
+    owned = [("var_value", fg.var_value[0][lo:hi], np.float32)]
+    if learning:
+        owned.append(("var_value_evid", fg.var_value_evid[0][lo:hi], np.float32))
+    else:
+        owned.append(("marginals", fg.count[fg.cstart[lo]:fg.cstart[hi]] / float(tallied_sweeps), np.float64))
+    if rank == 0:
+        os.makedirs(directory, exist_ok=True)
+    for name, a, dtype in owned:
+        lens = [len(a)]
+        if world > 1:
+            lens = [None] * world
+            dist.all_gather_object(lens, len(a))
+        off = sum(lens[:rank])
+        pos = dump_positions(sum(lens))
+        part = (a if pos is None else a[pos[(pos >= off) & (pos < off + len(a))] - off]).astype(dtype)
+        if world > 1:
+            parts = [None] * world if rank == 0 else None
+            dist.gather_object(part, parts, dst=0)
+            part = np.concatenate(parts) if rank == 0 else None
+        if rank == 0:
+            np.save(os.path.join(directory, name + ".npy"), part)
+    if learning and rank == 0:
+        w = fg.weight_value[0]
+        pos = dump_positions(len(w))
+        np.save(os.path.join(directory, "weight_value.npy"), (w if pos is None else w[pos]).astype(np.float64))
 
 
 def timed_blocks(run, fence, L, h, steps, reps):
@@ -555,6 +607,7 @@ def main():
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-extra", action="store_true", help="skip the secondary 1M-grid measurement")
     ap.add_argument("--seed", type=int, default=20240601)
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write what the timed call computed as DIR/<name>.npy")
     args = ap.parse_args()
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
@@ -651,9 +704,18 @@ def main():
     burn_extra = max(0, 10 - args.warmup)
     if burn_extra:
         run(burn_extra, True)
+    # one untimed call of exactly the timed one's length builds what a call of that length needs once per handle (its
+    # first tallying call of >= 16 sweeps captures the sweep sequences); then the tallies restart from zero, and the
+    # warm-up sweeps keep the device busy up to the timed call
+    run(args.steps)
+    if not learning:
+        zero = np.zeros(int(fg.cstart[-1]), np.int64)        # (named: it must outlive the call that reads it)
+        _lib.check(L.nsk_state_upload(h, None, None, None, _lib.ptr(zero)))
+        del zero
     run(args.warmup, True)
+    tallied = 0 if learning else args.steps
     import ctypes as C
-    blocks = timed_blocks(run, fence, L, h, args.steps, REPEATS)
+    blocks = timed_blocks(run, fence, L, h, args.steps, 1)
     if world > 1:        # every block: the slowest rank's time
         t = torch.tensor([b[0] for b in blocks], dtype=torch.float64, device="cuda")
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
@@ -668,7 +730,9 @@ def main():
     ms_ev, launches = _V(ms_ev_v), _V(launches_v)
 
     # invariants of the state the timed sweeps left behind (every rank checks its own shard)
-    checks = state_checks(fg, info, args.steps * REPEATS, (rows, cols) if is_grid else None, learning)
+    checks = state_checks(fg, info, tallied, (rows, cols) if is_grid else None, learning)
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, fg, learning, tallied, dist, rank, world)
     # hard invariants decide the exit code; the statistical ones (mean marginal, agreement with the
     # CPU chain) are always reported but only count once the chain has been burnt in (>= 10 warm-up
     # sweeps): a 2-sweep warm-up of a profiling pass still sits in the transient from the all-zero
@@ -680,7 +744,7 @@ def main():
                    or (burnt_in and k.endswith("_ok")))
     checks["statistics_count"] = burnt_in
     checks["statistics"] = "counted" if burnt_in else "skipped (warm-up < 10 sweeps)"
-    checks["burn_in_sweeps"] = args.warmup + burn_extra      # untimed sweeps before the first timed block
+    checks["burn_in_sweeps"] = args.warmup + burn_extra      # untimed burn-in sweeps (besides the untimed call of K)
     if world > 1:
         t = torch.tensor([1.0 if ok_local else 0.0], dtype=torch.float64, device="cuda")
         dist.all_reduce(t, op=dist.ReduceOp.MIN)

@@ -143,25 +143,32 @@ def test_writer_roundtrip(tmp_path):
     assert np.array_equal(fg.fmap, g[3])
 
 
-def test_reads_reference_generator_output(tmp_path):
-    """oracle/_ref/ising is the reference's own ising/ising.cpp compiled where it lies; our loader
-    must read what it writes (skipped where the reference tree never existed)."""
-    exe = os.path.join(REPO, "oracle", "_ref", "ising")
-    if not os.path.exists(exe):
-        pytest.skip("oracle/_ref/ising not built")
-    import subprocess
-    subprocess.check_call([exe], cwd=str(tmp_path), stdout=subprocess.DEVNULL)
-    ns = numbskull_amd.NumbSkull(directory=str(tmp_path), quiet=True)
+def check_generator_output(d, out):
+    """Our loader reads a graph the reference's ising/ising.cpp wrote into `d`, and our writer emits
+    the same bytes for it into `out`."""
+    ns = numbskull_amd.NumbSkull(directory=str(d), quiet=True)
     quiet(ns.loadFGFromFile)
     fg = ns.factorGraphs[0]
     assert len(fg.variable) == 2000 and len(fg.factor) == 3000 and len(fg.weight) == 3
     assert set(np.unique(fg.factor["factorFunction"])) == {3, 4}
     assert np.all(fg.variable["isEvidence"] == 1)
-    # and our writer emits the same bytes for the same graph
-    out = tmp_path / "again"
     graphgen.write_graph(str(out), fg.weight, fg.variable, fg.factor, fg.fmap)
     for fn in ("graph.weights", "graph.variables", "graph.factors", "graph.meta"):
-        assert (out / fn).read_bytes() == (tmp_path / fn).read_bytes(), fn
+        assert open(os.path.join(str(out), fn), "rb").read() == open(os.path.join(str(d), fn), "rb").read(), fn
+
+
+def test_reads_reference_generator_output(tmp_path):
+    """tests/golden/ising_generator holds one run of the reference's own ising/ising.cpp (it seeds
+    itself from std::random_device; tools/make_goldens.py).  Where that program has been built as
+    oracle/_ref/ising, a fresh run of it is checked as well."""
+    check_generator_output(os.path.join(GOLDEN, "ising_generator"), tmp_path / "golden_again")
+    exe = os.path.join(REPO, "oracle", "_ref", "ising")
+    if os.path.exists(exe):
+        import subprocess
+        fresh = tmp_path / "fresh"
+        fresh.mkdir()
+        subprocess.check_call([exe], cwd=str(fresh), stdout=subprocess.DEVNULL)
+        check_generator_output(fresh, tmp_path / "fresh_again")
 
 
 def test_unknown_factor_function_raises_not_implemented():

@@ -6,8 +6,9 @@ its sanctioned pure-Python mode -- its own CI runs every test with NUMBA_DISABLE
 (.travis.yml:55-57) -- through the identity ``numba.jit`` stand-in under
 tools/oracle_shim/.  Nothing from the reference is copied: the fixtures hold only inputs
 (record arrays built by numbskull_amd.graphgen / this script) and the outputs the
-reference computed for them.  The one exception is tests/golden/test_coin/, the 1.4 kB
-binary data files of the reference's own ``test/`` fixture (data, not source).
+reference computed for them.  The exceptions are tests/golden/test_coin/, the 1.4 kB
+binary data files of the reference's own ``test/`` fixture, and tests/golden/ising_generator/,
+the graph files one run of the reference's ising/ising.cpp wrote (data, not source).
 
 Seeding: the reference has no seed parameter; in pure-Python mode its draws come from
 numpy's global legacy MT19937 (np.random.rand(), inference.py:50) and Python's ``random``
@@ -406,8 +407,22 @@ def g7_rng():
     print("G7: %d arrays" % len(out))
 
 
+def ising_generator_dir():
+    """tests/golden/ising_generator = one run of the reference's ising/ising.cpp (oracle/_ref/ising, made by
+    build()).  It seeds itself from std::random_device, so a stored run is kept rather than rewritten."""
+    import subprocess
+    d = os.path.join(OUT, "ising_generator")
+    exe = os.path.join(REPO, "oracle", "_ref", "ising")
+    if os.path.isdir(d) or not os.path.exists(exe):
+        return
+    os.makedirs(d)
+    subprocess.check_call([exe], cwd=d, stdout=subprocess.DEVNULL)
+    print("ising generator: %s" % ", ".join(sorted(os.listdir(d))))
+
+
 def main():
     os.makedirs(OUT, exist_ok=True)
+    ising_generator_dir()
     coin_dir = coin_graph_dir()
     g1_eval_factor()
     g2_index_build(coin_dir)
