@@ -34,7 +34,15 @@ def make_parts(kind, nvar, learn, seed):
     from numbskull_amd.distributed import PartitionedSampler, shard_range
     parts, streams = [], []
     grid = None
-    if kind in ("grid", "shuffled_grid"):
+    if kind == "perturbed_grid":
+        # tests/perturbed.py shard_grid: a grid whose swaps make tiles far from the cuts read ghosts, or give one
+        # boundary value readers in two shards; nvar = (rows, cols, variant)
+        from perturbed import shard_grid
+        rows, cols, variant = nvar
+        nvar = rows * cols
+        grid = shard_grid(rows, cols, variant, learn, np.random.Generator(np.random.PCG64(20240602)))
+        kind = "grid"
+    elif kind in ("grid", "shuffled_grid"):
         rng = np.random.Generator(np.random.PCG64(20240602))
         rows, cols = nvar
         nvar = rows * cols
@@ -122,17 +130,20 @@ def wire_p2p(parts):
     return needs
 
 
-def run_case(kind, size, learn, tag, nsweeps=3, hyper=(1e-3, 0.95, 2, 0.01, 1), fused=False):
+def run_case(kind, size, learn, tag, nsweeps=3, hyper=(1e-3, 0.95, 2, 0.01, 1), fused=False, probe=None):
+    """``probe(parts, needs)``: called once the shards are wired (what a test asserts about their exchange plans)."""
     import torch
     from numbskull_amd.distributed import shard_range, plan_pairs
     seed = 20240601
     parts, streams, nvar = make_parts(kind, size, learn, seed)
-    hbv = kind not in ("grid", "shuffled_grid")
+    hbv = kind not in ("grid", "shuffled_grid", "perturbed_grid")
     oracles = []
     for p in parts:
         og = oracle_of(p.fg, head_by_vid=hbv)           # checks the layout and the colouring of every shard
         oracles.append((og, phases_from_colors(p.fg.colors()), og.initial_state()))
     needs = wire_p2p(parts)
+    if probe is not None:
+        probe(parts, needs)
     pairs = plan_pairs(needs, WORLD, nvar)
     L = _lib.lib()
     # what nsk_gibbs_sweeps_p2p / nsk_learn_sweeps_p2p enqueue per sweep -- the sweep's kernels, the pushes

@@ -192,3 +192,33 @@ def test_two_shards_of_a_grid_with_wide_quads_match_emulation(monkeypatch, learn
     out = shards.run_case("grid", (768, 1024), learn, "wide2shards (768x1024 grid, two shards)", nsweeps=3 if not fused else 4,
                           hyper=(1e-4, 0.95, 2, 0.01, 1), fused=fused)
     assert fused or sum(out["ghosts_per_rank"]) == 2 * 1024
+
+
+@pytest.mark.parametrize("variant,learn,fused", [("deep", False, False), ("deep", False, True), ("deep", True, False),
+                                                 ("two_readers", False, False), ("two_readers", True, False)])
+def test_shards_of_a_perturbed_grid_match_emulation(monkeypatch, variant, learn, fused):
+    """Shards of a 96 x 1000 grid with swaps across the cuts (tests/perturbed.py shard_grid), through the real
+    peer-to-peer path, bit-exact against the partitioned oracle emulation.  "deep", two shards: tiles 18-38 rows away
+    from the cut read ghosts, so the fused exchange's border tiles are no longer the rows next to the cut; fusion stays
+    on, and the fused sweeps equal the emulation only if every tile that reads a ghost waits for it.  "two_readers",
+    three shards: one value of shard 1 is read by shards 0 and 2, so shard 1's push map has two readers for it, fusion
+    switches itself off there and the exchange kernels carry the boundary."""
+    import test_config5_shards_gpu as shards
+    world = 2 if variant == "deep" else 3
+    monkeypatch.setattr(shards, "WORLD", world)
+    rows, cols = 96, 1000
+
+    def probe(parts, needs):
+        assert all(p.fg.info()["wide_quads"] > 0 for p in parts)
+        if variant == "deep":
+            # ghosts read far from the cut (row 48): by rows 10-30 of shard 0 and rows 60-81 of shard 1
+            assert {60900, 70300, 71300, 80701} <= set(needs[0]) and {10100, 11100, 20501, 30002} <= set(needs[1])
+            if not learn:
+                assert all(p.fg.info()["p2p_fused"] == 1 for p in parts)
+        else:
+            z = 48 * cols + 500
+            assert z in needs[0] and z in needs[2] and z not in needs[1]
+            assert parts[1].fg.info()["p2p_fused"] == 0
+
+    shards.run_case("perturbed_grid", (rows, cols, variant), learn, "perturbed%s (96x1000 grid, %d shards)" % (variant, world),
+                    nsweeps=4 if fused else 3, hyper=(1e-4, 0.95, 2, 0.01, 1), fused=fused, probe=probe)
