@@ -91,6 +91,27 @@ int nsk_state_upload(nsk_graph *g, const int64_t *var_value, const int64_t *var_
 int nsk_state_download(nsk_graph *g, int64_t *var_value, int64_t *var_value_evid,
                        double *weight_value, int64_t *count);
 
+/* Several chains on one handle (FactorGraph.inference(..., var_copy="all")).  A handle with R chains keeps
+ * R value arrays and R tallies over ONE compiled layout and weight table; one nsk_gibbs_sweeps call sweeps
+ * every chain, all at the same sweep index.  Chain r of a handle seeded s draws exactly what a one-chain
+ * handle seeded s ^ ((uint64_t)r << 32) draws (Philox key word 1 XOR r): chain 0 is the one-chain handle.
+ * Consequence: seeds that differ only in bits 32 and above give overlapping chains (chain r of seed s is
+ * chain 0 of seed s ^ (r << 32)).
+ * nsk_set_chains: 1 <= nchains <= 1024.  Chain 0 keeps its values and tally (as do the chains both counts
+ * have); new chains start as nsk_graph_create leaves a handle: initialValue, tally 0.  NSK_E_NOMEM when the
+ * state does not fit.  The value array moves: a pointer from nsk_device_buffer(NSK_BUF_VALUE) taken before is
+ * stale.  With R > 1 only chromatic inference and burn-in sweeps serve the handle: learning, the sequential
+ * scan, own_range / NSK_FLAG_PARTITION handles, nsk_pf_setup and the exchange, RCCL and peer-to-peer entry
+ * points return NSK_E_INVALID.
+ * nsk_chains_upload / nsk_chains_download: var_value is R x nvar (row r = chain r, caller's variable ids),
+ * count is R x ncount (chain r's tally); NULL = leave alone.  nsk_state_upload / nsk_state_download keep
+ * meaning chain 0 (plus the evidence chain and the shared weights).  nsk_profile_* counts a launch that
+ * serves every chain once. */
+int nsk_set_chains(nsk_graph *g, int nchains);
+int nsk_get_chains(nsk_graph *g);
+int nsk_chains_upload(nsk_graph *g, const int64_t *var_value, const int64_t *count);
+int nsk_chains_download(nsk_graph *g, int64_t *var_value, int64_t *count);
+
 /* RNG: the chromatic scan draws from Philox4x32-10 keyed by `seed`.  A variable's generator id is
  * its position in the compiled layout (nsk_graph_get_layout), so samples are a function of the seed
  * AND the layout the library chose (device, flags and diagnostic switches being equal, a graph

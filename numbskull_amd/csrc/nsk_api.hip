@@ -411,6 +411,7 @@ int nsk_set_scan(nsk_graph *g, int scan) {
     if (scan != NSK_SCAN_CHROMATIC && scan != NSK_SCAN_SEQUENTIAL) return fail(NSK_E_INVALID, "unknown scan order");
     if (scan == NSK_SCAN_SEQUENTIAL && (g->c.own_begin != 0 || g->c.own_end != g->c.nvar))
         return fail(NSK_E_INVALID, "sequential scan needs the whole graph on one handle");
+    if (scan == NSK_SCAN_SEQUENTIAL) NSK_ONE_CHAIN(g, "nsk_set_scan(NSK_SCAN_SEQUENTIAL)");
     if (scan == NSK_SCAN_SEQUENTIAL) { int rc = nsk_ensure_generic(g); if (rc) return rc; }
     g->scan = scan;
     return NSK_OK;
@@ -501,6 +502,12 @@ int nsk_unpack_tally(nsk_graph *g) {
 }
 
 int nsk_fold_position_tally(nsk_graph *g) {
+    if (g->nchains > 1 && !g->chain_swapped) {          // every chain's tally (they sweep in step)
+        const int pts = g->pos_tally_sweeps;
+        for (int r = 0; r < g->nchains; r++) { ChainSwap cs(g, r); g->pos_tally_sweeps = pts; (void)nsk_fold_position_tally(g); }
+        g->pos_tally_sweeps = 0;
+        return NSK_OK;
+    }
     (void)nsk_unpack_tally(g);
     const int np = (int)g->c.npos;
     if (np > 0 && g->c.nfast > 0 && g->pos_tally_sweeps > 0)
@@ -515,9 +522,10 @@ extern "C" {
 static int fold_counts(nsk_graph *g) {
     if (!g->cnt_dirty) return NSK_OK;
     const int n = (int)g->c.ncount;
-    if (n > 0)
-        k_fold_counts<<<dim3((n + NSK_BLOCK - 1) / NSK_BLOCK), dim3(NSK_BLOCK), 0, g->stream>>>(
-            g->cnt, g->cnt_total, n);
+    for (int r = 0; r < g->nchains; r++)
+        if (n > 0)
+            k_fold_counts<<<dim3((n + NSK_BLOCK - 1) / NSK_BLOCK), dim3(NSK_BLOCK), 0, g->stream>>>(
+                g->cnt + (size_t)r * (size_t)n, g->cnt_total + (size_t)r * (size_t)n, n);
     nsk_fold_position_tally(g);
     HIPCHECK(hipGetLastError());
     g->cnt_dirty = false;
@@ -565,6 +573,11 @@ static void narrow_values(const nsk_graph *g, const int64_t *src, VT *dst, int *
     for (int x : tirr) if (x) *regular = false;
 }
 
+template <typename VT>
+static void narrow_values_unchecked(const nsk_graph *g, const int64_t *src, VT *dst) {
+    nsk::parallel_for(g->c.nvar, [&](int64_t b0, int64_t b1, int) { for (int64_t i = b0; i < b1; i++) dst[i] = (VT)src[i]; });
+}
+
 extern "C" {
 
 
@@ -600,7 +613,7 @@ int nsk_state_upload(nsk_graph *g, const int64_t *var_value, const int64_t *var_
         for (int k = 0; k < 2; k++) {
             if (!srcs[k]) continue;
             g->chain_regular[k] = regular[k];
-            g->values_regular = g->chain_regular[0] && g->chain_regular[1];
+            g->values_regular = g->chain_regular[0] && g->chain_regular[1] && g->chains_regular;
             HIPCHECK(hipMemcpyAsync(g->xfer_dev, g->xfer_host[k], (size_t)nvar * vb, hipMemcpyHostToDevice, g->stream));
             if (vb == 1) k_state_scatter<int8_t><<<dim3(nb), dim3(NSK_BLOCK), 0, g->stream>>>((int8_t *)dsts[k], g->xfer_iid, (const int8_t *)g->xfer_dev, nvar);
             else k_state_scatter<int32_t><<<dim3(nb), dim3(NSK_BLOCK), 0, g->stream>>>((int32_t *)dsts[k], g->xfer_iid, (const int32_t *)g->xfer_dev, nvar);
@@ -620,6 +633,7 @@ int nsk_state_upload(nsk_graph *g, const int64_t *var_value, const int64_t *var_
         g->weights_dirty = true;
     }
     if (count && g->c.ncount) {
+        if (g->nchains > 1) { int rc = fold_counts(g); if (rc) return rc; }     // (the other chains' tallies stay theirs)
         HIPCHECK(hipMemcpyAsync(g->cnt_total, count, (size_t)g->c.ncount * sizeof(int64_t), hipMemcpyHostToDevice, g->stream));
         HIPCHECK(hipMemsetAsync(g->cnt, 0, (size_t)g->c.ncount * sizeof(int32_t), g->stream));
         if (g->c.npos) HIPCHECK(hipMemsetAsync(g->cnt_pos, 0, (size_t)g->c.npos, g->stream));
@@ -707,6 +721,137 @@ int nsk_state_download(nsk_graph *g, int64_t *var_value, int64_t *var_value_evid
         return fail(NSK_E_DEVICE, "peer-to-peer exchange: a peer's boundary values did not arrive within "
                                   "NSK_P2P_TIMEOUT_S; the downloaded state is incomplete");
     }
+    return NSK_OK;
+}
+
+// ---- several chains (nsk_set_chains) ---------------------------------------------------------------------------
+int nsk_set_chains(nsk_graph *g, int nchains) {
+    if (!g) return fail(NSK_E_INVALID, "null graph");
+    if (nchains < 1 || nchains > NSK_MAX_CHAINS) return fail(NSK_E_INVALID, "nsk_set_chains: the chain count must lie in [1, 1024]");
+    if (nchains == g->nchains) return NSK_OK;
+    if (nchains > 1) {
+        if (g->scan != NSK_SCAN_CHROMATIC) return fail(NSK_E_INVALID, "several chains: the sequential scan samples one chain");
+        if ((g->c.flags & NSK_FLAG_PARTITION) || g->c.own_begin != 0 || g->c.own_end != g->c.nvar)
+            return fail(NSK_E_INVALID, "several chains: the handle must own the whole graph (no own_range / NSK_FLAG_PARTITION)");
+        if (g->xworld > 0 || g->pworld > 0 || g->rccl_comm)
+            return fail(NSK_E_INVALID, "several chains: the handle exchanges a boundary (exchange, RCCL or peer-to-peer set up)");
+    }
+    HIPCHECK(hipSetDevice(g->device));
+    int rc = fold_counts(g);                 // every tally in its master: the chains keep them across the move
+    if (rc) return rc;
+    const Compiled &c = g->c;
+    const size_t vb = (size_t)c.vbytes, nid = (size_t)c.nid, npos = (size_t)c.npos, nc = (size_t)c.ncount;
+    const size_t vpad = c.ep_win.empty() ? 0 : 16;
+    const size_t half = (std::max(nid * vb + vpad + 16, npos + 16) + 255) / 256 * 256;     // values | position tally
+    const size_t stride = 2 * half, R = (size_t)nchains;
+    if (stride / 256 * (R - 1) >= ((size_t)1 << 31)) return fail(NSK_E_NOMEM, "nsk_set_chains: the chains' state does not fit");
+    uint8_t *slab = nullptr;
+    int32_t *cnt = nullptr;
+    long long *tot = nullptr;
+    if ((rc = dev_alloc(g, &slab, R * stride))) return rc;
+    if ((rc = dev_alloc(g, &cnt, R * std::max<size_t>(nc, 1)))) { dev_free(g, slab); return rc; }
+    if ((rc = dev_alloc(g, &tot, R * std::max<size_t>(nc, 1)))) { dev_free(g, slab); dev_free(g, cnt); return rc; }
+    HIPCHECK(hipMemsetAsync(slab, 0, R * stride, g->stream));
+    HIPCHECK(hipMemsetAsync(cnt, 0, R * std::max<size_t>(nc, 1) * sizeof(int32_t), g->stream));
+    HIPCHECK(hipMemsetAsync(tot, 0, R * std::max<size_t>(nc, 1) * sizeof(long long), g->stream));
+    // the chains both counts have keep their values and tallies; new ones start as nsk_graph_create leaves a handle
+    const int keep = std::min(nchains, g->nchains);
+    for (int r = 0; r < keep; r++) {
+        const size_t off = (size_t)r * g->chain_stride, o2 = (size_t)r * nc;
+        HIPCHECK(hipMemcpyAsync(slab + (size_t)r * stride, (char *)g->val + off, nid * vb + vpad + 16, hipMemcpyDeviceToDevice, g->stream));
+        if (nc) HIPCHECK(hipMemcpyAsync(tot + (size_t)r * nc, g->cnt_total + o2, nc * sizeof(long long), hipMemcpyDeviceToDevice, g->stream));
+    }
+    bool regular = keep > 1 ? g->chains_regular : true;
+    if (nchains > keep) {
+        std::vector<int32_t> init_i(nid, 0);
+        for (size_t v = 0; v < (size_t)c.nvar; v++) init_i[c.iid[v]] = c.v_init[v];
+        for (int r = keep; r < nchains; r++)
+            if ((rc = upload_values(g, slab + (size_t)r * stride, init_i.data(), nid))) return rc;
+        regular = regular && c.values_regular;
+    }
+    HIPCHECK(hipStreamSynchronize(g->stream));
+    // the arrays of the previous layout go (a one-chain handle's first call frees the ones nsk_graph_create made)
+    void *old_val = g->val;
+    uint8_t *old_pos = g->chain_stride ? nullptr : g->cnt_pos;     // (inside the old slab once the chain count was set)
+    int32_t *old_cnt = g->cnt;
+    long long *old_tot = g->cnt_total;
+    g->val = slab; g->cnt_pos = slab + half; g->cnt = cnt; g->cnt_total = tot;
+    g->chain_stride = stride;
+    g->nchains = nchains;
+    g->chains_regular = nchains > 1 ? regular : true;
+    g->values_regular = g->chain_regular[0] && g->chain_regular[1] && g->chains_regular;
+    dev_free(g, old_val); dev_free(g, old_pos); dev_free(g, old_cnt); dev_free(g, old_tot);
+    g->pos_tally_sweeps = 0;
+    g->cnt_dirty = false;
+    g->seg_plans_key = -1;                  // (the plans check the arrays' offsets from the value array)
+    nsk_drop_sweep_graph(g);                // (captured launches hold the old arrays' addresses)
+    return NSK_OK;
+}
+
+int nsk_get_chains(nsk_graph *g) { return g ? g->nchains : 0; }
+
+int nsk_chains_upload(nsk_graph *g, const int64_t *var_value, const int64_t *count) {
+    if (!g) return fail(NSK_E_INVALID, "null graph");
+    HIPCHECK(hipSetDevice(g->device));
+    const int64_t nvar = g->c.nvar;
+    const size_t vb = (size_t)g->c.vbytes, R = (size_t)g->nchains, nc = (size_t)g->c.ncount;
+    if (var_value && nvar) {
+        int rc = xfer_ensure(g);
+        if (rc) return rc;
+        // validate every chain before anything is copied: an error leaves the device state as it was
+        bool reg_rest = true, reg0 = true;
+        for (size_t r = 0; r < R; r++) {
+            int bad = 0;
+            bool reg = true;
+            if (vb == 1) narrow_values<int8_t>(g, var_value + r * (size_t)nvar, (int8_t *)g->xfer_host[0], &bad, &reg);
+            else narrow_values<int32_t>(g, var_value + r * (size_t)nvar, (int32_t *)g->xfer_host[0], &bad, &reg);
+            if (bad) return fail(NSK_E_RANGE, "variable value does not fit the device value type");
+            if (!reg && g->c.has_ufo)
+                return fail(NSK_E_RANGE, "a variable value lies outside its domain on a graph with UFO factors "
+                                         "(the value indexes the factor's member list)");
+            if (r == 0) reg0 = reg; else reg_rest = reg_rest && reg;
+        }
+        const int nb = (int)std::min<int64_t>(4096, (nvar + NSK_BLOCK - 1) / NSK_BLOCK);
+        for (size_t r = 0; r < R; r++) {
+            if (vb == 1) narrow_values_unchecked<int8_t>(g, var_value + r * (size_t)nvar, (int8_t *)g->xfer_host[0]);
+            else narrow_values_unchecked<int32_t>(g, var_value + r * (size_t)nvar, (int32_t *)g->xfer_host[0]);
+            void *dst = (char *)g->val + r * g->chain_stride;
+            HIPCHECK(hipMemcpyAsync(g->xfer_dev, g->xfer_host[0], (size_t)nvar * vb, hipMemcpyHostToDevice, g->stream));
+            if (vb == 1) k_state_scatter<int8_t><<<dim3(nb), dim3(NSK_BLOCK), 0, g->stream>>>((int8_t *)dst, g->xfer_iid, (const int8_t *)g->xfer_dev, nvar);
+            else k_state_scatter<int32_t><<<dim3(nb), dim3(NSK_BLOCK), 0, g->stream>>>((int32_t *)dst, g->xfer_iid, (const int32_t *)g->xfer_dev, nvar);
+            HIPCHECK(hipStreamSynchronize(g->stream));          // (the staging buffer serves the next chain)
+        }
+        g->chain_regular[0] = reg0;
+        if (R > 1) g->chains_regular = reg_rest;
+        g->values_regular = g->chain_regular[0] && g->chain_regular[1] && g->chains_regular;
+    }
+    if (count && nc) {
+        int rc = fold_counts(g);
+        if (rc) return rc;
+        HIPCHECK(hipMemcpyAsync(g->cnt_total, count, R * nc * sizeof(int64_t), hipMemcpyHostToDevice, g->stream));
+        HIPCHECK(hipMemsetAsync(g->cnt, 0, R * nc * sizeof(int32_t), g->stream));
+        if (g->c.npos)
+            for (size_t r = 0; r < R; r++) HIPCHECK(hipMemsetAsync(g->cnt_pos + r * g->chain_stride, 0, (size_t)g->c.npos, g->stream));
+        g->pos_tally_sweeps = 0;
+        g->cnt_dirty = false;
+    }
+    HIPCHECK(hipStreamSynchronize(g->stream));
+    return NSK_OK;
+}
+
+int nsk_chains_download(nsk_graph *g, int64_t *var_value, int64_t *count) {
+    if (!g) return fail(NSK_E_INVALID, "null graph");
+    HIPCHECK(hipSetDevice(g->device));
+    const size_t R = (size_t)g->nchains, nc = (size_t)g->c.ncount, nvar = (size_t)g->c.nvar;
+    int rc;
+    if (var_value)
+        for (size_t r = 0; r < R; r++)
+            if ((rc = download_values(g, (const char *)g->val + r * g->chain_stride, var_value + r * nvar, 0))) return rc;
+    if (count && nc) {
+        if ((rc = fold_counts(g))) return rc;
+        HIPCHECK(hipMemcpyAsync(count, g->cnt_total, R * nc * sizeof(int64_t), hipMemcpyDeviceToHost, g->stream));
+    }
+    HIPCHECK(hipStreamSynchronize(g->stream));
     return NSK_OK;
 }
 
@@ -973,6 +1118,7 @@ int nsk_exchange_setup(nsk_graph *g, int world, int rank, const int32_t *send_vi
                        const int32_t *recv_vids, const int64_t *recv_off, int64_t slot) {
     if (!g || world < 1 || rank < 0 || rank >= world || nsend < 0 || slot < nsend || !recv_off)
         return fail(NSK_E_INVALID, "bad exchange description");
+    NSK_ONE_CHAIN(g, "nsk_exchange_setup");
     HIPCHECK(hipSetDevice(g->device));
     const int64_t nrecv = recv_off[world];
     for (int64_t i = 0; i < nsend; i++)
@@ -1044,6 +1190,7 @@ extern "C" {
 static int exchange_step(nsk_graph *g, int which, bool pack) {
     if (!g) return fail(NSK_E_INVALID, "null graph");
     if (g->xworld == 0) return fail(NSK_E_INVALID, "nsk_exchange_setup has not been called");
+    NSK_ONE_CHAIN(g, "the exchange entry points");
     if (which != NSK_BUF_VALUE && which != NSK_BUF_VALUE_EVID) return fail(NSK_E_INVALID, "bad buffer id");
     HIPCHECK(hipSetDevice(g->device));
     { int frc = nsk_p2p_flush(g); if (frc) return frc; }
@@ -1060,6 +1207,7 @@ int nsk_exchange_unpack(nsk_graph *g, int which) { return exchange_step(g, which
 // id nvar + j, and every exchange recomputes the aggregates (both chains in learning) before it pushes.
 int nsk_pf_setup(nsk_graph *g, int64_t npf, const uint8_t *op, const int64_t *member_off, const int32_t *member_vids) {
     if (!g || npf < 0 || (npf && (!op || !member_off || !member_vids))) return fail(NSK_E_INVALID, "bad partial-factor description");
+    NSK_ONE_CHAIN(g, "nsk_pf_setup");
     HIPCHECK(hipSetDevice(g->device));
     { int frc = nsk_p2p_flush(g); if (frc) return frc; }
     std::vector<int32_t> off((size_t)npf + 1, 0), mem;
@@ -1106,6 +1254,7 @@ int nsk_p2p_setup(nsk_graph *g, int world, int rank, const int32_t *send_vids, c
                   const int64_t *peer_total) {
     if (!g || world < 1 || world > 16 || rank < 0 || rank >= world || !send_off || !recv_off || !peer_base || !peer_total)
         return fail(NSK_E_INVALID, "bad peer-to-peer description (at most 16 ranks: one node)");
+    NSK_ONE_CHAIN(g, "nsk_p2p_setup");
     HIPCHECK(hipSetDevice(g->device));
     const int64_t nsend = send_off[world], nrecv = recv_off[world];
     if (send_off[0] != 0 || recv_off[0] != 0 || nsend < 0 || nrecv < 0) return fail(NSK_E_INVALID, "bad list offsets");
@@ -1539,6 +1688,7 @@ extern "C" {
 int nsk_p2p_selftest(nsk_graph *g, int learn, int part) {
     if (!g) return fail(NSK_E_INVALID, "null graph");
     if (!g->p2p_ready) return fail(NSK_E_INVALID, "nsk_p2p_setup / nsk_p2p_export / nsk_p2p_import first");
+    NSK_ONE_CHAIN(g, "the peer-to-peer entry points");
     if (part < 0 || part > 3) return fail(NSK_E_INVALID, "bad part");
     HIPCHECK(hipSetDevice(g->device));
     { int frc = nsk_p2p_flush(g); if (frc) return frc; }
@@ -1553,6 +1703,7 @@ int nsk_p2p_selftest(nsk_graph *g, int learn, int part) {
 int nsk_p2p_fuse(nsk_graph *g, int on) {
     if (!g) return fail(NSK_E_INVALID, "null graph");
     if (!g->p2p_ready) return fail(NSK_E_INVALID, "nsk_p2p_setup / nsk_p2p_export / nsk_p2p_import first");
+    NSK_ONE_CHAIN(g, "the peer-to-peer entry points");
     HIPCHECK(hipSetDevice(g->device));
     { int frc = nsk_p2p_flush(g); if (frc) return frc; }
     if (on) {
@@ -1585,6 +1736,7 @@ int nsk_p2p_reset(nsk_graph *g) {
 int nsk_p2p_exchange(nsk_graph *g, int learn, int part) {
     if (!g) return fail(NSK_E_INVALID, "null graph");
     if (!g->p2p_ready) return fail(NSK_E_INVALID, "nsk_p2p_setup / nsk_p2p_export / nsk_p2p_import first");
+    NSK_ONE_CHAIN(g, "the peer-to-peer entry points");
     if (part < 0 || part > 3) return fail(NSK_E_INVALID, "bad part");
     HIPCHECK(hipSetDevice(g->device));
     { int frc = nsk_p2p_flush(g); if (frc) return frc; }
@@ -1594,6 +1746,7 @@ int nsk_p2p_exchange(nsk_graph *g, int learn, int part) {
 int nsk_gibbs_sweeps_p2p(nsk_graph *g, int64_t nsweeps, int sample_evidence, int burnin) {
     if (!g) return fail(NSK_E_INVALID, "null graph");
     if (!g->p2p_ready) return fail(NSK_E_INVALID, "nsk_p2p_setup / nsk_p2p_export / nsk_p2p_import first");
+    NSK_ONE_CHAIN(g, "the peer-to-peer entry points");
     if (nsweeps < 0 || nsweeps > INT32_MAX) return fail(NSK_E_INVALID, "bad sweep count");
     HIPCHECK(hipSetDevice(g->device));
     return nsk_gibbs_run(g, nsweeps, sample_evidence, burnin, true);      // (flushes a pending close unless it continues it)
@@ -1603,6 +1756,7 @@ int nsk_learn_sweeps_p2p(nsk_graph *g, int64_t nsweeps, double step, double deca
                          double reg_param, int64_t truncation, int learn_non_evidence) {
     if (!g) return fail(NSK_E_INVALID, "null graph");
     if (!g->p2p_ready) return fail(NSK_E_INVALID, "nsk_p2p_setup / nsk_p2p_export / nsk_p2p_import first");
+    NSK_ONE_CHAIN(g, "the peer-to-peer entry points");
     if (nsweeps < 0 || nsweeps > INT32_MAX) return fail(NSK_E_INVALID, "bad sweep count");
     HIPCHECK(hipSetDevice(g->device));
     { int frc = nsk_p2p_flush(g); if (frc) return frc; }
@@ -1654,6 +1808,7 @@ int nsk_comm_unique_id(const char *librccl_path, void *id128) {
 
 int nsk_comm_init(nsk_graph *g, int world, int rank, const void *id128, const char *librccl_path) {
     if (!g || !id128 || world < 1 || rank < 0 || rank >= world) return fail(NSK_E_INVALID, "bad argument");
+    NSK_ONE_CHAIN(g, "nsk_comm_init");
     int rc = load_rccl(librccl_path);
     if (rc) return rc;
     HIPCHECK(hipSetDevice(g->device));
@@ -1679,6 +1834,7 @@ static int native_exchange(nsk_graph *g, int which) {
 int nsk_gibbs_sweeps_exchange(nsk_graph *g, int64_t nsweeps, int sample_evidence, int burnin) {
     if (!g) return fail(NSK_E_INVALID, "null graph");
     if (!g->rccl_comm || g->xworld == 0) return fail(NSK_E_INVALID, "nsk_exchange_setup / nsk_comm_init first");
+    NSK_ONE_CHAIN(g, "the exchange entry points");
     for (int64_t s = 0; s < nsweeps; s++) {
         int rc = nsk_gibbs_sweeps(g, 1, sample_evidence, burnin);
         if (rc) return rc;
@@ -1691,6 +1847,7 @@ int nsk_learn_sweeps_exchange(nsk_graph *g, int64_t nsweeps, double step, double
                               double reg_param, int64_t truncation, int learn_non_evidence) {
     if (!g) return fail(NSK_E_INVALID, "null graph");
     if (!g->rccl_comm || g->xworld == 0) return fail(NSK_E_INVALID, "nsk_exchange_setup / nsk_comm_init first");
+    NSK_ONE_CHAIN(g, "the exchange entry points");
     const int nw = (int)g->c.nweight;
     for (int64_t s = 0; s < nsweeps; s++) {
         HIPCHECK(hipSetDevice(g->device));

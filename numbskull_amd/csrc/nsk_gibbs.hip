@@ -162,6 +162,53 @@ void nsk_ensure_seg_plans(nsk_graph *g, int sample_evidence) {
     g->p2p_border_all = border_all && border_total == (uint32_t)bt.size();
 }
 
+// One table launch of a class for EVERY chain of a handle with several (nsk_set_chains): k_gibbs_seg_tabw_chains /
+// k_gibbs_seg_tab_chains over R copies of the single-chain grid.  sweep_base: a captured launch (key and sweep index in
+// d_counters, sweep_off added).
+template <typename VT>
+static void launch_tab_chains(nsk_graph *g, const NskSegPlan &pl, int burnin, uint32_t K0, uint32_t K1, uint32_t S0, uint32_t S1,
+                              const unsigned long long *sweep_base, uint32_t sweep_off) {
+    const unsigned R = (unsigned)g->nchains;
+    if (sizeof(VT) == 1 && pl.tab.wide) {
+        const DevGraph<signed char> dw = view<signed char>(g);
+        const int nbw = nsk_tabw_grid(pl.tab.ntiles);
+        TabwCold cold{K0, K1, S0, S1, sweep_off, 0u, dw, pl.tab, pl.nrest, {}};
+        memcpy(cold.rest, pl.rest, sizeof(cold.rest));
+        const int nf = nsk_tabw_front_blocks(pl.nrest);
+        const dim3 grid(R * (unsigned)(nf + nbw));            // (the kernel derives nf + nbw from its hot arguments)
+#define NSK_TABW(NCH, MODE) k_gibbs_seg_tabw_chains<NCH, MODE><<<grid, dim3(NSK_BLOCK), 0, g->stream>>>(NSK_TABW_HOT_ARGS(g, pl.tab, nbw, nf, sweep_base), cold)
+        if (pl.nch == 1) { if (burnin) NSK_TABW(1, 1); else NSK_TABW(1, 0); }
+        else { if (burnin) NSK_TABW(2, 1); else NSK_TABW(2, 0); }
+#undef NSK_TABW
+    } else {
+        const DevGraph<VT> d = view<VT>(g);
+        const int nbp = nsk_tab_grid(pl.tab.ntiles);
+        const TabChains ch{(uint32_t)nbp, 0u, (long long)g->chain_stride};
+        const dim3 grid(R * (unsigned)nbp);
+        if (pl.nch == 1) k_gibbs_seg_tab_chains<VT, 1><<<grid, dim3(NSK_BLOCK), 0, g->stream>>>(d, pl.tab, burnin, K0, K1, S0, S1, sweep_base, sweep_off, ch);
+        else k_gibbs_seg_tab_chains<VT, 2><<<grid, dim3(NSK_BLOCK), 0, g->stream>>>(d, pl.tab, burnin, K0, K1, S0, S1, sweep_base, sweep_off, ch);
+    }
+}
+// batched chain launches: a handle with several chains whose sweep is table launches only, its values in their domains,
+// and the kernels' 32-bit offsets valid for the last chain
+static bool chains_batched(nsk_graph *g, int sample_evidence) {
+    if (g->nchains < 2 || g->chain_swapped || g->scan != NSK_SCAN_CHROMATIC || !g->values_regular || !nsk_tables_only(g) ||
+        nsk::diag_env("NSK_NO_CHAIN_BATCH"))
+        return false;
+    nsk_ensure_seg_plans(g, sample_evidence);
+    const long long shift = (long long)(g->nchains - 1) * (long long)(g->chain_stride / 256);
+    const auto fits = [&](const void *p) {
+        const long long d = ((const char *)p - (const char *)g->val) / 256 - shift;
+        return d > -(1ll << 31) && d < (1ll << 31);
+    };
+    for (const auto &v : g->seg_plans)
+        for (const NskSegPlan &pl : v) {
+            if (pl.kind < 8) return false;
+            if (g->c.vbytes == 1 && pl.tab.wide && !(fits(g->seg_wide) && fits(g->ztab))) return false;
+        }
+    return true;
+}
+
 template <typename VT>
 static int gibbs_impl(nsk_graph *g, int64_t nsweeps, int sample_evidence, int burnin) {
     DevGraph<VT> d = view<VT>(g);
@@ -280,7 +327,9 @@ static int gibbs_impl(nsk_graph *g, int64_t nsweeps, int sample_evidence, int bu
                         if (kind >= 8) {
                             // a wave per tile pair while that fits the resident grid, else its waves loop over quads
                             const int nbp = nsk_tab_grid(tab.ntiles);
-                            if (g->p2p_fused_now) {
+                            if (g->nchains > 1 && !g->chain_swapped)    // every chain in one launch (chains_batched)
+                                launch_tab_chains<VT>(g, pl, burnin, K0, K1, S0, S1, nullptr, 0u);
+                            else if (g->p2p_fused_now) {
                                 TabP2P px;
                                 nsk_p2p_fill(g, px, nullptr, g->p2p_tag, (int)ph == g->p2p_first_phase);
                                 if (nch == 1) k_gibbs_seg_tab_p2p<VT, 1><<<dim3(nbp), block, 0, g->stream>>>(d, tab, burnin, K0, K1, S0, S1, nullptr, 0u, px);
@@ -357,7 +406,8 @@ static bool graph_eligible(const nsk_graph *g, bool p2p) {
     // handle (10M grid: 12 us per class) a replay saves nothing and its launch latency shows in short runs.
     // A handle that exchanges peer to peer adds two tiny kernels per sweep: its sequences are captured up
     // to twice the size (the two shards of the 10M grid)
-    if (c.nsampled > (p2p ? 6000000 : 3000000)) return false;
+    // (a handle with several chains: the work of one launch is every chain's)
+    if (c.nsampled * (int64_t)std::max(1, g->nchains) > (p2p ? 6000000 : 3000000)) return false;
     return nsk_tables_only(g);
 }
 
@@ -381,7 +431,9 @@ static int graph_build(nsk_graph *g, int sample_evidence, int burnin, bool p2p, 
         for (size_t ph = 0; ph < g->seg_plans.size(); ph++)
             for (const NskSegPlan &pl : g->seg_plans[ph]) {
                 const int nbp = nsk_tab_grid(pl.tab.ntiles);
-                if (g->p2p_fused_now) {          // the exchange inside the launch: tag = counter + i + 1
+                if (g->nchains > 1)              // every chain in one launch (chains_batched)
+                    launch_tab_chains<VT>(g, pl, burnin, 0u, 0u, 0u, 0u, g->d_counters, (uint32_t)i);
+                else if (g->p2p_fused_now) {          // the exchange inside the launch: tag = counter + i + 1
                     TabP2P px;
                     nsk_p2p_fill(g, px, g->d_counters, (unsigned int)(i + 1), (int)ph == g->p2p_first_phase);
                     if (pl.nch == 1)
@@ -451,7 +503,7 @@ int nsk_gibbs_run(nsk_graph *g, int64_t nsweeps, int sample_evidence, int burnin
     // Packed tally (nsk_internal.h): a whole-graph handle whose every launch of this call is the wide-quad kernel's keeps
     // the tally inside the value bytes while the call runs; it is unpacked before the call returns
     g->pack_now = false;
-    if (!p2p && !burnin && g->scan == NSK_SCAN_CHROMATIC && g->values_regular && g->c.vbytes == 1 && nsweeps > 0 &&
+    if (!p2p && !burnin && g->nchains == 1 && g->scan == NSK_SCAN_CHROMATIC && g->values_regular && g->c.vbytes == 1 && nsweeps > 0 &&
         nsk_tables_only(g) && !nsk::diag_env("NSK_NO_PACK_TALLY")) {
         nsk_ensure_seg_plans(g, sample_evidence);
         bool all_wide = true;
@@ -511,10 +563,29 @@ int nsk_gibbs_run(nsk_graph *g, int64_t nsweeps, int sample_evidence, int burnin
     return NSK_OK;
 }
 
+// A handle with several chains (nsk_set_chains): the table launches of a sweep serve every chain at once (chains_batched:
+// eager or captured, through nsk_gibbs_run); any other handle samples chain after chain, each through a ChainSwap view
+// of the handle (its values and tallies, key word 1 XOR r) by the one-chain launches, from the same sweep index on.
+static int chains_run(nsk_graph *g, int64_t nsweeps, int sample_evidence, int burnin) {
+    if (g->scan != NSK_SCAN_CHROMATIC) return fail(NSK_E_INVALID, "several chains: the sequential scan samples one chain");
+    if (chains_batched(g, sample_evidence)) return nsk_gibbs_run(g, nsweeps, sample_evidence, burnin, false);
+    const uint64_t sweep0 = g->sweep;
+    const int pts0 = g->pos_tally_sweeps;
+    const int64_t done0 = g->sweeps_done;
+    for (int r = 0; r < g->nchains; r++) {
+        ChainSwap cs(g, r);
+        g->sweep = sweep0; g->pos_tally_sweeps = pts0; g->sweeps_done = done0;
+        const int rc = gibbs_eager(g, nsweeps, sample_evidence, burnin);
+        if (rc) return rc;
+    }
+    return NSK_OK;
+}
+
 extern "C" int nsk_gibbs_sweeps(nsk_graph *g, int64_t nsweeps, int sample_evidence, int burnin) {
     if (!g) return fail(NSK_E_INVALID, "null graph");
     if (nsweeps < 0 || nsweeps > INT32_MAX) return fail(NSK_E_INVALID, "bad sweep count");
     if (nsweeps == 0) return NSK_OK;
     HIPCHECK(hipSetDevice(g->device));
+    if (g->nchains > 1) return chains_run(g, nsweeps, sample_evidence, burnin);
     return nsk_gibbs_run(g, nsweeps, sample_evidence, burnin, false);
 }

@@ -181,9 +181,41 @@ struct nsk_graph {
     int scan = NSK_SCAN_CHROMATIC;
     bool cnt_dirty = false;
     int64_t sweeps_done = 0;
+    // Several chains (nsk_set_chains): R value arrays, position tallies, delta tallies and masters over ONE compiled
+    // layout and weight table.  Once a handle's chain count was set, chain r's values lie at val + r chain_stride and its
+    // uint8 position tally at cnt_pos + r chain_stride (one slab: values in the first half of each chain's stride, the
+    // tally in the second, so cnt_pos - val is the same for every chain -- k_gibbs_seg_tabw_chains); its int32 and int64
+    // tallies at cnt / cnt_total + r ncount.  The handle's pointers are chain 0's except while ChainSwap points them at
+    // another chain (launches of the kernel families that sample one chain per launch).
+    int nchains = 1;
+    size_t chain_stride = 0;
+    bool chains_regular = true;    // the values of chains 1 .. R - 1 lie in their domains (see values_regular)
+    bool chain_swapped = false;    // a ChainSwap is active: the pointers are one chain's, the sweep samples that chain only
     // profiling bracket
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
     int64_t launches = 0, launches_at_begin = 0;
+};
+
+#define NSK_MAX_CHAINS 1024
+// entry points that serve one chain only: refused on a handle with several (nsk_set_chains)
+#define NSK_ONE_CHAIN(G, WHAT)                                                                                         \
+    do {                                                                                                               \
+        if ((G)->nchains > 1)                                                                                          \
+            return nsk::fail(NSK_E_INVALID, std::string(WHAT) + ": the handle has several chains (nsk_set_chains); "   \
+                                            "only chromatic inference sweeps (nsk_gibbs_sweeps) serve them");          \
+    } while (0)
+// Points the handle's per-chain state at chain r while it lives: values, tallies, and the key (word 1 XOR r -- chain r
+// draws what a one-chain handle seeded seed ^ (r << 32) draws)
+struct ChainSwap {
+    nsk_graph *g;
+    void *val; uint8_t *cnt_pos; int32_t *cnt; long long *cnt_total; uint64_t seed;
+    ChainSwap(nsk_graph *g_, int r) : g(g_), val(g_->val), cnt_pos(g_->cnt_pos), cnt(g_->cnt), cnt_total(g_->cnt_total), seed(g_->seed) {
+        g->chain_swapped = true;
+        const size_t off = (size_t)r * g->chain_stride, nc = (size_t)r * (size_t)g->c.ncount;
+        g->val = (char *)val + off; g->cnt_pos = cnt_pos + off; g->cnt = cnt + nc; g->cnt_total = cnt_total + nc;
+        g->seed = seed ^ ((uint64_t)(uint32_t)r << 32);
+    }
+    ~ChainSwap() { g->val = val; g->cnt_pos = cnt_pos; g->cnt = cnt; g->cnt_total = cnt_total; g->seed = seed; g->chain_swapped = false; }
 };
 
 // Philox counter word 3 of every sweep kernel (see rng_tag)

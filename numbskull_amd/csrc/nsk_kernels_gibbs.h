@@ -1879,6 +1879,90 @@ __global__ __launch_bounds__(NSK_BLOCK) void k_gibbs_seg_tab(DevGraph<VT> g, Seg
     }
 }
 
+// ---- several chains (nsk_set_chains): one launch samples a class of every chain ----
+// The chains kernels are the one-chain kernels' loops (k_gibbs_seg_tab, k_gibbs_seg_tabw: same inner routines, tab_tiles /
+// wide_issue / wide_finish) with the workgroup's index taken within its chain -- `bx` of the chain's `nbx` workgroups --
+// and key word 1 XOR the chain.  (They are separate bodies, not a template flag on the one-chain kernels': sharing the
+// body changed those kernels' machine code -- register allocation and load order -- and they are kept as measured.)
+template <typename VT, int NCH>
+__device__ __forceinline__ void seg_tab_chains_body(const DevGraph<VT> &g, const SegTable &tab, int burnin,
+                                             uint32_t k0, uint32_t k1, uint32_t s0, uint32_t s1,
+                                             const unsigned long long *sweep_base, uint32_t sweep_off,
+                                             uint32_t bx, uint32_t nbx, uint32_t chain) {
+    if (sweep_base) {             // a captured launch (hipGraph): sweep index, key and shard tag live in device memory
+        const NSK_SCALAR unsigned long long *cb = (const NSK_SCALAR unsigned long long *)sweep_base;
+        const unsigned long long sw = cb[0] + sweep_off, key = cb[2];
+        s0 = (uint32_t)sw;
+        s1 = (uint32_t)(sw >> 32) ^ (uint32_t)cb[3];
+        k0 = (uint32_t)key;
+        k1 = (uint32_t)(key >> 32);
+    }
+    k1 ^= chain;
+    const int lane = (int)(threadIdx.x & 63);
+    const int nquads = tab.ntiles >> 2;                                 // virtual tiles: a multiple of 4
+    const int per = (nquads + 7) >> 3;                                  // quads per XCD
+    const int xcd = (int)(bx & 7);
+    const int wx = __builtin_amdgcn_readfirstlane((int)(bx >> 3) * (NSK_BLOCK / 64) + (int)(threadIdx.x >> 6));
+    const int wpx = (int)(nbx >> 3) * (NSK_BLOCK / 64);      // waves per XCD
+    const int q0 = min(nquads, xcd * per), q1 = min(nquads, (xcd + 1) * per);
+    const int qr = q0 + ((q1 - q0) / wpx) * wpx;                        // first quad dealt as pairs
+    // the segment of the last located quad stays in scalar registers: most launches have one
+    int c_lo = 0, c_hi = -1;
+    SegEntry en = tab.e[0];
+    // units: quads [q0, qr) one per trip, then the pairs of quads [qr, q1)
+    for (int U = wx; ; U += wpx) {
+        int Q, h = -1;
+        if (q0 + U < qr) Q = q0 + U;
+        else {
+            const int u = U - (qr - q0);                                // pair unit of the remainder
+            if (u >= 2 * (q1 - qr)) break;
+            Q = qr + (u >> 1);
+            h = u & 1;
+        }
+        if (4 * Q < c_lo || 4 * Q >= c_hi) {                            // wave-uniform, rare
+            const int sidx = seg_of_tile(tab, 4 * Q);
+            en = tab.e[sidx];
+            c_lo = en.tile_start;
+            c_hi = sidx + 1 < NSK_SEG_MAX ? tab.e[sidx + 1].tile_start : tab.ntiles;
+        }
+        const int lead = (int)(en.ntiles_lead >> 30);
+        const int t0q = 4 * Q - en.tile_start - lead;                   // segment tile of the quad's first tile
+        // (a wide quad -- nsk_compile.h seg_wide -- in a launch that is not the wide kernel's, most of its quads being
+        // of the other kind: tile by tile with the wide scheme's words)
+        bool ws = false;
+        if (sizeof(VT) == 1 && en.wide_off != NSK_NO_STREAM)
+            ws = ((const NSK_SCALAR uint32_t *)(g.seg_wide + en.wide_off))[(size_t)(Q - (en.tile_start >> 2)) * NSK_WIDE_STRIDE(NCH)] != 0xFFFFFFFFu;
+        // the quad's block: en.pos0 - 64 lead is a multiple of 256, so (pos >> 8, lane) names it
+        const uint32_t qb = quad_block((uint32_t)(en.pos0 + t0q * 64 + lane));
+        const u32x4 ra = philox4x32(k0, k1, qb, 2u, s0, s1);
+        u32x4 rb = {0u, 0u, 0u, 0u};
+        bool have_b = false;
+        if (h >= 0) {                                                   // wave-uniform
+            tab_tiles<VT, NCH, 2>(g, en, t0q + 2 * h, 2 * h, lane, burnin, ra, rb, have_b, qb, k0, k1, s0, s1, ws);
+        } else if (NSK_TAB_BATCH == 4) {
+            tab_tiles<VT, NCH, 4>(g, en, t0q, 0, lane, burnin, ra, rb, have_b, qb, k0, k1, s0, s1, ws);
+        } else {
+            tab_tiles<VT, NCH, 2>(g, en, t0q, 0, lane, burnin, ra, rb, have_b, qb, k0, k1, s0, s1, ws);
+            tab_tiles<VT, NCH, 2>(g, en, t0q + 2, 2, lane, burnin, ra, rb, have_b, qb, k0, k1, s0, s1, ws);
+        }
+    }
+}
+// One colour class of EVERY chain of a handle (nsk_set_chains) in one launch: workgroup b serves chain b / per_chain
+// (per_chain: whole rounds of XCDs, so each chain's workgroups keep the single-chain kernel's XCD split); a chain's
+// value array and position tally lie `stride` bytes after the previous chain's (nsk_internal.h chain slab), the
+// segment tables, adjacency and draw tables are the handle's one copy.  Chain r draws with key word 1 XOR r.
+struct TabChains { uint32_t per_chain, pad_; long long stride; };
+template <typename VT, int NCH>
+__global__ __launch_bounds__(NSK_BLOCK) void k_gibbs_seg_tab_chains(DevGraph<VT> g, SegTable tab, int burnin,
+                                                                    uint32_t k0, uint32_t k1, uint32_t s0, uint32_t s1,
+                                                                    const unsigned long long *sweep_base, uint32_t sweep_off, TabChains ch) {
+    const uint32_t chain = blockIdx.x / ch.per_chain;
+    DevGraph<VT> gc = g;
+    gc.val = (VT *)((char *)g.val + (long long)chain * ch.stride);
+    gc.cnt_pos = g.cnt_pos + (long long)chain * ch.stride;
+    seg_tab_chains_body<VT, NCH>(gc, tab, burnin, k0, k1, s0, s1, sweep_base, sweep_off, blockIdx.x - chain * ch.per_chain, ch.per_chain, chain);
+}
+
 // ---- the table launch of a class whose quads are (mostly) wide ones (SegTable.wide; int8 values) ----
 // Resident grid, XCD x walks the x-th eighth of the launch's quads, a wave's trip is a quad: value loads (the quad's
 // descriptor -- slot bases, exception list, slot mask -- was requested one trip ahead by a scalar load) -> Philox block
@@ -2146,6 +2230,224 @@ __global__ __launch_bounds__(NSK_BLOCK) NSK_TABW_ATTR void k_gibbs_seg_tabw(NSK_
         }
     }
 #endif
+}
+
+// TabwCold.rest quad of a chains launch (tabw_rest_quad): `bx` the workgroup's index within its chain, the chain's arrays
+// `cstride` bytes per chain on
+template <int NCH, int MODE>
+__device__ __forceinline__ void tabw_rest_quad_chains(const char NSK_SCALAR *ka, const unsigned long long *sweep_base,
+                                               uint32_t bx, uint32_t chain, long long cstride) {
+    const TabwCold NSK_SCALAR *cold = (const TabwCold NSK_SCALAR *)(ka + NSK_TABW_COLD_OFFSET);
+    if (bx >= cold->nrest) return;
+    const int lane = (int)(threadIdx.x & 63);
+    const int wv = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    const uint32_t ent = cold->rest[bx];
+    const int Q = (int)(ent & 0x7FFFFFFFu);
+    const bool flagged = (ent >> 31) != 0u;
+    const SegTable NSK_SCALAR *tb = &cold->tab;
+    int sidx = 0;
+    for (int i = 1; i < NSK_SEG_MAX && 4 * Q >= tb->e[i].tile_start; i++) sidx = i;      // (tile_start = ntiles beyond the last segment)
+    SegEntry en;
+    {
+        const NSK_SCALAR uint32_t *ep = (const NSK_SCALAR uint32_t *)(ka + NSK_TABW_COLD_OFFSET + offsetof(TabwCold, tab) +
+                                                                      offsetof(SegTable, e) + sizeof(SegEntry) * (size_t)sidx);
+        uint32_t ew[sizeof(SegEntry) / 4];
+#pragma unroll
+        for (int j = 0; j < (int)(sizeof(SegEntry) / 4); j++) ew[j] = ep[j];
+        __builtin_memcpy(&en, ew, sizeof(SegEntry));
+    }
+    uint32_t k0 = cold->k0, k1 = cold->k1, s0 = cold->s0, s1 = cold->s1;
+    if (sweep_base) {                 // a captured launch (hipGraph): sweep index, key and shard tag live in device memory
+        const NSK_SCALAR unsigned long long *cb = (const NSK_SCALAR unsigned long long *)sweep_base;
+        const unsigned long long sw = cb[0] + cold->sweep_off, key = cb[2];
+        s0 = (uint32_t)sw;
+        s1 = (uint32_t)(sw >> 32) ^ (uint32_t)cb[3];
+        k0 = (uint32_t)key;
+        k1 = (uint32_t)(key >> 32);
+    }
+    k1 ^= chain;
+    DevGraph<signed char> gf;
+    gf.val = cold->g.val; gf.cnt_pos = cold->g.cnt_pos; gf.ztab = cold->g.ztab; gf.seg_wide = cold->g.seg_wide;
+    gf.val += (long long)chain * cstride; gf.cnt_pos += (long long)chain * cstride;
+    gf.adj = cold->g.adj; gf.seg_aff = cold->g.seg_aff; gf.sink = cold->g.sink;
+    const int lead = (int)(en.ntiles_lead >> 30);
+    const int t0q = 4 * Q - en.tile_start - lead;                       // segment tile of the quad's first tile
+    const int p0 = en.pos0 + t0q * 64;                                  // the quad's first position (a multiple of 256)
+    const uint32_t qb = quad_block((uint32_t)(p0 + lane));
+    const u32x4 ra = philox4x32(k0, k1, qb, 2u, s0, s1);
+    u32x4 rb = {0u, 0u, 0u, 0u};
+    bool have_b = false;
+    tab_tiles<signed char, NCH, 1, MODE == 2>(gf, en, t0q + wv, wv, lane, MODE == 1 ? 1 : 0, ra, rb, have_b, qb, k0, k1, s0, s1, flagged);
+}
+// the body of k_gibbs_seg_tabw_chains (k_gibbs_seg_tabw's): `bx` the workgroup's index within its chain; the hot arguments are the
+// chain's own -- its `val`, the shared arrays' offsets from it
+template <int NCH, int MODE>
+__device__ __forceinline__ void seg_tabw_chains_body(NSK_TABW_HOT, uint32_t bx, uint32_t chain) {
+    const int lane = (int)(threadIdx.x & 63);
+    constexpr int ST = NSK_WIDE_STRIDE(NCH), ZN = 1 << NSK_ZT_BITS(NCH), ZR = (ZN + 63) / 64;
+    __shared__ uint32_t zt_all[(NSK_BLOCK / 64) * ZN];                  // one table per wave
+    const int wv = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    uint32_t *zt = zt_all + wv * ZN;
+    uint8_t *cnt_pos = (uint8_t *)val + (long long)d_cnt * 256;
+    const uint32_t *seg_wide = (const uint32_t *)((const char *)val + (long long)d_wide * 256);
+    const uint4 *ztab = (const uint4 *)((const char *)val + (long long)d_ztab * 256);
+    const int ntiles = (int)(ntiles_nseg & 0x0FFFFFFFu);          // (bits 28-31: segments - 1; tile_start = ntiles beyond them)
+    const uint32_t zmask0 = zmask0_wpx & 0xFFu;
+    const int wpx = (int)((zmask0_wpx >> 8) & 0xFFFFu);                 // waves per XCD
+    const int nfront = (int)(zmask0_wpx >> 24);                         // workgroups in front that sample the quads that are not wide (a multiple of 8)
+    if ((int)bx < nfront) {                         // (block-uniform)
+        tabw_rest_quad_chains<NCH, MODE>((const char NSK_SCALAR *)__builtin_amdgcn_kernarg_segment_ptr(), sweep_base, bx, chain,
+                                      2ll * d_cnt * 256);
+        return;
+    }
+    const int bid = (int)bx - nfront;
+    const int nquads = ntiles >> 2;                                     // virtual tiles: a multiple of 4
+    const int per = (nquads + 7) >> 3;                                  // quads per XCD
+    const int xcd = bid & 7;
+    const int wx = __builtin_amdgcn_readfirstlane((bid >> 3) * (NSK_BLOCK / 64)) + wv;
+    const int q0 = min(nquads, xcd * per), q1 = min(nquads, (xcd + 1) * per);
+    // the cold arguments: nothing of them is read before the first trip's requests are out (`keyed`)
+    const char NSK_SCALAR *ka = (const char NSK_SCALAR *)__builtin_amdgcn_kernarg_segment_ptr();
+    const TabwCold NSK_SCALAR *cold = nullptr;
+    uint32_t k0 = 0, k1 = 0, s0 = 0, s1 = 0;
+    DevGraph<signed char> gh;
+    gh.val = val; gh.cnt_pos = cnt_pos; gh.ztab = ztab; gh.seg_wide = seg_wide;
+    PhiloxKeys pk;
+    bool keyed = false;
+    // The wave's quads: Q = q0 + wx, + wpx, ... < q1, through the launch's segments in order.  The first segment's entry
+    // is in the preloaded arguments; a wave whose quad lies in a later one reads that entry from the kernel arguments
+    // (every segment is whole quads: no quad straddles two).  The trips inside a segment are the inner loop: the scalar
+    // unit is shared by the CU's waves, one instruction per cycle, so what a trip does not need to recompute is hoisted.
+    int sidx = 0, tstart = 0, tend = ts1, pos0s = pos00;
+    uint32_t ntl = ntl0, woff = woff0, zoff = zoff0, zmask = zmask0;
+    for (int Q = q0 + wx; Q < q1;) {
+        if (4 * Q >= tend) {                                            // (wave-uniform) on to the quad's segment
+            if (!cold) { asm volatile("" : "+s"(ka)); cold = (const TabwCold NSK_SCALAR *)(ka + NSK_TABW_COLD_OFFSET); }
+            const SegTable NSK_SCALAR *tb = &cold->tab;
+            do {
+                sidx++;
+                tend = sidx + 1 < NSK_SEG_MAX ? tb->e[sidx + 1].tile_start : ntiles;
+            } while (4 * Q >= tend);
+            tstart = (int)nsk_settled((uint32_t)tb->e[sidx].tile_start); pos0s = (int)nsk_settled((uint32_t)tb->e[sidx].pos0);
+            ntl = nsk_settled(tb->e[sidx].ntiles_lead); woff = nsk_settled(tb->e[sidx].wide_off);
+            zoff = nsk_settled(tb->e[sidx].zoff); zmask = nsk_settled(tb->e[sidx].zmask_ev) & 0xFFu;
+            tend = (int)nsk_settled((uint32_t)tend);
+        }
+        const int qs = tstart >> 2;                                     // the segment's first quad of the launch
+        const int Qe = min(q1, tend >> 2);                              // ... and the end of its quads in this XCD's share
+        const int lead = (int)(ntl >> 30), nt = (int)(ntl & 0x3FFFFFFFu);
+        // quads [qin_lo, qin_lo + qin_n) of the launch lie wholly inside the run (all but a first one with dead lead tiles
+        // and a last one with fewer than four tiles)
+        const int qin_lo = qs + (lead ? 1 : 0);
+        const uint32_t qin_n = (uint32_t)(qs + ((lead + nt) >> 2) - qin_lo);
+        const bool hasw = woff != NSK_NO_STREAM;
+        // descriptor of quad Q (!hasw: words of the array's front, not looked at), its address advancing with the trips
+        const NSK_SCALAR uint32_t *wq = (const NSK_SCALAR uint32_t *)(seg_wide + (hasw ? woff : 0u)) + (hasw ? (size_t)(Q - qs) * ST : 0);
+        const size_t wstep = hasw ? (size_t)wpx * ST : 0;
+        int p0 = pos0s + (4 * Q - tstart - lead) * 64;                  // the quad's first position
+        uint32_t cur[ST];
+#pragma unroll
+        for (int j = 0; j < ST; j++) cur[j] = wq[j];
+        // the wave's copy of the segment's thresholds (their top 27 bits), lanes = entries: requested here, stored to LDS
+        // behind the first trip's value requests
+        uint32_t ztv[ZR];
+#pragma unroll
+        for (int r = 0; r < ZR; r++) {
+            const uint32_t e = (uint32_t)lane + 64u * (uint32_t)r;
+            ztv[r] = e <= zmask ? ztab[zoff + e].x : 0u;
+        }
+        bool land = true;
+        for (; Q < Qe; Q += wpx, p0 += 256 * wpx) {
+            // (the descriptor's registers are free for the next one as soon as the bases are in the loads' addresses)
+            const bool flagged = hasw && cur[0] != 0xFFFFFFFFu, wide = flagged && (uint32_t)(Q - qin_lo) < qin_n;
+            const uint32_t exc0 = cur[4 * NCH], nexc = cur[4 * NCH + 1], smask = cur[4 * NCH + 2];
+            asm volatile("" :: "s"(cur[4 * NCH + 3])); // (the descriptor's spare word stays live while the request flies: its
+                                                       //  register handed to a temporary means a wait for the whole request)
+            WideTrip<NCH> tc;
+            if (wide) {
+                uint32_t bc[4 * NCH];
+#pragma unroll
+                for (int j = 0; j < 4 * NCH; j++) bc[j] = cur[j];
+                wide_issue<NCH, MODE>(gh, p0, bc, lane, tc);
+            }
+            // the next trip's descriptor, a scalar round trip ahead (always a load, into the registers the bases just
+            // left: past the segment's quads this quad's again)
+            if (Q + wpx < Qe) wq += wstep;
+#pragma unroll
+            for (int j = 0; j < ST; j++) cur[j] = wq[j];
+            if (land) {
+                land = false;
+                if (!keyed) {             // the wave's first requests are out: now the cold arguments
+                    keyed = true;
+                    if (!cold) { asm volatile("" : "+s"(ka)); cold = (const TabwCold NSK_SCALAR *)(ka + NSK_TABW_COLD_OFFSET); }
+                    k0 = cold->k0; k1 = cold->k1; s0 = cold->s0; s1 = cold->s1;
+                    if (sweep_base) {     // a captured launch (hipGraph): sweep index, key and shard tag live in device memory
+                        const NSK_SCALAR unsigned long long *cb = (const NSK_SCALAR unsigned long long *)sweep_base;
+                        const unsigned long long sw = cb[0] + cold->sweep_off, key = cb[2];
+                        s0 = (uint32_t)sw;
+                        s1 = (uint32_t)(sw >> 32) ^ (uint32_t)cb[3];
+                        k0 = (uint32_t)key;
+                        k1 = (uint32_t)(key >> 32);
+                    }
+                    k1 ^= chain;
+                    k0 = nsk_settled(k0); k1 = nsk_settled(k1); s0 = nsk_settled(s0); s1 = nsk_settled(s1);
+                    pk = philox_round_keys(k0, k1);
+                }
+#pragma unroll
+                for (int r = 0; r < ZR; r++)
+                    if (lane + 64 * r < ZN) zt[lane + 64 * r] = ztv[r];
+                asm volatile("" ::: "memory");                          // (LDS executes a wave's accesses in order: no barrier)
+            }
+            if (wide) {
+                wide_finish<NCH, MODE>(gh, zoff, p0, exc0, nexc, smask, tc, zt, lane, k0, k1, s0, s1,
+                                       ka + NSK_TABW_COLD_OFFSET + offsetof(TabwCold, g) + offsetof(DevGraph<signed char>, wide_exc), &pk);
+                continue;
+            }
+            // not a wide quad (a class end, mixed border cells): a workgroup in front has it -- or, in a launch with more
+            // such quads than those take, tile by tile here.  Its block: the run's first position less its lead tiles is
+            // a multiple of 256, so (pos >> 8, lane) names it
+            if (nfront) continue;
+            SegEntry en;
+            {
+                const NSK_SCALAR uint32_t *ep = (const NSK_SCALAR uint32_t *)(ka + NSK_TABW_COLD_OFFSET + offsetof(TabwCold, tab) +
+                                                                              offsetof(SegTable, e) + sizeof(SegEntry) * (size_t)sidx);
+                uint32_t ew[sizeof(SegEntry) / 4];
+#pragma unroll
+                for (int j = 0; j < (int)(sizeof(SegEntry) / 4); j++) ew[j] = ep[j];
+                __builtin_memcpy(&en, ew, sizeof(SegEntry));
+            }
+            DevGraph<signed char> gf = gh;                              // (the fall-back's arrays: read here, not kept)
+            gf.adj = cold->g.adj; gf.seg_aff = cold->g.seg_aff; gf.sink = cold->g.sink;
+            const int t0q = 4 * Q - tstart - lead;
+            const uint32_t qb = quad_block((uint32_t)(p0 + lane));
+            const u32x4 ra = philox4x32(k0, k1, qb, 2u, s0, s1);
+            u32x4 rb = {0u, 0u, 0u, 0u};
+            bool have_b = false;
+#pragma unroll 1
+            for (int t = 0; t < 4; t++)
+                tab_tiles<signed char, NCH, 1, MODE == 2>(gf, en, t0q + t, t, lane, MODE == 1 ? 1 : 0, ra, rb, have_b, qb, k0, k1, s0, s1, flagged);
+        }
+    }
+}
+// The kernel argument layout both wide kernels rely on (NSK_TABW_COLD_OFFSET): the hot arguments, then TabwCold
+struct TabwArgs { signed char *val; int d_cnt, d_wide, d_ztab, ts1; uint32_t ntl0; int pos00; uint32_t woff0, zoff0, ntiles_nseg, zmask0_wpx;
+                  const unsigned long long *sweep_base; TabwCold cold; };
+static_assert(offsetof(TabwArgs, cold) == NSK_TABW_COLD_OFFSET, "NSK_TABW_COLD_OFFSET: the hot arguments changed");
+// One class of EVERY chain of a handle (nsk_set_chains) in one launch, MODE 0 / 1.  The launch is the chains' single-chain
+// grids one after another -- per_chain = front workgroups + main grid, both whole rounds of XCDs, so every chain keeps the
+// single-chain kernel's XCD eighths -- and the hot arguments are chain 0's.  The chains' value arrays and position tallies
+// lie in one slab (nsk_internal.h): chain r's value array starts 2 r d_cnt 256-byte units after chain 0's (its position
+// tally d_cnt units after its values, as for chain 0), so no argument is added: chain r moves `val` by that much and the
+// offsets of the shared arrays (draw tables, quad descriptors) back by as much.  Chain r draws with key word 1 XOR r.
+template <int NCH, int MODE>
+__global__ __launch_bounds__(NSK_BLOCK) NSK_TABW_ATTR void k_gibbs_seg_tabw_chains(NSK_TABW_HOT, TabwCold cold_unused) {
+    (void)cold_unused;
+    const uint32_t wpx = (zmask0_wpx >> 8) & 0xFFFFu, nfront = zmask0_wpx >> 24;
+    const uint32_t per_chain = nfront + 8u * (wpx / (NSK_BLOCK / 64));
+    const uint32_t chain = blockIdx.x / per_chain;
+    const int shift = 2 * (int)chain * d_cnt;                           // 256-byte units
+    seg_tabw_chains_body<NCH, MODE>(val + (long long)shift * 256, d_cnt, d_wide - shift, d_ztab - shift, ts1, ntl0, pos00, woff0, zoff0,
+                                   ntiles_nseg, zmask0_wpx, sweep_base, blockIdx.x - chain * per_chain, chain);
 }
 
 // The fused-exchange flavour of tab_tiles / k_gibbs_seg_tab below (P2P = true is the only instantiation; buffer

@@ -24,6 +24,27 @@ from . import _lib
 from .timer import Timer
 
 
+def _all_copies(var_copy):
+    return isinstance(var_copy, str) and var_copy == "all"
+
+
+def split_rhat(half_counts, n):
+    """Split-R-hat per tally slot: ``half_counts`` (M, ncount) holds each half-chain's tally over ``n``
+    sweeps (M = 2 x chains).  With half-chain means p_j: B = n / (M - 1) sum (p_j - mean p)^2,
+    W = mean(n / (n - 1) p_j (1 - p_j)), R-hat = sqrt(((n - 1) / n W + B / n) / W); NaN where W = 0 or n < 2."""
+    hc = np.asarray(half_counts, np.float64)
+    out = np.full(hc.shape[1] if hc.ndim == 2 else 0, np.nan)
+    m = hc.shape[0] if hc.ndim == 2 else 0
+    if n < 2 or m < 2:
+        return out
+    p = hc / float(n)
+    b = n / (m - 1.0) * ((p - p.mean(axis=0)) ** 2).sum(axis=0)
+    w = (n / (n - 1.0) * p * (1.0 - p)).mean(axis=0)
+    ok = w > 0
+    out[ok] = np.sqrt(((n - 1.0) / n * w[ok] + b[ok] / n) / w[ok])
+    return out
+
+
 class FactorGraph(object):
     """A factor graph resident on one MI355X.
 
@@ -69,6 +90,9 @@ class FactorGraph(object):
         self.threads = workers          # accepted for compatibility; the GPU ignores it
         self.threadpool = None
         self.marginals = np.zeros(ncount)
+        # var_copy="all" (one chain per row of var_value): each chain's own tally, and split-R-hat per tally slot
+        self.chain_count = np.zeros((var_copies, ncount), np.int64)
+        self.rhat = np.full(ncount, np.nan)
         self.inference_epoch_time = 0.0
         self.inference_total_time = 0.0
         self.learning_epoch_time = 0.0
@@ -213,6 +237,8 @@ class FactorGraph(object):
         return out
 
     def _push(self, var_copy, weight_copy):
+        if self._handle is not None and _lib.lib().nsk_get_chains(self._handle) != 1:
+            _lib.check(_lib.lib().nsk_set_chains(self._handle, 1))      # back from var_copy="all": chain 0 only
         vv = _lib.as_c(self.var_value[var_copy], np.int64)
         ve = _lib.as_c(self.var_value_evid[var_copy], np.int64)
         wv = _lib.as_c(self.weight_value[weight_copy], np.float64)
@@ -244,6 +270,7 @@ class FactorGraph(object):
     # ------------------------------------------------------------------ reference API
     def clear(self):
         self.count[:] = 0
+        self.chain_count[:] = 0
 
     def getWeights(self, weight_copy=0):
         return self.weight_value[weight_copy][:]
@@ -278,19 +305,29 @@ class FactorGraph(object):
                                                int(bool(burnin))))
 
     def burnIn(self, epochs, sample_evidence, diagnostics=False, var_copy=0, weight_copy=0):
-        """factorgraph.py:129-143 -- `epochs` sweeps that do not touch the tally."""
+        """factorgraph.py:129-143 -- `epochs` sweeps that do not touch the tally.  ``var_copy="all"``:
+        every row of ``var_value`` is one chain, all swept by the same calls (nsk_set_chains)."""
         if diagnostics:
             print("FACTOR " + str(self.fid) + ": STARTED BURN-IN...")
         if epochs > 0:
-            self._push(var_copy, weight_copy)
-            self._sweep(epochs, sample_evidence, True)
-            self._pull(var_copy, weight_copy, weights=False, count=False)
+            if _all_copies(var_copy):
+                self._push_chains(weight_copy, count=False)
+                self._sweep(epochs, sample_evidence, True)
+                self._pull_chains(count=False)
+            else:
+                self._push(var_copy, weight_copy)
+                self._sweep(epochs, sample_evidence, True)
+                self._pull(var_copy, weight_copy, weights=False, count=False)
         if diagnostics:
             print("FACTOR " + str(self.fid) + ": DONE WITH BURN-IN")
 
     def inference(self, burnin_epochs, epochs, sample_evidence=False, diagnostics=False,
                   var_copy=0, weight_copy=0):
-        """factorgraph.py:145-175."""
+        """factorgraph.py:145-175.  ``var_copy="all"``: one chain per row of ``var_value``; ``count``
+        grows by the sum of the chains' tallies, ``chain_count`` keeps them apart, ``marginals`` pools
+        them and ``rhat`` is the split-R-hat of every tally slot over this call's sweeps."""
+        if _all_copies(var_copy):
+            return self._inference_chains(burnin_epochs, epochs, sample_evidence, diagnostics, weight_copy)
         if burnin_epochs > 0:
             self.burnIn(burnin_epochs, sample_evidence, diagnostics=diagnostics,
                         var_copy=var_copy, weight_copy=weight_copy)
@@ -321,10 +358,95 @@ class FactorGraph(object):
         if diagnostics:
             self.diagnostics(epochs)
 
+    # ------------------------------------------------------------------ several chains (var_copy="all")
+    def _chains(self):
+        """Point the handle at one chain per row of ``var_value``; returns the number of chains."""
+        nchains = int(self.var_value.shape[0])
+        L, h = _lib.lib(), self._engine()
+        if L.nsk_get_chains(h) != nchains:
+            _lib.check(L.nsk_set_chains(h, nchains))
+        ncount = len(self.count)
+        if not (isinstance(self.chain_count, np.ndarray) and self.chain_count.shape == (nchains, ncount)):
+            self.chain_count = np.zeros((nchains, ncount), np.int64)
+        return nchains
+
+    def _push_chains(self, weight_copy, count=True):
+        nchains = self._chains()
+        L, h = _lib.lib(), self._engine()
+        ve = _lib.as_c(self.var_value_evid[0], np.int64)
+        wv = _lib.as_c(self.weight_value[weight_copy], np.float64)
+        _lib.check(L.nsk_state_upload(h, None, _lib.ptr(ve), _lib.ptr(wv), None))
+        vv = _lib.as_c(self.var_value, np.int64)
+        cc = _lib.as_c(self.chain_count, np.int64) if count else None
+        _lib.check(L.nsk_chains_upload(h, _lib.ptr(vv), _lib.ptr(cc)))
+        return nchains
+
+    def _pull_chains(self, values=True, count=True):
+        """Download every chain's values into ``var_value`` (and returns the per-chain tallies)."""
+        L, h = _lib.lib(), self._engine()
+        vv = np.empty(self.var_value.shape, np.int64) if values else None
+        cc = np.empty(self.chain_count.shape, np.int64) if count else None
+        _lib.check(L.nsk_chains_download(h, _lib.ptr(vv), _lib.ptr(cc)))
+        if values:
+            self.var_value[:] = vv
+        return cc
+
+    def _inference_chains(self, burnin_epochs, epochs, sample_evidence, diagnostics, weight_copy):
+        nchains = self._chains()
+        if burnin_epochs > 0:
+            self.burnIn(burnin_epochs, sample_evidence, diagnostics=diagnostics, var_copy="all",
+                        weight_copy=weight_copy)
+        if diagnostics:
+            print("FACTOR " + str(self.fid) + ": STARTED INFERENCE")
+        self.rhat = np.full(len(self.count), np.nan)
+        if epochs > 0:
+            L, h = _lib.lib(), self._engine()
+            self._push_chains(weight_copy)
+            # split-R-hat: the per-chain tallies after h and after 2 h sweeps (h = epochs // 2) give 2 R half-chains
+            half = epochs // 2
+            parts = [half, half, epochs - 2 * half] if half >= 2 else [epochs]
+            snaps = [self.chain_count.copy()]
+            ep = 0
+            for k, n in enumerate(parts):
+                if n == 0:
+                    continue
+                if diagnostics:
+                    for _ in range(n):
+                        with Timer() as timer:
+                            self._sweep(1, sample_evidence, False)
+                            _lib.check(L.nsk_synchronize(h))
+                        self.inference_epoch_time = timer.interval
+                        self.inference_total_time += timer.interval
+                        print('Inference epoch #%d took %.03f sec.' % (ep, self.inference_epoch_time))
+                        ep += 1
+                else:
+                    with Timer() as timer:
+                        self._sweep(n, sample_evidence, False)
+                        _lib.check(L.nsk_synchronize(h))
+                    self.inference_epoch_time = timer.interval / n
+                    self.inference_total_time += timer.interval
+                if k < 2 and len(parts) > 1:
+                    snaps.append(self._pull_chains(values=False))
+            cc = self._pull_chains()
+            self.count += (cc - snaps[0]).sum(axis=0)
+            self.chain_count[:] = cc
+            if len(snaps) == 3:
+                self.rhat = split_rhat(np.concatenate([snaps[1] - snaps[0], snaps[2] - snaps[1]]), half)
+        if diagnostics:
+            print("FACTOR " + str(self.fid) + ": DONE WITH INFERENCE")
+        if epochs != 0:
+            self.marginals = self.count / float(epochs * nchains)
+        if diagnostics:
+            self.diagnostics(epochs * nchains)
+            finite = self.rhat[np.isfinite(self.rhat)]
+            print("Largest split R-hat over %d chains: %s" % (nchains, "%.4f" % finite.max() if len(finite) else "nan"))
+
     def learn(self, burnin_epochs, epochs, stepsize, decay, regularization, reg_param, truncation,
               diagnostics=False, verbose=False, learn_non_evidence=False, var_copy=0,
               weight_copy=0):
         """factorgraph.py:177-208."""
+        if _all_copies(var_copy):
+            raise ValueError('learning samples one chain: var_copy="all" is for burnIn / inference only')
         if burnin_epochs > 0:
             self.burnIn(burnin_epochs, True, diagnostics=diagnostics, var_copy=var_copy,
                         weight_copy=weight_copy)

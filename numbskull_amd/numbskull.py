@@ -7,7 +7,7 @@ class ``NumbSkull`` (152-391) with ``loadFactorGraphRaw`` / ``loadFactorGraph`` 
 (394-423).  Sampling and learning themselves run on the MI355X through
 :class:`numbskull_amd.factorgraph.FactorGraph`.
 
-Engine options that the reference does not have (``device``, ``seed``, ``scan``,
+Engine options that the reference does not have (``device``, ``seed``, ``scan``, ``chains``,
 ``head_by_vid``) live in ``engine_arguments`` so that the two reference tables keep their exact
 shape.
 """
@@ -83,6 +83,9 @@ engine_arguments = [
     _opt(('--seed',), 'seed', 0, int, 'SEED', 'sampler seed (Philox key / MT19937 seed)'),
     _opt(('--scan',), 'scan', 'chromatic', str, 'SCAN',
          '"chromatic" (parallel colour classes) or "sequential" (reference trajectory, slow)'),
+    _opt(('--chains',), 'chains', 1, int, 'CHAINS',
+         'independent inference chains swept together (chain r keys its generator with seed ^ (r << 32)); '
+         'marginals pool them and a split-R-hat is reported'),
     _opt(('--learn_cap',), 'learn_cap', 0.5, float, 'LEARN_CAP',
          'chromatic learning: cap on (visits of a weight in one colour class) x stepsize; 0 = off'),
 ]
@@ -111,6 +114,8 @@ class NumbSkull(object):
     # ------------------------------------------------------------------ graph construction
     def _new_graph(self, weight, variable, factor, fmap, vmap, factor_index, var_copies,
                    weight_copies, **extra):
+        if self.chains > 1:
+            var_copies = max(var_copies, self.chains)
         fg = FactorGraph(weight, variable, factor, fmap, vmap, factor_index, var_copies,
                          weight_copies, len(self.factorGraphs), self.nthreads,
                          device=self.device, seed=self.seed, scan=self.scan, learn_cap=self.learn_cap,
@@ -232,11 +237,12 @@ class NumbSkull(object):
     def inference(self, fgID=0, out=True):
         """Burn-in + inference epochs, then the marginals dump (numbskull.py:359-371)."""
         fg = self.factorGraphs[fgID]
+        chains = self.chains > 1
         fg.inference(self.burn_in, self.n_inference_epoch, sample_evidence=self.sample_evidence,
-                     diagnostics=not self.quiet)
+                     diagnostics=not self.quiet, var_copy="all" if chains else 0)
         if out:
             fg.dump_probabilities(os.path.join(self.output_dir, "inference_result.out.text"),
-                                  self.n_inference_epoch)
+                                  self.n_inference_epoch * (fg.var_value.shape[0] if chains else 1))
 
     def learning(self, fgID=0, out=True):
         """Burn-in + learning epochs, then the weights dump (numbskull.py:373-391)."""
