@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Benchmark of the Gibbs-sweep hot path on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload NAME] [--dump-outputs DIR]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload NAME] [--dump-outputs DIR] [--full]
 
 A "step" is one sweep of the hot path over every variable of the workload graph (one epoch of
 gibbsthread, numbskull/inference.py:10-33; for the *_learn workloads one epoch of learnthread,
@@ -19,10 +19,17 @@ Prints ONE JSON line (rank 0): metric = variable-updates/sec over all GPUs, plus
                bytes") / average launch duration measured with HIP events on the library's
                stream; the SURVEY.md section 8d CSR-model figure rides along as
                alg_bytes_per_update_csr
+A plain run does only what that line needs: set-up, warm-up, the timed call, --dump-outputs, the
+line.  --full adds what takes work of its own (--no-cpu-baseline / --no-extra leave parts out):
   cpu_baseline the CPU restatement of the reference algorithm (oracle/, Hogwild threads like the
                reference's run_pool) timed on this node's host cores on a bounded sample
   parity       invariants of the state after the timed region (tally bounds, mean marginal) and,
-               with the CPU baseline, the nearest-neighbour agreement statistic of both runs.
+               with the CPU baseline, the nearest-neighbour agreement statistic of both runs; a
+               broken state exits 3 (a plain run prints parity = null)
+  also         the default workload's secondary lines: one GPU, the 1M and 40M grids, 10M learning
+               and config #5's LR graphs; N GPUs, the 100M grid
+  roofline.stream_copy_GBs  the achievable HBM copy rate, measured in the same run
+  phases_us    N > 1: per-phase timings of rank 0's shard.
 
 N > 1: one rank per GPU (torch.distributed.run; started by this script as a child process when
 it is not already running under it), the grid range-partitioned by variable id with the
@@ -215,9 +222,13 @@ def cpu_baseline(fg, learning, budget_s=20.0, grid=None, head_by_vid=False, lr=(
             "_agreement": agree, "_mean_marginal": mean_marg, "_sweeps": total_n}
 
 
-def state_checks(fg, info, tallied_sweeps, grid, learning):
-    """Cheap invariants of the device state after the timed region (downloaded once)."""
+def download_state(fg):
+    """The device state (values, weights, tallies) into fg's host arrays, once after the timed region."""
     fg._pull(0, 0, values=True, weights=True, count=True)
+
+
+def state_checks(fg, info, tallied_sweeps, grid, learning):
+    """Cheap invariants of the state after the timed region, read from the host arrays download_state() filled."""
     own = fg.own_range if fg.own_range is not None else (0, len(fg.variable))
     v = fg.var_value[0][own[0]:own[1]]
     card = fg.variable["cardinality"][own[0]:own[1]]
@@ -262,7 +273,7 @@ def dump_outputs(directory, fg, learning, tallied_sweeps, dist, rank, world):
     (var_value_evid, float32) and the weights (weight_value, float64).  An output of more than DUMP_SAMPLE elements
     is written at dump_positions() of it (at most 32 MB in all).  N ranks: the owned variables of every rank in
     rank order (= global id order of the range partition); the weights, which every rank holds, from rank 0.
-    Collective when world > 1; reads the host arrays state_checks() downloaded."""
+    Collective when world > 1; reads the host arrays download_state() filled."""
     lo, hi = fg.own_range if fg.own_range is not None else (0, len(fg.variable))
     owned = [("var_value", fg.var_value[0][lo:hi], np.float32)]
     if learning:
@@ -359,6 +370,7 @@ def side_run(name, seed, steps, warmup):
     run(warmup, 1)                       # warm-up = burn-in: the tallies start after the transient
     blocks = timed_blocks(run, torch.cuda.synchronize, L, h, steps, REPEATS)
     dt, ms, nl = median_block(blocks)
+    download_state(fg)
     checks = state_checks(fg, info, steps * REPEATS, (rows, cols) if not is_lr else None, learning)
     clipped = fg.info()["learn_clipped"] if learning else None
     fg.close()
@@ -604,8 +616,10 @@ def main():
     ap.add_argument("--steps", type=int, default=200)
     ap.add_argument("--warmup", type=int, default=20)
     ap.add_argument("--workload", default="ising10m", choices=sorted(WORKLOADS))
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extra", action="store_true", help="skip the secondary 1M-grid measurement")
+    ap.add_argument("--full", action="store_true", help="also the CPU baseline, the state checks, the secondary "
+                    "workloads, the stream-copy rate and (N > 1) the per-phase timings")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baseline")
+    ap.add_argument("--no-extra", action="store_true", help="--full without the secondary workloads")
     ap.add_argument("--seed", type=int, default=20240601)
     ap.add_argument("--dump-outputs", metavar="DIR", help="write what the timed call computed as DIR/<name>.npy")
     args = ap.parse_args()
@@ -729,30 +743,34 @@ def main():
             self.value = v
     ms_ev, launches = _V(ms_ev_v), _V(launches_v)
 
+    if args.full or args.dump_outputs:
+        download_state(fg)
     # invariants of the state the timed sweeps left behind (every rank checks its own shard)
-    checks = state_checks(fg, info, tallied, (rows, cols) if is_grid else None, learning)
+    checks = state_checks(fg, info, tallied, (rows, cols) if is_grid else None, learning) if args.full else None
     if args.dump_outputs:
         dump_outputs(args.dump_outputs, fg, learning, tallied, dist, rank, world)
-    # hard invariants decide the exit code; the statistical ones (mean marginal, agreement with the
-    # CPU chain) are always reported but only count once the chain has been burnt in (>= 10 warm-up
-    # sweeps): a 2-sweep warm-up of a profiling pass still sits in the transient from the all-zero
-    # state -- the line then says parity.statistics = "skipped (warm-up < 10 sweeps)" instead of passing
-    # them silently
-    burnt_in = args.warmup + burn_extra >= 10
-    ok_local = all(bool(x) for k, x in checks.items()
-                   if k.endswith("_in_bounds") or k in ("values_in_domain", "weights_finite")
-                   or (burnt_in and k.endswith("_ok")))
-    checks["statistics_count"] = burnt_in
-    checks["statistics"] = "counted" if burnt_in else "skipped (warm-up < 10 sweeps)"
-    checks["burn_in_sweeps"] = args.warmup + burn_extra      # untimed burn-in sweeps (besides the untimed call of K)
-    if world > 1:
-        t = torch.tensor([1.0 if ok_local else 0.0], dtype=torch.float64, device="cuda")
-        dist.all_reduce(t, op=dist.ReduceOp.MIN)
-        checks["all_ranks_ok"] = bool(t.item() > 0.5)
-        ok_local = checks["all_ranks_ok"]
+    ok_local = True
+    if args.full:
+        # hard invariants decide the exit code; the statistical ones (mean marginal, agreement with the
+        # CPU chain) are always reported but only count once the chain has been burnt in (>= 10 warm-up
+        # sweeps): a 2-sweep warm-up of a profiling pass still sits in the transient from the all-zero
+        # state -- the line then says parity.statistics = "skipped (warm-up < 10 sweeps)" instead of passing
+        # them silently
+        burnt_in = args.warmup + burn_extra >= 10
+        ok_local = all(bool(x) for k, x in checks.items()
+                       if k.endswith("_in_bounds") or k in ("values_in_domain", "weights_finite")
+                       or (burnt_in and k.endswith("_ok")))
+        checks["statistics_count"] = burnt_in
+        checks["statistics"] = "counted" if burnt_in else "skipped (warm-up < 10 sweeps)"
+        checks["burn_in_sweeps"] = args.warmup + burn_extra      # untimed burn-in sweeps (besides the untimed call of K)
+        if world > 1:
+            t = torch.tensor([1.0 if ok_local else 0.0], dtype=torch.float64, device="cuda")
+            dist.all_reduce(t, op=dist.ReduceOp.MIN)
+            checks["all_ranks_ok"] = bool(t.item() > 0.5)
+            ok_local = checks["all_ranks_ok"]
 
     phases = None
-    if world > 1 and (not learning or sampler.p2p):      # per-phase timings of one shard's sweep (diagnostic)
+    if args.full and world > 1 and (not learning or sampler.p2p):      # per-phase timings of one shard's sweep (diagnostic)
         phases = sampler.phase_timings(20, learn=(lr[0], lr[2], lr[3], lr[4]) if learning else None)
         sampler.check()
         phases["exchange_path"] = "peer-to-peer writes + flags" if sampler.p2p else (
@@ -760,14 +778,14 @@ def main():
     # N ranks on the metric config: a second line that is not bound by launch latency -- the 100M grid (12.5M cells per
     # rank at N = 8; a 1.25M-cell shard of the 10M grid cannot scale below one launch floor per class)
     multi_also = None
-    if world > 1 and args.workload == "ising10m" and not args.no_extra:
+    if args.full and world > 1 and args.workload == "ising10m" and not args.no_extra:
         multi_also = multi_side_run("ising100m", args, dist, torch, rank, world, local_rank)
     ladder = None
     if world > 1:                       # every rank's rung of the exchange ladder (numbskull_amd/distributed.py)
         ladder = [None] * world
         dist.all_gather_object(ladder, sampler.ladder)
     copy_gbs = None
-    if rank == 0:
+    if rank == 0 and args.full:
         cg = C.c_double()
         if L.nsk_selftest_stream(local_rank, 4 << 30, 64, 5, C.byref(cg)) == 0:
             copy_gbs = cg.value           # achievable HBM copy rate on this GPU, same run (4 GiB,
@@ -850,7 +868,7 @@ def main():
             out["learn_clipped"] = fg.info()["learn_clipped"]
             out["learn_hyper"] = {"step": lr[0], "regularization": lr[2], "reg_param": lr[3],
                                   "learn_cap": info["learn_cap"]}
-        if not args.no_cpu_baseline and world == 1:
+        if args.full and not args.no_cpu_baseline and world == 1:
             cb = cpu_baseline(fg, learning, grid=(rows, cols) if is_grid else None,
                               head_by_vid=args.workload.startswith("lr"), lr=lr)
             agree, mm = cb.pop("_agreement"), cb.pop("_mean_marginal")
@@ -865,7 +883,7 @@ def main():
                 checks["edge_agreement_ok"] = bool(checks["edge_agreement_diff"] < 1e-3)
                 checks["mean_marginal_cpu"] = mm
                 ok_local = ok_local and (checks["edge_agreement_ok"] or not burnt_in)
-        if world == 1 and args.workload == "ising10m" and not args.no_extra:
+        if args.full and world == 1 and args.workload == "ising10m" and not args.no_extra:
             out["also"] = {"ising1m": side_run("ising1m", args.seed, 400, 100),
                            "ising10m_learn": side_run("ising10m_learn", args.seed, 100, 20),
                            "ising40m": side_run("ising40m", args.seed, 50, 10),
@@ -883,7 +901,8 @@ def main():
                                           "(stream_fits_infinity_cache); the 100M grid (--workload ising100m) is the one beyond it")
         if multi_also is not None:
             out["also"] = {"ising100m": multi_also}
-        checks["ok"] = bool(ok_local)
+        if checks is not None:
+            checks["ok"] = bool(ok_local)
         # the counter figures above (roofline.traffic / .issue, also.*.traffic_per_launch) are read from profiles/, not
         # measured by this run: say so at top level when they were collected at another library
         out["traffic_stale"] = bool(profiles_stale())
