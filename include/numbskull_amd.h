@@ -112,6 +112,35 @@ int nsk_get_chains(nsk_graph *g);
 int nsk_chains_upload(nsk_graph *g, const int64_t *var_value, const int64_t *count);
 int nsk_chains_download(nsk_graph *g, int64_t *var_value, int64_t *count);
 
+/* Sample traces (FactorGraph.sample): thinned joint samples recorded on the device.  While a trace is set up, one
+ * launch behind every `every`-th TALLIED sweep of nsk_gibbs_sweeps (burnin = 0) appends a ROW: the values of the
+ * traced variables in every chain of the handle, as they are after that sweep.  Burn-in sweeps are neither counted
+ * nor recorded; the count of tallied sweeps since the last row carries over from call to call.  Nothing waits on
+ * the host, and a traced call leaves exactly the values and tallies the same call leaves without a trace.  Rows are
+ * kept bit-packed on the device when every traced variable has cardinality 2, else as one element of value_bytes
+ * per column.
+ * nsk_trace_setup: vids = the caller's variable ids (sampled or evidence, any order, repeats allowed), NULL = all
+ * nvar variables; an id outside [0, nvar) is NSK_E_INDEX; every >= 1 and capacity >= 1 rows, else NSK_E_INVALID;
+ * nvids >= 1 with a list; NSK_E_NOMEM when capacity x chains rows do not fit.  capacity = 0 tears the trace down and
+ * frees it; setting up again replaces the trace (a call refused for its arguments leaves the old one; one that fails
+ * for lack of memory leaves none).  NSK_E_INVALID on an own_range / NSK_FLAG_PARTITION handle and on one that exchanges
+ * a boundary.
+ * nsk_trace_rows: rows recorded so far, the capacity (0: no trace), 1 / 0 for bit-packed / plain rows (any may be NULL).
+ * nsk_trace_download: synchronises, then writes rows first_row .. first_row + nrows - 1 as nrows x chains x nvids
+ * elements of value_bytes (int8_t or int32_t, as NSK_BUF_VALUE) in the caller's column order, unpacked;
+ * sweep_index[i] (may be NULL) = the handle's sweep index after which row first_row + i was taken.  Rows beyond
+ * those recorded: NSK_E_INVALID.
+ * nsk_trace_clear: rows and the count of sweeps since the last row back to 0; the buffer stays.
+ * A handle with a trace refuses, before it enqueues anything: a nsk_gibbs_sweeps call that needs more rows than
+ * are left (NSK_E_RANGE; state and sweeps_done untouched), sweeps while values lie outside their domains and the
+ * rows are bit-packed (NSK_E_RANGE), and with NSK_E_INVALID nsk_learn_sweeps, sweeps under the sequential scan,
+ * the exchange, RCCL and peer-to-peer entry points, and nsk_set_chains with another count.  nsk_profile_* keeps
+ * counting sweep-kernel launches only. */
+int nsk_trace_setup(nsk_graph *g, const int64_t *vids, int64_t nvids, int64_t every, int64_t capacity);
+int nsk_trace_rows(nsk_graph *g, int64_t *rows, int64_t *capacity, int64_t *packed);
+int nsk_trace_download(nsk_graph *g, int64_t first_row, int64_t nrows, void *out, int64_t *sweep_index);
+int nsk_trace_clear(nsk_graph *g);
+
 /* RNG: the chromatic scan draws from Philox4x32-10 keyed by `seed`.  A variable's generator id is
  * its position in the compiled layout (nsk_graph_get_layout), so samples are a function of the seed
  * AND the layout the library chose (device, flags and diagnostic switches being equal, a graph

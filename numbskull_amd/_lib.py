@@ -29,6 +29,7 @@ SYMBOLS = (
     "nsk_learn_sweeps_exchange", "nsk_pf_setup", "nsk_p2p_setup", "nsk_p2p_export", "nsk_p2p_import", "nsk_p2p_import_local",
     "nsk_gibbs_sweeps_p2p", "nsk_learn_sweeps_p2p", "nsk_p2p_exchange", "nsk_p2p_selftest", "nsk_p2p_fuse", "nsk_p2p_check", "nsk_p2p_reset", "nsk_profile_mark", "nsk_profile_read", "nsk_graph_order", "nsk_comm_volume", "nsk_graph_partition", "nsk_compute_var_map", "nsk_state_layout", "nsk_parse_factors", "nsk_parse_domains", "nsk_write_probabilities",
     "nsk_set_chains", "nsk_get_chains", "nsk_chains_upload", "nsk_chains_download",
+    "nsk_trace_setup", "nsk_trace_rows", "nsk_trace_download", "nsk_trace_clear",
     "nsk_selftest_exp", "nsk_selftest_philox", "nsk_selftest_stream", "nsk_device_count", "nsk_last_error", "nsk_version",
 )
 
@@ -94,6 +95,10 @@ def lib():
         L.nsk_get_chains.argtypes = [C.c_void_p]
         L.nsk_chains_upload.argtypes = [C.c_void_p] * 3
         L.nsk_chains_download.argtypes = [C.c_void_p] * 3
+        L.nsk_trace_setup.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int64]
+        L.nsk_trace_rows.argtypes = [C.c_void_p] + [C.POINTER(C.c_int64)] * 3
+        L.nsk_trace_download.argtypes = [C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p]
+        L.nsk_trace_clear.argtypes = [C.c_void_p]
         L.nsk_graph_create.argtypes = [C.POINTER(GraphDesc), C.POINTER(C.c_void_p)]
         L.nsk_graph_destroy.argtypes = [C.c_void_p]
         L.nsk_graph_get_info.argtypes = [C.c_void_p, C.POINTER(GraphInfo)]

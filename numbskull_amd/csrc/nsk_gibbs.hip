@@ -480,7 +480,9 @@ static int graph_build(nsk_graph *g, int sample_evidence, int burnin, bool p2p, 
     return NSK_OK;
 }
 
-int nsk_gibbs_run(nsk_graph *g, int64_t nsweeps, int sample_evidence, int burnin, bool p2p) {
+// keep_packed: a run of a traced call that another run of the same call follows (traced_sweeps) -- a packed tally stays in
+// the value bytes when the run ends; the next run decides pack_now from the same handle state and carries packed_sweeps on
+int nsk_gibbs_run(nsk_graph *g, int64_t nsweeps, int sample_evidence, int burnin, bool p2p, bool keep_packed) {
     int64_t left = nsweeps;
     // A shard whose sweep is table launches only exchanges its boundary INSIDE them (nsk_internal.h p2p_fused): the
     // ghosts the first sweep reads are packed into the receive block here, the wait for the peers' last flags and
@@ -510,8 +512,9 @@ int nsk_gibbs_run(nsk_graph *g, int64_t nsweeps, int sample_evidence, int burnin
         for (const auto &v : g->seg_plans) for (const NskSegPlan &pl : v) all_wide = all_wide && pl.kind >= 8 && pl.tab.wide;
         g->pack_now = all_wide;
     }
-    struct Done { nsk_graph *g; bool fuse; ~Done() { g->p2p_fused_now = false; if (fuse) g->p2p_close_pending = true;
-                                                      (void)nsk_unpack_tally(g); g->pack_now = false; } } done{g, fuse};
+    struct Done { nsk_graph *g; bool fuse, keep; ~Done() { g->p2p_fused_now = false; if (fuse) g->p2p_close_pending = true;
+                                                            if (!keep) (void)nsk_unpack_tally(g);
+                                                            g->pack_now = false; } } done{g, fuse, keep_packed};
     if (left >= NSK_GRAPH_SWEEPS && graph_eligible(g, p2p)) {
         // the plans of this (sample_evidence, tables) combination and the tables of the current weights (what an eager
         // sweep does in front of its launches; an eager sweep in front of the replays cost a 400-sweep call of the 1M grid
@@ -581,11 +584,47 @@ static int chains_run(nsk_graph *g, int64_t nsweeps, int sample_evidence, int bu
     return NSK_OK;
 }
 
+// (keep_packed: nsk_gibbs_run; only a one-chain handle keeps its tally in the value bytes)
+static int sweeps_run(nsk_graph *g, int64_t nsweeps, int sample_evidence, int burnin, bool keep_packed = false) {
+    if (g->nchains > 1) return chains_run(g, nsweeps, sample_evidence, burnin);
+    return nsk_gibbs_run(g, nsweeps, sample_evidence, burnin, false, keep_packed);
+}
+
+// Tallied sweeps of a handle that records a sample trace (nsk_trace_setup): the call is split into runs that end where a
+// row is due, every run goes through the path an untraced call takes (captured sequences and batched chain launches
+// included; chains that are not batched go chain after chain through the RUN), and one record launch follows it on
+// the stream.  A sweep's samples depend on the seed, the layout and the sweep index only, so the split call leaves the
+// values and tallies of the unsplit one.  A handle that keeps its tally in the value bytes (pack_now) stays packed
+// between the runs of one call: bit 0 is the value either way, and the record kernels read nothing else of a packed row.
+// Everything that can refuse does so before the first sweep is enqueued.
+static int traced_sweeps(nsk_graph *g, int64_t nsweeps, int sample_evidence) {
+    NskTrace &t = g->trace;
+    if (t.chains != g->nchains) return fail(NSK_E_INVALID, "nsk_gibbs_sweeps: the chain count changed under the sample trace");
+    if (t.packed && !g->values_regular)
+        return fail(NSK_E_RANGE, "nsk_gibbs_sweeps: a value lies outside its domain and the sample trace keeps one bit per binary variable");
+    if (t.rows + (t.phase + nsweeps) / t.every > t.capacity)
+        return fail(NSK_E_RANGE, "nsk_gibbs_sweeps: the call needs more rows than the sample trace has left");
+    for (int64_t left = nsweeps; left > 0;) {
+        const int64_t run = std::min(left, t.every - t.phase);
+        int rc = sweeps_run(g, run, sample_evidence, 0, t.packed && left > run);     // (the call's last run unpacks)
+        if (!rc) {
+            left -= run;
+            t.phase += run;
+            if (t.phase == t.every) { rc = nsk_trace_record(g); t.phase = 0; }
+        }
+        if (rc) { (void)nsk_unpack_tally(g); return rc; }
+    }
+    return NSK_OK;
+}
+
 extern "C" int nsk_gibbs_sweeps(nsk_graph *g, int64_t nsweeps, int sample_evidence, int burnin) {
     if (!g) return fail(NSK_E_INVALID, "null graph");
     if (nsweeps < 0 || nsweeps > INT32_MAX) return fail(NSK_E_INVALID, "bad sweep count");
     if (nsweeps == 0) return NSK_OK;
     HIPCHECK(hipSetDevice(g->device));
-    if (g->nchains > 1) return chains_run(g, nsweeps, sample_evidence, burnin);
-    return nsk_gibbs_run(g, nsweeps, sample_evidence, burnin, false);
+    if (g->trace.capacity > 0 && g->scan != NSK_SCAN_CHROMATIC)
+        return fail(NSK_E_INVALID, "nsk_gibbs_sweeps: the handle records a sample trace (nsk_trace_setup), which the sequential scan "
+                                   "does not serve; tear it down first (capacity = 0)");
+    if (g->trace.capacity > 0 && !burnin) return traced_sweeps(g, nsweeps, sample_evidence);
+    return sweeps_run(g, nsweeps, sample_evidence, burnin);
 }

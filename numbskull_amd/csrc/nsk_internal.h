@@ -33,8 +33,27 @@ struct NskSegPlan { int kind, nch; nsk::SegTable tab;         // one prepared se
 // wide kernel takes it, and its quads that are not wide ones
 struct NskLearnWidePlan { int key = -1; bool wide = false; int vt = 0; nsk::SegTable tab; uint32_t nrest = 0, rest[NSK_TABW_REST_MAX] = {}; };
 
+// Sample trace (nsk_trace_setup): thinned joint samples recorded on the device.  After every `every`-th tallied sweep
+// one k_trace_record_* launch appends a row: for every chain the values of the traced variables, in DEVICE column order
+// (sorted by internal id; every internal id when cols == nullptr, "all variables") -- bit-packed, ceil(ndev / 64) words a
+// chain, when every traced variable is binary, one element of vbytes a column otherwise.  pos[] undoes the order on download.
+struct NskTrace {
+    void *buf = nullptr;               // capacity x chains x row_bytes
+    int32_t *cols = nullptr;           // device column -> internal id (nullptr: the identity over [0, nid))
+    int64_t ncols = 0, ndev = 0;       // the caller's columns; the device's
+    int64_t every = 0, capacity = 0;   // capacity == 0: no trace set up
+    int64_t rows = 0, phase = 0;       // rows recorded; tallied sweeps since the last row (or set-up / clear)
+    bool packed = false;
+    int chains = 1;                    // the handle's chain count at set-up (nsk_set_chains refuses another while it lives)
+    size_t row_bytes = 0;              // one chain's share of a row
+    int64_t device_bytes = 0;          // what the trace added to the handle's device_bytes
+    std::vector<int64_t> pos;          // the caller's column j is device column pos[j]
+    std::vector<int64_t> sweep_index;  // per recorded row: the handle's sweep index it was taken after
+};
+
 struct nsk_graph {
     nsk::Compiled c;
+    NskTrace trace;
     std::vector<NskLearnWidePlan> learn_wide_plans;      // per Compiled::learn_seg entry
     // the inference sweep's segment launches per colour, kept across calls (the N-rank loops sweep one
     // epoch per call); key = sample_evidence | draw tables usable << 1
@@ -203,6 +222,14 @@ struct nsk_graph {
         if ((G)->nchains > 1)                                                                                          \
             return nsk::fail(NSK_E_INVALID, std::string(WHAT) + ": the handle has several chains (nsk_set_chains); "   \
                                             "only chromatic inference sweeps (nsk_gibbs_sweeps) serve them");          \
+    } while (0)
+// entry points a handle with a sample trace refuses (nsk_trace_setup): rows are taken behind the inference sweeps of
+// nsk_gibbs_sweeps only
+#define NSK_NO_TRACE(G, WHAT)                                                                                          \
+    do {                                                                                                               \
+        if ((G)->trace.capacity > 0)                                                                                   \
+            return nsk::fail(NSK_E_INVALID, std::string(WHAT) + ": the handle records a sample trace "                 \
+                                            "(nsk_trace_setup); tear it down first (capacity = 0)");                   \
     } while (0)
 // Points the handle's per-chain state at chain r while it lives: values, tallies, and the key (word 1 XOR r -- chain r
 // draws what a one-chain handle seeded seed ^ (r << 32) draws)
@@ -393,8 +420,9 @@ int nsk_p2p_ghost_pack(nsk_graph *g);
 int nsk_p2p_flush(nsk_graph *g);                   // enqueue the pending closing wait + unpack of a fused sweep sequence, if any
 void nsk_p2p_fill(nsk_graph *g, nsk::TabP2P &px, const unsigned long long *tag_base, unsigned int tag, bool wait);   // kernel argument of a fused launch
 void nsk_drop_sweep_graph(nsk_graph *g);            // the captured sweep sequence bakes exchange pointers: drop it when they change
-int nsk_gibbs_run(nsk_graph *g, int64_t nsweeps, int sample_evidence, int burnin, bool p2p);   // nsk_gibbs.hip
+int nsk_gibbs_run(nsk_graph *g, int64_t nsweeps, int sample_evidence, int burnin, bool p2p, bool keep_packed = false);   // nsk_gibbs.hip
 void nsk_refresh_prog_weights(nsk_graph *g, bool force = false);
 void nsk_refresh_ztab(nsk_graph *g, int set = 0, hipStream_t st = nullptr);
 int nsk_fold_position_tally(nsk_graph *g);
 int nsk_unpack_tally(nsk_graph *g);
+int nsk_trace_record(nsk_graph *g);                 // one row of the sample trace behind what the stream holds (nsk_api.hip)

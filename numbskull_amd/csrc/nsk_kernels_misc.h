@@ -51,6 +51,57 @@ __global__ __launch_bounds__(NSK_BLOCK) void k_state_gather(const VT *val, const
         by_vid[v] = val[iid[v]];
 }
 
+// ---- sample traces (nsk_trace_setup): one launch appends one row, blockIdx.y = chain --------------------------------
+// Chain r's values lie at val + r * chain_stride BYTES, its share of the row at row + r * (words | elements per chain).
+// cols: device column -> internal id, sorted (nullptr: the identity).  All indexing in 64 bits.
+// Bit-packed rows, gathered columns: a wave per 64-bit word -- 64 lanes gather, one ballot of the low bit, lane 0 stores.
+// (Bit 0 is the value also while a call keeps its tally in bits 1-7 of the value bytes, k_unpack_tally.)
+template <typename VT>
+__global__ __launch_bounds__(NSK_BLOCK) void k_trace_record_bits(const VT *val, long long chain_stride, const int32_t *cols, long long ncols,
+                                                                 unsigned long long *row, long long nwords) {
+    const VT *v = (const VT *)((const char *)val + (long long)blockIdx.y * chain_stride);
+    unsigned long long *o = row + (long long)blockIdx.y * nwords;
+    const long long lane = threadIdx.x & 63;
+    for (long long w = (long long)blockIdx.x * (NSK_BLOCK / 64) + (threadIdx.x >> 6); w < nwords; w += (long long)gridDim.x * (NSK_BLOCK / 64)) {
+        const long long j = w * 64 + lane;
+        int bit = 0;
+        if (j < ncols) bit = (int)(v[cols ? (long long)cols[j] : j] & 1);
+        const unsigned long long m = __ballot(bit);
+        if (lane == 0) o[w] = m;
+    }
+}
+// Bit-packed rows of EVERY internal id of a byte-valued handle (the full-state trace): a lane takes 16 value bytes in one
+// load, squeezes their low bits into 16 bits (byte i of x & 0x0101.. times 0x0102040810204080 lands in bit 56 + i, no
+// two products share a bit) and stores them as its quarter of a word; the value array is read front to back.  n values
+// (chains start on 256-byte boundaries; the bytes behind the last whole 16 are read one by one), nwords words a chain.
+static __global__ __launch_bounds__(NSK_BLOCK) void k_trace_record_dense(const signed char *val, long long chain_stride, long long n,
+                                                                         unsigned short *row, long long nwords) {
+    const signed char *v = val + (long long)blockIdx.y * chain_stride;
+    unsigned short *o = row + (long long)blockIdx.y * nwords * 4;
+    const long long ng = nwords * 4, nfull = n / 16;
+    for (long long q = (long long)blockIdx.x * NSK_BLOCK + threadIdx.x; q < ng; q += (long long)gridDim.x * NSK_BLOCK) {
+        unsigned int bits = 0;
+        if (q < nfull) {
+            const uint4 x = ((const uint4 *)v)[q];
+            const unsigned long long lo = ((unsigned long long)x.y << 32 | x.x) & 0x0101010101010101ull;
+            const unsigned long long hi = ((unsigned long long)x.w << 32 | x.z) & 0x0101010101010101ull;
+            bits = (unsigned int)((lo * 0x0102040810204080ull) >> 56) | (unsigned int)((hi * 0x0102040810204080ull) >> 56) << 8;
+        } else {
+            for (int k = 0; k < 16; k++)
+                if (q * 16 + k < n) bits |= (unsigned int)(v[q * 16 + k] & 1) << k;
+        }
+        o[q] = (unsigned short)bits;
+    }
+}
+// Plain rows (some traced variable is not binary): one element per column
+template <typename VT>
+__global__ __launch_bounds__(NSK_BLOCK) void k_trace_record_plain(const VT *val, long long chain_stride, const int32_t *cols, long long ncols, VT *row) {
+    const VT *v = (const VT *)((const char *)val + (long long)blockIdx.y * chain_stride);
+    VT *o = row + (long long)blockIdx.y * ncols;
+    for (long long j = (long long)blockIdx.x * NSK_BLOCK + threadIdx.x; j < ncols; j += (long long)gridDim.x * NSK_BLOCK)
+        o[j] = v[cols ? (long long)cols[j] : j];
+}
+
 // the int64 tally narrowed to int32 for the trip over PCIe (flag: some count does not fit)
 static __global__ __launch_bounds__(NSK_BLOCK) void k_count_narrow(const long long *total, int32_t *out, long long n, unsigned int *wide) {
     for (long long i = (long long)blockIdx.x * NSK_BLOCK + threadIdx.x; i < n; i += (long long)gridDim.x * NSK_BLOCK) {

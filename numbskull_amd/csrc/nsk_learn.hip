@@ -410,6 +410,7 @@ extern "C" int nsk_learn_sweeps(nsk_graph *g, int64_t nsweeps, double step, doub
                      double reg_param, int64_t truncation, int learn_non_evidence) {
     if (!g) return fail(NSK_E_INVALID, "null graph");
     NSK_ONE_CHAIN(g, "nsk_learn_sweeps");
+    NSK_NO_TRACE(g, "nsk_learn_sweeps");
     if (nsweeps < 0 || nsweeps > INT32_MAX) return fail(NSK_E_INVALID, "bad sweep count");
     if (regularization == 1 && truncation == 0) return fail(NSK_E_INVALID, "truncation must be non-zero (ZeroDivisionError in the reference)");
     if (nsweeps == 0) return NSK_OK;

@@ -1,0 +1,90 @@
+"""Diagnostics over a sample trace (``FactorGraph.sample``): autocorrelation and effective sample size.
+
+Pure numpy, no GPU.  A trace is an array of shape ``(samples, chains, columns)``; every function works per
+column.  The estimator is the one of Vehtari, Gelman, Simpson, Carpenter and Buerkner, "Rank-normalization,
+folding, and localization: an improved R-hat for assessing convergence of MCMC" (Bayesian Analysis 16(2), 2021),
+section 3.2 (the one Stan reports as ``ess_bulk`` without the rank normalisation; Gelman et al., Bayesian Data
+Analysis, 3rd edition, section 11.5): every chain is split in halves as for split R-hat, the within-chain
+variance W and the between-chain variance B give var+ = (n - 1) / n W + B / n, the autocorrelation at lag t is
+
+    rho_t = 1 - (W - mean over half-chains of their autocovariance at lag t) / var+ ,
+
+and the autocorrelation time sums the pairs P_k = rho_2k + rho_2k+1 while they stay positive (Geyer's initial
+positive sequence; Geyer, "Practical Markov chain Monte Carlo", Statistical Science 7(4), 1992):
+
+    tau = -1 + 2 sum_k P_k ,        ESS = (number of samples x number of chains) / tau .
+"""
+
+import numpy as np
+
+_CHUNK = 256          # columns per FFT batch (memory: ~ 64 bytes x samples x chains x _CHUNK)
+
+
+def _split(trace):
+    """(samples, chains, columns) -> float64 half-chains (n, 2 x chains, columns), or None where the estimators
+    are undefined (one chain, or fewer than 4 samples)."""
+    x = np.asarray(trace)
+    if x.ndim != 3:
+        raise ValueError("a trace has shape (samples, chains, columns), got %r" % (x.shape,))
+    s, m, _ = x.shape
+    if m < 2 or s < 4:
+        return None
+    n = s // 2
+    return np.concatenate([x[:n], x[s - n:]], axis=1).astype(np.float64)
+
+
+def _rho(h, max_lag):
+    """Combined autocorrelation estimates rho_0 .. rho_max_lag of half-chains h (n, m, c): (max_lag + 1, c);
+    NaN for a column without variance."""
+    n, m, c = h.shape
+    d = h - h.mean(axis=0)
+    size = 1 << int(2 * n - 1).bit_length()
+    f = np.fft.rfft(d, size, axis=0)
+    acov = np.fft.irfft(f * np.conj(f), size, axis=0)[:max_lag + 1] / n          # biased, per half-chain
+    w = acov[0].mean(axis=0) * n / (n - 1.0)
+    b_over_n = h.mean(axis=0).var(axis=0, ddof=1)
+    var_plus = (n - 1.0) / n * w + b_over_n
+    with np.errstate(divide="ignore", invalid="ignore"):
+        rho = 1.0 - (w - acov.mean(axis=1) * n / (n - 1.0)) / var_plus
+    rho[:, ~(var_plus > 0)] = np.nan
+    return rho
+
+
+def autocorrelation(trace, max_lag):
+    """Autocorrelation of every column at lags 0 .. ``max_lag``: array ``(max_lag + 1, columns)``.  Within- and
+    between-chain variances are combined as for split R-hat (module docstring), so chains that have not mixed show
+    as autocorrelation that does not decay.  NaN for a constant column, for one chain and for fewer than 4 samples."""
+    ncol = np.asarray(trace).shape[2] if np.asarray(trace).ndim == 3 else 0
+    h = _split(trace)
+    max_lag = int(max_lag)
+    if max_lag < 0:
+        raise ValueError("max_lag must not be negative")
+    out = np.full((max_lag + 1, ncol), np.nan)
+    if h is None:
+        return out
+    lag = min(max_lag, h.shape[0] - 1)
+    for c0 in range(0, ncol, _CHUNK):
+        out[:lag + 1, c0:c0 + _CHUNK] = _rho(h[:, :, c0:c0 + _CHUNK], lag)
+    return out
+
+
+def effective_sample_size(trace):
+    """Effective sample size of every column of a ``(samples, chains, columns)`` trace: array ``(columns,)``.
+    NaN for a constant column, for one chain and for fewer than 4 samples."""
+    ncol = np.asarray(trace).shape[2] if np.asarray(trace).ndim == 3 else 0
+    h = _split(trace)
+    out = np.full(ncol, np.nan)
+    if h is None:
+        return out
+    n, m, _ = h.shape
+    for c0 in range(0, ncol, _CHUNK):
+        rho = _rho(h[:, :, c0:c0 + _CHUNK], n - 1)
+        npair = rho.shape[0] // 2
+        pairs = rho[0:2 * npair:2] + rho[1:2 * npair:2]
+        keep = np.cumprod(np.nan_to_num(pairs) > 0, axis=0)           # the initial positive sequence
+        tau = -1.0 + 2.0 * (np.nan_to_num(pairs) * keep).sum(axis=0)
+        ess = np.full(rho.shape[1], np.nan)
+        ok = np.isfinite(rho[0]) & (tau > 0)
+        ess[ok] = n * m / tau[ok]
+        out[c0:c0 + _CHUNK] = ess
+    return out

@@ -441,6 +441,46 @@ class FactorGraph(object):
             finite = self.rhat[np.isfinite(self.rhat)]
             print("Largest split R-hat over %d chains: %s" % (nchains, "%.4f" % finite.max() if len(finite) else "nan"))
 
+    # ------------------------------------------------------------------ sample traces
+    def sample(self, epochs, var_ids=None, thin=1, burnin_epochs=0, sample_evidence=False, var_copy=0,
+               weight_copy=0):
+        """``inference(burnin_epochs, epochs, sample_evidence, var_copy=..., weight_copy=...)`` that also returns
+        the joint samples: after every ``thin``-th tallied sweep the device records the values of ``var_ids``
+        (any variables, any order; None = all) without returning to the host (nsk_trace_setup).  Returns an array
+        ``(epochs // thin, chains, len(var_ids))`` of int8 or int32 (the handle's value type); one chain unless
+        ``var_copy="all"``.  State, ``count``, ``chain_count``, ``marginals``, ``rhat`` and the timing attributes
+        come out as ``inference`` leaves them, and the trace is torn down before the call returns.
+        ``numbskull_amd.diagnostics`` computes autocorrelation and effective sample size of the result."""
+        epochs, thin = int(epochs), int(thin)
+        if thin < 1:
+            raise ValueError("thin must be at least 1")
+        L, h = _lib.lib(), self._engine()
+        if burnin_epochs > 0:
+            self.burnIn(burnin_epochs, sample_evidence, var_copy=var_copy, weight_copy=weight_copy)
+        # the chain count of the call, before the trace is sized for it
+        nchains = self._chains() if _all_copies(var_copy) else 1
+        if L.nsk_get_chains(h) != nchains:
+            _lib.check(L.nsk_set_chains(h, nchains))
+        vids = None if var_ids is None else _lib.as_c(np.asarray(var_ids).reshape(-1), np.int64)
+        ncols = self.variable.shape[0] if vids is None else len(vids)
+        rows = epochs // thin
+        dtype = np.int8 if self.info()["value_bytes"] == 1 else np.int32
+        out = np.zeros((rows, nchains, ncols), dtype)
+        traced = rows > 0 and ncols > 0         # (an empty result needs no trace)
+        if traced:
+            _lib.check(L.nsk_trace_setup(h, _lib.ptr(vids), ncols, thin, rows))
+        try:
+            self.inference(0, epochs, sample_evidence, var_copy=var_copy, weight_copy=weight_copy)
+            if traced:
+                _lib.check(L.nsk_trace_download(h, 0, rows, _lib.ptr(out), None))
+        except BaseException:
+            if traced:
+                L.nsk_trace_setup(h, None, 0, 1, 0)     # (its status must not replace the exception under way)
+            raise
+        if traced:
+            _lib.check(L.nsk_trace_setup(h, None, 0, 1, 0))
+        return out
+
     def learn(self, burnin_epochs, epochs, stepsize, decay, regularization, reg_param, truncation,
               diagnostics=False, verbose=False, learn_non_evidence=False, var_copy=0,
               weight_copy=0):
