@@ -141,6 +141,37 @@ int nsk_trace_rows(nsk_graph *g, int64_t *rows, int64_t *capacity, int64_t *pack
 int nsk_trace_download(nsk_graph *g, int64_t first_row, int64_t nrows, void *out, int64_t *sweep_index);
 int nsk_trace_clear(nsk_graph *g);
 
+/* Log-potential (FactorGraph.log_potential / factor_values / sample(..., log_potential=True)): the unnormalised
+ * log-probability of a state, the sum over ALL factors f of weight[f.weightId] * eval_factor(f, state), evaluated on
+ * the device one lane per factor.  Every term is one rounded float64 product; the sum is REPRODUCIBLE -- a function of
+ * graph, weights and state only: the same bits for any chain index or chain count of the handle, from a query or from
+ * a trace row, on every run (a fixed grid, fixed-order wave, block and final reductions, no floating-point atomics).  It
+ * differs from the exactly rounded sum by at most (nfactor + 1) * 2^-53 * sum |term|.
+ * The calls synchronise with the handle's stream and read values and weights as nsk_state_download /
+ * nsk_chains_download would return them at that moment; they change nothing (values, tallies, sweeps_done, generator
+ * state).  The first one uploads the factor and member records unless the handle's kernels read them already
+ * (16 bytes a factor, 8 an edge, 4 a variable; reported by nsk_graph_info.device_bytes; NSK_E_NOMEM when they do not fit) and holds
+ * the factors no sampled variable reaches to the rules nsk_graph_create applies to the others (NSK_E_INVALID names
+ * the first that breaks one).  A handle that never calls them allocates and launches nothing for them.
+ * which: NSK_BUF_VALUE (chains first_chain .. first_chain + nchains - 1 of the handle's chains) or NSK_BUF_VALUE_EVID
+ * (the evidence chain exists once: first_chain = 0, nchains = 1); anything else, nchains < 1 and a chain the handle
+ * does not have are NSK_E_INVALID, as are own_range / NSK_FLAG_PARTITION handles and handles that exchange a boundary
+ * (a shard's sum is not the graph's, and its ghosts are stale between exchanges).  The sequential scan is fine.
+ * nsk_log_potential: out[i] = log-potential of chain first_chain + i.
+ * nsk_factor_values: out[f] = eval_factor(f, state of `chain`) for the nfactor factors in the caller's order.
+ * nsk_trace_log_potential(g, 1): valid while a trace is set up (NSK_E_INVALID otherwise); allocates capacity x chains
+ * doubles, and from then on every record launch is followed on the stream by the evaluation of the state just
+ * recorded, every chain, whatever columns the trace keeps (rows recorded while it was off read 0).  0 switches it
+ * off and frees the buffer; nsk_trace_setup (replace or tear down) resets it to off; nsk_trace_clear keeps it.
+ * nsk_trace_download_log_potential: synchronises, then writes rows first_row .. first_row + nrows - 1 as
+ * nrows x chains doubles; rows beyond those recorded, or no lp column: NSK_E_INVALID.
+ * nsk_profile_* keeps counting sweep-kernel launches only. */
+int nsk_log_potential(nsk_graph *g, int which, int64_t first_chain, int64_t nchains, double *out);
+int nsk_factor_values(nsk_graph *g, int which, int64_t chain, double *out /* nfactor */);
+int nsk_trace_log_potential(nsk_graph *g, int on);
+int nsk_trace_download_log_potential(nsk_graph *g, int64_t first_row, int64_t nrows,
+                                     double *out /* nrows x chains */);
+
 /* RNG: the chromatic scan draws from Philox4x32-10 keyed by `seed`.  A variable's generator id is
  * its position in the compiled layout (nsk_graph_get_layout), so samples are a function of the seed
  * AND the layout the library chose (device, flags and diagnostic switches being equal, a graph

@@ -30,6 +30,7 @@ SYMBOLS = (
     "nsk_gibbs_sweeps_p2p", "nsk_learn_sweeps_p2p", "nsk_p2p_exchange", "nsk_p2p_selftest", "nsk_p2p_fuse", "nsk_p2p_check", "nsk_p2p_reset", "nsk_profile_mark", "nsk_profile_read", "nsk_graph_order", "nsk_comm_volume", "nsk_graph_partition", "nsk_compute_var_map", "nsk_state_layout", "nsk_parse_factors", "nsk_parse_domains", "nsk_write_probabilities",
     "nsk_set_chains", "nsk_get_chains", "nsk_chains_upload", "nsk_chains_download",
     "nsk_trace_setup", "nsk_trace_rows", "nsk_trace_download", "nsk_trace_clear",
+    "nsk_log_potential", "nsk_factor_values", "nsk_trace_log_potential", "nsk_trace_download_log_potential",
     "nsk_selftest_exp", "nsk_selftest_philox", "nsk_selftest_stream", "nsk_device_count", "nsk_last_error", "nsk_version",
 )
 
@@ -99,6 +100,10 @@ def lib():
         L.nsk_trace_rows.argtypes = [C.c_void_p] + [C.POINTER(C.c_int64)] * 3
         L.nsk_trace_download.argtypes = [C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p]
         L.nsk_trace_clear.argtypes = [C.c_void_p]
+        L.nsk_log_potential.argtypes = [C.c_void_p, C.c_int, C.c_int64, C.c_int64, C.c_void_p]
+        L.nsk_factor_values.argtypes = [C.c_void_p, C.c_int, C.c_int64, C.c_void_p]
+        L.nsk_trace_log_potential.argtypes = [C.c_void_p, C.c_int]
+        L.nsk_trace_download_log_potential.argtypes = [C.c_void_p, C.c_int64, C.c_int64, C.c_void_p]
         L.nsk_graph_create.argtypes = [C.POINTER(GraphDesc), C.POINTER(C.c_void_p)]
         L.nsk_graph_destroy.argtypes = [C.c_void_p]
         L.nsk_graph_get_info.argtypes = [C.c_void_p, C.POINTER(GraphInfo)]

@@ -49,11 +49,33 @@ struct NskTrace {
     int64_t device_bytes = 0;          // what the trace added to the handle's device_bytes
     std::vector<int64_t> pos;          // the caller's column j is device column pos[j]
     std::vector<int64_t> sweep_index;  // per recorded row: the handle's sweep index it was taken after
+    double *lp = nullptr;              // the lp column (nsk_trace_log_potential): capacity x chains log-potentials, or off
+    int64_t lp_bytes = 0;              // ... and what it added to the handle's device_bytes
 };
+
+// Log-potential (nsk_log_potential / nsk_factor_values / the trace's lp column): the factor walk of nsk_kernels_energy.h
+// reads f_rec, m_rec, v_card (and iid_of_vid on a graph with literal heads) -- the arrays nsk_ensure_generic uploads, taken
+// from it when it ran, uploaded at the first use otherwise (nsk_api.hip energy_ensure) -- and leaves one partial sum per
+// block and chain.  A handle that never asks holds none of this.
+struct NskEnergy {
+    bool ready = false;                // every factor was checked and the arrays are on the device
+    int chains = 0;                    // chains the buffers below serve
+    double *partial = nullptr;         // chains x nsk_energy_blocks(nfactor) block partials
+    double *result = nullptr;          // chains sums (a query's; a trace writes into its lp column)
+};
+
+// blocks of the factor walk, a function of nfactor ALONE (the sum must not depend on anything else): one lane per factor
+// up to 8 blocks per CU, grid-stride beyond; whole rounds of XCDs
+#define NSK_ENERGY_MAX_BLOCKS 2048
+static inline unsigned int nsk_energy_blocks(long long nfactor) {
+    const long long need = (nfactor + 255) / 256;
+    return (unsigned int)(need < 8 ? 8 : (need >= NSK_ENERGY_MAX_BLOCKS ? NSK_ENERGY_MAX_BLOCKS : (need + 7) / 8 * 8));
+}
 
 struct nsk_graph {
     nsk::Compiled c;
     NskTrace trace;
+    NskEnergy energy;
     std::vector<NskLearnWidePlan> learn_wide_plans;      // per Compiled::learn_seg entry
     // the inference sweep's segment launches per colour, kept across calls (the N-rank loops sweep one
     // epoch per call); key = sample_evidence | draw tables usable << 1
@@ -426,3 +448,6 @@ void nsk_refresh_ztab(nsk_graph *g, int set = 0, hipStream_t st = nullptr);
 int nsk_fold_position_tally(nsk_graph *g);
 int nsk_unpack_tally(nsk_graph *g);
 int nsk_trace_record(nsk_graph *g);                 // one row of the sample trace behind what the stream holds (nsk_api.hip)
+// the log-potential of `nchains` chains from `val` on / every factor's value, enqueued on the handle's stream (nsk_energy.hip)
+int nsk_energy_enqueue(nsk_graph *g, const void *val, int nchains, bool packed_bytes, double *out);
+int nsk_factor_values_enqueue(nsk_graph *g, const void *val, double *out);

@@ -13,6 +13,10 @@ and the autocorrelation time sums the pairs P_k = rho_2k + rho_2k+1 while they s
 positive sequence; Geyer, "Practical Markov chain Monte Carlo", Statistical Science 7(4), 1992):
 
     tau = -1 + 2 sum_k P_k ,        ESS = (number of samples x number of chains) / tau .
+
+The log-potentials ``lp`` of ``FactorGraph.sample(..., log_potential=True)``, shape ``(samples, chains)``, are one
+more column: ``effective_sample_size(lp[:, :, None])`` is the ESS of the joint state, and ``best_sample(lp)`` finds
+the most probable sample recorded.
 """
 
 import numpy as np
@@ -88,3 +92,13 @@ def effective_sample_size(trace):
         ess[ok] = n * m / tau[ok]
         out[c0:c0 + _CHUNK] = ess
     return out
+
+
+def best_sample(lp):
+    """``(row, chain)`` of the largest log-potential in ``lp`` (samples, chains): the most probable sample of a
+    ``FactorGraph.sample(..., log_potential=True)`` call, a MAP estimate; ties go to the first in row-major order."""
+    x = np.asarray(lp)
+    if x.ndim != 2 or x.size == 0:
+        raise ValueError("log-potentials have shape (samples, chains) with at least one entry, got %r" % (x.shape,))
+    row, chain = np.unravel_index(int(np.argmax(x)), x.shape)
+    return int(row), int(chain)

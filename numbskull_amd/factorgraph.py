@@ -443,14 +443,18 @@ class FactorGraph(object):
 
     # ------------------------------------------------------------------ sample traces
     def sample(self, epochs, var_ids=None, thin=1, burnin_epochs=0, sample_evidence=False, var_copy=0,
-               weight_copy=0):
+               weight_copy=0, log_potential=False):
         """``inference(burnin_epochs, epochs, sample_evidence, var_copy=..., weight_copy=...)`` that also returns
         the joint samples: after every ``thin``-th tallied sweep the device records the values of ``var_ids``
         (any variables, any order; None = all) without returning to the host (nsk_trace_setup).  Returns an array
         ``(epochs // thin, chains, len(var_ids))`` of int8 or int32 (the handle's value type); one chain unless
         ``var_copy="all"``.  State, ``count``, ``chain_count``, ``marginals``, ``rhat`` and the timing attributes
         come out as ``inference`` leaves them, and the trace is torn down before the call returns.
-        ``numbskull_amd.diagnostics`` computes autocorrelation and effective sample size of the result."""
+        ``numbskull_amd.diagnostics`` computes autocorrelation and effective sample size of the result.
+        ``log_potential=True`` returns ``(samples, lp)``: ``lp[i, r]``, float64 ``(epochs // thin, chains)``, is the
+        log-potential of the whole state of chain ``r`` when row ``i`` was taken, whatever ``var_ids`` keeps --
+        the doubles ``log_potential()`` gives for that state, evaluated on the device behind the row
+        (nsk_trace_log_potential)."""
         epochs, thin = int(epochs), int(thin)
         if thin < 1:
             raise ValueError("thin must be at least 1")
@@ -467,18 +471,57 @@ class FactorGraph(object):
         dtype = np.int8 if self.info()["value_bytes"] == 1 else np.int32
         out = np.zeros((rows, nchains, ncols), dtype)
         traced = rows > 0 and ncols > 0         # (an empty result needs no trace)
-        if traced:
+        lp = np.zeros((rows, nchains), np.float64) if log_potential else None
+        if log_potential and rows > 0 and not traced:      # no columns asked for: the lp column rides on a one-column trace
+            first = _lib.as_c(np.zeros(1), np.int64)
+            _lib.check(L.nsk_trace_setup(h, _lib.ptr(first), 1, thin, rows))
+            traced = True
+        elif traced:
             _lib.check(L.nsk_trace_setup(h, _lib.ptr(vids), ncols, thin, rows))
         try:
+            if traced and log_potential:
+                _lib.check(L.nsk_trace_log_potential(h, 1))
             self.inference(0, epochs, sample_evidence, var_copy=var_copy, weight_copy=weight_copy)
-            if traced:
+            if traced and ncols > 0:
                 _lib.check(L.nsk_trace_download(h, 0, rows, _lib.ptr(out), None))
+            if traced and log_potential:
+                _lib.check(L.nsk_trace_download_log_potential(h, 0, rows, _lib.ptr(lp)))
         except BaseException:
             if traced:
                 L.nsk_trace_setup(h, None, 0, 1, 0)     # (its status must not replace the exception under way)
             raise
         if traced:
             _lib.check(L.nsk_trace_setup(h, None, 0, 1, 0))
+        return (out, lp) if log_potential else out
+
+    # ------------------------------------------------------------------ log-potential
+    def log_potential(self, var_copy=0, weight_copy=0, evidence_chain=False):
+        """The unnormalised log-probability of a state: the sum over all factors of weight x factor value, evaluated
+        on the device (nsk_log_potential).  The state is ``var_value[var_copy]`` -- ``var_value_evid[var_copy]``
+        with ``evidence_chain=True`` -- under ``weight_value[weight_copy]``, pushed as ``inference`` pushes them.
+        Returns a float; ``var_copy="all"`` a float64 array with one entry per row of ``var_value``.  The sum is
+        reproducible: equal states under equal weights give equal doubles, whichever chain holds them."""
+        L, h = _lib.lib(), self._engine()
+        if _all_copies(var_copy):
+            if evidence_chain:
+                raise ValueError('the evidence chain exists once: var_copy="all" is for the free chains')
+            nchains = self._push_chains(weight_copy, count=False)
+            out = np.zeros(nchains, np.float64)
+            _lib.check(L.nsk_log_potential(h, _lib.BUF_VALUE, 0, nchains, _lib.ptr(out)))
+            return out
+        self._push(var_copy, weight_copy)
+        out = np.zeros(1, np.float64)
+        _lib.check(L.nsk_log_potential(h, _lib.BUF_VALUE_EVID if evidence_chain else _lib.BUF_VALUE, 0, 1, _lib.ptr(out)))
+        return float(out[0])
+
+    def factor_values(self, var_copy=0, evidence_chain=False):
+        """The value of every factor on ``var_value[var_copy]`` (``var_value_evid[var_copy]`` with
+        ``evidence_chain=True``): float64 ``(nfactor,)`` in the order of ``factor`` -- what the reference's
+        ``eval_factor`` returns for the state as it is, head quirks included (nsk_factor_values)."""
+        L, h = _lib.lib(), self._engine()
+        self._push(var_copy, 0)
+        out = np.zeros(self.factor.shape[0], np.float64)
+        _lib.check(L.nsk_factor_values(h, _lib.BUF_VALUE_EVID if evidence_chain else _lib.BUF_VALUE, 0, _lib.ptr(out)))
         return out
 
     def learn(self, burnin_epochs, epochs, stepsize, decay, regularization, reg_param, truncation,
