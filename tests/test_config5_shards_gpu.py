@@ -28,8 +28,9 @@ WORLD = 8
 LR_SEED = 20240603
 
 
-def make_parts(kind, nvar, learn, seed):
-    """One handle + PartitionedSampler per shard, every one on a stream of its own."""
+def make_parts(kind, nvar, learn, seed, weight=0.1):
+    """One handle + PartitionedSampler per shard, every one on a stream of its own.  ``weight``: the inference grid's
+    one weight."""
     import torch
     from numbskull_amd.distributed import PartitionedSampler, shard_range
     parts, streams = [], []
@@ -48,7 +49,7 @@ def make_parts(kind, nvar, learn, seed):
         nvar = rows * cols
         grid = (graphgen.ising_grid(rows, cols, weight=0.0, fixed=False, two_weights=True,
                                     evidence=rng.integers(0, 2, nvar)) if learn
-                else graphgen.ising_grid(rows, cols, weight=0.1))
+                else graphgen.ising_grid(rows, cols, weight=weight))
         if kind == "shuffled_grid":
             # the grid under randomly permuted variable ids (a loader that numbers variables in arrival order), then
             # repartitioned: numbskull_amd.partition puts a graph-aware variable order in front of the range partition
@@ -130,12 +131,12 @@ def wire_p2p(parts):
     return needs
 
 
-def run_case(kind, size, learn, tag, nsweeps=3, hyper=(1e-3, 0.95, 2, 0.01, 1), fused=False, probe=None):
+def run_case(kind, size, learn, tag, nsweeps=3, hyper=(1e-3, 0.95, 2, 0.01, 1), fused=False, probe=None, weight=0.1):
     """``probe(parts, needs)``: called once the shards are wired (what a test asserts about their exchange plans)."""
     import torch
     from numbskull_amd.distributed import shard_range, plan_pairs
     seed = 20240601
-    parts, streams, nvar = make_parts(kind, size, learn, seed)
+    parts, streams, nvar = make_parts(kind, size, learn, seed, weight)
     hbv = kind not in ("grid", "shuffled_grid", "perturbed_grid")
     oracles = []
     for p in parts:
