@@ -27,13 +27,12 @@ static inline int tabw_delta(const void *p, const void *base) {
 // it).  A handle that exchanges its boundary inside the table launches (p2p_fused) gets its segments split
 // into runs of border tiles (SegEntry.push_off = their first row in the push map) and runs of interior tiles.
 void nsk_ensure_seg_plans(nsk_graph *g, int sample_evidence) {
-    typedef NskSegPlan SegPlan;
     const size_t nphase = g->c.phase_start.size() - 1;
-    std::vector<std::vector<SegPlan>> &seg_plans = g->seg_plans;
+    std::vector<std::vector<NskSegPlan>> &seg_plans = g->seg_plans;
     const int plans_key = (sample_evidence ? 1 : 0) | (g->values_regular ? 2 : 0) | (g->p2p_fused ? 4 : 0);
     if (g->seg_plans_key == plans_key) return;
     g->seg_plans_key = plans_key;
-    seg_plans.assign(nphase, std::vector<SegPlan>());
+    seg_plans.assign(nphase, std::vector<NskSegPlan>());
     const bool use_tab = g->values_regular;
     struct Run { const Compiled::Segment *sg; int t0, nt; uint32_t push_off; };
     const std::vector<int32_t> &bt = g->p2p_border_tiles;
@@ -46,12 +45,9 @@ void nsk_ensure_seg_plans(nsk_graph *g, int sample_evidence) {
                 const auto it = std::lower_bound(bt.begin(), bt.end(), f);
                 if (it != bt.end() && *it < f + sg.ntiles) border_all = false;
             }
-    int first_phase = -1, last_phase = -1;            // classes with sampled segments
+    int first_phase = -1;            // the first class with sampled segments
     for (const Compiled::Segment &sg : g->c.segments)
-        if (sg.ev == 0 || sample_evidence) {
-            if (first_phase < 0 || sg.phase < first_phase) first_phase = sg.phase;
-            if (sg.phase > last_phase) last_phase = sg.phase;
-        }
+        if ((sg.ev == 0 || sample_evidence) && (first_phase < 0 || sg.phase < first_phase)) first_phase = sg.phase;
     g->p2p_first_phase = first_phase;
     for (size_t ph = 0; ph < nphase; ph++)
         for (int kind = 0; kind <= 8; kind++) {
@@ -70,7 +66,7 @@ void nsk_ensure_seg_plans(nsk_graph *g, int sample_evidence) {
                     };
                     tab.wide = (kind >= 8 && 8 * tab.wide >= tab.ntiles && tab.ntiles < (1 << 28) && fits(g->cnt_pos) && fits(g->seg_wide) &&
                                 fits(g->ztab) && !nsk::diag_env("NSK_NO_WIDE_KERNEL")) ? 1 : 0;
-                    SegPlan pl{kind, nch, tab};
+                    NskSegPlan pl{kind, nch, tab};
                     if (tab.wide) nsk_tabw_rest_list(g->c, pl.tab, pl.nch, pl.nrest, pl.rest);
                     seg_plans[ph].push_back(pl);
                     memset(&tab, 0, sizeof(tab));
@@ -101,7 +97,6 @@ void nsk_ensure_seg_plans(nsk_graph *g, int sample_evidence) {
                 // chain (flag, system-coherent ghost loads, pushes, acknowledgement, counter) is twice a trip long and
                 // overlaps the interior trips when it starts first; behind them it was a tail of every launch (a
                 // border wave that waits for a peer holds one of 6144 wave slots, nothing else)
-                (void)last_phase;
                 std::stable_sort(mine.begin(), mine.end(), [&](const Run &a, const Run &b) {
                     const bool ba = a.push_off != NSK_NO_STREAM, bb = b.push_off != NSK_NO_STREAM;
                     if (ba != bb) return ba;
@@ -153,41 +148,79 @@ void nsk_ensure_seg_plans(nsk_graph *g, int sample_evidence) {
     if (g->p2p_fused) {
         int first_border = -1;
         for (size_t ph = 0; ph < nphase && first_border < 0; ph++)
-            for (const SegPlan &pl : seg_plans[ph])
+            for (const NskSegPlan &pl : seg_plans[ph])
                 for (int i = 0; i < pl.tab.n && first_border < 0; i++)
                     if (pl.tab.e[i].push_off != NSK_NO_STREAM) first_border = (int)ph;
         if (first_border >= 0) g->p2p_first_phase = first_border;
     }
     g->p2p_border_total = border_total;
     g->p2p_border_all = border_all && border_total == (uint32_t)bt.size();
+    g->seg_plans_all_tab = g->seg_plans_all_wide = true;
+    for (const auto &v : seg_plans)
+        for (const NskSegPlan &pl : v) {
+            g->seg_plans_all_tab = g->seg_plans_all_tab && pl.kind >= 8;
+            g->seg_plans_all_wide = g->seg_plans_all_wide && pl.kind >= 8 && pl.tab.wide;
+        }
 }
 
-// One table launch of a class for EVERY chain of a handle with several (nsk_set_chains): k_gibbs_seg_tabw_chains /
-// k_gibbs_seg_tab_chains over R copies of the single-chain grid.  sweep_base: a captured launch (key and sweep index in
-// d_counters, sweep_off added).
-template <typename VT>
-static void launch_tab_chains(nsk_graph *g, const NskSegPlan &pl, int burnin, uint32_t K0, uint32_t K1, uint32_t S0, uint32_t S1,
-                              const unsigned long long *sweep_base, uint32_t sweep_off) {
-    const unsigned R = (unsigned)g->nchains;
-    if (sizeof(VT) == 1 && pl.tab.wide) {
-        const DevGraph<signed char> dw = view<signed char>(g);
-        const int nbw = nsk_tabw_grid(pl.tab.ntiles);
-        TabwCold cold{K0, K1, S0, S1, sweep_off, 0u, dw, pl.tab, pl.nrest, {}};
-        memcpy(cold.rest, pl.rest, sizeof(cold.rest));
-        const int nf = nsk_tabw_front_blocks(pl.nrest);
-        const dim3 grid(R * (unsigned)(nf + nbw));            // (the kernel derives nf + nbw from its hot arguments)
-#define NSK_TABW(NCH, MODE) k_gibbs_seg_tabw_chains<NCH, MODE><<<grid, dim3(NSK_BLOCK), 0, g->stream>>>(NSK_TABW_HOT_ARGS(g, pl.tab, nbw, nf, sweep_base), cold)
-        if (pl.nch == 1) { if (burnin) NSK_TABW(1, 1); else NSK_TABW(1, 0); }
-        else { if (burnin) NSK_TABW(2, 1); else NSK_TABW(2, 0); }
-#undef NSK_TABW
-    } else {
-        const DevGraph<VT> d = view<VT>(g);
-        const int nbp = nsk_tab_grid(pl.tab.ntiles);
-        const TabChains ch{(uint32_t)nbp, 0u, (long long)g->chain_stride};
-        const dim3 grid(R * (unsigned)nbp);
-        if (pl.nch == 1) k_gibbs_seg_tab_chains<VT, 1><<<grid, dim3(NSK_BLOCK), 0, g->stream>>>(d, pl.tab, burnin, K0, K1, S0, S1, sweep_base, sweep_off, ch);
-        else k_gibbs_seg_tab_chains<VT, 2><<<grid, dim3(NSK_BLOCK), 0, g->stream>>>(d, pl.tab, burnin, K0, K1, S0, S1, sweep_base, sweep_off, ch);
+// Where a table launch gets its counters.  An eager launch carries the Philox key, the sweep index and the exchange tag
+// in its arguments; a captured one (hipGraph) reads them from d_counters and adds the offsets of its sweep in the sequence.
+struct CounterSrc {
+    uint32_t K0, K1, S0, S1;
+    const unsigned long long *sweep_base;
+    uint32_t sweep_off;
+    unsigned int tag;
+    static CounterSrc eager(const nsk_graph *g) {
+        return {(uint32_t)g->seed, (uint32_t)(g->seed >> 32), (uint32_t)g->sweep, nsk_sweep_hi(g), nullptr, 0u, g->p2p_tag};
     }
+    static CounterSrc captured(const nsk_graph *g, int i) { return {0u, 0u, 0u, 0u, g->d_counters, (uint32_t)i, (unsigned int)(i + 1)}; }
+};
+
+// L(NCH, ...) with the chunk count of the plan `pl` as a constant
+#define NSK_BY_NCH(L, ...) do { if (pl.nch == 1) { L(1, __VA_ARGS__); } else { L(2, __VA_ARGS__); } } while (0)
+
+// The wide-quad launch of a plan (four positions to a lane) -- chains: for every chain of the handle, over as many copies
+// of the one-chain grid
+static void launch_tabw(nsk_graph *g, const NskSegPlan &pl, int burnin, const CounterSrc &src, bool chains) {
+    TabwCold cold{src.K0, src.K1, src.S0, src.S1, src.sweep_off, 0u, view<signed char>(g), pl.tab, pl.nrest, {}};
+    memcpy(cold.rest, pl.rest, sizeof(cold.rest));
+    const int nbw = nsk_tabw_grid(pl.tab.ntiles), nf = nsk_tabw_front_blocks(pl.nrest);
+    const dim3 grid((chains ? (unsigned)g->nchains : 1u) * (unsigned)(nf + nbw));     // (the kernel derives nf + nbw from its hot arguments)
+#define NSK_TABW(NCH, K, MODE) K<NCH, MODE><<<grid, dim3(NSK_BLOCK), 0, g->stream>>>(NSK_TABW_HOT_ARGS(g, pl.tab, nbw, nf, src.sweep_base), cold)
+    if (chains) { if (burnin) NSK_BY_NCH(NSK_TABW, k_gibbs_seg_tabw_chains, 1); else NSK_BY_NCH(NSK_TABW, k_gibbs_seg_tabw_chains, 0); }
+    else if (burnin) NSK_BY_NCH(NSK_TABW, k_gibbs_seg_tabw, 1);
+    else if (g->pack_now) NSK_BY_NCH(NSK_TABW, k_gibbs_seg_tabw, 2);      // the tally inside the value bytes
+    else NSK_BY_NCH(NSK_TABW, k_gibbs_seg_tabw, 0);
+#undef NSK_TABW
+}
+
+// One table launch (a plan of kind 8) of class `ph`, eager or captured: the one place that picks its kernel.  Every chain
+// of a handle with several in one launch (chains_batched; R copies of the one-chain grid), else the boundary exchange
+// inside the launch, else (mostly) wide quads, else a wave per tile pair.
+template <typename VT>
+static void launch_table(nsk_graph *g, const NskSegPlan &pl, int ph, int burnin, const CounterSrc &src) {
+    // (under a ChainSwap the one-chain launches sample the one chain.  The capture needs no such test, and this one is the
+    // same there: only nsk_gibbs_run captures, and chains_run sweeps a swapped handle through gibbs_eager alone.)
+    const bool chains = g->nchains > 1 && !g->chain_swapped;
+    const bool wide = sizeof(VT) == 1 && pl.tab.wide;
+    // a wave per tile pair while that fits the resident grid, else its waves loop over quads
+    const unsigned nbp = (unsigned)nsk_tab_grid(pl.tab.ntiles);
+#define NSK_TAB_ARGS view<VT>(g), pl.tab, burnin, src.K0, src.K1, src.S0, src.S1, src.sweep_base, src.sweep_off
+#define NSK_TAB(NCH, K, NB, ...) K<VT, NCH><<<dim3(NB), dim3(NSK_BLOCK), 0, g->stream>>>(__VA_ARGS__)
+    if (chains) {
+        const TabChains ch{nbp, 0u, (long long)g->chain_stride};
+        if (wide) launch_tabw(g, pl, burnin, src, true);
+        else NSK_BY_NCH(NSK_TAB, k_gibbs_seg_tab_chains, (unsigned)g->nchains * nbp, NSK_TAB_ARGS, ch);
+    }
+    else if (g->p2p_fused_now) {        // (the border waves of the sweep's first class with border tiles wait for the peers)
+        TabP2P px;
+        nsk_p2p_fill(g, px, src.sweep_base, src.tag, ph == g->p2p_first_phase);
+        NSK_BY_NCH(NSK_TAB, k_gibbs_seg_tab_p2p, nbp, NSK_TAB_ARGS, px);
+    }
+    else if (wide) launch_tabw(g, pl, burnin, src, false);
+    else NSK_BY_NCH(NSK_TAB, k_gibbs_seg_tab, nbp, NSK_TAB_ARGS);
+#undef NSK_TAB
+#undef NSK_TAB_ARGS
 }
 // batched chain launches: a handle with several chains whose sweep is table launches only, its values in their domains,
 // and the kernels' 32-bit offsets valid for the last chain
@@ -201,11 +234,11 @@ static bool chains_batched(nsk_graph *g, int sample_evidence) {
         const long long d = ((const char *)p - (const char *)g->val) / 256 - shift;
         return d > -(1ll << 31) && d < (1ll << 31);
     };
-    for (const auto &v : g->seg_plans)
-        for (const NskSegPlan &pl : v) {
-            if (pl.kind < 8) return false;
-            if (g->c.vbytes == 1 && pl.tab.wide && !(fits(g->seg_wide) && fits(g->ztab))) return false;
-        }
+    if (!g->seg_plans_all_tab) return false;
+    if (g->c.vbytes == 1 && !(fits(g->seg_wide) && fits(g->ztab)))
+        for (const auto &v : g->seg_plans)
+            for (const NskSegPlan &pl : v)
+                if (pl.tab.wide) return false;
     return true;
 }
 
@@ -222,8 +255,6 @@ static int gibbs_impl(nsk_graph *g, int64_t nsweeps, int sample_evidence, int bu
         const size_t nphase = g->c.phase_start.size() - 1;
         nsk_refresh_prog_weights(g);
         nsk_ensure_seg_plans(g, sample_evidence);
-        std::vector<std::vector<NskSegPlan>> &seg_plans = g->seg_plans;
-        typedef NskSegPlan SegPlan;
         for (int64_t s = 0; s < nsweeps; s++) {
             if (g->pack_now && !burnin && g->packed_sweeps >= 127) (void)nsk_unpack_tally(g);       // 7 tally bits per value byte
             if (g->p2p_fused_now) ++g->p2p_tag;            // the exchange rides in this sweep's table launches
@@ -253,15 +284,14 @@ static int gibbs_impl(nsk_graph *g, int64_t nsweeps, int sample_evidence, int bu
                     const int pcu = pcu_env ? std::max(1, std::min(32, atoi(pcu_env))) : 7;
                     const int gblocks = 8 * ((std::min(ngroups, 256 * pcu) + 7) / 8);
                     const dim3 grid(hblocks + gblocks + rblocks);
-                    const size_t smem = 0;
 #define NSK_EP_ARGS d, fb, fe, (int)g->c.phase_wb_base[ph], gt0, ngt, ngroups, (int)g->c.phase_ep_base[ph], gblocks, fe, he, hblocks, \
                     (int)g->c.phase_hub_base[ph], nbh, (int)g->c.phase_bighub_base[ph], g->rest_tiles + g->c.phase_rest_base[ph], nrest_all, sample_evidence, burnin, \
                     (uint32_t)g->seed, (uint32_t)(g->seed >> 32), (uint32_t)g->sweep, nsk_sweep_hi(g)
                     // (value array within the L2s: the register-capped twin with a fifth wave per SIMD)
                     const bool in_l2 = (size_t)g->c.nid * (size_t)g->c.vbytes <= ((size_t)24 << 20);
-                    if (cat8 && in_l2) k_gibbs_ep_w5<VT, 8><<<grid, dim3(NSK_BLOCK), smem, g->stream>>>(NSK_EP_ARGS);
-                    else if (cat8) k_gibbs_ep<VT, 8><<<grid, dim3(NSK_BLOCK), smem, g->stream>>>(NSK_EP_ARGS);
-                    else k_gibbs_ep<VT, 2><<<grid, dim3(NSK_BLOCK), smem, g->stream>>>(NSK_EP_ARGS);
+                    if (cat8 && in_l2) k_gibbs_ep_w5<VT, 8><<<grid, dim3(NSK_BLOCK), 0, g->stream>>>(NSK_EP_ARGS);
+                    else if (cat8) k_gibbs_ep<VT, 8><<<grid, dim3(NSK_BLOCK), 0, g->stream>>>(NSK_EP_ARGS);
+                    else k_gibbs_ep<VT, 2><<<grid, dim3(NSK_BLOCK), 0, g->stream>>>(NSK_EP_ARGS);
 #undef NSK_EP_ARGS
                     g->launches++;
                 }
@@ -299,8 +329,8 @@ static int gibbs_impl(nsk_graph *g, int64_t nsweeps, int sample_evidence, int bu
                     g->launches++;
                 }
                 if (fe > fb) {      // inlined-adjacency kernels
-                    const uint32_t K0 = (uint32_t)g->seed, K1 = (uint32_t)(g->seed >> 32);
-                    const uint32_t S0 = (uint32_t)g->sweep, S1 = nsk_sweep_hi(g);
+                    const CounterSrc src = CounterSrc::eager(g);
+                    const uint32_t K0 = src.K0, K1 = src.K1, S0 = src.S0, S1 = src.S1;
                     const int gt0 = (int)g->c.phase_gen_tile[ph];
                     const int ngt = (int)(g->c.phase_wb_base[ph + 1] - g->c.phase_wb_base[ph]) - gt0;
                     int gtb = (int)g->c.phase_gen_bin_tile[ph];
@@ -318,43 +348,18 @@ static int gibbs_impl(nsk_graph *g, int64_t nsweeps, int sample_evidence, int bu
                         g->launches++;
                     }
                     // segments of this colour: the launches prepared before the sweep loop
-                    for (const SegPlan &pl : seg_plans[ph]) {
-                        const SegTable &tab = pl.tab;
-                        const int kind = pl.kind, nch = pl.nch;
-                        const int nb = (tab.ntiles + 3) / 4;
-                        const dim3 grid(8 * ((nb + 7) / 8)), block(NSK_BLOCK);
-#define NSK_SEG(KIND, NCH) k_gibbs_seg<VT, KIND, NCH><<<grid, block, 0, g->stream>>>(d, tab, nb, burnin, K0, K1, S0, S1)
-                        if (kind >= 8) {
-                            // a wave per tile pair while that fits the resident grid, else its waves loop over quads
-                            const int nbp = nsk_tab_grid(tab.ntiles);
-                            if (g->nchains > 1 && !g->chain_swapped)    // every chain in one launch (chains_batched)
-                                launch_tab_chains<VT>(g, pl, burnin, K0, K1, S0, S1, nullptr, 0u);
-                            else if (g->p2p_fused_now) {
-                                TabP2P px;
-                                nsk_p2p_fill(g, px, nullptr, g->p2p_tag, (int)ph == g->p2p_first_phase);
-                                if (nch == 1) k_gibbs_seg_tab_p2p<VT, 1><<<dim3(nbp), block, 0, g->stream>>>(d, tab, burnin, K0, K1, S0, S1, nullptr, 0u, px);
-                                else k_gibbs_seg_tab_p2p<VT, 2><<<dim3(nbp), block, 0, g->stream>>>(d, tab, burnin, K0, K1, S0, S1, nullptr, 0u, px);
-                            }
-                            else if (sizeof(VT) == 1 && tab.wide) {          // (mostly) wide quads: four positions to a lane
-                                const DevGraph<signed char> dw = view<signed char>(g);
-                                const int nbw = nsk_tabw_grid(tab.ntiles);
-                                const int mode = burnin ? 1 : (g->pack_now ? 2 : 0);        // 2: the tally inside the value bytes
-                                TabwCold cold{K0, K1, S0, S1, 0u, 0u, dw, tab, pl.nrest, {}};
-                                memcpy(cold.rest, pl.rest, sizeof(cold.rest));
-                                const int nf = nsk_tabw_front_blocks(pl.nrest);
-#define NSK_TABW(NCH, MODE) k_gibbs_seg_tabw<NCH, MODE><<<dim3(nf + nbw), block, 0, g->stream>>>(NSK_TABW_HOT_ARGS(g, tab, nbw, nf, nullptr), cold)
-                                if (nch == 1) { if (mode == 0) NSK_TABW(1, 0); else if (mode == 1) NSK_TABW(1, 1); else NSK_TABW(1, 2); }
-                                else { if (mode == 0) NSK_TABW(2, 0); else if (mode == 1) NSK_TABW(2, 1); else NSK_TABW(2, 2); }
-#undef NSK_TABW
-                            }
-                            else if (nch == 1) k_gibbs_seg_tab<VT, 1><<<dim3(nbp), block, 0, g->stream>>>(d, tab, burnin, K0, K1, S0, S1, nullptr, 0u);
-                            else k_gibbs_seg_tab<VT, 2><<<dim3(nbp), block, 0, g->stream>>>(d, tab, burnin, K0, K1, S0, S1, nullptr, 0u);
-                        }
-                        else if (kind == 4) { if (nch == 1) NSK_SEG(4, 1); else NSK_SEG(4, 2); }
-                        else if (kind == 2) { if (nch == 1) NSK_SEG(2, 1); else NSK_SEG(2, 2); }
-                        else if (kind == 0) { if (nch == 1) NSK_SEG(0, 1); else NSK_SEG(0, 2); }
-                        else { if (nch == 1) NSK_SEG(3, 1); else NSK_SEG(3, 2); }
+                    for (const NskSegPlan &pl : g->seg_plans[ph]) {
+                        if (pl.kind >= 8) launch_table<VT>(g, pl, (int)ph, burnin, src);
+                        else {
+                            const int nb = (pl.tab.ntiles + 3) / 4;
+                            const dim3 grid(8 * ((nb + 7) / 8));
+#define NSK_SEG(NCH, KIND) k_gibbs_seg<VT, KIND, NCH><<<grid, dim3(NSK_BLOCK), 0, g->stream>>>(d, pl.tab, nb, burnin, K0, K1, S0, S1)
+                            if (pl.kind == 4) NSK_BY_NCH(NSK_SEG, 4);
+                            else if (pl.kind == 2) NSK_BY_NCH(NSK_SEG, 2);
+                            else if (pl.kind == 0) NSK_BY_NCH(NSK_SEG, 0);
+                            else NSK_BY_NCH(NSK_SEG, 3);
 #undef NSK_SEG
+                        }
                         g->launches++;
                     }
                     const int nrest = (int)(g->c.phase_rest_base[ph + 1] - g->c.phase_rest_base[ph]);
@@ -412,15 +417,13 @@ static bool graph_eligible(const nsk_graph *g, bool p2p) {
 }
 
 template <typename VT>
-static int graph_build(nsk_graph *g, int sample_evidence, int burnin, bool p2p, int key, bool big) {
+static int graph_build(nsk_graph *g, int burnin, bool p2p, int key, bool big) {
     hipGraphExec_t &exec = big ? g->sweep_graph_big : g->sweep_graph;
     int &exec_key = big ? g->sweep_graph_big_key : g->sweep_graph_key;
     int &exec_launches = big ? g->sweep_graph_big_launches : g->sweep_graph_launches;
     const int nsw = big ? NSK_GRAPH_SWEEPS_BIG : NSK_GRAPH_SWEEPS;
     if (exec) { (void)hipGraphExecDestroy(exec); exec = nullptr; }
     exec_key = -1;
-    // the segment plans (kept in the handle) are built by an eager sweep-free call path: make sure they exist
-    DevGraph<VT> d = view<VT>(g);
     hipGraph_t graph = nullptr;
     // (the legacy default stream cannot be captured: a caller that pointed the library at it -- torch's
     // current stream in a process without its own streams -- keeps the eager loop)
@@ -430,37 +433,7 @@ static int graph_build(nsk_graph *g, int sample_evidence, int burnin, bool p2p, 
     for (int i = 0; i < nsw; i++) {
         for (size_t ph = 0; ph < g->seg_plans.size(); ph++)
             for (const NskSegPlan &pl : g->seg_plans[ph]) {
-                const int nbp = nsk_tab_grid(pl.tab.ntiles);
-                if (g->nchains > 1)              // every chain in one launch (chains_batched)
-                    launch_tab_chains<VT>(g, pl, burnin, 0u, 0u, 0u, 0u, g->d_counters, (uint32_t)i);
-                else if (g->p2p_fused_now) {          // the exchange inside the launch: tag = counter + i + 1
-                    TabP2P px;
-                    nsk_p2p_fill(g, px, g->d_counters, (unsigned int)(i + 1), (int)ph == g->p2p_first_phase);
-                    if (pl.nch == 1)
-                        k_gibbs_seg_tab_p2p<VT, 1><<<dim3(nbp), dim3(NSK_BLOCK), 0, g->stream>>>(d, pl.tab, burnin, 0u, 0u, 0u, 0u,
-                                                                                                 g->d_counters, (uint32_t)i, px);
-                    else
-                        k_gibbs_seg_tab_p2p<VT, 2><<<dim3(nbp), dim3(NSK_BLOCK), 0, g->stream>>>(d, pl.tab, burnin, 0u, 0u, 0u, 0u,
-                                                                                                 g->d_counters, (uint32_t)i, px);
-                }
-                else if (sizeof(VT) == 1 && pl.tab.wide) {
-                    const DevGraph<signed char> dw = view<signed char>(g);
-                    const int nbw = nsk_tabw_grid(pl.tab.ntiles);
-                    const int mode = burnin ? 1 : (g->pack_now ? 2 : 0);
-                    TabwCold cold{0u, 0u, 0u, 0u, (uint32_t)i, 0u, dw, pl.tab, pl.nrest, {}};
-                    memcpy(cold.rest, pl.rest, sizeof(cold.rest));
-                    const int nf = nsk_tabw_front_blocks(pl.nrest);
-#define NSK_TABW(NCH, MODE) k_gibbs_seg_tabw<NCH, MODE><<<dim3(nf + nbw), dim3(NSK_BLOCK), 0, g->stream>>>(NSK_TABW_HOT_ARGS(g, pl.tab, nbw, nf, g->d_counters), cold)
-                    if (pl.nch == 1) { if (mode == 0) NSK_TABW(1, 0); else if (mode == 1) NSK_TABW(1, 1); else NSK_TABW(1, 2); }
-                    else { if (mode == 0) NSK_TABW(2, 0); else if (mode == 1) NSK_TABW(2, 1); else NSK_TABW(2, 2); }
-#undef NSK_TABW
-                }
-                else if (pl.nch == 1)
-                    k_gibbs_seg_tab<VT, 1><<<dim3(nbp), dim3(NSK_BLOCK), 0, g->stream>>>(d, pl.tab, burnin, 0u, 0u, 0u, 0u,
-                                                                                         g->d_counters, (uint32_t)i);
-                else
-                    k_gibbs_seg_tab<VT, 2><<<dim3(nbp), dim3(NSK_BLOCK), 0, g->stream>>>(d, pl.tab, burnin, 0u, 0u, 0u, 0u,
-                                                                                         g->d_counters, (uint32_t)i);
+                launch_table<VT>(g, pl, (int)ph, burnin, CounterSrc::captured(g, i));     // (the exchange tag of sweep i: counter + i + 1)
                 launches++;
             }
         if (p2p && !g->p2p_fused_now) {
@@ -476,7 +449,6 @@ static int graph_build(nsk_graph *g, int sample_evidence, int burnin, bool p2p, 
     if (e != hipSuccess) { exec = nullptr; return nsk::fail(NSK_E_DEVICE, std::string("hipGraphInstantiate: ") + hipGetErrorString(e)); }
     exec_key = key;
     exec_launches = launches;
-    (void)sample_evidence;
     return NSK_OK;
 }
 
@@ -490,8 +462,7 @@ int nsk_gibbs_run(nsk_graph *g, int64_t nsweeps, int sample_evidence, int burnin
     bool fuse = false;
     if (p2p && g->p2p_fused && g->scan == NSK_SCAN_CHROMATIC && g->values_regular && nsweeps > 0) {
         nsk_ensure_seg_plans(g, sample_evidence);
-        fuse = g->p2p_border_all;
-        for (const auto &v : g->seg_plans) for (const NskSegPlan &pl : v) fuse = fuse && pl.kind >= 8;
+        fuse = g->p2p_border_all && g->seg_plans_all_tab;
         // (a fused call right behind a fused call continues it: the receive block already holds what the first
         // sweep reads -- nothing to unpack into the value array and pack back)
         if (fuse && !g->p2p_close_pending) {
@@ -508,9 +479,7 @@ int nsk_gibbs_run(nsk_graph *g, int64_t nsweeps, int sample_evidence, int burnin
     if (!p2p && !burnin && g->nchains == 1 && g->scan == NSK_SCAN_CHROMATIC && g->values_regular && g->c.vbytes == 1 && nsweeps > 0 &&
         nsk_tables_only(g) && !nsk::diag_env("NSK_NO_PACK_TALLY")) {
         nsk_ensure_seg_plans(g, sample_evidence);
-        bool all_wide = true;
-        for (const auto &v : g->seg_plans) for (const NskSegPlan &pl : v) all_wide = all_wide && pl.kind >= 8 && pl.tab.wide;
-        g->pack_now = all_wide;
+        g->pack_now = g->seg_plans_all_wide;
     }
     struct Done { nsk_graph *g; bool fuse, keep; ~Done() { g->p2p_fused_now = false; if (fuse) g->p2p_close_pending = true;
                                                             if (!keep) (void)nsk_unpack_tally(g);
@@ -522,10 +491,8 @@ int nsk_gibbs_run(nsk_graph *g, int64_t nsweeps, int sample_evidence, int burnin
         int rc = NSK_OK;
         nsk_refresh_prog_weights(g);
         nsk_ensure_seg_plans(g, sample_evidence);
-        bool all_tab = true;
-        for (const auto &v : g->seg_plans) for (const NskSegPlan &pl : v) all_tab = all_tab && pl.kind >= 8;
         const int key = g->seg_plans_key | (burnin ? 8 : 0) | (p2p ? 16 : 0) | (fuse ? 32 : 0) | (g->pack_now ? 64 : 0);
-        if (all_tab && left >= NSK_GRAPH_SWEEPS) {
+        if (g->seg_plans_all_tab && left >= NSK_GRAPH_SWEEPS) {
             // two sizes: NSK_GRAPH_SWEEPS_BIG sweeps per replay while the call is long enough, NSK_GRAPH_SWEEPS for what is left
             for (int big = (left >= NSK_GRAPH_SWEEPS_BIG && !nsk::diag_env("NSK_NO_BIG_GRAPH")) ? 1 : 0; big >= 0; big--) {
                 const int nsw = big ? NSK_GRAPH_SWEEPS_BIG : NSK_GRAPH_SWEEPS;
@@ -533,8 +500,8 @@ int nsk_gibbs_run(nsk_graph *g, int64_t nsweeps, int sample_evidence, int burnin
                 int &exec_key = big ? g->sweep_graph_big_key : g->sweep_graph_key;
                 if (left < nsw || g->sweep_graph_off) continue;
                 if (exec_key != key) {
-                    rc = g->c.vbytes == 1 ? graph_build<int8_t>(g, sample_evidence, burnin, p2p, key, big != 0)
-                                          : graph_build<int32_t>(g, sample_evidence, burnin, p2p, key, big != 0);
+                    rc = g->c.vbytes == 1 ? graph_build<int8_t>(g, burnin, p2p, key, big != 0)
+                                          : graph_build<int32_t>(g, burnin, p2p, key, big != 0);
                     if (rc) {               // capture is an optimisation: without it the eager loop runs
                         g->sweep_graph_off = true;
                         (void)hipGetLastError();

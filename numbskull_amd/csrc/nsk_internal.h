@@ -29,9 +29,9 @@ int fail(int code, const std::string &msg);       // records nsk_last_error, ret
 struct NskSegPlan { int kind, nch; nsk::SegTable tab;         // one prepared segment launch (nsk_gibbs.hip)
                     uint32_t nrest = 0, rest[NSK_TABW_REST_MAX] = {}; };      // wide launches: the quads that are not wide (TabwCold.rest)
 
-// a learning launch over (mostly) wide quads, prepared once (nsk_learn.hip): its segment table in whole quads, whether the
-// wide kernel takes it, and its quads that are not wide ones
-struct NskLearnWidePlan { int key = -1; bool wide = false; int vt = 0; nsk::SegTable tab; uint32_t nrest = 0, rest[NSK_TABW_REST_MAX] = {}; };
+// one prepared learning segment launch (nsk_learn.hip), built for key = its draw tables are usable: the segment table -- in
+// whole quads, with the quads that are not wide ones, when the wide kernel takes the launch (wide); tile by tile otherwise
+struct NskLearnSegPlan { int key = -1; bool wide = false; nsk::SegTable tab; uint32_t nrest = 0, rest[NSK_TABW_REST_MAX] = {}; };
 
 // Sample trace (nsk_trace_setup): thinned joint samples recorded on the device.  After every `every`-th tallied sweep
 // one k_trace_record_* launch appends a row: for every chain the values of the traced variables, in DEVICE column order
@@ -76,11 +76,12 @@ struct nsk_graph {
     nsk::Compiled c;
     NskTrace trace;
     NskEnergy energy;
-    std::vector<NskLearnWidePlan> learn_wide_plans;      // per Compiled::learn_seg entry
+    std::vector<NskLearnSegPlan> learn_seg_plans;        // per Compiled::learn_seg entry
     // the inference sweep's segment launches per colour, kept across calls (the N-rank loops sweep one
     // epoch per call); key = sample_evidence | draw tables usable << 1
     std::vector<std::vector<NskSegPlan>> seg_plans;
     int seg_plans_key = -1;
+    bool seg_plans_all_tab = false, seg_plans_all_wide = false;   // every plan is a table launch (kind 8); ... a wide one (they live with the key)
     // captured sweep sequence (hipGraph): NSK_GRAPH_SWEEPS inference sweeps of a handle whose sweep is
     // table launches only (+ the peer-to-peer exchange), replayed with the sweep index in device memory
     hipGraphExec_t sweep_graph = nullptr;

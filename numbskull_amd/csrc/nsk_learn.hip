@@ -27,6 +27,64 @@ static void refresh_after_update(nsk_graph *g, int set, hipStream_t st) {
     }
 }
 
+// The segment launches of learning (Compiled::learn_seg), each prepared once per handle and per use_tab (its draw tables
+// are usable: the values lie in their domains) -- walking a launch's quad descriptors on the host for every launch of every
+// sweep cost more than the launch itself from a few million variables on.
+static void learn_seg_entry(SegEntry &en, const Compiled::SegLaunch &sl, int i, int nt, int lead, bool use_tab) {
+    en.ntiles_lead = (uint32_t)nt | ((uint32_t)lead << 30);
+    en.pos0 = sl.pos0[i]; en.adj_off = sl.adj_off[i]; en.prog = sl.prog[i]; en.zoff = sl.zoff[i];
+    en.zmask_ev = (sl.zmask[i] & 0xFFu) | (((uint32_t)sl.ev[i] & 0xFFu) << 8);
+    en.aff_off = use_tab ? sl.aff[i] : NSK_NO_STREAM;         // implicit adjacency (table kernels)
+}
+static const NskLearnSegPlan &learn_seg_plan(nsk_graph *g, const Compiled::SegLaunch &sl, bool use_tab, bool byte_values) {
+    if (g->learn_seg_plans.size() != g->c.learn_seg.size()) g->learn_seg_plans.assign(g->c.learn_seg.size(), NskLearnSegPlan());
+    NskLearnSegPlan &p = g->learn_seg_plans[(size_t)(&sl - g->c.learn_seg.data())];
+    if (p.key == (use_tab ? 1 : 0)) return p;
+    p = NskLearnSegPlan();
+    p.key = use_tab ? 1 : 0;
+    SegTable &tab = p.tab;
+    // (mostly) wide quads: the wide learning kernel, its tiles numbered in whole quads like the inference launches
+    // (lead = dead tiles in front of a segment that does not start on a quad boundary)
+    if (use_tab && byte_values) {
+        memset(&tab, 0, sizeof(tab));
+        tab.n = sl.n;
+        int nwide = 0;
+        for (int i = 0; i < NSK_SEG_MAX; i++) {
+            SegEntry &en = tab.e[i];
+            en.tile_start = tab.ntiles;
+            if (i >= sl.n) continue;
+            const int nt_i = sl.tile_start[i + 1] - sl.tile_start[i];
+            const int64_t pos0 = sl.pos0[i];
+            const int lead = (int)((pos0 / 64) & 3);
+            learn_seg_entry(en, sl, i, nt_i, lead, true);
+            en.push_off = NSK_NO_STREAM;
+            en.wide_off = sl.wide[i] >= 0 ? (uint32_t)sl.wide[i] : NSK_NO_STREAM;     // (the descriptors start at the quad of pos0)
+            if (sl.wide[i] >= 0) {
+                const int stride = NSK_WIDE_STRIDE(sl.nch);
+                for (int64_t P = (pos0 + 255) & ~(int64_t)255; P + 256 <= pos0 + 64 * (int64_t)nt_i; P += 256)
+                    if (g->c.seg_wide[(size_t)sl.wide[i] + (size_t)((P >> 8) - (pos0 >> 8)) * stride] != 0xFFFFFFFFu) nwide++;
+            }
+            tab.ntiles += (nt_i + lead + 3) & ~3;
+        }
+        const char *min_env = nsk::diag_env("NSK_WIDE_LEARN_MIN");                 // (diagnostic; the small-grid tests use 0)
+        const int min_quads = min_env ? atoi(min_env) : NSK_WIDE_LEARN_MIN_QUADS;
+        p.wide = 8 * nwide >= tab.ntiles && tab.ntiles > 0 && tab.ntiles / 4 >= min_quads && !nsk::diag_env("NSK_NO_WIDE_LEARN");
+        if (p.wide) { nsk_tabw_rest_list(g->c, tab, sl.nch, p.nrest, p.rest); return p; }
+    }
+    // tile by tile; table launches number their tiles virtually: every segment is padded to whole trips
+    memset(&tab, 0, sizeof(tab));
+    tab.n = sl.n;
+    int vt = 0;
+    for (int i = 0; i < NSK_SEG_MAX; i++) {
+        const int nt_i = i < sl.n ? sl.tile_start[i + 1] - sl.tile_start[i] : 0;
+        tab.e[i].tile_start = use_tab ? vt : (i < sl.n ? sl.tile_start[i] : sl.tile_start[sl.n]);
+        vt += (nt_i + NSK_LEARN_TPW - 1) / NSK_LEARN_TPW * NSK_LEARN_TPW;
+        learn_seg_entry(tab.e[i], sl, i, nt_i, 0, use_tab);
+    }
+    tab.ntiles = use_tab ? vt : sl.tile_start[sl.n];
+    return p;
+}
+
 // The chromatic learning sweep is instantiated four times (value type x accumulator flavour) and every
 // instantiation carries a dozen kernels: the Makefile compiles this file once per instantiation
 // (-DNSK_LEARN_PART=0..3, in parallel; part 0 also holds the entry point) -- one translation unit with all four
@@ -239,98 +297,37 @@ int nsk_learn_chromatic(nsk_graph *g, int64_t nsweeps, double step, double decay
             for (const Compiled::SegLaunch &sl : g->c.learn_seg) {       // homogeneous segments
                 if (sl.phase != (int)ph) continue;
                 const bool use_tab = sl.tab && g->values_regular;
-                SegTable tab;
-                memset(&tab, 0, sizeof(tab));
-                tab.n = sl.n;
-                // (mostly) wide quads: the wide learning kernel, its tiles numbered in whole quads like the inference
-                // launches (lead = dead tiles in front of a segment that does not start on a quad boundary)
-                if constexpr (sizeof(VT) == 1) if (use_tab) {
-                    // (prepared once per handle: walking the launch's quad descriptors on the host for every launch of every sweep
-                    //  cost more than the launch itself from a few million variables on)
-                    if (g->learn_wide_plans.size() != g->c.learn_seg.size()) g->learn_wide_plans.assign(g->c.learn_seg.size(), NskLearnWidePlan());
-                    NskLearnWidePlan &wp = g->learn_wide_plans[(size_t)(&sl - g->c.learn_seg.data())];
-                    if (wp.key != 1) {
-                        wp = NskLearnWidePlan();
-                        wp.key = 1;
-                        SegTable &wt = wp.tab;
-                        memset(&wt, 0, sizeof(wt));
-                        wt.n = sl.n;
-                        int vt = 0, nwide = 0;
-                        for (int i = 0; i < NSK_SEG_MAX; i++) {
-                            SegEntry &en = wt.e[i];
-                            en.tile_start = vt;
-                            if (i >= sl.n) continue;
-                            const int nt_i = sl.tile_start[i + 1] - sl.tile_start[i];
-                            const int64_t pos0 = sl.pos0[i];
-                            const int lead = (int)((pos0 / 64) & 3);
-                            en.ntiles_lead = (uint32_t)nt_i | ((uint32_t)lead << 30);
-                            en.pos0 = sl.pos0[i]; en.adj_off = sl.adj_off[i]; en.prog = sl.prog[i]; en.zoff = sl.zoff[i];
-                            en.zmask_ev = (sl.zmask[i] & 0xFFu) | (((uint32_t)sl.ev[i] & 0xFFu) << 8);
-                            en.aff_off = sl.aff[i];
-                            en.push_off = NSK_NO_STREAM;
-                            en.wide_off = sl.wide[i] >= 0 ? (uint32_t)sl.wide[i] : NSK_NO_STREAM;     // (the descriptors start at the quad of pos0)
-                            if (sl.wide[i] >= 0) {
-                                const int stride = NSK_WIDE_STRIDE(sl.nch);
-                                for (int64_t P = (pos0 + 255) & ~(int64_t)255; P + 256 <= pos0 + 64 * (int64_t)nt_i; P += 256)
-                                    if (g->c.seg_wide[(size_t)sl.wide[i] + (size_t)((P >> 8) - (pos0 >> 8)) * stride] != 0xFFFFFFFFu) nwide++;
-                            }
-                            vt += (nt_i + lead + 3) & ~3;
-                        }
-                        wt.ntiles = vt;
-                        wp.vt = vt;
-                        const char *min_env = nsk::diag_env("NSK_WIDE_LEARN_MIN");                 // (diagnostic; the small-grid tests use 0)
-                        const int min_quads = min_env ? atoi(min_env) : NSK_WIDE_LEARN_MIN_QUADS;
-                        wp.wide = 8 * nwide >= vt && vt > 0 && vt / 4 >= min_quads && !nsk::diag_env("NSK_NO_WIDE_LEARN");
-                        if (wp.wide) nsk_tabw_rest_list(g->c, wt, sl.nch, wp.nrest, wp.rest);
-                    }
-                    if (wp.wide) {
-                        const DevGraph<signed char> &dw = d;
-                        const bool fuse = SMALLW && pend.valid && pend.tabs_here;
-                        const ApplyArgs &prev = fuse ? pend.aa : no_update;
-                        TabwRest rest;
-                        rest.n = wp.nrest;
-                        memcpy(rest.q, wp.rest, sizeof(rest.q));
-                        const int grid = nsk_learn_tabw_grid(wp.vt) + (SMALLW ? NSK_SERVICE_BLOCKS : 0) + nsk_tabw_front_blocks(rest.n);
-                        if (sl.nch == 1) k_learn_seg_tabw<SMALLW, 1><<<dim3(grid), dim3(NSK_BLOCK), shmem, g->stream>>>(dw, wp.tab, lp, prev, rest);
-                        else k_learn_seg_tabw<SMALLW, 2><<<dim3(grid), dim3(NSK_BLOCK), shmem, g->stream>>>(dw, wp.tab, lp, prev, rest);
-                        if (fuse) pend.valid = false;
-                        g->launches++;
-                        continue;
-                    }
-                }
-                // table launches number their tiles virtually: every segment is padded to whole trips
-                int vt = 0;
-                for (int i = 0; i < NSK_SEG_MAX; i++) {
-                    SegEntry &en = tab.e[i];
-                    const int nt_i = i < sl.n ? sl.tile_start[i + 1] - sl.tile_start[i] : 0;
-                    en.tile_start = use_tab ? vt : (i < sl.n ? sl.tile_start[i] : sl.tile_start[sl.n]);
-                    vt += (nt_i + NSK_LEARN_TPW - 1) / NSK_LEARN_TPW * NSK_LEARN_TPW;
-                    en.ntiles_lead = (uint32_t)nt_i;
-                    en.pos0 = sl.pos0[i]; en.adj_off = sl.adj_off[i]; en.prog = sl.prog[i];
-                    en.zoff = sl.zoff[i];
-                    en.zmask_ev = (sl.zmask[i] & 0xFFu) | (((uint32_t)sl.ev[i] & 0xFFu) << 8);
-                    en.aff_off = use_tab ? sl.aff[i] : NSK_NO_STREAM;         // implicit adjacency (table kernel)
-                }
-                tab.ntiles = use_tab ? vt : sl.tile_start[sl.n];
-                const int grid = nsk_learn_seg_grid(sl, nw, SMALLW, g->values_regular);
+                const NskLearnSegPlan &pl = learn_seg_plan(g, sl, use_tab, sizeof(VT) == 1);
+                const SegTable &tab = pl.tab;
+                // the previous class's update rides in a table launch (block 0 of the service blocks in front)
+                const bool fuse = use_tab && SMALLW && pend.valid && pend.tabs_here;
+                const ApplyArgs &prev = fuse ? pend.aa : no_update;
+                const int service = SMALLW ? NSK_SERVICE_BLOCKS : 0;
 #define NSK_LSEG(KIND, NCH) k_learn_seg<VT, SMALLW, KIND, NCH><<<dim3(grid), dim3(NSK_BLOCK), shmem, g->stream>>>(d, tab, lp)
-                if (use_tab) {
-                    // the previous class's update rides in this launch (block 0 of the service blocks in front)
-                    const bool fuse = SMALLW && pend.valid && pend.tabs_here;
-                    const ApplyArgs &prev = fuse ? pend.aa : no_update;
-                    const int gridx = grid + (SMALLW ? NSK_SERVICE_BLOCKS : 0);
-#define NSK_LTAB(NCH) k_learn_seg_tab<VT, SMALLW, NCH, NSK_LEARN_TPW><<<dim3(gridx), dim3(NSK_BLOCK), shmem, g->stream>>>(d, tab, lp, prev)
-                    if (sl.nch == 1) NSK_LTAB(1); else NSK_LTAB(2);
-#undef NSK_LTAB
-                    if (fuse) pend.valid = false;
+#define NSK_LTAB(NCH) k_learn_seg_tab<VT, SMALLW, NCH, NSK_LEARN_TPW><<<dim3(grid + service), dim3(NSK_BLOCK), shmem, g->stream>>>(d, tab, lp, prev)
+#define NSK_LTABW(NCH) k_learn_seg_tabw<SMALLW, NCH><<<dim3(grid), dim3(NSK_BLOCK), shmem, g->stream>>>(d, tab, lp, prev, rest)
+                if (pl.wide) {
+                    if constexpr (sizeof(VT) == 1) {        // (only a plan over byte values is wide)
+                        TabwRest rest;
+                        rest.n = pl.nrest;
+                        memcpy(rest.q, pl.rest, sizeof(rest.q));
+                        const int grid = nsk_learn_tabw_grid(tab.ntiles) + service + nsk_tabw_front_blocks(rest.n);
+                        if (sl.nch == 1) NSK_LTABW(1); else NSK_LTABW(2);
+                    }
+                } else {
+                    const int grid = nsk_learn_seg_grid(sl, nw, SMALLW, g->values_regular);
+                    if (use_tab) { if (sl.nch == 1) NSK_LTAB(1); else NSK_LTAB(2); }
+                    else if (sl.tab) { if (sl.nch == 1) NSK_LSEG(0, 1); else NSK_LSEG(0, 2); }   // tables unusable: the
+                                                                           // generic slot algebra serves every function
+                    else if (sl.kind == 4) { if (sl.nch == 1) NSK_LSEG(4, 1); else NSK_LSEG(4, 2); }
+                    else if (sl.kind == 2) { if (sl.nch == 1) NSK_LSEG(2, 1); else NSK_LSEG(2, 2); }
+                    else if (sl.kind == 0) { if (sl.nch == 1) NSK_LSEG(0, 1); else NSK_LSEG(0, 2); }
+                    else { if (sl.nch == 1) NSK_LSEG(3, 1); else NSK_LSEG(3, 2); }
                 }
-                else if (sl.tab) { if (sl.nch == 1) NSK_LSEG(0, 1); else NSK_LSEG(0, 2); }   // tables unusable: the
-                                                                       // generic slot algebra serves every function
-                else if (sl.kind == 4) { if (sl.nch == 1) NSK_LSEG(4, 1); else NSK_LSEG(4, 2); }
-                else if (sl.kind == 2) { if (sl.nch == 1) NSK_LSEG(2, 1); else NSK_LSEG(2, 2); }
-                else if (sl.kind == 0) { if (sl.nch == 1) NSK_LSEG(0, 1); else NSK_LSEG(0, 2); }
-                else { if (sl.nch == 1) NSK_LSEG(3, 1); else NSK_LSEG(3, 2); }
+#undef NSK_LTABW
+#undef NSK_LTAB
 #undef NSK_LSEG
+                if (fuse) pend.valid = false;
                 g->launches++;
             }
             if (nlrest > 0 && !rest_in_general) {   // the other uniform and shape tiles: descriptor-driven kernel

@@ -78,6 +78,22 @@ def test_chains_on_a_perturbed_grid(monkeypatch):
     _compare_chains(graph, 3, True, calls=((3, True), (85, False)), seed=31)
 
 
+@pytest.mark.parametrize("switch", [None, ("NSK_NO_WIDE", "1")])
+def test_chains_on_two_chunk_tiles(monkeypatch, switch):
+    """4 x 8 x 1000 grid (5- and 6-slot classes: two-chunk tiles and quads), 3 chains in one launch per class: the
+    wide-quad chain kernel and, with wide quads switched off, the tile-pair one; 85 tallied sweeps replay both captured
+    sequence sizes and end eagerly."""
+    monkeypatch.setenv("NSK_DIAG", "1")
+    monkeypatch.setenv("NSK_WIDE_MIN", "0")
+    if switch:
+        monkeypatch.setenv(*switch)
+    fg, _ = _compare_chains(build_case("slots45_3d")[1], 3, True, calls=((3, True), (85, False)), seed=31)
+    if switch:
+        assert fg.info()["wide_quads"] == 0
+    else:
+        assert fg.info()["wide_quads"] > 0
+
+
 def test_chains_of_an_lr_graph_one_launch_per_chain():
     g = graphgen.mixed_lr_graph(200_000, seed=5)
     _compare_chains(g, 2, True, hbv=True)
