@@ -172,6 +172,38 @@ int nsk_trace_log_potential(nsk_graph *g, int on);
 int nsk_trace_download_log_potential(nsk_graph *g, int64_t first_row, int64_t nrows,
                                      double *out /* nrows x chains */);
 
+/* Per-weight sufficient statistics (FactorGraph.weight_statistics / sample(..., weight_statistics=...)): the
+ * log-potential's sum split by weight, S_w = the sum of eval_factor(f, state) over the factors f with weightId == w, in
+ * the caller's weight numbering; a weight without a factor reads 0.  scaled != 0: every term is the one rounded product
+ * featureValue[f] * eval_factor(f, state).  Evaluated on the device through a by-weight index list: one lane per weight
+ * of at most 16 factors, one wave per piece of at most 2048 factors of a longer one, and a second launch that adds the
+ * pieces of the weights that have several.  The sums are REPRODUCIBLE -- a function of graph, state and `scaled` only:
+ * how a weight is cut depends on its own length, every addition has a fixed order, there are no floating-point atomics
+ * and no constant is taken from the device; so S_w has the same bits for any chain index or chain count, for a query
+ * of all weights or a trace column of some, on every run.  S_w differs from the exactly rounded sum of its n_w terms by
+ * at most (n_w + 1) * 2^-53 * sum |term|, and is exact where the terms are integers.
+ * The calls follow nsk_log_potential in every rule: `which`, the chains, the handles refused (NSK_E_INVALID), reading
+ * without changing anything.  The first one uploads what nsk_log_potential uploads and, in addition, the by-weight list
+ * (4 bytes a factor), the work list of the weights asked for (8 bytes a short weight, 16 a piece) and, with `scaled`,
+ * the feature values (8 bytes a factor) -- all in nsk_graph_info.device_bytes; NSK_E_NOMEM names the size of what does
+ * not fit.  A handle that never calls them allocates and launches nothing for them.
+ * nsk_weight_stats: out[i * nweight + w] = S_w of chain first_chain + i.
+ * nsk_trace_weight_stats: valid while a trace is set up (NSK_E_INVALID otherwise).  wids = the caller's weight ids
+ * (nwids >= 1, repeats allowed, the column order kept; an id outside [0, nweight) is NSK_E_INDEX), or NULL with
+ * nwids = 0 for all nweight weights.  Allocates capacity x chains x nwids doubles, zeroed (NSK_E_NOMEM otherwise); from
+ * then on every record launch is followed on the stream by the evaluation of the state just recorded, every chain, of
+ * the factors of THOSE weights only.  Calling it again replaces the column (a call refused for its arguments leaves the
+ * old one); nwids < 0 switches it off and frees it; nsk_trace_setup (replace or tear down) resets it to off;
+ * nsk_trace_clear keeps it.  It is independent of the lp column.
+ * nsk_trace_download_weight_stats: synchronises, then writes rows first_row .. first_row + nrows - 1 as
+ * nrows x chains x nwids doubles; rows beyond those recorded, or no stats column: NSK_E_INVALID.
+ * nsk_profile_* keeps counting sweep-kernel launches only. */
+int nsk_weight_stats(nsk_graph *g, int which, int64_t first_chain, int64_t nchains, int scaled,
+                     double *out /* nchains x nweight */);
+int nsk_trace_weight_stats(nsk_graph *g, const int64_t *wids, int64_t nwids, int scaled);
+int nsk_trace_download_weight_stats(nsk_graph *g, int64_t first_row, int64_t nrows,
+                                    double *out /* nrows x chains x nwids */);
+
 /* RNG: the chromatic scan draws from Philox4x32-10 keyed by `seed`.  A variable's generator id is
  * its position in the compiled layout (nsk_graph_get_layout), so samples are a function of the seed
  * AND the layout the library chose (device, flags and diagnostic switches being equal, a graph

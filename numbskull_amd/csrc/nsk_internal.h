@@ -33,6 +33,34 @@ struct NskSegPlan { int kind, nch; nsk::SegTable tab;         // one prepared se
 // whole quads, with the quads that are not wide ones, when the wide kernel takes the launch (wide); tile by tile otherwise
 struct NskLearnSegPlan { int key = -1; bool wide = false; nsk::SegTable tab; uint32_t nrest = 0, rest[NSK_TABW_REST_MAX] = {}; };
 
+// Per-weight statistics (nsk_weight_stats / the trace's stats column; nsk_kernels_wstats.h).  A PLAN is the device work
+// list of a selection of weights: one lane per short weight, one wave per piece of a longer one, a second launch for
+// the weights of several pieces, each item with the output column it serves (nsk_api.hip wstats_plan_build).
+#define NSK_WSTATS_SHORT 16         // a weight of at most this many factors is one lane's
+#define NSK_WSTATS_PIECE 2048       // entries of one wave's piece (32 a lane)
+#define NSK_WSTATS_MAX_BLOCKS 2048  // the lanes and waves of a larger plan loop (8 blocks per CU)
+struct NskWstatsPlan {
+    uint2 *shorts = nullptr;
+    uint4 *pieces = nullptr, *multi = nullptr;
+    double *partial = nullptr;         // partial_chains x npartial piece sums of the weights of several pieces
+    unsigned int len_end[NSK_WSTATS_SHORT] = {};    // shorts below len_end[k] have at most k + 1 entries
+    int64_t nshort = 0, npiece = 0, nmulti = 0, npartial = 0, ncols = 0;
+    int partial_chains = 0;
+    int64_t device_bytes = 0;          // what the plan added to the handle's device_bytes
+};
+// The by-weight index list (built on the host and uploaded at the first use), the plan of ALL weights and a query's
+// result buffer.  wf_off stays on the host: the plans carry the offsets.  A handle that never asks holds none of this.
+struct NskWstats {
+    bool ready = false;
+    std::vector<uint32_t> wf_off;      // [nweight + 1] by weight SLOT (f_rec.z): its entries in wf_idx
+    std::vector<int32_t> wf_first;     // [nweight] the first of them (what the plans sort the short weights by)
+    int32_t *wf_idx = nullptr;         // [nfactor] device: factor ids, ascending inside a weight
+    bool all_ready = false;
+    NskWstatsPlan all;                 // every weight, output column = the caller's id
+    double *result = nullptr;          // result_chains x nweight
+    int result_chains = 0;
+};
+
 // Sample trace (nsk_trace_setup): thinned joint samples recorded on the device.  After every `every`-th tallied sweep
 // one k_trace_record_* launch appends a row: for every chain the values of the traced variables, in DEVICE column order
 // (sorted by internal id; every internal id when cols == nullptr, "all variables") -- bit-packed, ceil(ndev / 64) words a
@@ -51,6 +79,10 @@ struct NskTrace {
     std::vector<int64_t> sweep_index;  // per recorded row: the handle's sweep index it was taken after
     double *lp = nullptr;              // the lp column (nsk_trace_log_potential): capacity x chains log-potentials, or off
     int64_t lp_bytes = 0;              // ... and what it added to the handle's device_bytes
+    double *ws = nullptr;              // the stats column (nsk_trace_weight_stats): capacity x chains x ws_plan.ncols sums, or off
+    NskWstatsPlan ws_plan;             // ... the work list of its selection
+    bool ws_scaled = false;
+    int64_t ws_bytes = 0;              // ... and what column and plan added to the handle's device_bytes
 };
 
 // Log-potential (nsk_log_potential / nsk_factor_values / the trace's lp column): the factor walk of nsk_kernels_energy.h
@@ -76,6 +108,7 @@ struct nsk_graph {
     nsk::Compiled c;
     NskTrace trace;
     NskEnergy energy;
+    NskWstats wstats;
     std::vector<NskLearnSegPlan> learn_seg_plans;        // per Compiled::learn_seg entry
     // the inference sweep's segment launches per colour, kept across calls (the N-rank loops sweep one
     // epoch per call); key = sample_evidence | draw tables usable << 1
@@ -452,3 +485,7 @@ int nsk_trace_record(nsk_graph *g);                 // one row of the sample tra
 // the log-potential of `nchains` chains from `val` on / every factor's value, enqueued on the handle's stream (nsk_energy.hip)
 int nsk_energy_enqueue(nsk_graph *g, const void *val, int nchains, bool packed_bytes, double *out);
 int nsk_factor_values_enqueue(nsk_graph *g, const void *val, double *out);
+// the per-weight statistics of `nchains` chains from `val` on, as `plan` lists them: chain r's sums at out + r * out_stride
+// (nsk_wstats.hip; the columns of weights without a factor are not written)
+int nsk_wstats_enqueue(nsk_graph *g, const NskWstatsPlan &plan, const void *val, int nchains, bool packed_bytes, bool scaled,
+                       double *out, int64_t out_stride);

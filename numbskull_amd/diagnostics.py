@@ -17,6 +17,10 @@ positive sequence; Geyer, "Practical Markov chain Monte Carlo", Statistical Scie
 The log-potentials ``lp`` of ``FactorGraph.sample(..., log_potential=True)``, shape ``(samples, chains)``, are one
 more column: ``effective_sample_size(lp[:, :, None])`` is the ESS of the joint state, and ``best_sample(lp)`` finds
 the most probable sample recorded.
+
+The per-weight statistics of ``FactorGraph.sample(..., weight_statistics=...)``, shape ``(samples, chains, weights)``,
+are a trace like any other; ``moment_gap`` compares their mean with a target (the evidence chain's statistics, or an
+exact expectation): the log-likelihood gradient of weight learning, with its Monte-Carlo standard error.
 """
 
 import numpy as np
@@ -102,3 +106,26 @@ def best_sample(lp):
         raise ValueError("log-potentials have shape (samples, chains) with at least one entry, got %r" % (x.shape,))
     row, chain = np.unravel_index(int(np.argmax(x)), x.shape)
     return int(row), int(chain)
+
+
+def moment_gap(stats, target):
+    """``(gap, mcse)`` of per-weight statistics ``stats`` (samples, chains, weights) against ``target`` (weights,):
+    ``gap`` is the mean over samples and chains minus ``target`` -- with ``target`` the statistics of the evidence
+    chain, minus the log-likelihood gradient the learning sweeps estimate one visit at a time -- and ``mcse`` its
+    Monte-Carlo standard error, the standard deviation over samples and chains divided by
+    ``sqrt(effective_sample_size(stats))``.  ``mcse`` is NaN where the statistic never moves and wherever the
+    effective sample size is undefined (one chain, fewer than 4 samples)."""
+    x = np.asarray(stats, np.float64)
+    t = np.asarray(target, np.float64)
+    if x.ndim != 3 or x.shape[0] * x.shape[1] == 0:
+        raise ValueError("statistics have shape (samples, chains, weights) with at least one sample, got %r" % (x.shape,))
+    if t.shape != (x.shape[2],):
+        raise ValueError("target has shape (weights,) = (%d,), got %r" % (x.shape[2], t.shape))
+    flat = x.reshape(-1, x.shape[2])
+    gap = flat.mean(axis=0) - t
+    sd = flat.std(axis=0, ddof=1) if flat.shape[0] > 1 else np.full(x.shape[2], np.nan)
+    ess = effective_sample_size(x)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        mcse = sd / np.sqrt(ess)
+    mcse[~(sd > 0)] = np.nan
+    return gap, mcse

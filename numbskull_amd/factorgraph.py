@@ -443,7 +443,7 @@ class FactorGraph(object):
 
     # ------------------------------------------------------------------ sample traces
     def sample(self, epochs, var_ids=None, thin=1, burnin_epochs=0, sample_evidence=False, var_copy=0,
-               weight_copy=0, log_potential=False):
+               weight_copy=0, log_potential=False, weight_statistics=None, feature_scaled=False):
         """``inference(burnin_epochs, epochs, sample_evidence, var_copy=..., weight_copy=...)`` that also returns
         the joint samples: after every ``thin``-th tallied sweep the device records the values of ``var_ids``
         (any variables, any order; None = all) without returning to the host (nsk_trace_setup).  Returns an array
@@ -454,10 +454,26 @@ class FactorGraph(object):
         ``log_potential=True`` returns ``(samples, lp)``: ``lp[i, r]``, float64 ``(epochs // thin, chains)``, is the
         log-potential of the whole state of chain ``r`` when row ``i`` was taken, whatever ``var_ids`` keeps --
         the doubles ``log_potential()`` gives for that state, evaluated on the device behind the row
-        (nsk_trace_log_potential)."""
+        (nsk_trace_log_potential).
+        ``weight_statistics=True`` or a list of weight ids (any order, repeats allowed) adds a LAST element to the
+        returned tuple: float64 ``(epochs // thin, chains, nsel)``, the per-weight sufficient statistics
+        ``weight_statistics()`` gives for the state of every row, evaluated on the device behind the row for the
+        selected weights only (nsk_trace_weight_stats); ``feature_scaled`` as in ``weight_statistics``.
+        ``numbskull_amd.diagnostics.moment_gap`` compares them with a target."""
         epochs, thin = int(epochs), int(thin)
         if thin < 1:
             raise ValueError("thin must be at least 1")
+        stats_on = weight_statistics is not None and weight_statistics is not False
+        wids = None
+        if stats_on and weight_statistics is not True:
+            wids = np.asarray(weight_statistics)
+            if wids.ndim != 1 or wids.size == 0 or wids.dtype.kind not in "iu":
+                raise ValueError("weight_statistics is True or a non-empty list of weight ids")
+            if wids.min() < 0 or wids.max() >= self.weight.shape[0]:
+                raise IndexError("weight_statistics: weight id out of range")
+            wids = _lib.as_c(wids, np.int64)
+        if feature_scaled and not stats_on:
+            raise ValueError("feature_scaled goes with weight_statistics")
         L, h = _lib.lib(), self._engine()
         if burnin_epochs > 0:
             self.burnIn(burnin_epochs, sample_evidence, var_copy=var_copy, weight_copy=weight_copy)
@@ -472,7 +488,10 @@ class FactorGraph(object):
         out = np.zeros((rows, nchains, ncols), dtype)
         traced = rows > 0 and ncols > 0         # (an empty result needs no trace)
         lp = np.zeros((rows, nchains), np.float64) if log_potential else None
-        if log_potential and rows > 0 and not traced:      # no columns asked for: the lp column rides on a one-column trace
+        nsel = 0 if not stats_on else (self.weight.shape[0] if wids is None else len(wids))
+        stats = np.zeros((rows, nchains, nsel), np.float64) if stats_on else None
+        stats_traced = stats_on and nsel > 0
+        if (log_potential or stats_traced) and rows > 0 and not traced:      # no columns asked for: the lp and stats columns ride on a one-column trace
             first = _lib.as_c(np.zeros(1), np.int64)
             _lib.check(L.nsk_trace_setup(h, _lib.ptr(first), 1, thin, rows))
             traced = True
@@ -481,18 +500,46 @@ class FactorGraph(object):
         try:
             if traced and log_potential:
                 _lib.check(L.nsk_trace_log_potential(h, 1))
+            if traced and stats_traced:
+                _lib.check(L.nsk_trace_weight_stats(h, _lib.ptr(wids), 0 if wids is None else nsel, 1 if feature_scaled else 0))
             self.inference(0, epochs, sample_evidence, var_copy=var_copy, weight_copy=weight_copy)
             if traced and ncols > 0:
                 _lib.check(L.nsk_trace_download(h, 0, rows, _lib.ptr(out), None))
             if traced and log_potential:
                 _lib.check(L.nsk_trace_download_log_potential(h, 0, rows, _lib.ptr(lp)))
+            if traced and stats_traced:
+                _lib.check(L.nsk_trace_download_weight_stats(h, 0, rows, _lib.ptr(stats)))
         except BaseException:
             if traced:
                 L.nsk_trace_setup(h, None, 0, 1, 0)     # (its status must not replace the exception under way)
             raise
         if traced:
             _lib.check(L.nsk_trace_setup(h, None, 0, 1, 0))
+        if stats_on:
+            return (out, lp, stats) if log_potential else (out, stats)
         return (out, lp) if log_potential else out
+
+    # ------------------------------------------------------------------ per-weight statistics
+    def weight_statistics(self, var_copy=0, evidence_chain=False, feature_scaled=False):
+        """The sufficient statistics of a state: for every weight the sum of the values of its factors (the
+        log-potential's sum split by weight), evaluated on the device (nsk_weight_stats); with ``feature_scaled`` every
+        factor value is multiplied by the factor's ``featureValue`` first.  The state is ``var_value[var_copy]`` --
+        ``var_value_evid[var_copy]`` with ``evidence_chain=True`` -- pushed as ``log_potential`` pushes it.  Returns
+        float64 ``(nweight,)``, in the order of ``weight``; ``var_copy="all"`` ``(chains, nweight)``.  A weight without a
+        factor reads 0.  The sums are reproducible: equal states give equal doubles, whichever chain holds them."""
+        if _all_copies(var_copy) and evidence_chain:
+            raise ValueError('the evidence chain exists once: var_copy="all" is for the free chains')
+        L, h = _lib.lib(), self._engine()
+        nw, scaled = self.weight.shape[0], 1 if feature_scaled else 0
+        if _all_copies(var_copy):
+            nchains = self._push_chains(0, count=False)
+            out = np.zeros((nchains, nw), np.float64)
+            _lib.check(L.nsk_weight_stats(h, _lib.BUF_VALUE, 0, nchains, scaled, _lib.ptr(out)))
+            return out
+        self._push(var_copy, 0)
+        out = np.zeros(nw, np.float64)
+        _lib.check(L.nsk_weight_stats(h, _lib.BUF_VALUE_EVID if evidence_chain else _lib.BUF_VALUE, 0, 1, scaled, _lib.ptr(out)))
+        return out
 
     # ------------------------------------------------------------------ log-potential
     def log_potential(self, var_copy=0, weight_copy=0, evidence_chain=False):
