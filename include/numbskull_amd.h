@@ -253,6 +253,7 @@ int nsk_learn_sweeps(nsk_graph *g, int64_t nsweeps, double step, double decay,
 /* Introspection used by tests, bench and the multi-GPU host code. */
 typedef struct {
     int64_t nvar, nowned, ncolors, value_bytes, device_bytes;
+    /* device_bytes: bytes the handle holds now; it drops when a later call frees arrays */
     int64_t nfast, ngeneric;          /* variables on the inlined / the generic kernel path       */
     double alg_bytes_inference;       /* algorithmic bytes per sweep       */
     double alg_bytes_learning;

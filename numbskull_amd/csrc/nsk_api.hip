@@ -1,4 +1,5 @@
-// nsk_api.hip -- sweep kernels (gfx950) and the C-ABI entry points of include/numbskull_amd.h.
+// nsk_api.hip -- the C-ABI entry points of include/numbskull_amd.h: handle life cycle, state transfer, chains, exchanges
+// (sweep drivers: nsk_gibbs.hip / nsk_learn.hip; diagnostics: nsk_trace.hip, nsk_energy.hip, nsk_wstats.hip).
 //
 // Replaces the callee side of the reference's three run_pool(...) call sites
 // (numbskull/factorgraph.py:141,163,202): gibbsthread (inference.py:10-33) and
@@ -52,50 +53,6 @@ struct RcclApi {
     decltype(&ncclGetErrorString) GetErrorString = nullptr;
 };
 static RcclApi g_rccl;
-
-
-
-
-
-template <typename T>
-static int dev_alloc(nsk_graph *g, T **ptr, size_t n) {
-    size_t bytes = (n ? n : 1) * sizeof(T);
-    void *p = nullptr;
-    // (diagnostic, NSK_DIAG=1 NSK_ALLOC_ALIGN=1: arrays of a megabyte or more start on a 2 MB boundary whatever the
-    // allocator does -- where the arrays of the table kernels lie moves their launch time by 3 %)
-    static const bool align2m = nsk::diag_env("NSK_ALLOC_ALIGN") != nullptr;
-    const size_t big = (size_t)1 << 20, two = (size_t)2 << 20;
-    const bool al = align2m && bytes >= big;
-    hipError_t e = hipMalloc(&p, al ? bytes + two : bytes);
-    if (e != hipSuccess) return fail(NSK_E_NOMEM, std::string("hipMalloc: ") + hipGetErrorString(e));
-    g->allocs.push_back(p);
-    g->device_bytes += (int64_t)bytes;
-    if (al) {
-        void *raw = p;
-        p = (void *)(((uintptr_t)p + two - 1) / two * two);
-        if (p != raw) g->alloc_alias.push_back({p, raw});       // (dev_free must hand hipFree the allocation, not the aligned pointer)
-    }
-    *ptr = (T *)p;
-    return NSK_OK;
-}
-
-// frees an array dev_alloc handed out before the handle is destroyed (arrays that are re-allocated: nsk_pf_setup)
-static void dev_free(nsk_graph *g, void *p) {
-    if (!p) return;
-    void *raw = p;
-    for (size_t i = 0; i < g->alloc_alias.size(); i++)
-        if (g->alloc_alias[i].first == p) { raw = g->alloc_alias[i].second; g->alloc_alias.erase(g->alloc_alias.begin() + (long)i); break; }
-    g->allocs.erase(std::remove(g->allocs.begin(), g->allocs.end(), raw), g->allocs.end());
-    (void)hipFree(raw);
-}
-
-template <typename T>
-static int dev_upload(nsk_graph *g, T **ptr, const std::vector<T> &h) {
-    int rc = dev_alloc(g, ptr, h.size());
-    if (rc) return rc;
-    if (!h.empty()) HIPCHECK(hipMemcpyAsync(*ptr, h.data(), h.size() * sizeof(T), hipMemcpyHostToDevice, g->stream));
-    return NSK_OK;
-}
 
 // May this device keep XCD-private accumulators (workgroup-scope atomics in the issuing XCD's L2,
 // private copies picked by HW_REG_XCC_ID)?  gfx942 / gfx950 by architecture name AND a self-test, run
@@ -195,7 +152,7 @@ int nsk_graph_destroy(nsk_graph *g) {
     if (g->stream) (void)hipStreamSynchronize(g->stream);
     for (int q = 0; q < 16; q++)           // peers' allocations mapped with hipIpc
         if (g->p2p_peer_ipc[q] && g->p2p_peer_base[q]) (void)hipIpcCloseMemHandle(g->p2p_peer_base[q]);
-    for (void *p : g->allocs) (void)hipFree(p);
+    for (const NskLedger::Entry &e : g->mem.entries) nsk_free_raw(e.raw);
     for (int k = 0; k < 2; k++) if (g->xfer_host[k]) (void)hipHostFree(g->xfer_host[k]);
     if (g->cnt_host) (void)hipHostFree(g->cnt_host);
     if (g->sweep_graph) (void)hipGraphExecDestroy(g->sweep_graph);
@@ -749,9 +706,10 @@ int nsk_set_chains(nsk_graph *g, int nchains) {
     uint8_t *slab = nullptr;
     int32_t *cnt = nullptr;
     long long *tot = nullptr;
+    NskRollback rb(g->mem, nsk_free_raw);       // (an early return below leaves none of the three behind)
     if ((rc = dev_alloc(g, &slab, R * stride))) return rc;
-    if ((rc = dev_alloc(g, &cnt, R * std::max<size_t>(nc, 1)))) { dev_free(g, slab); return rc; }
-    if ((rc = dev_alloc(g, &tot, R * std::max<size_t>(nc, 1)))) { dev_free(g, slab); dev_free(g, cnt); return rc; }
+    if ((rc = dev_alloc(g, &cnt, R * std::max<size_t>(nc, 1)))) return rc;
+    if ((rc = dev_alloc(g, &tot, R * std::max<size_t>(nc, 1)))) return rc;
     HIPCHECK(hipMemsetAsync(slab, 0, R * stride, g->stream));
     HIPCHECK(hipMemsetAsync(cnt, 0, R * std::max<size_t>(nc, 1) * sizeof(int32_t), g->stream));
     HIPCHECK(hipMemsetAsync(tot, 0, R * std::max<size_t>(nc, 1) * sizeof(long long), g->stream));
@@ -771,17 +729,15 @@ int nsk_set_chains(nsk_graph *g, int nchains) {
         regular = regular && c.values_regular;
     }
     HIPCHECK(hipStreamSynchronize(g->stream));
+    rb.commit();
     // the arrays of the previous layout go (a one-chain handle's first call frees the ones nsk_graph_create made)
-    void *old_val = g->val;
-    uint8_t *old_pos = g->chain_stride ? nullptr : g->cnt_pos;     // (inside the old slab once the chain count was set)
-    int32_t *old_cnt = g->cnt;
-    long long *old_tot = g->cnt_total;
+    dev_free(g, g->val); dev_free(g, g->cnt); dev_free(g, g->cnt_total);
+    if (!g->chain_stride) dev_free(g, g->cnt_pos);                  // (inside the old slab once the chain count was set)
     g->val = slab; g->cnt_pos = slab + half; g->cnt = cnt; g->cnt_total = tot;
     g->chain_stride = stride;
     g->nchains = nchains;
     g->chains_regular = nchains > 1 ? regular : true;
     g->values_regular = g->chain_regular[0] && g->chain_regular[1] && g->chains_regular;
-    dev_free(g, old_val); dev_free(g, old_pos); dev_free(g, old_cnt); dev_free(g, old_tot);
     g->pos_tally_sweeps = 0;
     g->cnt_dirty = false;
     g->seg_plans_key = -1;                  // (the plans check the arrays' offsets from the value array)
@@ -856,591 +812,6 @@ int nsk_chains_download(nsk_graph *g, int64_t *var_value, int64_t *count) {
     return NSK_OK;
 }
 
-// ---- sample traces (nsk_internal.h NskTrace) --------------------------------------------------------------------
-static void wstats_plan_free(nsk_graph *g, NskWstatsPlan &plan) {
-    dev_free(g, plan.shorts); dev_free(g, plan.pieces); dev_free(g, plan.multi); dev_free(g, plan.partial);
-    g->device_bytes -= plan.device_bytes;
-    plan = NskWstatsPlan();
-}
-
-static void trace_free(nsk_graph *g) {
-    NskTrace &t = g->trace;
-    dev_free(g, t.buf);
-    dev_free(g, t.cols);
-    dev_free(g, t.lp);
-    dev_free(g, t.ws);
-    g->device_bytes -= t.device_bytes + t.lp_bytes + t.ws_bytes;
-    wstats_plan_free(g, t.ws_plan);
-    t = NskTrace();
-}
-
-int nsk_trace_setup(nsk_graph *g, const int64_t *vids, int64_t nvids, int64_t every, int64_t capacity) {
-    if (!g) return fail(NSK_E_INVALID, "null graph");
-    HIPCHECK(hipSetDevice(g->device));
-    HIPCHECK(hipStreamSynchronize(g->stream));          // (record launches into the buffer that goes)
-    if (capacity == 0) { if (g->trace.capacity > 0) trace_free(g); return NSK_OK; }
-    const Compiled &c = g->c;
-    if ((c.flags & NSK_FLAG_PARTITION) || c.own_begin != 0 || c.own_end != c.nvar)
-        return fail(NSK_E_INVALID, "nsk_trace_setup: the handle must own the whole graph (no own_range / NSK_FLAG_PARTITION)");
-    if (g->xworld > 0 || g->pworld > 0 || g->rccl_comm)
-        return fail(NSK_E_INVALID, "nsk_trace_setup: the handle exchanges a boundary (exchange, RCCL or peer-to-peer set up)");
-    if (every < 1 || capacity < 1) return fail(NSK_E_INVALID, "nsk_trace_setup: every and capacity must be at least 1");
-    if (vids && nvids < 1) return fail(NSK_E_INVALID, "nsk_trace_setup: a list of variable ids needs at least one");
-    if (!vids && c.nvar < 1) return fail(NSK_E_INVALID, "nsk_trace_setup: the graph has no variables");
-    NskTrace t;
-    t.ncols = vids ? nvids : c.nvar;
-    t.every = every;
-    t.chains = g->nchains;
-    t.packed = true;
-    t.pos.resize((size_t)t.ncols);
-    std::vector<int32_t> cols;
-    if (vids) {
-        for (int64_t j = 0; j < nvids; j++) {
-            if (vids[j] < 0 || vids[j] >= c.nvar) return fail(NSK_E_INDEX, "nsk_trace_setup: variable id out of range");
-            t.packed = t.packed && c.v_card[(size_t)vids[j]] == 2;
-            cols.push_back(c.iid[(size_t)vids[j]]);
-        }
-        std::sort(cols.begin(), cols.end());            // a full-state trace reads the value array front to back
-        cols.erase(std::unique(cols.begin(), cols.end()), cols.end());
-        for (int64_t j = 0; j < nvids; j++)
-            t.pos[(size_t)j] = std::lower_bound(cols.begin(), cols.end(), c.iid[(size_t)vids[j]]) - cols.begin();
-        t.ndev = (int64_t)cols.size();
-    } else {                                            // every variable: the device records every internal id, no index list
-        for (int64_t v = 0; v < c.nvar; v++) { t.packed = t.packed && c.v_card[(size_t)v] == 2; t.pos[(size_t)v] = c.iid[(size_t)v]; }
-        t.ndev = c.nid;
-    }
-    t.row_bytes = t.packed ? (size_t)((t.ndev + 63) / 64) * 8 : (size_t)t.ndev * (size_t)c.vbytes;
-    const double total = (double)capacity * (double)t.chains * (double)t.row_bytes;
-    if (total >= 281474976710656.0) return fail(NSK_E_NOMEM, "nsk_trace_setup: the trace does not fit");
-    // the arguments hold: the trace this one replaces goes now, before the new buffer is asked for (the two need not fit
-    // side by side; a set-up that fails for lack of memory leaves no trace)
-    if (g->trace.capacity > 0) trace_free(g);
-    const int64_t bytes_before = g->device_bytes;
-    uint8_t *buf = nullptr;
-    int rc = dev_alloc(g, &buf, (size_t)capacity * (size_t)t.chains * t.row_bytes);
-    if (rc) return rc;
-    t.buf = buf;
-    if (vids) {
-        rc = dev_upload(g, &t.cols, cols);
-        if (rc) { dev_free(g, buf); g->device_bytes = bytes_before; return rc; }
-        HIPCHECK(hipStreamSynchronize(g->stream));      // (the upload reads a local vector)
-    }
-    t.device_bytes = g->device_bytes - bytes_before;
-    t.capacity = capacity;
-    g->trace = std::move(t);
-    return NSK_OK;
-}
-
-int nsk_trace_rows(nsk_graph *g, int64_t *rows, int64_t *capacity, int64_t *packed) {
-    if (!g) return fail(NSK_E_INVALID, "null graph");
-    if (rows) *rows = g->trace.rows;
-    if (capacity) *capacity = g->trace.capacity;
-    if (packed) *packed = g->trace.capacity > 0 && g->trace.packed ? 1 : 0;
-    return NSK_OK;
-}
-
-int nsk_trace_clear(nsk_graph *g) {
-    if (!g) return fail(NSK_E_INVALID, "null graph");
-    if (g->trace.capacity == 0) return fail(NSK_E_INVALID, "nsk_trace_clear: no trace is set up");
-    g->trace.rows = g->trace.phase = 0;
-    g->trace.sweep_index.clear();
-    return NSK_OK;
-}
-
-}  // extern "C"
-
-// rows as downloaded (device column order, packed or plain) -> the caller's columns, over the host threads
-template <typename VT>
-static void trace_unpack(const NskTrace &t, const uint8_t *host, int64_t nrows, VT *out) {
-    const int64_t ncols = t.ncols, nrc = nrows * t.chains;
-    const int64_t *pos = t.pos.data();
-    nsk::parallel_for(nrc * ncols, [&](int64_t b0, int64_t b1, int) {
-        int64_t rc = ncols ? b0 / ncols : 0, j = ncols ? b0 % ncols : 0;
-        for (int64_t e = b0; e < b1; e++) {
-            const uint8_t *row = host + (size_t)rc * t.row_bytes;
-            const int64_t p = pos[j];
-            out[e] = t.packed ? (VT)((((const unsigned long long *)row)[p >> 6] >> (p & 63)) & 1ull) : ((const VT *)row)[p];
-            if (++j == ncols) { j = 0; rc++; }
-        }
-    });
-}
-
-extern "C" {
-
-int nsk_trace_download(nsk_graph *g, int64_t first_row, int64_t nrows, void *out, int64_t *sweep_index) {
-    if (!g) return fail(NSK_E_INVALID, "null graph");
-    const NskTrace &t = g->trace;
-    if (t.capacity == 0) return fail(NSK_E_INVALID, "nsk_trace_download: no trace is set up");
-    if (first_row < 0 || nrows < 0 || first_row + nrows > t.rows) return fail(NSK_E_INVALID, "nsk_trace_download: rows beyond those recorded");
-    if (nrows > 0 && !out) return fail(NSK_E_INVALID, "null argument");
-    HIPCHECK(hipSetDevice(g->device));
-    HIPCHECK(hipStreamSynchronize(g->stream));
-    const size_t per_row = (size_t)t.chains * t.row_bytes, vb = (size_t)g->c.vbytes;
-    const int64_t step = std::max<int64_t>(1, (int64_t)(((size_t)256 << 20) / std::max<size_t>(per_row, 1)));   // staging of 256 MB at most
-    std::vector<uint8_t> host((size_t)std::min(step, std::max<int64_t>(nrows, 1)) * per_row + 8);
-    for (int64_t r0 = 0; r0 < nrows; r0 += step) {
-        const int64_t n = std::min(step, nrows - r0);
-        if (per_row) HIPCHECK(hipMemcpy(host.data(), (const char *)t.buf + (size_t)(first_row + r0) * per_row, (size_t)n * per_row, hipMemcpyDeviceToHost));
-        const size_t off = (size_t)r0 * (size_t)t.chains * (size_t)t.ncols;
-        if (vb == 1) trace_unpack<int8_t>(t, host.data(), n, (int8_t *)out + off);
-        else trace_unpack<int32_t>(t, host.data(), n, (int32_t *)out + off);
-    }
-    if (sweep_index) for (int64_t i = 0; i < nrows; i++) sweep_index[i] = t.sweep_index[(size_t)(first_row + i)];
-    return NSK_OK;
-}
-
-}  // extern "C"
-
-// ---- log-potential (nsk_internal.h NskEnergy, nsk_kernels_energy.h) ---------------------------------------------------
-// The handles the sample trace serves: a shard's sum is not the graph's, and ghosts are stale between exchanges
-static int energy_whole_graph(const nsk_graph *g, const char *what) {
-    const Compiled &c = g->c;
-    if ((c.flags & NSK_FLAG_PARTITION) || c.own_begin != 0 || c.own_end != c.nvar)
-        return fail(NSK_E_INVALID, std::string(what) + ": the handle must own the whole graph (no own_range / NSK_FLAG_PARTITION)");
-    if (g->xworld > 0 || g->pworld > 0 || g->rccl_comm)
-        return fail(NSK_E_INVALID, std::string(what) + ": the handle exchanges a boundary (exchange, RCCL or peer-to-peer set up)");
-    return NSK_OK;
-}
-
-// nsk_graph_create validates the factors a sampled variable reaches (nsk_compile.cpp validate_reachable); the walk
-// evaluates EVERY factor, so the others are held to the same rules here, on the compiled records.  Returns the lowest
-// factor that breaks one (-1: none) and whether some factor reads its head at the literal edge index.
-static int64_t energy_check_factors(const nsk_graph *g, bool *literal_out) {
-    const Compiled &c = g->c;
-    const int64_t nedge = c.nedge, nid = c.nid, nw = c.nweight, nvar = c.nvar;
-    const bool head_by_vid = (c.flags & NSK_FLAG_HEAD_BY_VID) != 0;
-    const int nt = nsk::compile_threads();
-    std::vector<int64_t> first((size_t)nt, -1);
-    std::vector<int> literal((size_t)nt, 0);
-    nsk::parallel_for(c.nfactor, [&](int64_t b0, int64_t b1, int t) {
-        auto members_ok = [&](int64_t lo, int64_t hi) {
-            for (int64_t l = lo; l < hi; l++) if (c.m_rec[2 * (size_t)l] < 0 || c.m_rec[2 * (size_t)l] >= nid) return false;
-            return true;
-        };
-        for (int64_t f = b0; f < b1; f++) {
-            const uint32_t head = c.f_rec[4 * (size_t)f];
-            const int fn = (int)(head & 0xffu) - 1;
-            const int64_t ar = (int64_t)(head >> 8), s = (int32_t)c.f_rec[4 * (size_t)f + 1], wz = (int32_t)c.f_rec[4 * (size_t)f + 2];
-            bool ok = known_function(fn) && wz >= 0 && wz < nw;
-            if (ok && fn != -1) {
-                int64_t need = 0;       // member positions the function reads regardless of arity
-                bool arity1 = false;
-                switch (fn) {
-                case 0: case 7: case 8: case 9: case 13: case 16: case 17: arity1 = true; break;
-                case 3: case 18: case 19: case 20: case 30: need = 1; break;
-                case 21: case 22: case 25: case 26: need = 2; break;
-                case 23: case 24: need = 3; break;
-                default: break;
-                }
-                const int64_t e = s + ar;
-                ok = s >= 0 && e <= nedge && s + need <= nedge && !(arity1 && ar < 1) && members_ok(s, std::max(e, s + need));
-                if (ok && fn == 30) {   // UFO: the first member's value indexes the member list (values are kept regular then)
-                    const int64_t reach = s + c.v_card_i[(size_t)c.m_rec[2 * (size_t)s]] - 2;
-                    ok = c.has_ufo && reach < nedge && members_ok(s, reach + 1);
-                }
-                if (ok && (fn == 13 || fn == 16 || fn == 17) && !head_by_vid) { literal[(size_t)t] = 1; ok = e - 1 < nvar; }
-                if (ok && fn == 8) ok = ar < (int64_t)c.logtab.size();
-            }
-            if (!ok) { first[(size_t)t] = f; return; }
-        }
-    });
-    *literal_out = false;
-    for (int x : literal) if (x) *literal_out = true;
-    int64_t bad = -1;
-    for (int64_t x : first) if (x >= 0 && (bad < 0 || x < bad)) bad = x;
-    return bad;
-}
-
-// The arrays of the walk and the partial sums for `chains` chains, at the first use (and when more chains ask)
-static int energy_ensure(nsk_graph *g, int chains, const char *what) {
-    NskEnergy &en = g->energy;
-    Compiled &c = g->c;
-    HIPCHECK(hipSetDevice(g->device));
-    if (!en.ready) {
-        bool literal = false;
-        const int64_t bad = energy_check_factors(g, &literal);
-        if (bad >= 0)
-            return fail(NSK_E_INVALID, std::string(what) + ": factor " + std::to_string(bad) + ", which no sampled variable reaches, cannot be "
-                                       "evaluated (unknown function, or a weight, member or head index outside the arrays)");
-        uint32_t *f_rec = nullptr;
-        int32_t *m_rec = nullptr, *v_card = nullptr, *iid = nullptr;
-        const int64_t bytes_before = g->device_bytes;
-        int rc = NSK_OK;
-        if (!g->f_rec) rc = dev_upload(g, &f_rec, c.f_rec);
-        if (!rc && !g->m_rec) rc = dev_upload(g, &m_rec, c.m_rec);
-        if (!rc && !g->v_card) rc = dev_upload(g, &v_card, c.v_card_i);
-        if (!rc && literal && !g->iid_of_vid && !g->xfer_iid) rc = dev_upload(g, &iid, c.iid);
-        if (!rc && hipStreamSynchronize(g->stream) != hipSuccess) rc = fail(NSK_E_DEVICE, "hipStreamSynchronize failed");
-        if (rc) {
-            dev_free(g, f_rec); dev_free(g, m_rec); dev_free(g, v_card); dev_free(g, iid);
-            g->device_bytes = bytes_before;
-            if (rc != NSK_E_NOMEM) return rc;
-            const double mb = ((double)c.f_rec.size() * 4 + (double)c.m_rec.size() * 4 + (double)c.v_card_i.size() * 4) / 1048576.0;
-            return fail(NSK_E_NOMEM, std::string(what) + ": the factor and member records the evaluation reads (" +
-                                     std::to_string((long long)mb) + " MB) do not fit on the device");
-        }
-        if (f_rec) g->f_rec = f_rec;
-        if (m_rec) g->m_rec = m_rec;
-        if (v_card) g->v_card = v_card;
-        if (literal && !g->iid_of_vid) g->iid_of_vid = iid ? iid : g->xfer_iid;     // (the state transfers hold the same table)
-        en.ready = true;
-    }
-    if (chains > en.chains) {
-        const size_t nb = (size_t)nsk_energy_blocks((long long)c.nfactor);
-        double *partial = nullptr, *result = nullptr;
-        int rc = dev_alloc(g, &partial, (size_t)chains * nb);
-        if (!rc && (rc = dev_alloc(g, &result, (size_t)chains))) { dev_free(g, partial); g->device_bytes -= (int64_t)((size_t)chains * nb * sizeof(double)); }
-        if (rc) return rc;
-        HIPCHECK(hipStreamSynchronize(g->stream));      // (launches that write the buffers that go)
-        if (en.partial) {
-            dev_free(g, en.partial); dev_free(g, en.result);
-            g->device_bytes -= (int64_t)(((size_t)en.chains * nb + (size_t)en.chains) * sizeof(double));
-        }
-        en.partial = partial; en.result = result; en.chains = chains;
-    }
-    return NSK_OK;
-}
-
-extern "C" {
-
-int nsk_log_potential(nsk_graph *g, int which, int64_t first_chain, int64_t nchains, double *out) {
-    if (!g) return fail(NSK_E_INVALID, "null graph");
-    if (!out) return fail(NSK_E_INVALID, "null argument");
-    if (which != NSK_BUF_VALUE && which != NSK_BUF_VALUE_EVID) return fail(NSK_E_INVALID, "nsk_log_potential: which must be NSK_BUF_VALUE or NSK_BUF_VALUE_EVID");
-    const int64_t R = which == NSK_BUF_VALUE ? g->nchains : 1;
-    if (first_chain < 0 || nchains < 1 || first_chain >= R || nchains > R - first_chain)
-        return fail(NSK_E_INVALID, "nsk_log_potential: chains outside those the handle has (the evidence chain exists once)");
-    int rc = energy_whole_graph(g, "nsk_log_potential");
-    if (rc) return rc;
-    if ((rc = energy_ensure(g, (int)nchains, "nsk_log_potential"))) return rc;
-    const char *val = which == NSK_BUF_VALUE ? (const char *)g->val + (size_t)first_chain * g->chain_stride : (const char *)g->val_evid;
-    if ((rc = nsk_energy_enqueue(g, val, (int)nchains, g->packed_sweeps > 0, g->energy.result))) return rc;
-    HIPCHECK(hipMemcpyAsync(out, g->energy.result, (size_t)nchains * sizeof(double), hipMemcpyDeviceToHost, g->stream));
-    HIPCHECK(hipStreamSynchronize(g->stream));
-    return NSK_OK;
-}
-
-int nsk_factor_values(nsk_graph *g, int which, int64_t chain, double *out) {
-    if (!g) return fail(NSK_E_INVALID, "null graph");
-    if (which != NSK_BUF_VALUE && which != NSK_BUF_VALUE_EVID) return fail(NSK_E_INVALID, "nsk_factor_values: which must be NSK_BUF_VALUE or NSK_BUF_VALUE_EVID");
-    if (chain < 0 || chain >= (which == NSK_BUF_VALUE ? g->nchains : 1))
-        return fail(NSK_E_INVALID, "nsk_factor_values: chain outside those the handle has (the evidence chain exists once)");
-    int rc = energy_whole_graph(g, "nsk_factor_values");
-    if (rc) return rc;
-    if (g->c.nfactor == 0) return NSK_OK;
-    if (!out) return fail(NSK_E_INVALID, "null argument");
-    if ((rc = energy_ensure(g, 0, "nsk_factor_values"))) return rc;
-    // the values cross PCIe from a buffer that lives for this call only (8 bytes a factor)
-    double *dev = nullptr;
-    const size_t n = (size_t)g->c.nfactor;
-    if ((rc = dev_alloc(g, &dev, n))) return fail(NSK_E_NOMEM, "nsk_factor_values: one double per factor does not fit on the device");
-    const char *val = which == NSK_BUF_VALUE ? (const char *)g->val + (size_t)chain * g->chain_stride : (const char *)g->val_evid;
-    rc = nsk_factor_values_enqueue(g, val, dev);
-    hipError_t e = hipSuccess;
-    if (!rc) e = hipMemcpyAsync(out, dev, n * sizeof(double), hipMemcpyDeviceToHost, g->stream);
-    if (!rc && e == hipSuccess) e = hipStreamSynchronize(g->stream);
-    dev_free(g, dev);
-    g->device_bytes -= (int64_t)(n * sizeof(double));
-    if (rc) return rc;
-    HIPCHECK(e);
-    return NSK_OK;
-}
-
-int nsk_trace_log_potential(nsk_graph *g, int on) {
-    if (!g) return fail(NSK_E_INVALID, "null graph");
-    NskTrace &t = g->trace;
-    if (t.capacity == 0) return fail(NSK_E_INVALID, "nsk_trace_log_potential: no trace is set up");
-    HIPCHECK(hipSetDevice(g->device));
-    HIPCHECK(hipStreamSynchronize(g->stream));
-    if (!on) {
-        dev_free(g, t.lp);
-        g->device_bytes -= t.lp_bytes;
-        t.lp = nullptr; t.lp_bytes = 0;
-        return NSK_OK;
-    }
-    if (t.lp) return NSK_OK;
-    int rc = energy_ensure(g, t.chains, "nsk_trace_log_potential");
-    if (rc) return rc;
-    const int64_t bytes_before = g->device_bytes;
-    double *lp = nullptr;
-    if ((rc = dev_alloc(g, &lp, (size_t)t.capacity * (size_t)t.chains))) return rc;
-    HIPCHECK(hipMemsetAsync(lp, 0, (size_t)t.capacity * (size_t)t.chains * sizeof(double), g->stream));     // (rows recorded while it was off read 0)
-    t.lp = lp;
-    t.lp_bytes = g->device_bytes - bytes_before;
-    return NSK_OK;
-}
-
-int nsk_trace_download_log_potential(nsk_graph *g, int64_t first_row, int64_t nrows, double *out) {
-    if (!g) return fail(NSK_E_INVALID, "null graph");
-    const NskTrace &t = g->trace;
-    if (t.capacity == 0) return fail(NSK_E_INVALID, "nsk_trace_download_log_potential: no trace is set up");
-    if (!t.lp) return fail(NSK_E_INVALID, "nsk_trace_download_log_potential: the trace keeps no lp column (nsk_trace_log_potential)");
-    if (first_row < 0 || nrows < 0 || first_row + nrows > t.rows) return fail(NSK_E_INVALID, "nsk_trace_download_log_potential: rows beyond those recorded");
-    if (nrows > 0 && !out) return fail(NSK_E_INVALID, "null argument");
-    HIPCHECK(hipSetDevice(g->device));
-    HIPCHECK(hipStreamSynchronize(g->stream));
-    if (nrows > 0)
-        HIPCHECK(hipMemcpy(out, t.lp + (size_t)first_row * (size_t)t.chains, (size_t)nrows * (size_t)t.chains * sizeof(double), hipMemcpyDeviceToHost));
-    return NSK_OK;
-}
-
-}  // extern "C"
-
-// ---- per-weight statistics (nsk_internal.h NskWstats, nsk_kernels_wstats.h) -----------------------------------------
-// The by-weight index list at the first use (after energy_ensure: every factor's weight slot was checked), and the
-// feature values when a scaled sum asks for them
-static int wstats_ensure(nsk_graph *g, bool scaled, const char *what) {
-    NskWstats &ws = g->wstats;
-    Compiled &c = g->c;
-    HIPCHECK(hipSetDevice(g->device));
-    if (!ws.ready) {
-        const size_t nw = (size_t)c.nweight, nf = (size_t)c.nfactor;
-        std::vector<uint32_t> off(nw + 1, 0);
-        for (size_t f = 0; f < nf; f++) off[(size_t)c.f_rec[4 * f + 2] + 1]++;
-        for (size_t w = 0; w < nw; w++) off[w + 1] += off[w];
-        std::vector<int32_t> idx(nf);
-        std::vector<uint32_t> at(off.begin(), off.end() - 1);
-        for (size_t f = 0; f < nf; f++) idx[at[(size_t)c.f_rec[4 * f + 2]]++] = (int32_t)f;     // ascending inside a weight
-        const int64_t bytes_before = g->device_bytes;
-        int32_t *dev = nullptr;
-        int rc = dev_upload(g, &dev, idx);
-        if (!rc && hipStreamSynchronize(g->stream) != hipSuccess) rc = fail(NSK_E_DEVICE, "hipStreamSynchronize failed");
-        if (rc) {
-            dev_free(g, dev);
-            g->device_bytes = bytes_before;
-            if (rc != NSK_E_NOMEM) return rc;
-            return fail(NSK_E_NOMEM, std::string(what) + ": the by-weight factor list (" + std::to_string((long long)(nf * 4 / 1048576)) +
-                                     " MB) does not fit on the device");
-        }
-        ws.wf_off = std::move(off); ws.wf_first.resize(nw);
-        for (size_t w = 0; w < nw; w++) ws.wf_first[w] = ws.wf_off[w] < ws.wf_off[w + 1] ? idx[ws.wf_off[w]] : 0;
-        ws.wf_idx = dev;
-        ws.ready = true;
-    }
-    if (scaled && !g->f_feat) {
-        const int64_t bytes_before = g->device_bytes;
-        double *feat = nullptr;
-        int rc = dev_upload(g, &feat, c.f_feat);
-        if (!rc && hipStreamSynchronize(g->stream) != hipSuccess) rc = fail(NSK_E_DEVICE, "hipStreamSynchronize failed");
-        if (rc) {
-            dev_free(g, feat);
-            g->device_bytes = bytes_before;
-            if (rc != NSK_E_NOMEM) return rc;
-            return fail(NSK_E_NOMEM, std::string(what) + ": the feature values (" + std::to_string((long long)(c.f_feat.size() * 8 / 1048576)) +
-                                     " MB) do not fit on the device");
-        }
-        g->f_feat = feat;
-    }
-    return NSK_OK;
-}
-
-// partial sums of the plan's weights of several pieces, for `chains` chains (grown when more ask)
-static int wstats_partial_ensure(nsk_graph *g, NskWstatsPlan &plan, int chains) {
-    if (plan.npartial == 0 || chains <= plan.partial_chains) return NSK_OK;
-    double *partial = nullptr;
-    const int64_t bytes_before = g->device_bytes;
-    int rc = dev_alloc(g, &partial, (size_t)chains * (size_t)plan.npartial);
-    if (rc) return rc;
-    HIPCHECK(hipStreamSynchronize(g->stream));      // (launches that write the buffer that goes)
-    const int64_t grown = g->device_bytes - bytes_before;
-    if (plan.partial) {
-        dev_free(g, plan.partial);
-        const int64_t old = (int64_t)((size_t)plan.partial_chains * (size_t)plan.npartial * sizeof(double));
-        g->device_bytes -= old; plan.device_bytes -= old;
-    }
-    plan.device_bytes += grown;
-    plan.partial = partial; plan.partial_chains = chains;
-    return NSK_OK;
-}
-
-// The work list of the weights whose SLOTS are slot[0 .. ncols): column j of the output is weight slot[j]'s sum.  How a
-// weight is cut is a function of its own length (nsk_kernels_wstats.h); a weight named twice is evaluated twice.
-static int wstats_plan_build(nsk_graph *g, NskWstatsPlan &plan, const int32_t *slot, int64_t ncols, int chains, const char *what) {
-    const NskWstats &ws = g->wstats;
-    NskWstatsPlan p;
-    p.ncols = ncols;
-    std::vector<std::vector<uint64_t>> bylen(NSK_WSTATS_SHORT);       // first factor << 32 | column, per length
-    std::vector<uint4> pieces, multi;
-    for (int64_t j = 0; j < ncols; j++) {
-        const size_t s = (size_t)slot[j];
-        const uint32_t off = ws.wf_off[s], len = ws.wf_off[s + 1] - off;
-        if (len == 0) continue;                     // (reads 0: the output is zeroed where it is allocated)
-        if (len <= NSK_WSTATS_SHORT) { bylen[len - 1].push_back((uint64_t)(uint32_t)ws.wf_first[s] << 32 | (uint64_t)j); continue; }
-        const uint32_t npc = (len + NSK_WSTATS_PIECE - 1) / NSK_WSTATS_PIECE;
-        if (npc == 1) { pieces.push_back(make_uint4(off, len, (uint32_t)j, 0u)); continue; }
-        multi.push_back(make_uint4((uint32_t)p.npartial, npc, (uint32_t)j, 0u));
-        for (uint32_t k = 0; k < npc; k++)
-            pieces.push_back(make_uint4(off + k * NSK_WSTATS_PIECE, std::min<uint32_t>(NSK_WSTATS_PIECE, len - k * NSK_WSTATS_PIECE), (uint32_t)(p.npartial + k), 1u));
-        p.npartial += npc;
-    }
-    std::vector<uint2> shorts;
-    for (int k = 0; k < NSK_WSTATS_SHORT; k++) {
-        std::sort(bylen[(size_t)k].begin(), bylen[(size_t)k].end());
-        for (uint64_t key : bylen[(size_t)k]) { const size_t s = (size_t)slot[(size_t)(key & 0xffffffffu)]; shorts.push_back(make_uint2(ws.wf_off[s], (uint32_t)(key & 0xffffffffu))); }
-        p.len_end[k] = (unsigned int)shorts.size();
-        std::vector<uint64_t>().swap(bylen[(size_t)k]);
-    }
-    p.nshort = (int64_t)shorts.size(); p.npiece = (int64_t)pieces.size(); p.nmulti = (int64_t)multi.size();
-    const int64_t bytes_before = g->device_bytes;
-    int rc = NSK_OK;
-    if (p.nshort) rc = dev_upload(g, &p.shorts, shorts);
-    if (!rc && p.npiece) rc = dev_upload(g, &p.pieces, pieces);
-    if (!rc && p.nmulti) rc = dev_upload(g, &p.multi, multi);
-    if (!rc && hipStreamSynchronize(g->stream) != hipSuccess) rc = fail(NSK_E_DEVICE, "hipStreamSynchronize failed");
-    p.device_bytes = g->device_bytes - bytes_before;
-    if (!rc) rc = wstats_partial_ensure(g, p, chains);
-    if (rc) {
-        const double mb = ((double)p.nshort * 8 + (double)p.npiece * 16 + (double)p.nmulti * 16 + (double)p.npartial * 8 * chains) / 1048576.0;
-        wstats_plan_free(g, p);
-        if (rc != NSK_E_NOMEM) return rc;
-        return fail(NSK_E_NOMEM, std::string(what) + ": the work list of the weights (" + std::to_string((long long)mb) + " MB) does not fit on the device");
-    }
-    plan = p;
-    return NSK_OK;
-}
-
-// slot of the caller's weight id
-static inline int32_t wstats_slot(const Compiled &c, int64_t wid) { return c.wmap.empty() ? (int32_t)wid : c.wmap[(size_t)wid]; }
-
-extern "C" {
-
-int nsk_weight_stats(nsk_graph *g, int which, int64_t first_chain, int64_t nchains, int scaled, double *out) {
-    if (!g) return fail(NSK_E_INVALID, "null graph");
-    if (!out) return fail(NSK_E_INVALID, "null argument");
-    if (which != NSK_BUF_VALUE && which != NSK_BUF_VALUE_EVID) return fail(NSK_E_INVALID, "nsk_weight_stats: which must be NSK_BUF_VALUE or NSK_BUF_VALUE_EVID");
-    const int64_t R = which == NSK_BUF_VALUE ? g->nchains : 1;
-    if (first_chain < 0 || nchains < 1 || first_chain >= R || nchains > R - first_chain)
-        return fail(NSK_E_INVALID, "nsk_weight_stats: chains outside those the handle has (the evidence chain exists once)");
-    int rc = energy_whole_graph(g, "nsk_weight_stats");
-    if (rc) return rc;
-    const Compiled &c = g->c;
-    if (c.nweight == 0) return NSK_OK;
-    if ((rc = energy_ensure(g, 0, "nsk_weight_stats"))) return rc;
-    if ((rc = wstats_ensure(g, scaled != 0, "nsk_weight_stats"))) return rc;
-    NskWstats &ws = g->wstats;
-    if (!ws.all_ready) {
-        std::vector<int32_t> slot((size_t)c.nweight);
-        for (int64_t w = 0; w < c.nweight; w++) slot[(size_t)w] = wstats_slot(c, w);
-        if ((rc = wstats_plan_build(g, ws.all, slot.data(), c.nweight, (int)nchains, "nsk_weight_stats"))) return rc;
-        ws.all_ready = true;
-    }
-    if ((rc = wstats_partial_ensure(g, ws.all, (int)nchains))) return rc;
-    if (nchains > ws.result_chains) {
-        double *result = nullptr;
-        const size_t n = (size_t)nchains * (size_t)c.nweight;
-        if ((rc = dev_alloc(g, &result, n)))
-            return fail(NSK_E_NOMEM, "nsk_weight_stats: one double per chain and weight (" + std::to_string((long long)(n * 8 / 1048576)) + " MB) does not fit on the device");
-        HIPCHECK(hipStreamSynchronize(g->stream));
-        if (ws.result) { dev_free(g, ws.result); g->device_bytes -= (int64_t)((size_t)ws.result_chains * (size_t)c.nweight * sizeof(double)); }
-        HIPCHECK(hipMemsetAsync(result, 0, n * sizeof(double), g->stream));     // (weights without a factor are never written)
-        ws.result = result; ws.result_chains = (int)nchains;
-    }
-    const char *val = which == NSK_BUF_VALUE ? (const char *)g->val + (size_t)first_chain * g->chain_stride : (const char *)g->val_evid;
-    if ((rc = nsk_wstats_enqueue(g, ws.all, val, (int)nchains, g->packed_sweeps > 0, scaled != 0, ws.result, c.nweight))) return rc;
-    HIPCHECK(hipMemcpyAsync(out, ws.result, (size_t)nchains * (size_t)c.nweight * sizeof(double), hipMemcpyDeviceToHost, g->stream));
-    HIPCHECK(hipStreamSynchronize(g->stream));
-    return NSK_OK;
-}
-
-int nsk_trace_weight_stats(nsk_graph *g, const int64_t *wids, int64_t nwids, int scaled) {
-    if (!g) return fail(NSK_E_INVALID, "null graph");
-    NskTrace &t = g->trace;
-    if (t.capacity == 0) return fail(NSK_E_INVALID, "nsk_trace_weight_stats: no trace is set up");
-    const Compiled &c = g->c;
-    if (nwids >= 0 && (wids ? nwids < 1 : nwids != 0))
-        return fail(NSK_E_INVALID, "nsk_trace_weight_stats: a list of weight ids needs at least one (NULL with 0: all weights)");
-    if (nwids > 0)
-        for (int64_t j = 0; j < nwids; j++)
-            if (wids[j] < 0 || wids[j] >= c.nweight) return fail(NSK_E_INDEX, "nsk_trace_weight_stats: weight id out of range");
-    HIPCHECK(hipSetDevice(g->device));
-    HIPCHECK(hipStreamSynchronize(g->stream));
-    int rc = NSK_OK;
-    if (nwids >= 0) {       // (before the column that stands goes)
-        if ((rc = energy_whole_graph(g, "nsk_trace_weight_stats"))) return rc;
-        if ((rc = energy_ensure(g, 0, "nsk_trace_weight_stats"))) return rc;
-        if ((rc = wstats_ensure(g, scaled != 0, "nsk_trace_weight_stats"))) return rc;
-    }
-    dev_free(g, t.ws);
-    g->device_bytes -= t.ws_bytes;
-    t.ws = nullptr; t.ws_bytes = 0; t.ws_scaled = false;
-    wstats_plan_free(g, t.ws_plan);
-    if (nwids < 0) return NSK_OK;
-    const int64_t ncols = wids ? nwids : c.nweight;
-    const double total = (double)t.capacity * (double)t.chains * (double)ncols;
-    if (total >= 35184372088832.0) return fail(NSK_E_NOMEM, "nsk_trace_weight_stats: the column does not fit");
-    std::vector<int32_t> slot((size_t)ncols);
-    for (int64_t j = 0; j < ncols; j++) slot[(size_t)j] = wstats_slot(c, wids ? wids[j] : j);
-    if ((rc = wstats_plan_build(g, t.ws_plan, slot.data(), ncols, t.chains, "nsk_trace_weight_stats"))) return rc;
-    const int64_t bytes_before = g->device_bytes;
-    double *col = nullptr;
-    const size_t n = (size_t)t.capacity * (size_t)t.chains * (size_t)ncols;
-    if ((rc = dev_alloc(g, &col, n))) {
-        wstats_plan_free(g, t.ws_plan);
-        return fail(NSK_E_NOMEM, "nsk_trace_weight_stats: capacity x chains x weights doubles (" + std::to_string((long long)(n * 8 / 1048576)) + " MB) do not fit on the device");
-    }
-    HIPCHECK(hipMemsetAsync(col, 0, (n ? n : 1) * sizeof(double), g->stream));     // (weights without a factor, rows recorded while it was off)
-    t.ws = col;
-    t.ws_bytes = g->device_bytes - bytes_before;
-    t.ws_scaled = scaled != 0;
-    return NSK_OK;
-}
-
-int nsk_trace_download_weight_stats(nsk_graph *g, int64_t first_row, int64_t nrows, double *out) {
-    if (!g) return fail(NSK_E_INVALID, "null graph");
-    const NskTrace &t = g->trace;
-    if (t.capacity == 0) return fail(NSK_E_INVALID, "nsk_trace_download_weight_stats: no trace is set up");
-    if (!t.ws) return fail(NSK_E_INVALID, "nsk_trace_download_weight_stats: the trace keeps no stats column (nsk_trace_weight_stats)");
-    if (first_row < 0 || nrows < 0 || first_row + nrows > t.rows) return fail(NSK_E_INVALID, "nsk_trace_download_weight_stats: rows beyond those recorded");
-    const size_t row = (size_t)t.chains * (size_t)t.ws_plan.ncols;
-    if (nrows > 0 && row > 0 && !out) return fail(NSK_E_INVALID, "null argument");
-    HIPCHECK(hipSetDevice(g->device));
-    HIPCHECK(hipStreamSynchronize(g->stream));
-    if (nrows > 0 && row > 0)
-        HIPCHECK(hipMemcpy(out, t.ws + (size_t)first_row * row, (size_t)nrows * row * sizeof(double), hipMemcpyDeviceToHost));
-    return NSK_OK;
-}
-
-}  // extern "C"
-
-// One row behind whatever the stream holds: every chain's traced values as they are then (called by nsk_gibbs_sweeps
-// where a row is due; the caller has checked the capacity before it enqueued a sweep)
-int nsk_trace_record(nsk_graph *g) {
-    NskTrace &t = g->trace;
-    if (t.rows >= t.capacity) return fail(NSK_E_RANGE, "the sample trace is full");
-    char *row = (char *)t.buf + (size_t)t.rows * (size_t)t.chains * t.row_bytes;
-    const unsigned R = (unsigned)t.chains;
-    const long long stride = (long long)g->chain_stride, ndev = t.ndev;
-    const bool bytes = g->c.vbytes == 1;
-    const auto blocks = [](long long items, long long per_block) { return (unsigned)std::max<long long>(1, std::min<long long>(2048, (items + per_block - 1) / per_block)); };
-    if (ndev > 0 && t.packed) {
-        const long long nwords = (long long)(t.row_bytes / 8);
-        if (!t.cols && bytes)
-            k_trace_record_dense<<<dim3(blocks(nwords * 4, NSK_BLOCK), R), dim3(NSK_BLOCK), 0, g->stream>>>((const signed char *)g->val, stride, ndev, (unsigned short *)row, nwords);
-        else if (bytes)
-            k_trace_record_bits<int8_t><<<dim3(blocks(nwords, NSK_BLOCK / 64), R), dim3(NSK_BLOCK), 0, g->stream>>>((const int8_t *)g->val, stride, t.cols, ndev, (unsigned long long *)row, nwords);
-        else
-            k_trace_record_bits<int32_t><<<dim3(blocks(nwords, NSK_BLOCK / 64), R), dim3(NSK_BLOCK), 0, g->stream>>>((const int32_t *)g->val, stride, t.cols, ndev, (unsigned long long *)row, nwords);
-    } else if (ndev > 0) {
-        if (bytes) k_trace_record_plain<int8_t><<<dim3(blocks(ndev, NSK_BLOCK), R), dim3(NSK_BLOCK), 0, g->stream>>>((const int8_t *)g->val, stride, t.cols, ndev, (int8_t *)row);
-        else k_trace_record_plain<int32_t><<<dim3(blocks(ndev, NSK_BLOCK), R), dim3(NSK_BLOCK), 0, g->stream>>>((const int32_t *)g->val, stride, t.cols, ndev, (int32_t *)row);
-    }
-    HIPCHECK(hipGetLastError());
-    if (t.lp) {     // the lp column: the state just recorded, every chain (a tally kept in the value bytes leaves bit 0 the value)
-        int rc = nsk_energy_enqueue(g, g->val, t.chains, g->packed_sweeps > 0, t.lp + (size_t)t.rows * (size_t)t.chains);
-        if (rc) return rc;
-    }
-    if (t.ws) {     // the stats column: likewise, the weights of its selection
-        const size_t row = (size_t)t.chains * (size_t)t.ws_plan.ncols;
-        int rc = nsk_wstats_enqueue(g, t.ws_plan, g->val, t.chains, g->packed_sweeps > 0, t.ws_scaled, t.ws + (size_t)t.rows * row, t.ws_plan.ncols);
-        if (rc) return rc;
-    }
-    t.sweep_index.push_back((int64_t)g->sweep);
-    t.rows++;
-    return NSK_OK;
-}
-
-extern "C" {
-
 // 64-bit hash of the compiled layout (nsk_graph_info.layout_hash): FNV-1a over 8-byte words, one lane per array,
 // the lanes folded in a fixed order
 #define hash_array(v) hash_bytes((v).data(), (v).size() * sizeof((v)[0]))
@@ -1500,7 +871,7 @@ static void fill_info(const Compiled &c, nsk_graph_info *info) {
 int nsk_graph_get_info(nsk_graph *g, nsk_graph_info *info) {
     if (!g || !info) return fail(NSK_E_INVALID, "null argument");
     fill_info(g->c, info);
-    info->device_bytes = g->device_bytes;
+    info->device_bytes = g->mem.total;
     info->sweeps_done = g->sweeps_done;
     info->learn_cap = g->learn_cap;
     if (g->clip_count) {
@@ -1916,17 +1287,16 @@ int nsk_p2p_export(nsk_graph *g, void *handle64, void **base) {
     const size_t bytes = nsk_p2p_bytes(g->pworld, (size_t)g->p_nrecv, vb, nw);
     if (g->p2p_base && g->p2p_bytes < bytes) {          // a later set-up with longer lists: a new allocation
         HIPCHECK(hipStreamSynchronize(g->stream));
-        g->allocs.erase(std::remove(g->allocs.begin(), g->allocs.end(), g->p2p_base), g->allocs.end());
-        (void)hipFree(g->p2p_base);
-        g->device_bytes -= (int64_t)g->p2p_bytes;
+        dev_free(g, g->p2p_base);
         g->p2p_base = nullptr;
     }
     if (!g->p2p_base) {
         // fine-grained: a peer's stores and this rank's polling loads are coherent while kernels run
-        HIPCHECK(hipExtMallocWithFlags(&g->p2p_base, bytes, hipDeviceMallocFinegrained));
-        g->allocs.push_back(g->p2p_base);
+        uint8_t *base8 = nullptr;
+        int rc = dev_alloc(g, &base8, bytes, true);
+        if (rc) return rc;
+        g->p2p_base = base8;
         g->p2p_bytes = bytes;
-        g->device_bytes += (int64_t)bytes;
     }
     HIPCHECK(hipMemsetAsync(g->p2p_base, 0, g->p2p_bytes, g->stream));
     HIPCHECK(hipMemsetAsync(g->p2p_err, 0, 4 * sizeof(unsigned int), g->stream));
@@ -2021,14 +1391,10 @@ static int p2p_fuse_plan(nsk_graph *g) {
             if (e != 0xFFFFFFFFu) return NSK_OK;                                     // a second reader
             e = ((uint32_t)q << 28) | (uint32_t)(g->p_dbase[q] + (k - g->p_soff[q]));
         }
-    if (g->p2p_push_map) {
-        g->allocs.erase(std::remove(g->allocs.begin(), g->allocs.end(), (void *)g->p2p_push_map), g->allocs.end());
-        (void)hipFree(g->p2p_push_map);
-        g->p2p_push_map = nullptr;
-    }
+    dev_free(g, g->p2p_push_map);
+    g->p2p_push_map = nullptr;
     int rc = dev_upload(g, &g->p2p_push_map, pm);
     if (rc) return rc;
-    if (!g->d_counters) {}      // (the border counter lives behind the error mark: p2p_err[3])
     g->p2p_border_tiles.swap(tiles);
     g->p2p_ghost_lo = ghost_lo;
     g->p2p_fused = true;

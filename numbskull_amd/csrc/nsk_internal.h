@@ -1,6 +1,6 @@
 // nsk_internal.h -- host-side state of a compiled graph handle, shared by the translation units of
 // the library (nsk_api.hip: C-ABI, state sync, exchange; nsk_gibbs.hip / nsk_learn.hip: the sweep
-// drivers of numbskull/factorgraph.py:141,163,202).
+// drivers of numbskull/factorgraph.py:141,163,202; nsk_trace.hip, nsk_energy.hip, nsk_wstats.hip: the diagnostics).
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -11,6 +11,7 @@
 #include <vector>
 
 #include "../../include/numbskull_amd.h"
+#include "nsk_alloc.h"
 #include "nsk_compile.h"
 #include "nsk_device.h"
 #include "nsk_kernels_gibbs.h"
@@ -35,7 +36,7 @@ struct NskLearnSegPlan { int key = -1; bool wide = false; nsk::SegTable tab; uin
 
 // Per-weight statistics (nsk_weight_stats / the trace's stats column; nsk_kernels_wstats.h).  A PLAN is the device work
 // list of a selection of weights: one lane per short weight, one wave per piece of a longer one, a second launch for
-// the weights of several pieces, each item with the output column it serves (nsk_api.hip wstats_plan_build).
+// the weights of several pieces, each item with the output column it serves (nsk_wstats.hip wstats_plan_build).
 #define NSK_WSTATS_SHORT 16         // a weight of at most this many factors is one lane's
 #define NSK_WSTATS_PIECE 2048       // entries of one wave's piece (32 a lane)
 #define NSK_WSTATS_MAX_BLOCKS 2048  // the lanes and waves of a larger plan loop (8 blocks per CU)
@@ -46,7 +47,6 @@ struct NskWstatsPlan {
     unsigned int len_end[NSK_WSTATS_SHORT] = {};    // shorts below len_end[k] have at most k + 1 entries
     int64_t nshort = 0, npiece = 0, nmulti = 0, npartial = 0, ncols = 0;
     int partial_chains = 0;
-    int64_t device_bytes = 0;          // what the plan added to the handle's device_bytes
 };
 // The by-weight index list (built on the host and uploaded at the first use), the plan of ALL weights and a query's
 // result buffer.  wf_off stays on the host: the plans carry the offsets.  A handle that never asks holds none of this.
@@ -74,20 +74,17 @@ struct NskTrace {
     bool packed = false;
     int chains = 1;                    // the handle's chain count at set-up (nsk_set_chains refuses another while it lives)
     size_t row_bytes = 0;              // one chain's share of a row
-    int64_t device_bytes = 0;          // what the trace added to the handle's device_bytes
     std::vector<int64_t> pos;          // the caller's column j is device column pos[j]
     std::vector<int64_t> sweep_index;  // per recorded row: the handle's sweep index it was taken after
     double *lp = nullptr;              // the lp column (nsk_trace_log_potential): capacity x chains log-potentials, or off
-    int64_t lp_bytes = 0;              // ... and what it added to the handle's device_bytes
     double *ws = nullptr;              // the stats column (nsk_trace_weight_stats): capacity x chains x ws_plan.ncols sums, or off
     NskWstatsPlan ws_plan;             // ... the work list of its selection
     bool ws_scaled = false;
-    int64_t ws_bytes = 0;              // ... and what column and plan added to the handle's device_bytes
 };
 
 // Log-potential (nsk_log_potential / nsk_factor_values / the trace's lp column): the factor walk of nsk_kernels_energy.h
 // reads f_rec, m_rec, v_card (and iid_of_vid on a graph with literal heads) -- the arrays nsk_ensure_generic uploads, taken
-// from it when it ran, uploaded at the first use otherwise (nsk_api.hip energy_ensure) -- and leaves one partial sum per
+// from it when it ran, uploaded at the first use otherwise (nsk_energy.hip energy_ensure) -- and leaves one partial sum per
 // block and chain.  A handle that never asks holds none of this.
 struct NskEnergy {
     bool ready = false;                // every factor was checked and the arrays are on the device
@@ -133,9 +130,7 @@ struct nsk_graph {
     hipStream_t side[3] = {nullptr, nullptr, nullptr};
     hipEvent_t ev_fork = nullptr, ev_join[3] = {nullptr, nullptr, nullptr};
     bool no_overlap = nsk::diag_env("NSK_NO_OVERLAP") != nullptr;     // diagnostic: one stream
-    std::vector<void *> allocs;
-    std::vector<std::pair<void *, void *>> alloc_alias;   // (aligned pointer handed out, allocation) where they differ (NSK_ALLOC_ALIGN)
-    int64_t device_bytes = 0;
+    NskLedger mem;                     // every device array below and what it counts for (nsk_alloc.h; nsk_graph_info.device_bytes)
     // device arrays
     int32_t *p_vid = nullptr, *p_slot = nullptr, *p_cnt = nullptr, *slot_off = nullptr, *fidx = nullptr;
     uint32_t *p_info = nullptr, *f_rec = nullptr;
@@ -270,6 +265,36 @@ struct nsk_graph {
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
     int64_t launches = 0, launches_at_begin = 0;
 };
+
+// The allocation helpers of every translation unit: a device array is entered in the handle's ledger with the
+// (n ? n : 1) * sizeof(T) bytes it counts for (fine: a fine-grained allocation, the peer-to-peer block) ...
+template <typename T>
+static int dev_alloc(nsk_graph *g, T **ptr, size_t n, bool fine = false) {
+    size_t bytes = (n ? n : 1) * sizeof(T);
+    void *p = nullptr;
+    // (diagnostic, NSK_DIAG=1 NSK_ALLOC_ALIGN=1: arrays of a megabyte or more start on a 2 MB boundary whatever the
+    // allocator does -- where the arrays of the table kernels lie moves their launch time by 3 %)
+    static const bool align2m = nsk::diag_env("NSK_ALLOC_ALIGN") != nullptr;
+    const size_t big = (size_t)1 << 20, two = (size_t)2 << 20;
+    const bool al = align2m && bytes >= big && !fine;
+    hipError_t e = fine ? hipExtMallocWithFlags(&p, bytes, hipDeviceMallocFinegrained) : hipMalloc(&p, al ? bytes + two : bytes);
+    if (e != hipSuccess) return nsk::fail(fine ? NSK_E_DEVICE : NSK_E_NOMEM, std::string(fine ? "hipExtMallocWithFlags: " : "hipMalloc: ") + hipGetErrorString(e));
+    void *raw = p;
+    if (al) p = (void *)(((uintptr_t)p + two - 1) / two * two);
+    g->mem.add(p, raw, bytes);
+    *ptr = (T *)p;
+    return NSK_OK;
+}
+// ... and dev_free takes it off again (null is a no-op)
+static inline void nsk_free_raw(void *raw) { (void)hipFree(raw); }
+static inline void dev_free(nsk_graph *g, void *p) { if (void *raw = g->mem.remove(p)) nsk_free_raw(raw); }
+template <typename T>
+static int dev_upload(nsk_graph *g, T **ptr, const std::vector<T> &h) {
+    int rc = dev_alloc(g, ptr, h.size());
+    if (rc) return rc;
+    if (!h.empty()) HIPCHECK(hipMemcpyAsync(*ptr, h.data(), h.size() * sizeof(T), hipMemcpyHostToDevice, g->stream));
+    return NSK_OK;
+}
 
 #define NSK_MAX_CHAINS 1024
 // entry points that serve one chain only: refused on a handle with several (nsk_set_chains)
@@ -481,7 +506,13 @@ void nsk_refresh_prog_weights(nsk_graph *g, bool force = false);
 void nsk_refresh_ztab(nsk_graph *g, int set = 0, hipStream_t st = nullptr);
 int nsk_fold_position_tally(nsk_graph *g);
 int nsk_unpack_tally(nsk_graph *g);
-int nsk_trace_record(nsk_graph *g);                 // one row of the sample trace behind what the stream holds (nsk_api.hip)
+int nsk_trace_record(nsk_graph *g);                 // one row of the sample trace behind what the stream holds (nsk_trace.hip)
+void wstats_plan_free(nsk_graph *g, NskWstatsPlan &plan);      // nsk_wstats.hip (the trace's stats column goes with the trace)
+// the handles the diagnostics serve (whole graph, no exchange); the arrays of the factor walk at the first use (nsk_energy.hip)
+int energy_whole_graph(const nsk_graph *g, const char *what);
+int energy_ensure(nsk_graph *g, int chains, const char *what);
+namespace nsk { struct EnergyArgs; }
+nsk::EnergyArgs energy_args(const nsk_graph *g);
 // the log-potential of `nchains` chains from `val` on / every factor's value, enqueued on the handle's stream (nsk_energy.hip)
 int nsk_energy_enqueue(nsk_graph *g, const void *val, int nchains, bool packed_bytes, double *out);
 int nsk_factor_values_enqueue(nsk_graph *g, const void *val, double *out);

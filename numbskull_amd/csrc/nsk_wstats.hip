@@ -1,6 +1,6 @@
-// nsk_wstats.hip -- launches of the per-weight statistics (nsk_kernels_wstats.h) on the handle's stream.  The entry
-// points (nsk_weight_stats, nsk_trace_weight_stats), the by-weight list and the plans live in nsk_api.hip; the sample
-// trace calls nsk_wstats_enqueue behind every record launch when its stats column is on.
+// nsk_wstats.hip -- the per-weight statistics (nsk_internal.h NskWstats): the entry points (nsk_weight_stats, the sample
+// trace's stats column), the by-weight list, the plans, and the launches of the kernels (nsk_kernels_wstats.h) on the
+// handle's stream; the sample trace calls nsk_wstats_enqueue behind every record launch when its stats column is on.
 #include <hip/hip_runtime.h>
 
 #include "nsk_internal.h"
@@ -30,12 +30,7 @@ int nsk_wstats_enqueue(nsk_graph *g, const NskWstatsPlan &plan, const void *val,
     if (!g->energy.ready || !ws.ready || nchains < 1 || (plan.npartial > 0 && nchains > plan.partial_chains) || (scaled && !g->f_feat))
         return fail(NSK_E_INVALID, "weight statistics: the by-weight list is not set up");
     WstatsArgs a;
-    a.e.f_rec = (const uint4 *)g->f_rec; a.e.m_rec = (const int2 *)g->m_rec;
-    a.e.v_card = g->v_card; a.e.iid_of_vid = g->iid_of_vid;
-    a.e.w = g->w; a.e.logtab = g->logtab;
-    a.e.nfactor = (long long)g->c.nfactor;
-    a.e.chain_stride = (long long)g->chain_stride;
-    a.e.head_by_vid = (g->c.flags & NSK_FLAG_HEAD_BY_VID) ? 1 : 0;
+    a.e = energy_args(g);
     a.wf_idx = ws.wf_idx;
     a.feat = scaled ? g->f_feat : nullptr;
     a.shorts = plan.shorts; a.pieces = plan.pieces; a.multi = plan.multi;
@@ -51,3 +46,213 @@ int nsk_wstats_enqueue(nsk_graph *g, const NskWstatsPlan &plan, const void *val,
     HIPCHECK(hipGetLastError());
     return NSK_OK;
 }
+
+// ---- per-weight statistics (nsk_internal.h NskWstats, nsk_kernels_wstats.h) -----------------------------------------
+// The by-weight index list at the first use (after energy_ensure: every factor's weight slot was checked), and the
+// feature values when a scaled sum asks for them
+static int wstats_ensure(nsk_graph *g, bool scaled, const char *what) {
+    NskWstats &ws = g->wstats;
+    Compiled &c = g->c;
+    HIPCHECK(hipSetDevice(g->device));
+    if (!ws.ready) {
+        const size_t nw = (size_t)c.nweight, nf = (size_t)c.nfactor;
+        std::vector<uint32_t> off(nw + 1, 0);
+        for (size_t f = 0; f < nf; f++) off[(size_t)c.f_rec[4 * f + 2] + 1]++;
+        for (size_t w = 0; w < nw; w++) off[w + 1] += off[w];
+        std::vector<int32_t> idx(nf);
+        std::vector<uint32_t> at(off.begin(), off.end() - 1);
+        for (size_t f = 0; f < nf; f++) idx[at[(size_t)c.f_rec[4 * f + 2]]++] = (int32_t)f;     // ascending inside a weight
+        NskRollback rb(g->mem, nsk_free_raw);
+        int32_t *dev = nullptr;
+        int rc = dev_upload(g, &dev, idx);
+        if (!rc && hipStreamSynchronize(g->stream) != hipSuccess) rc = fail(NSK_E_DEVICE, "hipStreamSynchronize failed");
+        if (rc) {
+            if (rc != NSK_E_NOMEM) return rc;
+            return fail(NSK_E_NOMEM, std::string(what) + ": the by-weight factor list (" + std::to_string((long long)(nf * 4 / 1048576)) +
+                                     " MB) does not fit on the device");
+        }
+        rb.commit();
+        ws.wf_off = std::move(off); ws.wf_first.resize(nw);
+        for (size_t w = 0; w < nw; w++) ws.wf_first[w] = ws.wf_off[w] < ws.wf_off[w + 1] ? idx[ws.wf_off[w]] : 0;
+        ws.wf_idx = dev;
+        ws.ready = true;
+    }
+    if (scaled && !g->f_feat) {
+        NskRollback rb(g->mem, nsk_free_raw);
+        double *feat = nullptr;
+        int rc = dev_upload(g, &feat, c.f_feat);
+        if (!rc && hipStreamSynchronize(g->stream) != hipSuccess) rc = fail(NSK_E_DEVICE, "hipStreamSynchronize failed");
+        if (rc) {
+            if (rc != NSK_E_NOMEM) return rc;
+            return fail(NSK_E_NOMEM, std::string(what) + ": the feature values (" + std::to_string((long long)(c.f_feat.size() * 8 / 1048576)) +
+                                     " MB) do not fit on the device");
+        }
+        rb.commit();
+        g->f_feat = feat;
+    }
+    return NSK_OK;
+}
+
+// partial sums of the plan's weights of several pieces, for `chains` chains (grown when more ask)
+static int wstats_partial_ensure(nsk_graph *g, NskWstatsPlan &plan, int chains) {
+    if (plan.npartial == 0 || chains <= plan.partial_chains) return NSK_OK;
+    double *partial = nullptr;
+    int rc = dev_alloc(g, &partial, (size_t)chains * (size_t)plan.npartial);
+    if (rc) return rc;
+    HIPCHECK(hipStreamSynchronize(g->stream));      // (launches that write the buffer that goes)
+    dev_free(g, plan.partial);
+    plan.partial = partial; plan.partial_chains = chains;
+    return NSK_OK;
+}
+
+// The work list of the weights whose SLOTS are slot[0 .. ncols): column j of the output is weight slot[j]'s sum.  How a
+// weight is cut is a function of its own length (nsk_kernels_wstats.h); a weight named twice is evaluated twice.
+static int wstats_plan_build(nsk_graph *g, NskWstatsPlan &plan, const int32_t *slot, int64_t ncols, int chains, const char *what) {
+    const NskWstats &ws = g->wstats;
+    NskWstatsPlan p;
+    p.ncols = ncols;
+    std::vector<std::vector<uint64_t>> bylen(NSK_WSTATS_SHORT);       // first factor << 32 | column, per length
+    std::vector<uint4> pieces, multi;
+    for (int64_t j = 0; j < ncols; j++) {
+        const size_t s = (size_t)slot[j];
+        const uint32_t off = ws.wf_off[s], len = ws.wf_off[s + 1] - off;
+        if (len == 0) continue;                     // (reads 0: the output is zeroed where it is allocated)
+        if (len <= NSK_WSTATS_SHORT) { bylen[len - 1].push_back((uint64_t)(uint32_t)ws.wf_first[s] << 32 | (uint64_t)j); continue; }
+        const uint32_t npc = (len + NSK_WSTATS_PIECE - 1) / NSK_WSTATS_PIECE;
+        if (npc == 1) { pieces.push_back(make_uint4(off, len, (uint32_t)j, 0u)); continue; }
+        multi.push_back(make_uint4((uint32_t)p.npartial, npc, (uint32_t)j, 0u));
+        for (uint32_t k = 0; k < npc; k++)
+            pieces.push_back(make_uint4(off + k * NSK_WSTATS_PIECE, std::min<uint32_t>(NSK_WSTATS_PIECE, len - k * NSK_WSTATS_PIECE), (uint32_t)(p.npartial + k), 1u));
+        p.npartial += npc;
+    }
+    std::vector<uint2> shorts;
+    for (int k = 0; k < NSK_WSTATS_SHORT; k++) {
+        std::sort(bylen[(size_t)k].begin(), bylen[(size_t)k].end());
+        for (uint64_t key : bylen[(size_t)k]) { const size_t s = (size_t)slot[(size_t)(key & 0xffffffffu)]; shorts.push_back(make_uint2(ws.wf_off[s], (uint32_t)(key & 0xffffffffu))); }
+        p.len_end[k] = (unsigned int)shorts.size();
+        std::vector<uint64_t>().swap(bylen[(size_t)k]);
+    }
+    p.nshort = (int64_t)shorts.size(); p.npiece = (int64_t)pieces.size(); p.nmulti = (int64_t)multi.size();
+    NskRollback rb(g->mem, nsk_free_raw);
+    int rc = NSK_OK;
+    if (p.nshort) rc = dev_upload(g, &p.shorts, shorts);
+    if (!rc && p.npiece) rc = dev_upload(g, &p.pieces, pieces);
+    if (!rc && p.nmulti) rc = dev_upload(g, &p.multi, multi);
+    if (!rc && hipStreamSynchronize(g->stream) != hipSuccess) rc = fail(NSK_E_DEVICE, "hipStreamSynchronize failed");
+    if (!rc) rc = wstats_partial_ensure(g, p, chains);
+    if (rc) {
+        if (rc != NSK_E_NOMEM) return rc;
+        const double mb = ((double)p.nshort * 8 + (double)p.npiece * 16 + (double)p.nmulti * 16 + (double)p.npartial * 8 * chains) / 1048576.0;
+        return fail(NSK_E_NOMEM, std::string(what) + ": the work list of the weights (" + std::to_string((long long)mb) + " MB) does not fit on the device");
+    }
+    rb.commit();
+    plan = p;
+    return NSK_OK;
+}
+
+void wstats_plan_free(nsk_graph *g, NskWstatsPlan &plan) {
+    dev_free(g, plan.shorts); dev_free(g, plan.pieces); dev_free(g, plan.multi); dev_free(g, plan.partial);
+    plan = NskWstatsPlan();
+}
+
+// slot of the caller's weight id
+static inline int32_t wstats_slot(const Compiled &c, int64_t wid) { return c.wmap.empty() ? (int32_t)wid : c.wmap[(size_t)wid]; }
+
+extern "C" {
+
+int nsk_weight_stats(nsk_graph *g, int which, int64_t first_chain, int64_t nchains, int scaled, double *out) {
+    if (!g) return fail(NSK_E_INVALID, "null graph");
+    if (!out) return fail(NSK_E_INVALID, "null argument");
+    if (which != NSK_BUF_VALUE && which != NSK_BUF_VALUE_EVID) return fail(NSK_E_INVALID, "nsk_weight_stats: which must be NSK_BUF_VALUE or NSK_BUF_VALUE_EVID");
+    const int64_t R = which == NSK_BUF_VALUE ? g->nchains : 1;
+    if (first_chain < 0 || nchains < 1 || first_chain >= R || nchains > R - first_chain)
+        return fail(NSK_E_INVALID, "nsk_weight_stats: chains outside those the handle has (the evidence chain exists once)");
+    int rc = energy_whole_graph(g, "nsk_weight_stats");
+    if (rc) return rc;
+    const Compiled &c = g->c;
+    if (c.nweight == 0) return NSK_OK;
+    if ((rc = energy_ensure(g, 0, "nsk_weight_stats"))) return rc;
+    if ((rc = wstats_ensure(g, scaled != 0, "nsk_weight_stats"))) return rc;
+    NskWstats &ws = g->wstats;
+    if (!ws.all_ready) {
+        std::vector<int32_t> slot((size_t)c.nweight);
+        for (int64_t w = 0; w < c.nweight; w++) slot[(size_t)w] = wstats_slot(c, w);
+        if ((rc = wstats_plan_build(g, ws.all, slot.data(), c.nweight, (int)nchains, "nsk_weight_stats"))) return rc;
+        ws.all_ready = true;
+    }
+    if ((rc = wstats_partial_ensure(g, ws.all, (int)nchains))) return rc;
+    if (nchains > ws.result_chains) {
+        double *result = nullptr;
+        const size_t n = (size_t)nchains * (size_t)c.nweight;
+        if ((rc = dev_alloc(g, &result, n)))
+            return fail(NSK_E_NOMEM, "nsk_weight_stats: one double per chain and weight (" + std::to_string((long long)(n * 8 / 1048576)) + " MB) does not fit on the device");
+        HIPCHECK(hipStreamSynchronize(g->stream));
+        dev_free(g, ws.result);
+        HIPCHECK(hipMemsetAsync(result, 0, n * sizeof(double), g->stream));     // (weights without a factor are never written)
+        ws.result = result; ws.result_chains = (int)nchains;
+    }
+    const char *val = which == NSK_BUF_VALUE ? (const char *)g->val + (size_t)first_chain * g->chain_stride : (const char *)g->val_evid;
+    if ((rc = nsk_wstats_enqueue(g, ws.all, val, (int)nchains, g->packed_sweeps > 0, scaled != 0, ws.result, c.nweight))) return rc;
+    HIPCHECK(hipMemcpyAsync(out, ws.result, (size_t)nchains * (size_t)c.nweight * sizeof(double), hipMemcpyDeviceToHost, g->stream));
+    HIPCHECK(hipStreamSynchronize(g->stream));
+    return NSK_OK;
+}
+
+int nsk_trace_weight_stats(nsk_graph *g, const int64_t *wids, int64_t nwids, int scaled) {
+    if (!g) return fail(NSK_E_INVALID, "null graph");
+    NskTrace &t = g->trace;
+    if (t.capacity == 0) return fail(NSK_E_INVALID, "nsk_trace_weight_stats: no trace is set up");
+    const Compiled &c = g->c;
+    if (nwids >= 0 && (wids ? nwids < 1 : nwids != 0))
+        return fail(NSK_E_INVALID, "nsk_trace_weight_stats: a list of weight ids needs at least one (NULL with 0: all weights)");
+    if (nwids > 0)
+        for (int64_t j = 0; j < nwids; j++)
+            if (wids[j] < 0 || wids[j] >= c.nweight) return fail(NSK_E_INDEX, "nsk_trace_weight_stats: weight id out of range");
+    HIPCHECK(hipSetDevice(g->device));
+    HIPCHECK(hipStreamSynchronize(g->stream));
+    int rc = NSK_OK;
+    if (nwids >= 0) {       // (before the column that stands goes)
+        if ((rc = energy_whole_graph(g, "nsk_trace_weight_stats"))) return rc;
+        if ((rc = energy_ensure(g, 0, "nsk_trace_weight_stats"))) return rc;
+        if ((rc = wstats_ensure(g, scaled != 0, "nsk_trace_weight_stats"))) return rc;
+    }
+    dev_free(g, t.ws);
+    t.ws = nullptr; t.ws_scaled = false;
+    wstats_plan_free(g, t.ws_plan);
+    if (nwids < 0) return NSK_OK;
+    const int64_t ncols = wids ? nwids : c.nweight;
+    const double total = (double)t.capacity * (double)t.chains * (double)ncols;
+    if (total >= 35184372088832.0) return fail(NSK_E_NOMEM, "nsk_trace_weight_stats: the column does not fit");
+    std::vector<int32_t> slot((size_t)ncols);
+    for (int64_t j = 0; j < ncols; j++) slot[(size_t)j] = wstats_slot(c, wids ? wids[j] : j);
+    NskRollback rb(g->mem, nsk_free_raw);
+    NskWstatsPlan plan;
+    if ((rc = wstats_plan_build(g, plan, slot.data(), ncols, t.chains, "nsk_trace_weight_stats"))) return rc;
+    double *col = nullptr;
+    const size_t n = (size_t)t.capacity * (size_t)t.chains * (size_t)ncols;
+    if ((rc = dev_alloc(g, &col, n)))
+        return fail(NSK_E_NOMEM, "nsk_trace_weight_stats: capacity x chains x weights doubles (" + std::to_string((long long)(n * 8 / 1048576)) + " MB) do not fit on the device");
+    HIPCHECK(hipMemsetAsync(col, 0, (n ? n : 1) * sizeof(double), g->stream));     // (weights without a factor, rows recorded while it was off)
+    rb.commit();
+    t.ws_plan = plan;
+    t.ws = col;
+    t.ws_scaled = scaled != 0;
+    return NSK_OK;
+}
+
+int nsk_trace_download_weight_stats(nsk_graph *g, int64_t first_row, int64_t nrows, double *out) {
+    if (!g) return fail(NSK_E_INVALID, "null graph");
+    const NskTrace &t = g->trace;
+    if (t.capacity == 0) return fail(NSK_E_INVALID, "nsk_trace_download_weight_stats: no trace is set up");
+    if (!t.ws) return fail(NSK_E_INVALID, "nsk_trace_download_weight_stats: the trace keeps no stats column (nsk_trace_weight_stats)");
+    if (first_row < 0 || nrows < 0 || first_row + nrows > t.rows) return fail(NSK_E_INVALID, "nsk_trace_download_weight_stats: rows beyond those recorded");
+    const size_t row = (size_t)t.chains * (size_t)t.ws_plan.ncols;
+    if (nrows > 0 && row > 0 && !out) return fail(NSK_E_INVALID, "null argument");
+    HIPCHECK(hipSetDevice(g->device));
+    HIPCHECK(hipStreamSynchronize(g->stream));
+    if (nrows > 0 && row > 0)
+        HIPCHECK(hipMemcpy(out, t.ws + (size_t)first_row * row, (size_t)nrows * row * sizeof(double), hipMemcpyDeviceToHost));
+    return NSK_OK;
+}
+
+}  // extern "C"
