@@ -53,6 +53,7 @@ inline const char *diag_env(const char *name) {
     return getenv(name);
 }
 
+// (a new data member must be added to layout_hash, nsk_compile.cpp: it folds every member, in declaration order)
 struct Compiled {
     // sizes
     int64_t nvar = 0, nweight = 0, nfactor = 0, nedge = 0, ncount = 0;
@@ -93,7 +94,7 @@ struct Compiled {
     int64_t nhub_ep = 0;
     // A tile whose 64 lanes share one header sequence (same function, member count and weight per
     // entry) with at most 8 member slots is "uniform": its stream holds member words only and its
-    // per-slot program (weight id, function code, first/last/ignore flags; nsk_compile.cpp) is kept
+    // per-slot program (weight id, function code, first/last/ignore flags; nsk_compile_tiles.cpp) is kept
     // once in tile_hdr, padded to 8 words, for the scalar unit to read.
     std::vector<uint32_t> tile_hdr;
     // first positions of the tiles with per-lane headers, per phase (the learning sweep hands
@@ -246,6 +247,9 @@ struct Compiled {
 
 // returns NSK_OK or an NSK_E_* code with `err` filled
 int compile_graph(const nsk_graph_desc *d, Compiled &out, std::string &err);
+
+// 64-bit hash of every data member of a compiled layout (nsk_graph_info.layout_hash with NSK_LAYOUT_HASH=1)
+int64_t layout_hash(const Compiled &c);
 
 // true for function ids of inference.py:74-143
 bool known_function(int fn);

@@ -58,7 +58,7 @@ int energy_whole_graph(const nsk_graph *g, const char *what) {
     return NSK_OK;
 }
 
-// nsk_graph_create validates the factors a sampled variable reaches (nsk_compile.cpp validate_reachable); the walk
+// nsk_graph_create validates the factors a sampled variable reaches (nsk_compile_colour.cpp validate_reachable); the walk
 // evaluates EVERY factor, so the others are held to the same rules here, on the compiled records.  Returns the lowest
 // factor that breaks one (-1: none) and whether some factor reads its head at the literal edge index.
 static int64_t energy_check_factors(const nsk_graph *g, bool *literal_out) {

@@ -149,7 +149,7 @@ def _small_graphs(golden):
         "lr_manyw": (graphgen.mixed_lr_graph(3000, seed=6, nweights=1500), True),
         # other members drawn from [v - 2, v + 2]: a fifth of them is the variable itself -- body
         # member AND head of IMPLY_MLN / IMPLY_MLN_CAT, own edges with different dense_equal_to --
-        # the two-role entries of the general tiles (nsk_compile.cpp general_words)
+        # the two-role entries of the general tiles (nsk_compile_words.cpp general_words_walk)
         "lr_selfdup": (graphgen.mixed_lr_graph(3000, seed=8, nweights=40, window=2), True),
         "pairs_manyw": (_pairs_many_weights(), False),
         # one weight per factor: tiles share a word layout but not weights (shape tiles)

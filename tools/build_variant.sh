@@ -15,5 +15,6 @@ else
   /opt/rocm/bin/hipcc $FLAGS $extra -c -o build/nsk_gibbs_$v.o nsk_gibbs.hip
   objs="build/nsk_gibbs_$v.o $LEARN"
 fi
-/opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -fPIC -pthread -o ../variants/libnsk_$v.so build/nsk_api.o $objs build/nsk_compile.o build/nsk_host.o build/nsk_partition.o
+# (the host objects -- the graph compiler's stage files among them -- are the Makefile's list)
+/opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -fPIC -pthread -o ../variants/libnsk_$v.so build/nsk_api.o build/nsk_energy.o build/nsk_wstats.o build/nsk_trace.o $objs $(make -s print-host-obj)
 echo built ../variants/libnsk_$v.so
