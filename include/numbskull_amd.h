@@ -293,6 +293,14 @@ typedef struct {
     int64_t tab_quads;                /* position quads (256 consecutive positions) of the segments with draw tables */
     int64_t wide_quads;               /* ... of them the WIDE ones: one lane samples four consecutive positions from
                                          dword loads (nsk_graph_get_generators bit 41)                              */
+    int64_t hubs;                     /* variables a whole wave or workgroup samples (positions of the wave-per-variable
+                                         ranges that hold a variable): lists of 32 entries and more, and every generic-
+                                         path variable of a colour with few of them                                  */
+    int64_t hubs_ep;                  /* ... of them those with an entry-parallel stream (one lane per list entry; the
+                                         others take the generic wave walk)                                          */
+    int64_t hubs_block;               /* ... of those the ones a whole workgroup evaluates (more than 128 entries in a
+                                         colour laid out as entry-parallel groups); the other hubs_ep - hubs_block
+                                         take one wave each                                                          */
 } nsk_graph_info;
 int nsk_graph_get_info(nsk_graph *g, nsk_graph_info *info);
 int nsk_graph_get_colors(nsk_graph *g, int32_t *color /* nvar, -1 for ghosts */);

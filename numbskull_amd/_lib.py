@@ -56,7 +56,8 @@ class GraphInfo(C.Structure):
                 ("learn_clipped", C.c_int64), ("grad_shift", C.c_int64),
                 ("acc_copies", C.c_int64), ("learn_lag", C.c_int64), ("direct_weights", C.c_int64),
                 ("weight_slots", C.c_int64), ("layout_hash", C.c_int64), ("p2p_fused", C.c_int64),
-                ("tab_quads", C.c_int64), ("wide_quads", C.c_int64)]
+                ("tab_quads", C.c_int64), ("wide_quads", C.c_int64),
+                ("hubs", C.c_int64), ("hubs_ep", C.c_int64), ("hubs_block", C.c_int64)]
 
 
 _lib = None

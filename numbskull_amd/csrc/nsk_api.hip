@@ -838,6 +838,11 @@ static void fill_info(const Compiled &c, nsk_graph_info *info) {
     info->p2p_fused = 0;
     info->tab_quads = c.ntab_quads;
     info->wide_quads = c.nwide_quads;
+    info->hubs = 0;
+    for (size_t k = 0; k < c.phase_heavy_end.size(); k++)
+        for (int64_t p = c.phase_fast_end[k]; p < c.phase_heavy_end[k]; p++) info->hubs += c.p_vid[(size_t)p] >= 0;
+    info->hubs_ep = c.nhub_ep;
+    info->hubs_block = c.phase_bighub_base.empty() ? 0 : c.phase_bighub_base.back();   // (bighub_pos is padded when empty)
 }
 
 int nsk_graph_get_info(nsk_graph *g, nsk_graph_info *info) {

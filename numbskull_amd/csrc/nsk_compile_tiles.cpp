@@ -256,6 +256,23 @@ void CompileCtx::find_direct_weights() {
             const int64_t wid = d->factor[f].weightId;
             if (wid >= 0 && wid < nw) nfac_of[(size_t)wid] = 2;
         }
+        // a NOOP factor reads no member, so the colouring may put two of its members into one class: two visits
+        // of its weight in that class, which only the accumulators take.  (Its member list is not validated: it is
+        // read here only where it lies inside fmap.)
+        std::vector<std::pair<int32_t, int64_t>> seen;                // (colour, variable) of a NOOP factor's members
+        for (int64_t f = 0; f < nfac; f++) {
+            const nsk_factor &fa = d->factor[f];
+            if (fa.factorFunction != -1 || fa.arity < 2 || fa.weightId < 0 || fa.weightId >= nw) continue;
+            if (fa.ftv_offset < 0 || fa.arity > c.nedge || fa.ftv_offset > c.nedge - fa.arity) continue;
+            seen.clear();
+            for (int64_t l = fa.ftv_offset; l < fa.ftv_offset + fa.arity; l++) {
+                const int64_t v = d->fmap[l].vid;
+                if (v >= 0 && v < c.nvar && c.color[(size_t)v] >= 0) seen.push_back({c.color[(size_t)v], v});
+            }
+            std::sort(seen.begin(), seen.end());
+            for (size_t a = 1; a < seen.size(); a++)
+                if (seen[a].first == seen[a - 1].first && seen[a].second != seen[a - 1].second) { nfac_of[(size_t)fa.weightId] = 2; break; }
+        }
         for (int64_t t = 0; t < nwb; t++) {                          // weights named by uniform tiles' programs
             const uint32_t *td = &c.tiles[4 * t];
             if (td[2] == 0xFFFFFFFFu || ((td[3] >> 8) & 7u) >= 6u) continue;

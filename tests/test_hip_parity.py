@@ -154,7 +154,10 @@ def _small_graphs(golden):
         "pairs_manyw": (_pairs_many_weights(), False),
         # one weight per factor: tiles share a word layout but not weights (shape tiles)
         "boolw": (_boolw(), False),
-        # hub variables (factor lists >= 128 entries): one wave per variable
+        # hub variables (factor lists >= 32 entries): one wave per variable, on the generic wave walk only -- two of
+        # its hubs exceed the 256-entry cap of the entry-parallel route in their colours, the third is a labelling-
+        # function factor's.  The entry-parallel routes (one wave, one workgroup) and the edges of all four hub
+        # routes: tests/test_hubs_gpu.py; which route a graph takes: tests/test_hubs_cpu.py
         "hubs": (_hub_graph(), False),
         "lr_bigcard": (_big_cardinality_graph(), False),
         # every function of the general tiles (kind 6) on dataType-0 and -1 variables of
