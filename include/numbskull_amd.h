@@ -204,6 +204,39 @@ int nsk_trace_weight_stats(nsk_graph *g, const int64_t *wids, int64_t nwids, int
 int nsk_trace_download_weight_stats(nsk_graph *g, int64_t first_row, int64_t nrows,
                                     double *out /* nrows x chains x nwids */);
 
+/* Effective sample size from the trace, on the device (FactorGraph.mixing): per column of a BIT-PACKED trace, the
+ * split-chain estimator of numbskull_amd.diagnostics.effective_sample_size with the lags cut at max_lag, in one
+ * streaming pass over the packed rows -- no row is unpacked or leaves the device.  Rows first_row .. first_row +
+ * nrows - 1 of the R chains are split as for split R-hat: n = nrows / 2, half-chains rows [0, n) and [nrows - n, nrows)
+ * of every chain, H = 2 R of them (one chain is allowed: H = 2; the middle row of an odd nrows is unused).  For 0 / 1
+ * columns every sum is a count over bit words; per column the device forms, in int64 and exactly, for k = 0 .. L,
+ * L = min(max_lag, n - 1),
+ *   A(k) = sum over half-chains h of  n^2 c_h(k) - n S_h (head_h(k) + tail_h(k)) + (n - k) S_h^2
+ * (S_h the half-chain's sum, c_h(k) the sum of x(t) x(t + k) over t < n - k, head_h(k) and tail_h(k) the sums of its
+ * first and last n - k rows: n^3 times the summed biased autocovariance at lag k), S1 = sum of S_h and S2 = sum of S_h^2.
+ * The float64 epilogue, one rounded operation a step in the order DESIGN.md section 4 writes down: D = H n n (n - 1),
+ * W = A(0) / D, B = (H S2 - S1^2) / (H (H - 1) n n), V = (n - 1) / n W + B, rho_k = 1 - ((A(0) - A(k)) / D) / V,
+ * P_j = rho_2j + rho_2j+1 for j < (L + 1) / 2, tau = -1 + 2 x the sum of the initial run of P_j > 0.
+ * nsk_trace_ess: per column mean = S1 / (H n); tau (NaN unless V > 0 and tau > 0); rhat2 = V / W (NaN unless V > 0;
+ * split R-hat is its square root); truncated = 1 when every pair up to the last was positive and L < n - 1 (the
+ * sequence did not end inside the window: tau is a lower bound, thin more).  The effective sample size is n H / tau.
+ * The arrays are ncols long, in the caller's column order of nsk_trace_setup (repeats, and all nvar variables for
+ * vids = NULL); any may be NULL.
+ * nsk_trace_autocov_counts: the integers themselves for the trace columns cols[0 .. ncols_sel) (indices into the
+ * caller's columns; any order, repeats allowed; outside [0, ncols): NSK_E_INDEX):
+ * out[j (L + 3) ..] = A(0 .. L), S1, S2 of column cols[j].
+ * Both synchronise with the handle's stream, read the trace and change nothing (rows, values, tallies, sweeps_done, the lp and
+ * stats columns).  Their result buffers (25 bytes a device column; 8 (L + 3) a column of the words selected) are
+ * allocated for the call and freed before it returns: nsk_graph_info.device_bytes shows them only meanwhile;
+ * NSK_E_NOMEM names their size when they do not fit.  nsk_profile_* keeps counting sweep-kernel launches only.
+ * Refused before any launch -- NSK_E_INVALID: no trace, plain (not bit-packed) rows, nrows < 4, max_lag outside
+ * [1, 63]; NSK_E_RANGE: 4 H n^3 reaches 2^63 (decided from nrows and the chain count alone, before the rows recorded
+ * are looked at); then NSK_E_INVALID: rows beyond those recorded. */
+int nsk_trace_ess(nsk_graph *g, int64_t first_row, int64_t nrows, int64_t max_lag, double *mean /* ncols */,
+                  double *tau, double *rhat2, uint8_t *truncated);
+int nsk_trace_autocov_counts(nsk_graph *g, int64_t first_row, int64_t nrows, int64_t max_lag, const int64_t *cols,
+                             int64_t ncols_sel, int64_t *out /* ncols_sel x (L + 3) */);
+
 /* RNG: the chromatic scan draws from Philox4x32-10 keyed by `seed`.  A variable's generator id is
  * its position in the compiled layout (nsk_graph_get_layout), so samples are a function of the seed
  * AND the layout the library chose (device, flags and diagnostic switches being equal, a graph

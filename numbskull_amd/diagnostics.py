@@ -21,6 +21,11 @@ the most probable sample recorded.
 The per-weight statistics of ``FactorGraph.sample(..., weight_statistics=...)``, shape ``(samples, chains, weights)``,
 are a trace like any other; ``moment_gap`` compares their mean with a target (the evidence chain's statistics, or an
 exact expectation): the log-likelihood gradient of weight learning, with its Monte-Carlo standard error.
+
+``autocov_counts`` and ``ess_from_counts`` restate, in numpy, what ``FactorGraph.mixing`` computes on the device from
+a bit-packed trace (nsk_trace_ess): for 0 / 1 columns the estimator above is integer counts --
+exact in int64 -- and a short float64 epilogue, the lags cut at ``max_lag``.  With ``max_lag = n - 1`` it is the
+estimator of ``effective_sample_size``.
 """
 
 import numpy as np
@@ -96,6 +101,89 @@ def effective_sample_size(trace):
         ess[ok] = n * m / tau[ok]
         out[c0:c0 + _CHUNK] = ess
     return out
+
+
+def counts_fit_int64(n, H):
+    """Whether the integers of ``autocov_counts`` for ``H`` half-chains of ``n`` rows fit int64 with every
+    intermediate: ``4 H n^3 < 2^63`` (the bound nsk_trace_ess refuses beyond, NSK_E_RANGE)."""
+    return 4 * int(H) * int(n) ** 3 < 2 ** 63
+
+
+def autocov_counts(trace, max_lag):
+    """The integers of the device estimator from a downloaded 0 / 1 trace ``(samples, chains, columns)``:
+    ``(n, H, A, S1, S2)`` with ``n = samples // 2`` rows in each of the ``H = 2 x chains`` half-chains (rows ``[0, n)``
+    and ``[samples - n, samples)`` of every chain), and per column, in int64, for ``k = 0 .. L``,
+    ``L = min(max_lag, n - 1)``,
+
+        A[k] = sum over half-chains h of  n^2 c_h(k) - n S_h (head_h(k) + tail_h(k)) + (n - k) S_h^2
+
+    (``S_h`` the half-chain's sum, ``c_h(k)`` the sum of ``x_t x_{t+k}`` over ``t < n - k``, ``head_h(k)`` / ``tail_h(k)``
+    the sums of its first / last ``n - k`` rows; ``n^3`` times the summed biased autocovariance at lag ``k``), shape
+    ``(L + 1, columns)``; ``S1`` the sum of the ``S_h`` and ``S2`` of their squares, shape ``(columns,)``.  One chain
+    is allowed here (``H = 2``)."""
+    x = np.asarray(trace)
+    if x.ndim != 3:
+        raise ValueError("a trace has shape (samples, chains, columns), got %r" % (x.shape,))
+    s, m, ncol = x.shape
+    max_lag = int(max_lag)
+    if s < 4:
+        raise ValueError("at least 4 samples are needed")
+    if max_lag < 1:
+        raise ValueError("max_lag must be at least 1")
+    if x.size and not ((x == 0) | (x == 1)).all():
+        raise ValueError("the counts are defined for 0 / 1 columns")
+    n, H = s // 2, 2 * m
+    if not counts_fit_int64(n, H):
+        raise OverflowError("4 x half-chains x (samples // 2)^3 reaches 2^63: the counts do not fit int64")
+    h = np.concatenate([x[:n], x[s - n:]], axis=1).astype(np.int64)       # (n, H, columns)
+    L = min(max_lag, n - 1)
+    S = h.sum(axis=0)                                                      # (H, columns)
+    A = np.zeros((L + 1, ncol), np.int64)
+    for k in range(L + 1):
+        c = (h[:n - k] * h[k:]).sum(axis=0)
+        head, tail = h[:n - k].sum(axis=0), h[k:].sum(axis=0)
+        A[k] = (n * n * c - n * S * (head + tail) + (n - k) * S * S).sum(axis=0)
+    return n, H, A, S.sum(axis=0), (S * S).sum(axis=0)
+
+
+def ess_from_counts(n, H, A, S1, S2):
+    """The float64 epilogue of the device estimator (nsk_trace_ess), element for element: from the integers of
+    ``autocov_counts`` -- ``A`` of shape ``(L + 1, columns)``, ``L >= 1`` -- returns ``(mean, tau, rhat2, truncated)``
+    per column.  Every step is one rounded float64 operation, in the device's order:
+
+        D = H n n (n - 1) (left to right),  W = A[0] / D,  B = (H S2 - S1^2) / (H (H - 1) n n),
+        V = (n - 1) / n W + B,  rho_k = 1 - ((A[0] - A[k]) / D) / V  (both integer forms in int64),
+        P_j = rho_2j + rho_2j+1 for j < (L + 1) // 2,  tau = -1 + 2 x (the initial run of P_j > 0 added in ascending j).
+
+    ``mean = S1 / (H n)``; ``tau`` is NaN unless ``V > 0`` and ``tau > 0``; ``rhat2 = V / W`` is NaN unless ``V > 0``;
+    ``truncated`` (uint8) is 1 where every pair was positive and ``L < n - 1``: the sequence did not end inside the
+    window, so ``tau`` is a lower bound and ``n H / tau`` an upper bound of the effective sample size."""
+    n, H = int(n), int(H)
+    A = np.asarray(A, np.int64)
+    S1, S2 = np.asarray(S1, np.int64), np.asarray(S2, np.int64)
+    L = A.shape[0] - 1
+    D = np.float64(H) * np.float64(n) * np.float64(n) * np.float64(n - 1)
+    Bden = np.float64(H) * np.float64(H - 1) * np.float64(n) * np.float64(n)
+    c1 = np.float64(n - 1) / np.float64(n)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        W = A[0].astype(np.float64) / D
+        B = (H * S2 - S1 * S1).astype(np.float64) / Bden
+        V = c1 * W + B
+        ok = V > 0
+        run = ok.copy()
+        total = np.zeros(A.shape[1], np.float64)
+        for j in range((L + 1) // 2):
+            r0 = 1.0 - ((A[0] - A[2 * j]).astype(np.float64) / D) / V
+            r1 = 1.0 - ((A[0] - A[2 * j + 1]).astype(np.float64) / D) / V
+            P = r0 + r1
+            run &= P > 0
+            total = np.where(run, total + P, total)
+        tau = -1.0 + 2.0 * total
+        tau[~(ok & (tau > 0))] = np.nan
+        rhat2 = np.where(ok, V / W, np.nan)
+        mean = S1.astype(np.float64) / np.float64(H * n)
+    truncated = (run & (L < n - 1)).astype(np.uint8)
+    return mean, tau, rhat2, truncated
 
 
 def best_sample(lp):

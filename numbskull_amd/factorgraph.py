@@ -14,6 +14,7 @@ initialValue of evidence, ``weight['isFixed']``, ``factor``, ``fmap``, ``vmap``,
 place call ``invalidate()`` so that the next call recompiles.
 """
 
+import collections
 import ctypes as C
 import sys
 import warnings
@@ -26,6 +27,10 @@ from .timer import Timer
 
 def _all_copies(var_copy):
     return isinstance(var_copy, str) and var_copy == "all"
+
+
+# what FactorGraph.mixing returns, one entry per selected variable (samples: the samples the figures rest on)
+Mixing = collections.namedtuple("Mixing", ["ess", "tau", "rhat", "mean", "truncated", "samples"])
 
 
 def split_rhat(half_counts, n):
@@ -518,6 +523,56 @@ class FactorGraph(object):
         if stats_on:
             return (out, lp, stats) if log_potential else (out, stats)
         return (out, lp) if log_potential else out
+
+    def mixing(self, epochs, var_ids=None, thin=1, burnin_epochs=0, sample_evidence=False, max_lag=63):
+        """How well every selected variable has mixed, computed on the device from the trace and without downloading
+        a row: ``inference(burnin_epochs, epochs, sample_evidence, var_copy="all")`` -- one chain per row of
+        ``var_value`` -- under a trace of ``var_ids`` (binary variables, any order, repeats allowed; None = all), a row
+        after every ``thin``-th sweep, then nsk_trace_ess over the ``epochs // thin`` rows.  Returns the named tuple
+        ``Mixing(ess, tau, rhat, mean, truncated, samples)``: per variable the effective sample size, the
+        autocorrelation time, split R-hat, the mean and a uint8 flag, and the number of samples they rest on
+        (``2 x (rows // 2) x chains``).  It is the estimator of ``diagnostics.effective_sample_size`` with the lags
+        cut at ``max_lag`` (1 .. 63; the same estimator while ``rows // 2 <= max_lag + 1``): where ``truncated`` is 1
+        the autocorrelation had not decayed inside the window, ``tau`` is a lower bound and ``ess`` an upper bound --
+        thin more.  A constant column (an evidence variable) reads NaN.  With one chain, or fewer than 4 rows, every
+        figure is NaN, as in ``diagnostics``.  State, ``count``, ``chain_count``, ``marginals`` and ``rhat`` come out
+        as ``inference`` leaves them; the trace is torn down before the call returns.  ValueError when a selected
+        variable is not binary."""
+        epochs, thin, max_lag = int(epochs), int(thin), int(max_lag)
+        if thin < 1:
+            raise ValueError("thin must be at least 1")
+        if max_lag < 1 or max_lag > 63:
+            raise ValueError("max_lag must lie in [1, 63]")
+        vids = None if var_ids is None else _lib.as_c(np.asarray(var_ids).reshape(-1), np.int64)
+        if vids is not None and len(vids) and (vids.min() < 0 or vids.max() >= self.variable.shape[0]):
+            raise IndexError("mixing: variable id out of range")
+        card = self.variable["cardinality"] if vids is None else self.variable["cardinality"][vids]
+        if (card != 2).any():
+            raise ValueError("mixing: every selected variable must be binary (cardinality 2)")
+        L, h = _lib.lib(), self._engine()
+        if burnin_epochs > 0:
+            self.burnIn(burnin_epochs, sample_evidence, var_copy="all")
+        nchains = self._chains()
+        ncols = self.variable.shape[0] if vids is None else len(vids)
+        rows = epochs // thin
+        mean, tau, rhat2 = (np.full(ncols, np.nan) for _ in range(3))
+        truncated = np.zeros(ncols, np.uint8)
+        measured = nchains >= 2 and rows >= 4 and ncols > 0
+        if measured:
+            _lib.check(L.nsk_trace_setup(h, _lib.ptr(vids), ncols, thin, rows))
+        try:
+            self.inference(0, epochs, sample_evidence, var_copy="all")
+            if measured:
+                _lib.check(L.nsk_trace_ess(h, 0, rows, max_lag, _lib.ptr(mean), _lib.ptr(tau), _lib.ptr(rhat2), _lib.ptr(truncated)))
+        except BaseException:
+            if measured:
+                L.nsk_trace_setup(h, None, 0, 1, 0)     # (its status must not replace the exception under way)
+            raise
+        if measured:
+            _lib.check(L.nsk_trace_setup(h, None, 0, 1, 0))
+        samples = 2 * (rows // 2) * nchains
+        with np.errstate(invalid="ignore"):
+            return Mixing(samples / tau, tau, np.sqrt(rhat2), mean, truncated, samples)
 
     # ------------------------------------------------------------------ per-weight statistics
     def weight_statistics(self, var_copy=0, evidence_chain=False, feature_scaled=False):
