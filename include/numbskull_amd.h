@@ -401,7 +401,9 @@ int nsk_set_stream(nsk_graph *g, void *hip_stream);
  *                       rank agreed on; recv_vids / recv_off: the same lists of all `world` ranks,
  *                       concatenated (-1: a variable this handle does not hold -- a shard-local graph
  *                       keeps only the ghosts it reads -- is skipped); slot: elements reserved per
- *                       rank in the gathered buffer
+ *                       rank in the gathered buffer.  May be repeated: the arrays of the previous
+ *                       set-up are freed, so pointers obtained from nsk_device_buffer for the four
+ *                       staging buffers (NSK_BUF_SEND .. NSK_BUF_RECV_EVID) are invalid afterwards
  *   nsk_exchange_pack   SEND[i] = value[send_vids[i]]          (which = NSK_BUF_VALUE[_EVID])
  *   nsk_exchange_unpack value[recv_vids[j]] = RECV[src*slot + j - recv_off[src]] for every src != rank
  * The all-gather of SEND into RECV is done by the caller (torch.distributed) or by the native loop

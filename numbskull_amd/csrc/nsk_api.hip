@@ -1,16 +1,14 @@
-// nsk_api.hip -- the C-ABI entry points of include/numbskull_amd.h: handle life cycle, state transfer, chains, exchanges
-// (sweep drivers: nsk_gibbs.hip / nsk_learn.hip; diagnostics: nsk_trace.hip, nsk_energy.hip, nsk_wstats.hip).
+// nsk_api.hip -- the C-ABI entry points of include/numbskull_amd.h: handle life cycle, state transfer, chains, info
+// (sweep drivers: nsk_gibbs.hip / nsk_learn.hip; boundary exchange: nsk_exchange.hip; diagnostics: nsk_trace.hip,
+// nsk_energy.hip, nsk_wstats.hip).
 //
 // Replaces the callee side of the reference's three run_pool(...) call sites
 // (numbskull/factorgraph.py:141,163,202): gibbsthread (inference.py:10-33) and
 // learnthread/sample_and_sgd (learning.py:12-125).
 #include <hip/hip_runtime.h>
-#include <dlfcn.h>
-#include <rccl/rccl.h>      // types only: the library is bound at run time with dlopen
 
 #include <algorithm>
 #include <chrono>
-#include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -18,10 +16,6 @@
 #include <mutex>
 #include <string>
 #include <vector>
-
-#include "../../include/numbskull_amd.h"
-#include "nsk_compile.h"
-#include "nsk_device.h"
 
 #include "nsk_internal.h"
 #include "nsk_kernels_learn.h"
@@ -41,18 +35,6 @@ int fail(int code, const std::string &msg) {
 }
 void set_error(const std::string &m) { g_err = m; }
 }
-
-// RCCL entry points, bound at run time (nsk_comm_init)
-struct RcclApi {
-    void *lib = nullptr;
-    decltype(&ncclGetUniqueId) GetUniqueId = nullptr;
-    decltype(&ncclCommInitRank) CommInitRank = nullptr;
-    decltype(&ncclAllGather) AllGather = nullptr;
-    decltype(&ncclAllReduce) AllReduce = nullptr;
-    decltype(&ncclCommDestroy) CommDestroy = nullptr;
-    decltype(&ncclGetErrorString) GetErrorString = nullptr;
-};
-static RcclApi g_rccl;
 
 // May this device keep XCD-private accumulators (workgroup-scope atomics in the issuing XCD's L2,
 // private copies picked by HW_REG_XCC_ID)?  gfx942 / gfx950 by architecture name AND a self-test, run
@@ -150,8 +132,7 @@ int nsk_graph_destroy(nsk_graph *g) {
     if (!g) return NSK_OK;
     (void)hipSetDevice(g->device);
     if (g->stream) (void)hipStreamSynchronize(g->stream);
-    for (int q = 0; q < 16; q++)           // peers' allocations mapped with hipIpc
-        if (g->p2p_peer_ipc[q] && g->p2p_peer_base[q]) (void)hipIpcCloseMemHandle(g->p2p_peer_base[q]);
+    nsk_exchange_release(g);
     for (const NskLedger::Entry &e : g->mem.entries) nsk_free_raw(e.raw);
     for (int k = 0; k < 2; k++) if (g->xfer_host[k]) (void)hipHostFree(g->xfer_host[k]);
     if (g->cnt_host) (void)hipHostFree(g->cnt_host);
@@ -159,7 +140,6 @@ int nsk_graph_destroy(nsk_graph *g) {
     if (g->sweep_graph_big) (void)hipGraphExecDestroy(g->sweep_graph_big);
     if (g->ev0) (void)hipEventDestroy(g->ev0);
     if (g->ev1) (void)hipEventDestroy(g->ev1);
-    if (g->rccl_comm && g_rccl.CommDestroy) (void)g_rccl.CommDestroy((ncclComm_t)g->rccl_comm);
     if (g->own_stream && g->stream) (void)hipStreamDestroy(g->stream);
     for (int i = 0; i < 3; i++) {
         if (g->side[i]) (void)hipStreamDestroy(g->side[i]);
@@ -671,10 +651,10 @@ int nsk_state_download(nsk_graph *g, int64_t *var_value, int64_t *var_value_evid
     // a peer-to-peer exchange that timed out since the last check left ghost values (and merged weights)
     // incomplete: the state handed back is then not a result -- say so here too, not only in nsk_p2p_check
     unsigned int p2p_err = 0;
-    if (g->p2p_err) HIPCHECK(hipMemcpyAsync(&p2p_err, g->p2p_err, sizeof(p2p_err), hipMemcpyDeviceToHost, g->stream));
+    if (g->p2p.err) HIPCHECK(hipMemcpyAsync(&p2p_err, g->p2p.err, sizeof(p2p_err), hipMemcpyDeviceToHost, g->stream));
     HIPCHECK(hipStreamSynchronize(g->stream));
     if (p2p_err) {
-        HIPCHECK(hipMemsetAsync(g->p2p_err, 0, sizeof(unsigned int), g->stream));          // reported once
+        HIPCHECK(hipMemsetAsync(g->p2p.err, 0, sizeof(unsigned int), g->stream));          // reported once
         return fail(NSK_E_DEVICE, "peer-to-peer exchange: a peer's boundary values did not arrive within "
                                   "NSK_P2P_TIMEOUT_S; the downloaded state is incomplete");
     }
@@ -691,7 +671,7 @@ int nsk_set_chains(nsk_graph *g, int nchains) {
         if (g->scan != NSK_SCAN_CHROMATIC) return fail(NSK_E_INVALID, "several chains: the sequential scan samples one chain");
         if ((g->c.flags & NSK_FLAG_PARTITION) || g->c.own_begin != 0 || g->c.own_end != g->c.nvar)
             return fail(NSK_E_INVALID, "several chains: the handle must own the whole graph (no own_range / NSK_FLAG_PARTITION)");
-        if (g->xworld > 0 || g->pworld > 0 || g->rccl_comm)
+        if (g->gather.world > 0 || g->p2p.world > 0 || g->gather.comm)
             return fail(NSK_E_INVALID, "several chains: the handle exchanges a boundary (exchange, RCCL or peer-to-peer set up)");
     }
     HIPCHECK(hipSetDevice(g->device));
@@ -860,7 +840,7 @@ int nsk_graph_get_info(nsk_graph *g, nsk_graph_info *info) {
     info->compile_seconds = g->compile_seconds;
     info->acc_copies = g->acc_copies + (g->bins_xcd ? 16 : 0);
     info->learn_lag = (g->learn_lag && g->smallw) ? 1 : 0;
-    info->p2p_fused = g->p2p_fused ? 1 : 0;
+    info->p2p_fused = g->p2p.fused ? 1 : 0;
     return NSK_OK;
 }
 
@@ -972,10 +952,10 @@ int nsk_device_buffer(nsk_graph *g, int which, void **ptr, int64_t *nbytes) {
     case NSK_BUF_VALUE: *ptr = g->val; if (nbytes) *nbytes = g->c.nid * g->c.vbytes; return NSK_OK;
     case NSK_BUF_VALUE_EVID: *ptr = g->val_evid; if (nbytes) *nbytes = g->c.nid * g->c.vbytes; return NSK_OK;
     case NSK_BUF_WEIGHT: *ptr = g->w; if (nbytes) *nbytes = g->c.nweight * 8; g->weights_exposed = true; return NSK_OK;
-    case NSK_BUF_SEND: *ptr = g->x_send; if (nbytes) *nbytes = g->xslot * g->c.vbytes; return NSK_OK;
-    case NSK_BUF_RECV: *ptr = g->x_recv; if (nbytes) *nbytes = g->xslot * g->c.vbytes * g->xworld; return NSK_OK;
-    case NSK_BUF_SEND_EVID: *ptr = g->x_send_evid; if (nbytes) *nbytes = g->xslot * g->c.vbytes; return NSK_OK;
-    case NSK_BUF_RECV_EVID: *ptr = g->x_recv_evid; if (nbytes) *nbytes = g->xslot * g->c.vbytes * g->xworld; return NSK_OK;
+    case NSK_BUF_SEND: *ptr = g->gather.send; if (nbytes) *nbytes = g->gather.slot * g->c.vbytes; return NSK_OK;
+    case NSK_BUF_RECV: *ptr = g->gather.recv; if (nbytes) *nbytes = g->gather.slot * g->c.vbytes * g->gather.world; return NSK_OK;
+    case NSK_BUF_SEND_EVID: *ptr = g->gather.send_evid; if (nbytes) *nbytes = g->gather.slot * g->c.vbytes; return NSK_OK;
+    case NSK_BUF_RECV_EVID: *ptr = g->gather.recv_evid; if (nbytes) *nbytes = g->gather.slot * g->c.vbytes * g->gather.world; return NSK_OK;
     default: return fail(NSK_E_INVALID, "unknown buffer id");
     }
 }
@@ -1038,769 +1018,6 @@ int nsk_selftest_stream(int device, int64_t nbytes, int width, int iters, double
     *gbytes_per_s = 2.0 * (double)nbytes * iters / ((double)ms * 1e-3) / 1e9;
     (void)hipEventDestroy(e0); (void)hipEventDestroy(e1);
     (void)hipFree(a); (void)hipFree(b);
-    return NSK_OK;
-}
-
-int nsk_ghost_needs(nsk_graph *g, int64_t *count, int32_t *vids) {
-    if (!g || !count) return fail(NSK_E_INVALID, "null argument");
-    *count = (int64_t)g->c.ghost_needs.size();
-    if (vids && *count) memcpy(vids, g->c.ghost_needs.data(), (size_t)*count * sizeof(int32_t));
-    return NSK_OK;
-}
-
-int nsk_exchange_setup(nsk_graph *g, int world, int rank, const int32_t *send_vids, int64_t nsend,
-                       const int32_t *recv_vids, const int64_t *recv_off, int64_t slot) {
-    if (!g || world < 1 || rank < 0 || rank >= world || nsend < 0 || slot < nsend || !recv_off)
-        return fail(NSK_E_INVALID, "bad exchange description");
-    NSK_ONE_CHAIN(g, "nsk_exchange_setup");
-    HIPCHECK(hipSetDevice(g->device));
-    const int64_t nrecv = recv_off[world];
-    for (int64_t i = 0; i < nsend; i++)
-        if (send_vids[i] < g->c.own_begin || send_vids[i] >= g->c.own_end)
-            return fail(NSK_E_INDEX, "send list names a variable this handle does not own");
-    std::vector<int32_t> rslot((size_t)nrecv);
-    for (int src = 0; src < world; src++) {
-        if (recv_off[src + 1] - recv_off[src] > slot) return fail(NSK_E_INVALID, "slot smaller than a rank's list");
-        for (int64_t j = recv_off[src]; j < recv_off[src + 1]; j++) {
-            if (recv_vids[j] < -1 || recv_vids[j] >= g->c.nvar) return fail(NSK_E_INDEX, "receive list out of range");
-            rslot[j] = (src == rank || recv_vids[j] < 0) ? -1 : (int32_t)(src * slot + (j - recv_off[src]));
-        }
-    }
-    g->xworld = world; g->xrank = rank; g->xslot = slot; g->xnsend = nsend; g->xnrecv = nrecv;
-    std::vector<int32_t> sv(send_vids, send_vids + nsend), rv(recv_vids, recv_vids + nrecv);
-    for (auto &x : sv) x = g->c.iid[x];                        // the kernels address values by internal id
-    for (auto &x : rv) x = x < 0 ? 0 : g->c.iid[x];          // (skipped entries: slot -1, never written)
-    int rc;
-    if ((rc = dev_upload(g, &g->x_send_vids, sv))) return rc;
-    if ((rc = dev_upload(g, &g->x_recv_vids, rv))) return rc;
-    if ((rc = dev_upload(g, &g->x_recv_slot, rslot))) return rc;
-    const size_t vb = (size_t)g->c.vbytes;
-    uint8_t *t = nullptr;
-    if ((rc = dev_alloc(g, &t, (size_t)slot * vb))) return rc; g->x_send = t;
-    if ((rc = dev_alloc(g, &t, (size_t)slot * vb * world))) return rc; g->x_recv = t;
-    if ((rc = dev_alloc(g, &t, (size_t)slot * vb))) return rc; g->x_send_evid = t;
-    if ((rc = dev_alloc(g, &t, (size_t)slot * vb * world))) return rc; g->x_recv_evid = t;
-    HIPCHECK(hipMemsetAsync(g->x_send, 0, (size_t)(slot ? slot : 1) * vb, g->stream));
-    HIPCHECK(hipMemsetAsync(g->x_send_evid, 0, (size_t)(slot ? slot : 1) * vb, g->stream));
-    if (!g->w_start) {
-        if ((rc = dev_alloc(g, &g->w_start, (size_t)g->c.nweight))) return rc;
-        if ((rc = dev_alloc(g, &g->w_delta, (size_t)g->c.nweight))) return rc;
-    }
-    HIPCHECK(hipStreamSynchronize(g->stream));
-    return NSK_OK;
-}
-
-}  // extern "C"
-
-void nsk_drop_sweep_graph(nsk_graph *g) {
-    if (g->sweep_graph) { (void)hipGraphExecDestroy(g->sweep_graph); g->sweep_graph = nullptr; }
-    g->sweep_graph_key = -1;
-    if (g->sweep_graph_big) { (void)hipGraphExecDestroy(g->sweep_graph_big); g->sweep_graph_big = nullptr; }
-    g->sweep_graph_big_key = -1;
-}
-
-template <typename VT>
-static int exchange_kernels(nsk_graph *g, int which, bool pack) {
-    VT *val = (VT *)(which == NSK_BUF_VALUE ? g->val : g->val_evid);
-    VT *sb = (VT *)(which == NSK_BUF_VALUE ? g->x_send : g->x_send_evid);
-    VT *rb = (VT *)(which == NSK_BUF_VALUE ? g->x_recv : g->x_recv_evid);
-    if (pack) {
-        const int n = (int)g->xnsend;
-        if (n > 0)
-            k_exchange_pack<VT><<<dim3((n + NSK_BLOCK - 1) / NSK_BLOCK), dim3(NSK_BLOCK), 0, g->stream>>>(
-                val, g->x_send_vids, sb, n);
-    } else {
-        const int n = (int)g->xnrecv;
-        if (n > 0)
-            k_exchange_unpack<VT><<<dim3((n + NSK_BLOCK - 1) / NSK_BLOCK), dim3(NSK_BLOCK), 0, g->stream>>>(
-                val, g->x_recv_vids, g->x_recv_slot, rb, n);
-    }
-    HIPCHECK(hipGetLastError());
-    return NSK_OK;
-}
-
-extern "C" {
-
-static int exchange_step(nsk_graph *g, int which, bool pack) {
-    if (!g) return fail(NSK_E_INVALID, "null graph");
-    if (g->xworld == 0) return fail(NSK_E_INVALID, "nsk_exchange_setup has not been called");
-    NSK_ONE_CHAIN(g, "the exchange entry points");
-    NSK_NO_TRACE(g, "the exchange entry points");
-    if (which != NSK_BUF_VALUE && which != NSK_BUF_VALUE_EVID) return fail(NSK_E_INVALID, "bad buffer id");
-    HIPCHECK(hipSetDevice(g->device));
-    { int frc = nsk_p2p_flush(g); if (frc) return frc; }
-    return g->c.vbytes == 1 ? exchange_kernels<int8_t>(g, which, pack) : exchange_kernels<int32_t>(g, which, pack);
-}
-
-int nsk_exchange_pack(nsk_graph *g, int which) { return exchange_step(g, which, true); }
-int nsk_exchange_unpack(nsk_graph *g, int which) { return exchange_step(g, which, false); }
-
-// ---- peer-to-peer exchange ------------------------------------------------------------------------
-// Partial factors (messages.py:1333-1355): `npf` aggregates over variables this handle holds; op 0 = "some member is
-// 1" (OR), 1 = "no member is 0" (AND / ISTRUE); members of aggregate j = member_vids[member_off[j] .. member_off[j+1]).
-// The value arrays grow by npf slots behind the internal ids; a peer-to-peer send list names aggregate j as variable
-// id nvar + j, and every exchange recomputes the aggregates (both chains in learning) before it pushes.
-int nsk_pf_setup(nsk_graph *g, int64_t npf, const uint8_t *op, const int64_t *member_off, const int32_t *member_vids) {
-    if (!g || npf < 0 || (npf && (!op || !member_off || !member_vids))) return fail(NSK_E_INVALID, "bad partial-factor description");
-    NSK_ONE_CHAIN(g, "nsk_pf_setup");
-    HIPCHECK(hipSetDevice(g->device));
-    { int frc = nsk_p2p_flush(g); if (frc) return frc; }
-    std::vector<int32_t> off((size_t)npf + 1, 0), mem;
-    std::vector<uint8_t> ops((size_t)npf);
-    for (int64_t j = 0; j < npf; j++) {
-        if (op[j] > 1 || member_off[j + 1] < member_off[j] || member_off[0] != 0) return fail(NSK_E_INVALID, "bad partial-factor description");
-        ops[(size_t)j] = op[j];
-        for (int64_t k = member_off[j]; k < member_off[j + 1]; k++) {
-            if (member_vids[k] < 0 || member_vids[k] >= g->c.nvar) return fail(NSK_E_INDEX, "partial factor over a variable this handle does not hold");
-            mem.push_back(g->c.iid[member_vids[k]]);
-        }
-        off[(size_t)j + 1] = (int32_t)mem.size();
-    }
-    HIPCHECK(hipStreamSynchronize(g->stream));
-    nsk_drop_sweep_graph(g);
-    // value arrays with npf more slots (contents kept)
-    const size_t vb = (size_t)g->c.vbytes, nid = (size_t)g->c.nid;
-    for (int chain = 0; chain < 2; chain++) {
-        void *&arr = chain ? g->val_evid : g->val;
-        uint8_t *bigger = nullptr;
-        int rc = dev_alloc(g, &bigger, (nid + (size_t)npf) * vb + 16);
-        if (rc) return rc;
-        HIPCHECK(hipMemsetAsync(bigger, 0, (nid + (size_t)npf) * vb + 16, g->stream));
-        HIPCHECK(hipMemcpyAsync(bigger, arr, nid * vb, hipMemcpyDeviceToDevice, g->stream));
-        HIPCHECK(hipStreamSynchronize(g->stream));
-        dev_free(g, arr);
-        arr = bigger;
-    }
-    // (a second set-up replaces the first one's descriptions)
-    dev_free(g, g->pf_op); g->pf_op = nullptr;
-    dev_free(g, g->pf_off); g->pf_off = nullptr;
-    dev_free(g, g->pf_mem); g->pf_mem = nullptr;
-    int rc;
-    if ((rc = dev_upload(g, &g->pf_op, ops))) return rc;
-    if ((rc = dev_upload(g, &g->pf_off, off))) return rc;
-    if ((rc = dev_upload(g, &g->pf_mem, mem))) return rc;
-    HIPCHECK(hipStreamSynchronize(g->stream));
-    g->npf = npf;
-    return NSK_OK;
-}
-
-int nsk_p2p_setup(nsk_graph *g, int world, int rank, const int32_t *send_vids, const int64_t *send_off,
-                  const int32_t *recv_vids, const int64_t *recv_off, const int64_t *peer_base,
-                  const int64_t *peer_total) {
-    if (!g || world < 1 || world > 16 || rank < 0 || rank >= world || !send_off || !recv_off || !peer_base || !peer_total)
-        return fail(NSK_E_INVALID, "bad peer-to-peer description (at most 16 ranks: one node)");
-    NSK_ONE_CHAIN(g, "nsk_p2p_setup");
-    HIPCHECK(hipSetDevice(g->device));
-    const int64_t nsend = send_off[world], nrecv = recv_off[world];
-    if (send_off[0] != 0 || recv_off[0] != 0 || nsend < 0 || nrecv < 0) return fail(NSK_E_INVALID, "bad list offsets");
-    for (int q = 0; q < world; q++) {
-        if (send_off[q + 1] < send_off[q] || recv_off[q + 1] < recv_off[q]) return fail(NSK_E_INVALID, "bad list offsets");
-        const int64_t seg = send_off[q + 1] - send_off[q];
-        if (peer_base[q] < 0 || peer_base[q] + seg > peer_total[q]) return fail(NSK_E_INVALID, "a send segment does not fit its reader's buffer");
-    }
-    if (send_off[rank + 1] != send_off[rank] || recv_off[rank + 1] != recv_off[rank])
-        return fail(NSK_E_INVALID, "a rank does not exchange with itself");
-    if (peer_total[rank] != nrecv) return fail(NSK_E_INVALID, "peer_total[rank] must be this rank's receive total");
-    std::vector<int32_t> sv((size_t)nsend), rv((size_t)nrecv);
-    for (int64_t i = 0; i < nsend; i++) {
-        if (send_vids[i] >= g->c.nvar && send_vids[i] < g->c.nvar + g->npf) {       // partial-factor aggregate (nsk_pf_setup)
-            sv[(size_t)i] = (int32_t)(g->c.nid + (send_vids[i] - g->c.nvar));
-            continue;
-        }
-        if (send_vids[i] < g->c.own_begin || send_vids[i] >= g->c.own_end)
-            return fail(NSK_E_INDEX, "send list names a variable this handle does not own");
-        sv[(size_t)i] = g->c.iid[send_vids[i]];               // the kernels address values by internal id
-    }
-    for (int64_t j = 0; j < nrecv; j++) {
-        if (recv_vids[j] < 0 || recv_vids[j] >= g->c.nvar || (recv_vids[j] >= g->c.own_begin && recv_vids[j] < g->c.own_end))
-            return fail(NSK_E_INDEX, "receive list names a variable this handle owns or does not hold");
-        rv[(size_t)j] = g->c.iid[recv_vids[j]];
-    }
-    nsk_drop_sweep_graph(g);
-    g->p2p_ready = false;
-    g->pworld = world; g->prank = rank; g->p_nsend = nsend; g->p_nrecv = nrecv;
-    g->p_soff.assign(send_off, send_off + world + 1);
-    g->p_roff.assign(recv_off, recv_off + world + 1);
-    g->p_dbase.assign(peer_base, peer_base + world);
-    g->p_dtotal.assign(peer_total, peer_total + world);
-    g->p2p_peer_mask = 0;
-    for (int q = 0; q < world; q++)             // symmetric: q is a peer when either side reads from the other
-        if (q != rank && (send_off[q + 1] > send_off[q] || recv_off[q + 1] > recv_off[q])) g->p2p_peer_mask |= 1u << q;
-    int rc;
-    if ((rc = dev_upload(g, &g->p_send_iid, sv))) return rc;
-    if ((rc = dev_upload(g, &g->p_recv_iid, rv))) return rc;
-    g->p_send_host = sv;
-    g->p_recv_host = rv;
-    g->p2p_fused = false;
-    if (!g->w_start) {
-        if ((rc = dev_alloc(g, &g->w_start, (size_t)g->c.nweight))) return rc;
-        if ((rc = dev_alloc(g, &g->w_delta, (size_t)g->c.nweight))) return rc;
-    }
-    if (!g->p2p_err) {
-        if ((rc = dev_alloc(g, &g->p2p_err, 4))) return rc;          // [0] error mark, [1] [2] the kernels' tickets
-        HIPCHECK(hipMemsetAsync(g->p2p_err, 0, 4 * sizeof(unsigned int), g->stream));
-    }
-    if (const char *t = getenv("NSK_P2P_TIMEOUT_S")) {
-        const double sec = atof(t);
-        if (sec > 0) g->p2p_timeout_ticks = (unsigned long long)(sec * 1e8);
-    }
-    HIPCHECK(hipStreamSynchronize(g->stream));
-    return NSK_OK;
-}
-
-static void p2p_close_peers(nsk_graph *g) {
-    for (int q = 0; q < 16; q++) {
-        if (g->p2p_peer_ipc[q] && g->p2p_peer_base[q]) (void)hipIpcCloseMemHandle(g->p2p_peer_base[q]);
-        g->p2p_peer_base[q] = nullptr;
-        g->p2p_peer_ipc[q] = false;
-    }
-}
-
-int nsk_p2p_export(nsk_graph *g, void *handle64, void **base) {
-    if (!g) return fail(NSK_E_INVALID, "null argument");
-    if (g->pworld == 0) return fail(NSK_E_INVALID, "nsk_p2p_setup has not been called");
-    HIPCHECK(hipSetDevice(g->device));
-    const size_t vb = (size_t)g->c.vbytes, nw = (size_t)g->c.nweight;
-    const size_t bytes = nsk_p2p_bytes(g->pworld, (size_t)g->p_nrecv, vb, nw);
-    if (g->p2p_base && g->p2p_bytes < bytes) {          // a later set-up with longer lists: a new allocation
-        HIPCHECK(hipStreamSynchronize(g->stream));
-        dev_free(g, g->p2p_base);
-        g->p2p_base = nullptr;
-    }
-    if (!g->p2p_base) {
-        // fine-grained: a peer's stores and this rank's polling loads are coherent while kernels run
-        uint8_t *base8 = nullptr;
-        int rc = dev_alloc(g, &base8, bytes, true);
-        if (rc) return rc;
-        g->p2p_base = base8;
-        g->p2p_bytes = bytes;
-    }
-    HIPCHECK(hipMemsetAsync(g->p2p_base, 0, g->p2p_bytes, g->stream));
-    HIPCHECK(hipMemsetAsync(g->p2p_err, 0, 4 * sizeof(unsigned int), g->stream));
-    HIPCHECK(hipStreamSynchronize(g->stream));
-    g->p2p_tag = 0;
-    g->p2p_ready = false;
-    static_assert(sizeof(hipIpcMemHandle_t) == 64, "hipIpcMemHandle_t is 64 bytes");
-    if (handle64) {
-        hipIpcMemHandle_t h;
-        HIPCHECK(hipIpcGetMemHandle(&h, g->p2p_base));
-        memcpy(handle64, &h, 64);
-    }
-    if (base) *base = g->p2p_base;
-    return NSK_OK;
-}
-
-}  // extern "C"
-
-// Does every sampled variable of the handle live in a table segment (the grids and their shards)?
-bool nsk_tables_only(const nsk_graph *g) {
-    const nsk::Compiled &c = g->c;
-    const size_t nphase = c.phase_start.size() - 1;
-    if (g->scan != NSK_SCAN_CHROMATIC || nphase == 0) return false;
-    for (size_t ph = 0; ph < nphase; ph++) {
-        const int64_t ntiles = c.phase_wb_base[ph + 1] - c.phase_wb_base[ph];
-        if (c.phase_end[ph] > c.phase_fast_end[ph]) return false;                    // generic-path variables / hubs
-        if (ntiles > c.phase_gen_tile[ph]) return false;                             // general tiles
-        if (c.phase_rest_base[ph + 1] > c.phase_rest_base[ph]) return false;         // tiles outside segments
-    }
-    for (const nsk::Compiled::Segment &sg : c.segments) if (sg.ztab < 0) return false;
-    return true;
-}
-
-// Fused boundary exchange (nsk_internal.h p2p_fused): decide whether the handle qualifies and build the push map.
-// Conditions: every sampled variable in a table segment; the receive list is the run of ghost ids in order (the
-// compiler numbers the ghosts a handle reads first and ascending, so the receive block IS the ghost array); every
-// boundary value has exactly one reader (range shards of a grid; a value read by several ranks keeps the
-// exchange kernels).
-static int p2p_fuse_plan(nsk_graph *g) {
-    g->p2p_fused = false;
-    g->p2p_border_tiles.clear();
-    if (nsk::diag_env("NSK_NO_P2P_FUSE") || !nsk_tables_only(g)) return NSK_OK;
-    const nsk::Compiled &c = g->c;
-    const std::vector<int32_t> &sv = g->p_send_host, &rv = g->p_recv_host;
-    if (rv.empty() && sv.empty()) return NSK_OK;
-    const uint32_t ghost_lo = rv.empty() ? (uint32_t)c.nid : (uint32_t)rv[0];
-    for (size_t j = 0; j < rv.size(); j++) if ((uint32_t)rv[j] != ghost_lo + (uint32_t)j) return NSK_OK;
-    if (ghost_lo < (uint32_t)c.npos) return NSK_OK;
-    for (int q = 0; q < g->pworld; q++) if (g->p_dtotal[q] >= (1ll << 28)) return NSK_OK;
-    // tiles that read a ghost: slot bases of the implicit adjacency, or the stream words
-    std::vector<int32_t> tiles;
-    for (int32_t p : sv) tiles.push_back(p >> 6);
-    for (const nsk::Compiled::Segment &sg : c.segments) {
-        const int nch = sg.nslots > 4 ? 2 : 1;
-        for (int64_t t = 0; t < sg.ntiles; t++) {
-            bool reads = false;
-            const uint32_t *ab = sg.aff >= 0 ? &c.seg_aff[((size_t)sg.aff + (size_t)t * nch) * 4] : nullptr;
-            if (ab && ab[0] != 0xFFFFFFFFu) {
-                for (int j = 0; j < 4 * nch && !reads; j++) reads = ab[j] + 63u >= ghost_lo && ab[j] < ghost_lo + (uint32_t)rv.size();
-            } else {
-                const uint32_t *w = &c.adj[((size_t)sg.adj_off + (size_t)t * 64 * nch) * 4];
-                for (int i = 0; i < 256 * nch && !reads; i++) reads = w[i] - ghost_lo < (uint32_t)rv.size();
-            }
-            if (reads) tiles.push_back((int32_t)(sg.pos0 / 64 + t));
-        }
-    }
-    std::sort(tiles.begin(), tiles.end());
-    tiles.erase(std::unique(tiles.begin(), tiles.end()), tiles.end());
-    // fewer, longer runs (a launch carries at most NSK_SEG_MAX segment entries): a short segment with a border
-    // tile is border as a whole, and so are gaps of a few tiles between border tiles of one segment -- such a tile
-    // pushes nothing (its row of the map is empty), it only waits and counts like its neighbours
-    {
-        std::vector<int32_t> extra;
-        for (const nsk::Compiled::Segment &sg : c.segments) {
-            const int32_t f = (int32_t)(sg.pos0 / 64), e = f + sg.ntiles;
-            auto lo = std::lower_bound(tiles.begin(), tiles.end(), f), hi = std::lower_bound(tiles.begin(), tiles.end(), e);
-            if (lo == hi) continue;
-            if (sg.ntiles <= 64) { for (int32_t t = f; t < e; t++) extra.push_back(t); continue; }
-            for (auto it = lo; it + 1 < hi; ++it)
-                if (it[1] - it[0] > 1 && it[1] - it[0] <= 16) for (int32_t t = it[0] + 1; t < it[1]; t++) extra.push_back(t);
-        }
-        tiles.insert(tiles.end(), extra.begin(), extra.end());
-        std::sort(tiles.begin(), tiles.end());
-        tiles.erase(std::unique(tiles.begin(), tiles.end()), tiles.end());
-    }
-    std::vector<uint32_t> pm(tiles.size() * 64, 0xFFFFFFFFu);
-    for (int q = 0; q < g->pworld; q++)
-        for (int64_t k = g->p_soff[q]; k < g->p_soff[q + 1]; k++) {
-            const int32_t pos = sv[(size_t)k];
-            const size_t row = (size_t)(std::lower_bound(tiles.begin(), tiles.end(), pos >> 6) - tiles.begin());
-            uint32_t &e = pm[row * 64 + (size_t)(pos & 63)];
-            if (e != 0xFFFFFFFFu) return NSK_OK;                                     // a second reader
-            e = ((uint32_t)q << 28) | (uint32_t)(g->p_dbase[q] + (k - g->p_soff[q]));
-        }
-    dev_free(g, g->p2p_push_map);
-    g->p2p_push_map = nullptr;
-    int rc = dev_upload(g, &g->p2p_push_map, pm);
-    if (rc) return rc;
-    g->p2p_border_tiles.swap(tiles);
-    g->p2p_ghost_lo = ghost_lo;
-    g->p2p_fused = true;
-    g->seg_plans_key = -1;          // the segment plans split at the border tiles
-    return NSK_OK;
-}
-
-extern "C" {
-
-static int p2p_finish_import(nsk_graph *g) {
-    if (g->c.nweight)       // the weights every rank starts the next learning epoch from
-        HIPCHECK(hipMemcpyAsync(g->w_start, g->w, (size_t)g->c.nweight * sizeof(double), hipMemcpyDeviceToDevice, g->stream));
-    int rc = p2p_fuse_plan(g);
-    if (rc) return rc;
-    HIPCHECK(hipStreamSynchronize(g->stream));
-    nsk_drop_sweep_graph(g);
-    g->p2p_tag = 0;
-    g->p2p_close_pending = false;
-    g->p2p_ready = true;
-    return NSK_OK;
-}
-
-int nsk_p2p_import(nsk_graph *g, const void *all_handles) {
-    if (!g || !all_handles) return fail(NSK_E_INVALID, "null argument");
-    if (!g->p2p_base) return fail(NSK_E_INVALID, "nsk_p2p_export first");
-    HIPCHECK(hipSetDevice(g->device));
-    p2p_close_peers(g);
-    for (int q = 0; q < g->pworld; q++) {
-        if (q == g->prank) { g->p2p_peer_base[q] = g->p2p_base; continue; }
-        hipIpcMemHandle_t h;
-        memcpy(&h, (const char *)all_handles + (size_t)q * 64, 64);
-        HIPCHECK(hipIpcOpenMemHandle(&g->p2p_peer_base[q], h, hipIpcMemLazyEnablePeerAccess));
-        g->p2p_peer_ipc[q] = true;
-    }
-    return p2p_finish_import(g);
-}
-
-int nsk_p2p_import_local(nsk_graph *g, void *const *bases) {
-    if (!g || !bases) return fail(NSK_E_INVALID, "null argument");
-    if (!g->p2p_base) return fail(NSK_E_INVALID, "nsk_p2p_export first");
-    HIPCHECK(hipSetDevice(g->device));
-    p2p_close_peers(g);
-    for (int q = 0; q < g->pworld; q++) {
-        if (q != g->prank && !bases[q]) return fail(NSK_E_INVALID, "null peer allocation");
-        g->p2p_peer_base[q] = q == g->prank ? g->p2p_base : bases[q];
-    }
-    return p2p_finish_import(g);
-}
-
-}  // extern "C"
-
-// part 0 = one whole exchange (the sweep loops); 1 = the pushes, 2 = wait + unpack (+ the owner's half of the
-// weight merge), 3 = the closing half of the weight merge -- the parts on their own serve the tests that drive
-// several handles from one process (issued breadth-first) and the phase timings
-template <typename VT>
-static int p2p_exchange(nsk_graph *g, const unsigned long long *tag_base, unsigned int tag_off, bool learn, int part, int selftest = 0) {
-    const int world = g->pworld, me = g->prank;
-    const int nw = (int)g->c.nweight;
-    if ((part == 0 || part == 1) && !tag_base) ++g->p2p_tag;
-    const unsigned int tag = tag_base ? tag_off : g->p2p_tag;
-    const bool weights = learn && nw > 0 && world > 1;
-    // a learning epoch's weight deltas go to every rank, so every rank is a peer of every other
-    const unsigned int mask = weights ? (((1u << world) - 1u) & ~(1u << me)) : g->p2p_peer_mask;
-    if (!mask) return NSK_OK;
-    P2PPlan plan;
-    memset(&plan, 0, sizeof(plan));
-    for (int q = 0; q < world; q++) {
-        plan.base[q] = g->p2p_peer_base[q];
-        plan.soff[q] = (unsigned long long)g->p_soff[q];
-        plan.roff[q] = (unsigned long long)g->p_roff[q];
-        plan.dbase[q] = (unsigned long long)g->p_dbase[q];
-        plan.dtotal[q] = (unsigned long long)g->p_dtotal[q];
-    }
-    for (int q = world; q <= 16; q++) { plan.soff[q] = (unsigned long long)g->p_nsend; plan.roff[q] = (unsigned long long)g->p_nrecv; }
-    P2PWeights pw;
-    // big: lists beyond 2^16 values or tables beyond 2^16 weights -- many-block launches with one-wave flag kernels
-    // between them (k_p2p_push_big); otherwise one or two <= 64-block launches that raise and poll themselves
-    const char *big_env = nsk::diag_env("NSK_P2P_BIG_MIN");             // (diagnostic; read per exchange so that tests can set it)
-    const int64_t big_min = big_env ? atoll(big_env) : 65536;
-    const bool big = std::max(g->p_nsend, g->p_nrecv) > big_min || (weights && nw > big_min);
-    pw.w = weights ? g->w : nullptr; pw.w_start = weights ? g->w_start : nullptr; pw.nw = weights ? nw : 0;
-    const int64_t wwork = weights ? ((int64_t)nw + 3) / 4 : 0;          // (a block's threads take a few weights each)
-    auto blocks = [&](int64_t work) { return (int)std::max<int64_t>(1, std::min<int64_t>(64, (work + 4 * NSK_BLOCK - 1) / (4 * NSK_BLOCK))); };
-    auto many = [&](int64_t work) { return dim3((unsigned)std::max<int64_t>(1, std::min<int64_t>(1024, (work + NSK_BLOCK - 1) / NSK_BLOCK))); };
-    VT *val = (VT *)g->val, *val_evid = (VT *)g->val_evid;
-    const int both = learn ? 1 : 0;
-    auto push_big = [&]() {
-        k_p2p_push_big<VT><<<many(std::max<int64_t>(g->p_nsend, pw.nw)), dim3(NSK_BLOCK), 0, g->stream>>>(
-            val, val_evid, both, g->p_send_iid, (long long)g->p_nsend, plan, pw, world, me, tag, tag_base, selftest);
-        k_p2p_raise<<<dim3(1), dim3(64), 0, g->stream>>>(plan, 0, world, me, mask, tag, tag_base);
-    };
-    auto unpack_big = [&]() {
-        k_p2p_wait<<<dim3(1), dim3(64), 0, g->stream>>>(g->p2p_base, 0, world, mask, tag, tag_base, g->p2p_err, g->p2p_timeout_ticks);
-        k_p2p_unpack_big<VT><<<many(std::max<int64_t>(g->p_nrecv, (pw.nw + world - 1) / world)), dim3(NSK_BLOCK), 0, g->stream>>>(
-            val, val_evid, both, g->p_recv_iid, (long long)g->p_nrecv, g->p2p_base, plan, pw, world, me, tag, tag_base, g->p2p_err, selftest);
-        if (weights) k_p2p_raise<<<dim3(1), dim3(64), 0, g->stream>>>(plan, 1, world, me, mask, tag, tag_base);
-    };
-    auto gather = [&]() {
-        if (!weights) return;
-        if (big) k_p2p_wait<<<dim3(1), dim3(64), 0, g->stream>>>(g->p2p_base, 1, world, mask, tag, tag_base, g->p2p_err, g->p2p_timeout_ticks);
-        k_p2p_gather_w<VT><<<big ? many(nw) : dim3((unsigned)blocks(wwork)), dim3(NSK_BLOCK), 0, g->stream>>>(
-            g->w, g->w_start, nw, g->p2p_base, (long long)g->p_nrecv, world, mask, tag, g->p2p_err, g->p2p_timeout_ticks, selftest, big ? 1 : 0);
-        if (!selftest) g->weights_dirty = true;
-    };
-    if ((part == 0 || part == 1) && g->npf > 0 && !selftest)         // the partial-factor aggregates this rank's readers take
-        k_pf_compute<VT><<<dim3((unsigned)((g->npf + NSK_BLOCK - 1) / NSK_BLOCK)), dim3(NSK_BLOCK), 0, g->stream>>>(
-            val, val_evid, both, g->pf_op, g->pf_off, g->pf_mem, (int)g->npf, (long long)g->c.nid);
-    if (part == 0) {                            // the sweep loops: push, flags, wait and unpack in one launch
-        if (big) { push_big(); unpack_big(); }
-        else {
-            const int nb = blocks(std::max(std::max(g->p_nsend, g->p_nrecv), wwork));
-            k_p2p_exchange<VT, true><<<dim3(nb), dim3(NSK_BLOCK), 0, g->stream>>>(
-                val, val_evid, both, g->p_send_iid, (long long)g->p_nsend, plan, pw, g->p_recv_iid,
-                (long long)g->p_nrecv, g->p2p_base, world, me, mask, g->p2p_err + 1, tag, g->p2p_err, tag_base, g->p2p_timeout_ticks, selftest);
-        }
-        gather();
-    } else if (part == 1) {
-        if (big) push_big();
-        else {
-            // at most 64 blocks (grid-stride): the closing ticket adds must not queue up
-            const int nb = blocks(std::max(g->p_nsend, wwork));
-            k_p2p_push<VT><<<dim3(nb), dim3(NSK_BLOCK), 0, g->stream>>>(val, val_evid, both, g->p_send_iid, (long long)g->p_nsend, plan, pw, world, me,
-                                                                       mask, g->p2p_err + 1, tag, tag_base, selftest);
-        }
-    } else if (part == 2) {
-        if (big) unpack_big();
-        else {
-            const int nb = blocks(std::max(g->p_nrecv, wwork));
-            k_p2p_exchange<VT, false><<<dim3(nb), dim3(NSK_BLOCK), 0, g->stream>>>(
-                val, val_evid, both, g->p_send_iid, (long long)g->p_nsend, plan, pw, g->p_recv_iid,
-                (long long)g->p_nrecv, g->p2p_base, world, me, mask, g->p2p_err + 1, tag, g->p2p_err, tag_base, g->p2p_timeout_ticks, selftest);
-        }
-    } else {
-        gather();
-    }
-    HIPCHECK(hipGetLastError());
-    return NSK_OK;
-}
-
-int nsk_p2p_enqueue(nsk_graph *g, const unsigned long long *tag_base, unsigned int tag_off, bool learn, int part) {
-    return g->c.vbytes == 1 ? p2p_exchange<int8_t>(g, tag_base, tag_off, learn, part)
-                            : p2p_exchange<int32_t>(g, tag_base, tag_off, learn, part);
-}
-
-// kernel argument of a fused table launch
-void nsk_p2p_fill(nsk_graph *g, nsk::TabP2P &px, const unsigned long long *tag_base, unsigned int tag, bool wait) {
-    memset(&px, 0, sizeof(px));
-    px.wait = wait ? 1 : 0;
-    px.mine = g->p2p_base;
-    for (int q = 0; q < g->pworld; q++) { px.peer[q] = g->p2p_peer_base[q]; px.dtotal[q] = (unsigned long long)g->p_dtotal[q]; }
-    px.push_map = g->p2p_push_map;
-    px.counter = g->p2p_err + 3;
-    px.err = g->p2p_err;
-    px.tag_base = tag_base;
-    px.timeout_ticks = g->p2p_timeout_ticks;
-    px.ghost_lo = g->p2p_ghost_lo;
-    px.nrecv = (uint32_t)g->p_nrecv;
-    px.border_total = g->p2p_border_total;
-    px.tag = tag;
-    px.peer_mask = g->p2p_peer_mask;
-    px.world = g->pworld;
-    px.me = g->prank;
-}
-
-// the ghost values of the value array into the receive block of the LAST exchange's parity: what the first fused
-// sweep of a call reads (the caller may have uploaded a state since)
-template <typename VT>
-static __global__ __launch_bounds__(NSK_BLOCK) void k_p2p_ghost_pack(const VT *val, const int32_t *recv_iid, long long nrecv, void *mine,
-                                                                      int world, unsigned int tag) {
-    VT *rb = (VT *)((char *)mine + nsk_p2p_recv_off(world)) + (size_t)(tag & 1u) * 2 * (size_t)nrecv;
-    for (long long j = (long long)blockIdx.x * NSK_BLOCK + threadIdx.x; j < nrecv; j += (long long)gridDim.x * NSK_BLOCK)
-        rb[j] = val[recv_iid[j]];
-}
-int nsk_p2p_ghost_pack(nsk_graph *g) {
-    if (g->p_nrecv == 0) return NSK_OK;
-    const int nb = (int)std::min<int64_t>(64, (g->p_nrecv + NSK_BLOCK - 1) / NSK_BLOCK);
-    if (g->c.vbytes == 1)
-        k_p2p_ghost_pack<int8_t><<<dim3(nb), dim3(NSK_BLOCK), 0, g->stream>>>((const int8_t *)g->val, g->p_recv_iid, (long long)g->p_nrecv,
-                                                                             g->p2p_base, g->pworld, g->p2p_tag);
-    else
-        k_p2p_ghost_pack<int32_t><<<dim3(nb), dim3(NSK_BLOCK), 0, g->stream>>>((const int32_t *)g->val, g->p_recv_iid, (long long)g->p_nrecv,
-                                                                              g->p2p_base, g->pworld, g->p2p_tag);
-    HIPCHECK(hipGetLastError());
-    return NSK_OK;
-}
-
-// A fused sweep sequence ends with its last class launch; the wait for the peers' last flags and the copy of the
-// received values into the value array's ghost ids (what downloads, the other kernels and the next call's pack
-// read) is enqueued lazily -- before the next thing that needs it -- so that a caller driving several ranks from
-// one process can issue every rank's sweeps before any rank's wait.
-int nsk_p2p_flush(nsk_graph *g) {
-    if (!g || !g->p2p_close_pending) return NSK_OK;
-    g->p2p_close_pending = false;
-    return nsk_p2p_enqueue(g, nullptr, 0, false, 2);          // wait for tag p2p_tag + unpack
-}
-
-extern "C" {
-
-int nsk_p2p_check(nsk_graph *g) {
-    if (!g) return fail(NSK_E_INVALID, "null graph");
-    if (!g->p2p_err) return NSK_OK;
-    HIPCHECK(hipSetDevice(g->device));
-    { int frc = nsk_p2p_flush(g); if (frc) return frc; }
-    unsigned int err = 0;
-    HIPCHECK(hipMemcpyAsync(&err, g->p2p_err, sizeof(err), hipMemcpyDeviceToHost, g->stream));
-    HIPCHECK(hipStreamSynchronize(g->stream));
-    if (err) {
-        HIPCHECK(hipMemsetAsync(g->p2p_err, 0, sizeof(unsigned int), g->stream));      // reported once
-        if (err & NSK_P2P_ERR_PAYLOAD)
-            return fail(NSK_E_DEVICE, "peer-to-peer self-test: a peer's flag arrived but the payload read back differs from "
-                                      "what the peer wrote (peer writes are not visible to this device's kernels)");
-        return fail(NSK_E_DEVICE, "peer-to-peer exchange: a peer's boundary values did not arrive within "
-                                  "NSK_P2P_TIMEOUT_S; the ghost values of this handle are incomplete");
-    }
-    return NSK_OK;
-}
-
-}  // extern "C"
-
-// learn == 2: the memory protocol of the fused exchange (k_p2p_fused_selftest)
-template <typename VT>
-static int p2p_fused_selftest(nsk_graph *g, int part) {
-    if (!g->p2p_peer_mask) return NSK_OK;
-    if (part != 2) ++g->p2p_tag;
-    P2PPlan plan;
-    memset(&plan, 0, sizeof(plan));
-    for (int q = 0; q < g->pworld; q++) {
-        plan.base[q] = g->p2p_peer_base[q];
-        plan.soff[q] = (unsigned long long)g->p_soff[q];
-        plan.roff[q] = (unsigned long long)g->p_roff[q];
-        plan.dbase[q] = (unsigned long long)g->p_dbase[q];
-        plan.dtotal[q] = (unsigned long long)g->p_dtotal[q];
-    }
-    for (int q = g->pworld; q <= 16; q++) { plan.soff[q] = (unsigned long long)g->p_nsend; plan.roff[q] = (unsigned long long)g->p_nrecv; }
-    k_p2p_fused_selftest<VT><<<dim3(1), dim3(NSK_BLOCK), 0, g->stream>>>((long long)g->p_nsend, (long long)g->p_nrecv, plan, g->p2p_base,
-                                                                         g->pworld, g->prank, g->p2p_peer_mask, g->p2p_tag, g->p2p_err,
-                                                                         g->p2p_timeout_ticks, part);
-    HIPCHECK(hipGetLastError());
-    return NSK_OK;
-}
-
-extern "C" {
-
-int nsk_p2p_selftest(nsk_graph *g, int learn, int part) {
-    if (!g) return fail(NSK_E_INVALID, "null graph");
-    if (!g->p2p_ready) return fail(NSK_E_INVALID, "nsk_p2p_setup / nsk_p2p_export / nsk_p2p_import first");
-    NSK_ONE_CHAIN(g, "the peer-to-peer entry points");
-    if (part < 0 || part > 3) return fail(NSK_E_INVALID, "bad part");
-    HIPCHECK(hipSetDevice(g->device));
-    { int frc = nsk_p2p_flush(g); if (frc) return frc; }
-    if (learn == 2) {
-        if (part == 3) return NSK_OK;
-        return g->c.vbytes == 1 ? p2p_fused_selftest<int8_t>(g, part) : p2p_fused_selftest<int32_t>(g, part);
-    }
-    return g->c.vbytes == 1 ? p2p_exchange<int8_t>(g, nullptr, 0, learn != 0, part, 1)
-                            : p2p_exchange<int32_t>(g, nullptr, 0, learn != 0, part, 1);
-}
-
-int nsk_p2p_fuse(nsk_graph *g, int on) {
-    if (!g) return fail(NSK_E_INVALID, "null graph");
-    if (!g->p2p_ready) return fail(NSK_E_INVALID, "nsk_p2p_setup / nsk_p2p_export / nsk_p2p_import first");
-    NSK_ONE_CHAIN(g, "the peer-to-peer entry points");
-    HIPCHECK(hipSetDevice(g->device));
-    { int frc = nsk_p2p_flush(g); if (frc) return frc; }
-    if (on) {
-        int rc = p2p_fuse_plan(g);
-        if (rc) return rc;
-    } else if (g->p2p_fused) {
-        g->p2p_fused = false;
-        g->p2p_border_tiles.clear();
-        g->seg_plans_key = -1;
-    }
-    nsk_drop_sweep_graph(g);
-    return g->p2p_fused ? 1 : 0;
-}
-
-int nsk_p2p_reset(nsk_graph *g) {
-    if (!g) return fail(NSK_E_INVALID, "null graph");
-    if (!g->p2p_base) return fail(NSK_E_INVALID, "nsk_p2p_setup / nsk_p2p_export first");
-    HIPCHECK(hipSetDevice(g->device));
-    { int frc = nsk_p2p_flush(g); if (frc) return frc; }
-    HIPCHECK(hipStreamSynchronize(g->stream));
-    nsk_drop_sweep_graph(g);
-    HIPCHECK(hipMemsetAsync(g->p2p_base, 0, g->p2p_bytes, g->stream));
-    HIPCHECK(hipMemsetAsync(g->p2p_err, 0, 4 * sizeof(unsigned int), g->stream));
-    HIPCHECK(hipStreamSynchronize(g->stream));
-    g->p2p_tag = 0;
-    g->p2p_close_pending = false;
-    return NSK_OK;
-}
-
-int nsk_p2p_exchange(nsk_graph *g, int learn, int part) {
-    if (!g) return fail(NSK_E_INVALID, "null graph");
-    if (!g->p2p_ready) return fail(NSK_E_INVALID, "nsk_p2p_setup / nsk_p2p_export / nsk_p2p_import first");
-    NSK_ONE_CHAIN(g, "the peer-to-peer entry points");
-    NSK_NO_TRACE(g, "the peer-to-peer entry points");
-    if (part < 0 || part > 3) return fail(NSK_E_INVALID, "bad part");
-    HIPCHECK(hipSetDevice(g->device));
-    { int frc = nsk_p2p_flush(g); if (frc) return frc; }
-    return nsk_p2p_enqueue(g, nullptr, 0, learn != 0, part);
-}
-
-int nsk_gibbs_sweeps_p2p(nsk_graph *g, int64_t nsweeps, int sample_evidence, int burnin) {
-    if (!g) return fail(NSK_E_INVALID, "null graph");
-    if (!g->p2p_ready) return fail(NSK_E_INVALID, "nsk_p2p_setup / nsk_p2p_export / nsk_p2p_import first");
-    NSK_ONE_CHAIN(g, "the peer-to-peer entry points");
-    NSK_NO_TRACE(g, "the peer-to-peer entry points");
-    if (nsweeps < 0 || nsweeps > INT32_MAX) return fail(NSK_E_INVALID, "bad sweep count");
-    HIPCHECK(hipSetDevice(g->device));
-    return nsk_gibbs_run(g, nsweeps, sample_evidence, burnin, true);      // (flushes a pending close unless it continues it)
-}
-
-int nsk_learn_sweeps_p2p(nsk_graph *g, int64_t nsweeps, double step, double decay, int regularization,
-                         double reg_param, int64_t truncation, int learn_non_evidence) {
-    if (!g) return fail(NSK_E_INVALID, "null graph");
-    if (!g->p2p_ready) return fail(NSK_E_INVALID, "nsk_p2p_setup / nsk_p2p_export / nsk_p2p_import first");
-    NSK_ONE_CHAIN(g, "the peer-to-peer entry points");
-    NSK_NO_TRACE(g, "the peer-to-peer entry points");
-    if (nsweeps < 0 || nsweeps > INT32_MAX) return fail(NSK_E_INVALID, "bad sweep count");
-    HIPCHECK(hipSetDevice(g->device));
-    { int frc = nsk_p2p_flush(g); if (frc) return frc; }
-    const int nw = (int)g->c.nweight;
-    // the caller may have written the weight buffer since the last epoch: this call starts from what is there
-    if (nw && nsweeps) HIPCHECK(hipMemcpyAsync(g->w_start, g->w, (size_t)nw * sizeof(double), hipMemcpyDeviceToDevice, g->stream));
-    for (int64_t s = 0; s < nsweeps; s++) {
-        int rc = nsk_learn_sweeps(g, 1, step, 1.0, regularization, reg_param, truncation, learn_non_evidence);
-        if (rc) return rc;
-        if ((rc = nsk_p2p_enqueue(g, nullptr, 0, true, 0))) return rc;     // values of both chains + weight deltas; w_start = merged w
-        step *= decay;
-    }
-    return NSK_OK;
-}
-
-// ---- native RCCL loop -----------------------------------------------------------------------------
-static int load_rccl(const char *path) {
-    if (g_rccl.lib) return NSK_OK;
-    void *h = dlopen(path && path[0] ? path : "librccl.so", RTLD_NOW | RTLD_LOCAL);
-    if (!h) return fail(NSK_E_DEVICE, std::string("dlopen(librccl): ") + dlerror());
-    g_rccl.GetUniqueId = (decltype(g_rccl.GetUniqueId))dlsym(h, "ncclGetUniqueId");
-    g_rccl.CommInitRank = (decltype(g_rccl.CommInitRank))dlsym(h, "ncclCommInitRank");
-    g_rccl.AllGather = (decltype(g_rccl.AllGather))dlsym(h, "ncclAllGather");
-    g_rccl.AllReduce = (decltype(g_rccl.AllReduce))dlsym(h, "ncclAllReduce");
-    g_rccl.CommDestroy = (decltype(g_rccl.CommDestroy))dlsym(h, "ncclCommDestroy");
-    g_rccl.GetErrorString = (decltype(g_rccl.GetErrorString))dlsym(h, "ncclGetErrorString");
-    if (!g_rccl.GetUniqueId || !g_rccl.CommInitRank || !g_rccl.AllGather || !g_rccl.AllReduce || !g_rccl.CommDestroy)
-        return fail(NSK_E_DEVICE, "librccl lacks the expected symbols");
-    g_rccl.lib = h;
-    return NSK_OK;
-}
-
-#define RCCLCHECK(expr)                                                                         \
-    do {                                                                                        \
-        ncclResult_t r_ = (expr);                                                               \
-        if (r_ != ncclSuccess)                                                                  \
-            return fail(NSK_E_DEVICE, std::string(#expr) + ": " +                              \
-                        (g_rccl.GetErrorString ? g_rccl.GetErrorString(r_) : "rccl error"));    \
-    } while (0)
-
-int nsk_comm_unique_id(const char *librccl_path, void *id128) {
-    if (!id128) return fail(NSK_E_INVALID, "null argument");
-    int rc = load_rccl(librccl_path);
-    if (rc) return rc;
-    static_assert(sizeof(ncclUniqueId) == 128, "ncclUniqueId is 128 bytes");
-    RCCLCHECK(g_rccl.GetUniqueId((ncclUniqueId *)id128));
-    return NSK_OK;
-}
-
-int nsk_comm_init(nsk_graph *g, int world, int rank, const void *id128, const char *librccl_path) {
-    if (!g || !id128 || world < 1 || rank < 0 || rank >= world) return fail(NSK_E_INVALID, "bad argument");
-    NSK_ONE_CHAIN(g, "nsk_comm_init");
-    int rc = load_rccl(librccl_path);
-    if (rc) return rc;
-    HIPCHECK(hipSetDevice(g->device));
-    ncclUniqueId id;
-    memcpy(&id, id128, sizeof(id));
-    ncclComm_t comm = nullptr;
-    RCCLCHECK(g_rccl.CommInitRank(&comm, world, id, rank));
-    g->rccl_comm = comm;
-    return NSK_OK;
-}
-
-static int native_exchange(nsk_graph *g, int which) {
-    int rc = exchange_step(g, which, true);
-    if (rc) return rc;
-    const void *sb = which == NSK_BUF_VALUE ? g->x_send : g->x_send_evid;
-    void *rb = which == NSK_BUF_VALUE ? g->x_recv : g->x_recv_evid;
-    if (g->xslot > 0)
-        RCCLCHECK(g_rccl.AllGather(sb, rb, (size_t)g->xslot, g->c.vbytes == 1 ? ncclInt8 : ncclInt32,
-                                   (ncclComm_t)g->rccl_comm, g->stream));
-    return exchange_step(g, which, false);
-}
-
-int nsk_gibbs_sweeps_exchange(nsk_graph *g, int64_t nsweeps, int sample_evidence, int burnin) {
-    if (!g) return fail(NSK_E_INVALID, "null graph");
-    if (!g->rccl_comm || g->xworld == 0) return fail(NSK_E_INVALID, "nsk_exchange_setup / nsk_comm_init first");
-    NSK_ONE_CHAIN(g, "the exchange entry points");
-    NSK_NO_TRACE(g, "the exchange entry points");
-    for (int64_t s = 0; s < nsweeps; s++) {
-        int rc = nsk_gibbs_sweeps(g, 1, sample_evidence, burnin);
-        if (rc) return rc;
-        if ((rc = native_exchange(g, NSK_BUF_VALUE))) return rc;
-    }
-    return NSK_OK;
-}
-
-int nsk_learn_sweeps_exchange(nsk_graph *g, int64_t nsweeps, double step, double decay, int regularization,
-                              double reg_param, int64_t truncation, int learn_non_evidence) {
-    if (!g) return fail(NSK_E_INVALID, "null graph");
-    if (!g->rccl_comm || g->xworld == 0) return fail(NSK_E_INVALID, "nsk_exchange_setup / nsk_comm_init first");
-    NSK_ONE_CHAIN(g, "the exchange entry points");
-    NSK_NO_TRACE(g, "the exchange entry points");
-    const int nw = (int)g->c.nweight;
-    for (int64_t s = 0; s < nsweeps; s++) {
-        HIPCHECK(hipSetDevice(g->device));
-        if (nw) HIPCHECK(hipMemcpyAsync(g->w_start, g->w, (size_t)nw * sizeof(double), hipMemcpyDeviceToDevice, g->stream));
-        int rc = nsk_learn_sweeps(g, 1, step, 1.0, regularization, reg_param, truncation, learn_non_evidence);
-        if (rc) return rc;
-        if ((rc = native_exchange(g, NSK_BUF_VALUE))) return rc;
-        if ((rc = native_exchange(g, NSK_BUF_VALUE_EVID))) return rc;
-        if (nw) {       // w = w_start + sum over ranks of (w - w_start): numbskull_master.py:223-224
-            const dim3 grid((nw + NSK_BLOCK - 1) / NSK_BLOCK), block(NSK_BLOCK);
-            k_weight_delta<<<grid, block, 0, g->stream>>>(g->w, g->w_start, g->w_delta, nw);
-            RCCLCHECK(g_rccl.AllReduce(g->w_delta, g->w_delta, (size_t)nw, ncclDouble, ncclSum,
-                                       (ncclComm_t)g->rccl_comm, g->stream));
-            k_weight_merge<<<grid, block, 0, g->stream>>>(g->w, g->w_start, g->w_delta, nw);
-            g->weights_dirty = true;
-        }
-        step *= decay;
-    }
     return NSK_OK;
 }
 

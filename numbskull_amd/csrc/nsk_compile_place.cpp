@@ -519,7 +519,7 @@ int CompileCtx::assign_internal_ids() {
     {
         // (the ghosts the sampled variables READ come first among the others, in id order: the receive list of
         // a peer-to-peer exchange -- all of them, ascending -- is then one contiguous run of internal ids, which
-        // lets a shard's kernels read ghost values straight from the exchange buffer, nsk_api.hip)
+        // lets a shard's kernels read ghost values straight from the exchange buffer, nsk_exchange.hip)
         int64_t next = c.npos;
         for (int32_t v : c.ghost_needs) if (c.v_pos[v] < 0) c.iid[v] = (int32_t)next++;
         for (int64_t v = 0; v < nvar; v++)

@@ -53,7 +53,7 @@ int energy_whole_graph(const nsk_graph *g, const char *what) {
     const Compiled &c = g->c;
     if ((c.flags & NSK_FLAG_PARTITION) || c.own_begin != 0 || c.own_end != c.nvar)
         return fail(NSK_E_INVALID, std::string(what) + ": the handle must own the whole graph (no own_range / NSK_FLAG_PARTITION)");
-    if (g->xworld > 0 || g->pworld > 0 || g->rccl_comm)
+    if (g->gather.world > 0 || g->p2p.world > 0 || g->gather.comm)
         return fail(NSK_E_INVALID, std::string(what) + ": the handle exchanges a boundary (exchange, RCCL or peer-to-peer set up)");
     return NSK_OK;
 }

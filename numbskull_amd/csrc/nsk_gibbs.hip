@@ -29,16 +29,16 @@ static inline int tabw_delta(const void *p, const void *base) {
 void nsk_ensure_seg_plans(nsk_graph *g, int sample_evidence) {
     const size_t nphase = g->c.phase_start.size() - 1;
     std::vector<std::vector<NskSegPlan>> &seg_plans = g->seg_plans;
-    const int plans_key = (sample_evidence ? 1 : 0) | (g->values_regular ? 2 : 0) | (g->p2p_fused ? 4 : 0);
+    const int plans_key = (sample_evidence ? 1 : 0) | (g->values_regular ? 2 : 0) | (g->p2p.fused ? 4 : 0);
     if (g->seg_plans_key == plans_key) return;
     g->seg_plans_key = plans_key;
     seg_plans.assign(nphase, std::vector<NskSegPlan>());
     const bool use_tab = g->values_regular;
     struct Run { const Compiled::Segment *sg; int t0, nt; uint32_t push_off; };
-    const std::vector<int32_t> &bt = g->p2p_border_tiles;
+    const std::vector<int32_t> &bt = g->p2p.border_tiles;
     uint32_t border_total = 0;
     bool border_all = true;
-    if (g->p2p_fused)          // border tiles of segments this call does not sample: the fused exchange cannot run
+    if (g->p2p.fused)          // border tiles of segments this call does not sample: the fused exchange cannot run
         for (const Compiled::Segment &sg : g->c.segments)
             if (!(sg.ev == 0 || sample_evidence)) {
                 const int32_t f = (int32_t)(sg.pos0 / 64);
@@ -48,7 +48,7 @@ void nsk_ensure_seg_plans(nsk_graph *g, int sample_evidence) {
     int first_phase = -1;            // the first class with sampled segments
     for (const Compiled::Segment &sg : g->c.segments)
         if ((sg.ev == 0 || sample_evidence) && (first_phase < 0 || sg.phase < first_phase)) first_phase = sg.phase;
-    g->p2p_first_phase = first_phase;
+    g->p2p.first_phase = first_phase;
     for (size_t ph = 0; ph < nphase; ph++)
         for (int kind = 0; kind <= 8; kind++) {
             if (kind == 1 || (kind > 4 && kind < 8)) continue;   // IMPLY_NATURAL shares the AND step (3)
@@ -79,7 +79,7 @@ void nsk_ensure_seg_plans(nsk_graph *g, int sample_evidence) {
                     const int k3 = (use_tab && sg.ztab >= 0) ? 8 : sg.kind == 1 ? 3 : (int)sg.kind;
                     if (k3 != kind || (sg.nslots > 4 ? 2 : 1) != nch) continue;
                     if (!(sg.ev == 0 || sample_evidence)) continue;      // inference.py:24
-                    if (!g->p2p_fused || kind < 8) { mine.push_back(Run{&sg, 0, sg.ntiles, NSK_NO_STREAM}); continue; }
+                    if (!g->p2p.fused || kind < 8) { mine.push_back(Run{&sg, 0, sg.ntiles, NSK_NO_STREAM}); continue; }
                     // runs of border / interior tiles (a tile's rank among the border tiles = its push-map row)
                     const int32_t f = (int32_t)(sg.pos0 / 64);
                     size_t bi = (size_t)(std::lower_bound(bt.begin(), bt.end(), f) - bt.begin());
@@ -145,16 +145,16 @@ void nsk_ensure_seg_plans(nsk_graph *g, int sample_evidence) {
     // segments: a cut whose boundary variables all have the other colour (a chain, a bipartite cut) has no border tile
     // there, and then nothing in the sweep would wait -- ghosts read before they arrived, pushes over a block a peer
     // still reads.
-    if (g->p2p_fused) {
+    if (g->p2p.fused) {
         int first_border = -1;
         for (size_t ph = 0; ph < nphase && first_border < 0; ph++)
             for (const NskSegPlan &pl : seg_plans[ph])
                 for (int i = 0; i < pl.tab.n && first_border < 0; i++)
                     if (pl.tab.e[i].push_off != NSK_NO_STREAM) first_border = (int)ph;
-        if (first_border >= 0) g->p2p_first_phase = first_border;
+        if (first_border >= 0) g->p2p.first_phase = first_border;
     }
-    g->p2p_border_total = border_total;
-    g->p2p_border_all = border_all && border_total == (uint32_t)bt.size();
+    g->p2p.border_total = border_total;
+    g->p2p.border_all = border_all && border_total == (uint32_t)bt.size();
     g->seg_plans_all_tab = g->seg_plans_all_wide = true;
     for (const auto &v : seg_plans)
         for (const NskSegPlan &pl : v) {
@@ -171,7 +171,7 @@ struct CounterSrc {
     uint32_t sweep_off;
     unsigned int tag;
     static CounterSrc eager(const nsk_graph *g) {
-        return {(uint32_t)g->seed, (uint32_t)(g->seed >> 32), (uint32_t)g->sweep, nsk_sweep_hi(g), nullptr, 0u, g->p2p_tag};
+        return {(uint32_t)g->seed, (uint32_t)(g->seed >> 32), (uint32_t)g->sweep, nsk_sweep_hi(g), nullptr, 0u, g->p2p.tag};
     }
     static CounterSrc captured(const nsk_graph *g, int i) { return {0u, 0u, 0u, 0u, g->d_counters, (uint32_t)i, (unsigned int)(i + 1)}; }
 };
@@ -212,9 +212,9 @@ static void launch_table(nsk_graph *g, const NskSegPlan &pl, int ph, int burnin,
         if (wide) launch_tabw(g, pl, burnin, src, true);
         else NSK_BY_NCH(NSK_TAB, k_gibbs_seg_tab_chains, (unsigned)g->nchains * nbp, NSK_TAB_ARGS, ch);
     }
-    else if (g->p2p_fused_now) {        // (the border waves of the sweep's first class with border tiles wait for the peers)
+    else if (g->p2p.fused_now) {        // (the border waves of the sweep's first class with border tiles wait for the peers)
         TabP2P px;
-        nsk_p2p_fill(g, px, src.sweep_base, src.tag, ph == g->p2p_first_phase);
+        nsk_p2p_fill(g, px, src.sweep_base, src.tag, ph == g->p2p.first_phase);
         NSK_BY_NCH(NSK_TAB, k_gibbs_seg_tab_p2p, nbp, NSK_TAB_ARGS, px);
     }
     else if (wide) launch_tabw(g, pl, burnin, src, false);
@@ -257,7 +257,7 @@ static int gibbs_impl(nsk_graph *g, int64_t nsweeps, int sample_evidence, int bu
         nsk_ensure_seg_plans(g, sample_evidence);
         for (int64_t s = 0; s < nsweeps; s++) {
             if (g->pack_now && !burnin && g->packed_sweeps >= 127) (void)nsk_unpack_tally(g);       // 7 tally bits per value byte
-            if (g->p2p_fused_now) ++g->p2p_tag;            // the exchange rides in this sweep's table launches
+            if (g->p2p.fused_now) ++g->p2p.tag;            // the exchange rides in this sweep's table launches
             for (size_t ph = 0; ph < nphase; ph++) {
                 const int fb = (int)g->c.phase_start[ph], fe = (int)g->c.phase_fast_end[ph];
                 const int e = (int)g->c.phase_end[ph];
@@ -400,6 +400,29 @@ static int gibbs_eager(nsk_graph *g, int64_t nsweeps, int sample_evidence, int b
 // ---- captured sweep sequences (hipGraph) -------------------------------------------------------------
 // A handle whose inference sweep consists of table launches only (grids and their shards: two ~4 us
 // kernels per sweep, plus two exchange kernels in an N-rank run) is bound by launches, not by kernels.
+// Does every sampled variable of the handle live in a table segment (the grids and their shards)?
+bool nsk_tables_only(const nsk_graph *g) {
+    const nsk::Compiled &c = g->c;
+    const size_t nphase = c.phase_start.size() - 1;
+    if (g->scan != NSK_SCAN_CHROMATIC || nphase == 0) return false;
+    for (size_t ph = 0; ph < nphase; ph++) {
+        const int64_t ntiles = c.phase_wb_base[ph + 1] - c.phase_wb_base[ph];
+        if (c.phase_end[ph] > c.phase_fast_end[ph]) return false;                    // generic-path variables / hubs
+        if (ntiles > c.phase_gen_tile[ph]) return false;                             // general tiles
+        if (c.phase_rest_base[ph + 1] > c.phase_rest_base[ph]) return false;         // tiles outside segments
+    }
+    for (const nsk::Compiled::Segment &sg : c.segments) if (sg.ztab < 0) return false;
+    return true;
+}
+
+// the captured sweep sequences bake array addresses and exchange pointers: dropped when those change
+void nsk_drop_sweep_graph(nsk_graph *g) {
+    if (g->sweep_graph) { (void)hipGraphExecDestroy(g->sweep_graph); g->sweep_graph = nullptr; }
+    g->sweep_graph_key = -1;
+    if (g->sweep_graph_big) { (void)hipGraphExecDestroy(g->sweep_graph_big); g->sweep_graph_big = nullptr; }
+    g->sweep_graph_big_key = -1;
+}
+
 // NSK_GRAPH_SWEEPS sweeps -- class launches, peer-to-peer push and wait/unpack -- are captured once into
 // a hipGraph whose kernels read the sweep index (and the exchange tag) from device memory + a per-node
 // offset, so the same executable graph serves every replay; a one-thread kernel at its end advances the
@@ -436,7 +459,7 @@ static int graph_build(nsk_graph *g, int burnin, bool p2p, int key, bool big) {
                 launch_table<VT>(g, pl, (int)ph, burnin, CounterSrc::captured(g, i));     // (the exchange tag of sweep i: counter + i + 1)
                 launches++;
             }
-        if (p2p && !g->p2p_fused_now) {
+        if (p2p && !g->p2p.fused_now) {
             int rc = nsk_p2p_enqueue(g, g->d_counters, (unsigned int)(i + 1));
             if (rc) { (void)hipStreamEndCapture(g->stream, &graph); if (graph) (void)hipGraphDestroy(graph); return rc; }
         }
@@ -460,19 +483,19 @@ int nsk_gibbs_run(nsk_graph *g, int64_t nsweeps, int sample_evidence, int burnin
     // ghosts the first sweep reads are packed into the receive block here, the wait for the peers' last flags and
     // the unpack into the value array are enqueued lazily (nsk_p2p_flush)
     bool fuse = false;
-    if (p2p && g->p2p_fused && g->scan == NSK_SCAN_CHROMATIC && g->values_regular && nsweeps > 0) {
+    if (p2p && g->p2p.fused && g->scan == NSK_SCAN_CHROMATIC && g->values_regular && nsweeps > 0) {
         nsk_ensure_seg_plans(g, sample_evidence);
-        fuse = g->p2p_border_all && g->seg_plans_all_tab;
+        fuse = g->p2p.border_all && g->seg_plans_all_tab;
         // (a fused call right behind a fused call continues it: the receive block already holds what the first
         // sweep reads -- nothing to unpack into the value array and pack back)
-        if (fuse && !g->p2p_close_pending) {
+        if (fuse && !g->p2p.close_pending) {
             int rc = nsk_p2p_ghost_pack(g);
             if (rc) return rc;
         }
     }
     if (!fuse) { int frc = nsk_p2p_flush(g); if (frc) return frc; }
-    g->p2p_close_pending = false;
-    g->p2p_fused_now = fuse;
+    g->p2p.close_pending = false;
+    g->p2p.fused_now = fuse;
     // Packed tally (nsk_internal.h): a whole-graph handle whose every launch of this call is the wide-quad kernel's keeps
     // the tally inside the value bytes while the call runs; it is unpacked before the call returns
     g->pack_now = false;
@@ -481,7 +504,7 @@ int nsk_gibbs_run(nsk_graph *g, int64_t nsweeps, int sample_evidence, int burnin
         nsk_ensure_seg_plans(g, sample_evidence);
         g->pack_now = g->seg_plans_all_wide;
     }
-    struct Done { nsk_graph *g; bool fuse, keep; ~Done() { g->p2p_fused_now = false; if (fuse) g->p2p_close_pending = true;
+    struct Done { nsk_graph *g; bool fuse, keep; ~Done() { g->p2p.fused_now = false; if (fuse) g->p2p.close_pending = true;
                                                             if (!keep) (void)nsk_unpack_tally(g);
                                                             g->pack_now = false; } } done{g, fuse, keep_packed};
     if (left >= NSK_GRAPH_SWEEPS && graph_eligible(g, p2p)) {
@@ -508,13 +531,13 @@ int nsk_gibbs_run(nsk_graph *g, int64_t nsweeps, int sample_evidence, int burnin
                         continue;
                     }
                 }
-                k_graph_counters<<<dim3(1), dim3(1), 0, g->stream>>>(g->d_counters, g->sweep, g->p2p_tag, 1, g->seed, g->rng_tag);
+                k_graph_counters<<<dim3(1), dim3(1), 0, g->stream>>>(g->d_counters, g->sweep, g->p2p.tag, 1, g->seed, g->rng_tag);
                 while (left >= nsw && exec_key == key) {
                     if (!burnin && g->pos_tally_sweeps + nsw > 255) nsk_fold_position_tally(g);   // uint8 tally
                     if (g->pack_now && g->packed_sweeps + nsw > 127) (void)nsk_unpack_tally(g);   // 7 bits in a value byte
                     HIPCHECK(hipGraphLaunch(exec, g->stream));
                     g->sweep += (uint64_t)nsw;
-                    if (p2p) g->p2p_tag += (unsigned int)nsw;
+                    if (p2p) g->p2p.tag += (unsigned int)nsw;
                     if (!burnin) { g->pos_tally_sweeps += nsw; g->cnt_dirty = true; if (g->pack_now) g->packed_sweeps += nsw; }
                     g->sweeps_done += nsw;
                     g->launches += big ? g->sweep_graph_big_launches : g->sweep_graph_launches;

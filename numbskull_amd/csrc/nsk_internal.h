@@ -1,6 +1,7 @@
 // nsk_internal.h -- host-side state of a compiled graph handle, shared by the translation units of
-// the library (nsk_api.hip: C-ABI, state sync, exchange; nsk_gibbs.hip / nsk_learn.hip: the sweep
-// drivers of numbskull/factorgraph.py:141,163,202; nsk_trace.hip, nsk_energy.hip, nsk_wstats.hip: the diagnostics).
+// the library (nsk_api.hip: C-ABI, state sync; nsk_exchange.hip: the multi-GPU boundary exchange; nsk_gibbs.hip /
+// nsk_learn.hip: the sweep drivers of numbskull/factorgraph.py:141,163,202; nsk_trace.hip, nsk_energy.hip, nsk_wstats.hip:
+// the diagnostics).
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -91,6 +92,59 @@ struct NskEnergy {
     int chains = 0;                    // chains the buffers below serve
     double *partial = nullptr;         // chains x nsk_energy_blocks(nfactor) block partials
     double *result = nullptr;          // chains sums (a query's; a trace writes into its lp column)
+};
+
+// Boundary exchange, the collective path (nsk_exchange.hip: nsk_exchange_setup, nsk_comm_init, nsk_*_sweeps_exchange):
+// every rank packs the values its peers read into `send`, an all-gather -- the caller's, or RCCL's through `comm` --
+// fills `recv` with every rank's slot, and the unpack scatters them to the ghost ids.  The handle owns the seven
+// arrays (the ledger frees them; a repeated set-up replaces all seven) and the communicator (nsk_exchange_release).
+struct NskGather {
+    int world = 0;                     // 0: not set up
+    int64_t slot = 0, nsend = 0, nrecv = 0;
+    int32_t *send_vids = nullptr, *recv_vids = nullptr, *recv_slot = nullptr;      // internal ids; position in recv (-1: skipped)
+    void *send = nullptr, *recv = nullptr, *send_evid = nullptr, *recv_evid = nullptr;   // slot and slot x world values, per chain
+    void *comm = nullptr;              // ncclComm_t (nsk_comm_init); survives a repeated set-up
+    void reset() { void *keep = comm; *this = NskGather(); comm = keep; }          // back to "not set up" (the arrays are the caller's to free first)
+};
+
+// Boundary exchange, the peer-to-peer path (nsk_exchange.hip: nsk_pf_setup, nsk_p2p_*): pairwise boundary lists, ONE
+// fine-grained allocation per rank (flags | received values of both chains, two parities | weight deltas;
+// nsk_kernels_misc.h), the peers' mappings of theirs, the exchange counter.  The handle owns the device arrays (ledger;
+// a repeated nsk_p2p_setup replaces send_iid / recv_iid, nsk_p2p_export a block that became too small, the fuse plan
+// its push map) and the hipIpc mappings of the peers' blocks (closed at the next import and by nsk_exchange_release).
+struct NskP2PSetup {                   // what one nsk_p2p_setup .. import establishes
+    int world = 0, rank = 0;           // world 0: not set up
+    int64_t nsend = 0, nrecv = 0;
+    std::vector<int64_t> soff, roff, dbase, dtotal;
+    int32_t *send_iid = nullptr, *recv_iid = nullptr;
+    std::vector<int32_t> send_host, recv_host;      // the send / receive lists (internal ids), host copies
+    unsigned int peer_mask = 0, tag = 0;
+    bool ready = false;                // set up, exported and the peers' blocks imported
+    // Fused boundary exchange of the table launches (p2p_fuse_plan, nsk_kernels_gibbs.h TabP2P): the inference sweeps
+    // of a handle that lives in table segments read their ghosts from the receive block and push their boundary values
+    // from inside the class launches -- no exchange kernels per sweep
+    bool fused = false;                // the handle qualifies (decided when the peers' buffers are imported)
+    bool fused_now = false;            // ... and the running nsk_gibbs_sweeps_p2p call sweeps that way
+    bool close_pending = false;        // the closing wait + unpack of the last fused sweep is not enqueued yet
+    std::vector<int32_t> border_tiles; // sorted: tiles (position >> 6) that own a value a peer reads or read a ghost;
+                                       //   a tile's rank here is its row in the push map
+    uint32_t ghost_lo = 0, border_total = 0;   // first ghost id; border tiles one sweep of the current plans samples
+    int first_phase = -1;              // the sweep's first class with table launches: its border tiles wait for the flags
+    bool border_all = true;            // ... and that is every border tile (else the call takes the exchange kernels)
+};
+struct NskP2P : NskP2PSetup {          // ... and what outlives it: the block, the push map, the error / ticket words, the peers' mappings
+    void *base = nullptr;
+    size_t bytes = 0;
+    uint32_t *push_map = nullptr;      // [rows][64] reader << 28 | index in the reader's receive block; NSK_NO_STREAM
+    unsigned int *err = nullptr;       // [0] error mark, [1] [2] the kernels' tickets, [3] the fused launches' counter
+    void *peer_base[16] = {nullptr};
+    bool peer_ipc[16] = {false};       // mapped with hipIpcOpenMemHandle
+    unsigned long long timeout_ticks = 3000000000ull;      // 30 s of the 100 MHz wall clock (NSK_P2P_TIMEOUT_S)
+    // partial-factor aggregates this rank computes for its readers (nsk_pf_setup): value slots [nid, nid + npf)
+    int64_t npf = 0;
+    uint8_t *pf_op = nullptr;
+    int32_t *pf_off = nullptr, *pf_mem = nullptr;
+    void reset() { (NskP2PSetup &)*this = NskP2PSetup(); }     // back to "not set up" (send_iid / recv_iid are the caller's to free first)
 };
 
 // blocks of the factor walk, a function of nfactor ALONE (the sum must not depend on anything else): one lane per factor
@@ -198,46 +252,10 @@ struct nsk_graph {
     bool weights_exposed = false;
     std::vector<double> w_stage;        // host staging of weight transfers when the table is in slot order (wmap)
     bool adj_wt_skip = false;       // learning reads weights directly: skip the shape-tile rows until the next inference   // the weight buffer was handed out: assume it changes between calls
-    // boundary exchange (multi-GPU)
-    int xworld = 0, xrank = 0;
-    int64_t xslot = 0, xnsend = 0, xnrecv = 0;
-    int32_t *x_send_vids = nullptr, *x_recv_vids = nullptr, *x_recv_slot = nullptr;
-    void *x_send = nullptr, *x_recv = nullptr, *x_send_evid = nullptr, *x_recv_evid = nullptr;
-    double *w_start = nullptr, *w_delta = nullptr;
-    // peer-to-peer exchange (nsk_p2p_*): pairwise boundary lists, ONE fine-grained allocation per rank
-    // (flags | received values of both chains, two parities | weight deltas; nsk_kernels_misc.h), the
-    // peers' mappings of theirs, the exchange counter
-    int pworld = 0, prank = 0;
-    int64_t p_nsend = 0, p_nrecv = 0;
-    std::vector<int64_t> p_soff, p_roff, p_dbase, p_dtotal;
-    int32_t *p_send_iid = nullptr, *p_recv_iid = nullptr;
-    void *p2p_base = nullptr;
-    size_t p2p_bytes = 0;
-    unsigned int *p2p_err = nullptr;
-    void *p2p_peer_base[16] = {nullptr};
-    bool p2p_peer_ipc[16] = {false};                // mapped with hipIpcOpenMemHandle (closed at destroy / re-import)
-    unsigned int p2p_peer_mask = 0, p2p_tag = 0;
-    unsigned long long p2p_timeout_ticks = 3000000000ull;      // 30 s of the 100 MHz wall clock (NSK_P2P_TIMEOUT_S)
-    bool p2p_ready = false;
-    // partial-factor aggregates this rank computes for its readers (nsk_pf_setup): value slots [nid, nid + npf)
-    int64_t npf = 0;
-    uint8_t *pf_op = nullptr;
-    int32_t *pf_off = nullptr, *pf_mem = nullptr;
-    // Fused boundary exchange of the table launches (nsk_api.hip p2p_fuse_plan, nsk_kernels_gibbs.h TabP2P): the
-    // inference sweeps of a handle that lives in table segments read their ghosts from the receive block and
-    // push their boundary values from inside the class launches -- no exchange kernels per sweep
-    bool p2p_fused = false;                 // the handle qualifies (decided when the peers' buffers are imported)
-    bool p2p_fused_now = false;             // ... and the running nsk_gibbs_sweeps_p2p call sweeps that way
-    bool p2p_close_pending = false;         // the closing wait + unpack of the last fused sweep is not enqueued yet
-    std::vector<int32_t> p2p_border_tiles;  // sorted: tiles (position >> 6) that own a value a peer reads or read a ghost;
-                                            //   a tile's rank here is its row in the push map
-    uint32_t *p2p_push_map = nullptr;       // [rows][64] reader << 28 | index in the reader's receive block; NSK_NO_STREAM
-    uint32_t p2p_ghost_lo = 0, p2p_border_total = 0;   // first ghost id; border tiles one sweep of the current plans samples
-    int p2p_first_phase = -1;               // the sweep's first class with table launches: its border tiles wait for the flags
-    bool p2p_border_all = true;             // ... and that is every border tile (else the call takes the exchange kernels)
-    std::vector<int32_t> p_send_host, p_recv_host;      // the send / receive lists (internal ids), host copies
-    // native RCCL
-    void *rccl_lib = nullptr, *rccl_comm = nullptr;
+    // boundary exchange (multi-GPU): the collective path, the peer-to-peer path, and what the weight merge of both keeps
+    NskGather gather;
+    NskP2P p2p;
+    double *w_start = nullptr, *w_delta = nullptr;     // the weights an epoch started from; this rank's share of the change (nsk_ensure_w_start)
     long long *cnt_total = nullptr, *G = nullptr;
     uint32_t *K = nullptr, *T = nullptr;
     nsk::MTState *mt_np = nullptr, *mt_py = nullptr;
@@ -493,11 +511,12 @@ int nsk_ensure_lag_sets(nsk_graph *g);                 // second set of weights 
 // one peer-to-peer exchange on the library's stream; tag_base != null: a captured launch whose tag is
 // the device counter + tag_off; learn: both chains + the weight deltas; part 0 = all of it, 1 = the
 // pushes only, 2 = wait + unpack (+ the owner's half of the weight merge), 3 = the closing half of the
-// weight merge (nsk_api.hip)
+// weight merge (nsk_exchange.hip)
 int nsk_p2p_enqueue(nsk_graph *g, const unsigned long long *tag_base, unsigned int tag_off, bool learn = false, int part = 0);
-bool nsk_tables_only(const nsk_graph *g);           // every sampled variable lives in a table segment (nsk_api.hip)
+bool nsk_tables_only(const nsk_graph *g);           // every sampled variable lives in a table segment (nsk_gibbs.hip)
 void nsk_ensure_seg_plans(nsk_graph *g, int sample_evidence);    // nsk_gibbs.hip
 int nsk_p2p_ghost_pack(nsk_graph *g);
+void nsk_exchange_release(nsk_graph *g);           // nsk_graph_destroy: the peers' hipIpc mappings and the RCCL communicator (nsk_exchange.hip)
 int nsk_p2p_flush(nsk_graph *g);                   // enqueue the pending closing wait + unpack of a fused sweep sequence, if any
 void nsk_p2p_fill(nsk_graph *g, nsk::TabP2P &px, const unsigned long long *tag_base, unsigned int tag, bool wait);   // kernel argument of a fused launch
 void nsk_drop_sweep_graph(nsk_graph *g);            // the captured sweep sequence bakes exchange pointers: drop it when they change

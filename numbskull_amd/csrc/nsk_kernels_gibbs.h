@@ -1544,7 +1544,7 @@ template <> __device__ __forceinline__ void nsk_buf_st<int32_t>(nsk_rsrc r, uint
     __builtin_amdgcn_raw_buffer_store_b32((unsigned int)x, r, (int)(voff == NSK_BUF_OOB ? voff : voff * 4u), (int)(soff * 4u), 0);
 }
 
-// ---- fused boundary exchange of a shard's table launches (N ranks, peer to peer; nsk_api.hip p2p_fuse_plan) ----
+// ---- fused boundary exchange of a shard's table launches (N ranks, peer to peer; nsk_exchange.hip p2p_fuse_plan) ----
 // The shard's ghosts are read straight from its receive block of the exchange allocation (parity of the last
 // exchange) and the border tiles write their new values into the readers' blocks themselves (the other parity):
 // a sweep of a shard is its class launches and nothing else -- no push, wait or unpack kernels.  Segments are

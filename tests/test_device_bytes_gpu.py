@@ -1,7 +1,7 @@
 """nsk_graph_info.device_bytes is what the handle holds NOW: every array the library frees before the handle is
 destroyed leaves the count by exactly what it entered it with (numbskull_amd/csrc/nsk_alloc.h), so a round trip through
-another chain count, a repeated nsk_pf_setup, or every optional diagnostic switched on and off again ends at the
-reading it started from -- and none of it changes a result bit."""
+another chain count, a repeated nsk_pf_setup, nsk_p2p_setup or nsk_exchange_setup, or every optional diagnostic
+switched on and off again ends at the reading it started from -- and none of it changes a result bit."""
 
 import ctypes as C
 
@@ -76,6 +76,108 @@ def test_partial_factors_twice():
         second = _bytes(p.fg)
         print("%d aggregates over %d members: %d, again %d" % (len(ops), len(mem), first, second))
         assert second == first
+    finally:
+        for q in parts:
+            q.fg.close()
+
+
+def _two_shards():
+    """ising_grid(16, 16) in two range shards on one device, as test_hip_parity's peer-to-peer timeout test builds them"""
+    import torch
+    import numbskull_amd
+    from numbskull_amd.distributed import PartitionedSampler, shard_range
+    g = graphgen.ising_grid(16, 16, weight=0.2)
+    parts = []
+    for r in range(2):
+        ns = numbskull_amd.NumbSkull(quiet=True, seed=3)
+        ns.loadFactorGraph(*[x.copy() if isinstance(x, np.ndarray) else x for x in g[:5]], int(g[5]),
+                           own_range=shard_range(r, 2, 256))
+        with torch.cuda.stream(torch.cuda.Stream()):
+            ps = PartitionedSampler(ns.factorGraphs[0], None, torch, r, 1, nvar_global=256)
+        ps.world = 2
+        parts.append(ps)
+    needs = [p.global_needs() for p in parts]
+    for p in parts:
+        p.all_needs = needs
+    return parts
+
+
+def _wire(parts):
+    """nsk_p2p_setup / nsk_p2p_export on every shard, then nsk_p2p_import_local: the readings afterwards"""
+    L = _lib.lib()
+    bases = (C.c_void_p * 2)()
+    for p in parts:
+        _lib.check(p.p2p_setup())
+        b = C.c_void_p()
+        _lib.check(L.nsk_p2p_export(p.h, None, C.byref(b)))
+        bases[p.rank] = b.value
+    for p in parts:
+        _lib.check(L.nsk_p2p_import_local(p.h, bases))
+        p.p2p = True
+    return [_bytes(p.fg) for p in parts]
+
+
+def _swept(parts):
+    """4 nsk_gibbs_sweeps_p2p sweeps, one per call and breadth-first over the shards (test_config5_shards_gpu.run_case: no
+    rank waits for a peer whose sweep is not issued); values by variable id and tallies of every shard"""
+    L = _lib.lib()
+    for _ in range(4):
+        for p in parts:
+            _lib.check(L.nsk_gibbs_sweeps_p2p(p.h, 1, 1, 0))
+    for p in parts:
+        p.check()
+    out = []
+    for p in parts:
+        p.fg._pull(0, 0)
+        out.append((p.val.cpu().numpy().copy(), p.fg.count.copy()))
+    return out
+
+
+def test_p2p_setup_twice(monkeypatch):
+    """A repeated nsk_p2p_setup frees the lists it replaces, keeps the fused plan and changes no result bit.  (Before
+    set-ups freed what they replace the first one's lists stayed until the handle was destroyed: 28291 bytes per shard
+    after the first set-up, 28419 after the second -- two lists of 16 internal ids.)"""
+    monkeypatch.setenv("NSK_P2P_TIMEOUT_S", "5")            # (a peer that never arrives fails the test in 5 s, not 30)
+    twice, once = _two_shards(), _two_shards()
+    try:
+        first = _wire(twice)
+        second = _wire(twice)
+        print("device_bytes per shard: first set-up %s, second %s" % (first, second))
+        assert second == first
+        _wire(once)
+        fused = [p.fg.info()["p2p_fused"] for p in twice]
+        print("p2p_fused", fused)
+        assert fused == [p.fg.info()["p2p_fused"] for p in once]
+        for (va, ca), (vb, cb) in zip(_swept(twice), _swept(once)):
+            assert va.dtype == vb.dtype and np.array_equal(va, vb)
+            assert np.array_equal(ca, cb) and ca.sum() > 0
+        assert [_bytes(p.fg) for p in twice] == [_bytes(p.fg) for p in once]
+    finally:
+        for p in twice + once:
+            p.fg.close()
+
+
+def test_exchange_setup_twice():
+    """... and so does a repeated nsk_exchange_setup: seven arrays replaced, the staging buffers re-wrapped by
+    install_boundaries.  (Before: 26259 bytes after the first set-up, 26675 after the second.)"""
+    from numbskull_amd.distributed import plan_boundaries
+    L = _lib.lib()
+    parts = _two_shards()
+    try:
+        p = parts[0]
+        lists, slot = plan_boundaries(p.all_needs, 2, 256)
+        p.install_boundaries(lists, slot)
+        first = _bytes(p.fg)
+        p.install_boundaries(lists, slot)
+        second = _bytes(p.fg)
+        print("slot %d: first set-up %d, second %d" % (slot, first, second))
+        assert slot > 0 and second == first
+        ptr, nb = C.c_void_p(), C.c_int64()
+        _lib.check(L.nsk_device_buffer(p.h, _lib.BUF_RECV, C.byref(ptr), C.byref(nb)))
+        assert ptr.value and nb.value == slot * 2 * p.fg.info()["value_bytes"]
+        _lib.check(L.nsk_exchange_pack(p.h, _lib.BUF_VALUE))
+        _lib.check(L.nsk_exchange_unpack(p.h, _lib.BUF_VALUE))
+        _lib.check(L.nsk_synchronize(p.h))
     finally:
         for q in parts:
             q.fg.close()

@@ -260,7 +260,7 @@ def test_tie_inside_a_captured_sequence(monkeypatch):
 
 # ---- 8: the fused peer-to-peer copy of the branch (tab_tiles_x): a 64 x 300 grid in two range shards on one device,
 # their boundary exchanged inside the table launches.  v is a cell of shard 0's last row in the shard's first class: it
-# reads a ghost (the cell below it belongs to shard 1), so its tile is a border tile (nsk_api.hip p2p_fuse_plan) and the
+# reads a ghost (the cell below it belongs to shard 1), so its tile is a border tile (nsk_exchange.hip p2p_fuse_plan) and the
 # fused launch samples it with tab_tiles_x.  Sweep 0 reads the ghosts' initial values, so shard 0's own oracle IS the
 # emulation there; the comparison at w_a and w_b is the harness's (owned values, ghosts and tallies of both shards).
 def test_tie_in_the_fused_peer_to_peer_launch(monkeypatch):

@@ -15,6 +15,7 @@ else
   /opt/rocm/bin/hipcc $FLAGS $extra -c -o build/nsk_gibbs_$v.o nsk_gibbs.hip
   objs="build/nsk_gibbs_$v.o $LEARN"
 fi
-# (the host objects -- the graph compiler's stage files among them -- are the Makefile's list)
-/opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -fPIC -pthread -o ../variants/libnsk_$v.so build/nsk_api.o build/nsk_energy.o build/nsk_wstats.o build/nsk_trace.o $objs $(make -s print-host-obj)
+# (the host objects -- the graph compiler's stage files among them -- and the device objects beside the sweep drivers
+#  are the Makefile's lists)
+/opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -fPIC -pthread -o ../variants/libnsk_$v.so $(make -s print-dev-obj) $objs $(make -s print-host-obj)
 echo built ../variants/libnsk_$v.so
