@@ -237,6 +237,29 @@ int nsk_trace_ess(nsk_graph *g, int64_t first_row, int64_t nrows, int64_t max_la
 int nsk_trace_autocov_counts(nsk_graph *g, int64_t first_row, int64_t nrows, int64_t max_lag, const int64_t *cols,
                              int64_t ncols_sel, int64_t *out /* ncols_sel x (L + 3) */);
 
+/* Pairwise joint marginals from the trace, on the device (FactorGraph.pairwise): for pairs (a, b) of columns of a
+ * BIT-PACKED trace, how often both are 1 and how often each is, over rows first_row .. first_row + nrows - 1 of the R
+ * chains (the window is not split) -- the 2 x 2 table of a pair is these three integers and the row count; no row is
+ * unpacked or leaves the device.  pairs[2 j], pairs[2 j + 1] are indices into the caller's columns of nsk_trace_setup,
+ * the numbering nsk_trace_autocov_counts takes for cols: any order, repeats allowed, a == b allowed.
+ *   out[(j R + r) 3 + 0 .. 2] = n11, n1(a), n1(b) of chain r: the rows of the window where both columns are 1, where
+ *   column a is, where column b is.
+ * Two launches.  The 64-column words the pairs touch are each transposed once, 64 rows x 64 columns at a time, into a
+ * scratch array T[word][bit][chain][block of 64 rows] whose words hold one column's rows along time (0 beyond the
+ * window); then one wave per pair walks the R x ceil(nrows / 64) neighbouring words of both columns and sums
+ * popcount(Ta & Tb), popcount(Ta), popcount(Tb) per chain in int64.  Integers throughout, no atomics: the counts are
+ * those of numbskull_amd.diagnostics.pair_counts on the downloaded rows, exactly.
+ * The call synchronises with the handle's stream, reads the trace and changes nothing (rows, values, tallies,
+ * sweeps_done, the lp and stats columns).  Its buffers -- T, 512 bytes per touched word, chain and row block; the word
+ * list, 4 bytes a word; the pairs as columns of T, 16 bytes a pair; the results, 24 bytes per pair and chain -- are
+ * allocated for the call and freed before it returns: nsk_graph_info.device_bytes shows them only meanwhile;
+ * NSK_E_NOMEM names their size when they do not fit.  nsk_profile_* keeps counting sweep-kernel launches only.
+ * Refused before any launch -- NSK_E_INVALID: null graph, no trace, plain (not bit-packed) rows, nrows < 1,
+ * first_row < 0, npairs < 0, pairs or out NULL with npairs > 0, rows beyond those recorded; NSK_E_INDEX: a column index
+ * outside [0, ncols).  npairs == 0 is NSK_OK with nothing done. */
+int nsk_trace_pair_counts(nsk_graph *g, int64_t first_row, int64_t nrows, const int64_t *pairs /* npairs x 2 */,
+                          int64_t npairs, int64_t *out /* npairs x chains x 3 */);
+
 /* RNG: the chromatic scan draws from Philox4x32-10 keyed by `seed`.  A variable's generator id is
  * its position in the compiled layout (nsk_graph_get_layout), so samples are a function of the seed
  * AND the layout the library chose (device, flags and diagnostic switches being equal, a graph

@@ -1,10 +1,12 @@
-// nsk_tracestat.hip -- statistics of the sample trace computed where it lies (nsk_trace_ess, nsk_trace_autocov_counts):
-// the checks, the result buffers (allocated for the call alone), the launch of k_trace_autocov (nsk_kernels_tracestat.h)
+// nsk_tracestat.hip -- statistics of the sample trace computed where it lies (nsk_trace_ess, nsk_trace_autocov_counts,
+// nsk_trace_pair_counts): the checks, the scratch and result buffers (allocated for the call alone), the launches of
+// k_trace_autocov (nsk_kernels_tracestat.h) and of k_trace_transpose / k_trace_pair_counts (nsk_kernels_tracepairs.h)
 // on the handle's stream and the permutation of the results to the caller's columns.  They read the trace and change
 // nothing on the handle; the profiling bracket does not count their launches (sweep kernels only).
 #include <hip/hip_runtime.h>
 
 #include "nsk_internal.h"
+#include "nsk_kernels_tracepairs.h"
 #include "nsk_kernels_tracestat.h"
 
 using namespace nsk;
@@ -62,8 +64,8 @@ static int tracestat_launch(nsk_graph *g, const TraceStatArgs &a) {
     return NSK_OK;
 }
 
-static int tracestat_nomem(const char *what, double bytes) {
-    return fail(NSK_E_NOMEM, std::string(what) + ": the result buffers (" + std::to_string((long long)(bytes / 1048576.0)) + " MB) do not fit on the device");
+static int tracestat_nomem(const char *what, double bytes, const char *which = "result") {
+    return fail(NSK_E_NOMEM, std::string(what) + ": the " + which + " buffers (" + std::to_string((long long)(bytes / 1048576.0)) + " MB) do not fit on the device");
 }
 
 extern "C" {
@@ -146,6 +148,75 @@ int nsk_trace_autocov_counts(nsk_graph *g, int64_t first_row, int64_t nrows, int
             for (size_t k = 0; k < per; k++) out[(size_t)j * per + k] = (int64_t)src[k];
         }
     });
+    return NSK_OK;
+}
+
+int nsk_trace_pair_counts(nsk_graph *g, int64_t first_row, int64_t nrows, const int64_t *pairs, int64_t npairs, int64_t *out) {
+    const std::string w("nsk_trace_pair_counts");
+    if (!g) return fail(NSK_E_INVALID, "null graph");
+    const NskTrace &t = g->trace;
+    if (t.capacity == 0) return fail(NSK_E_INVALID, w + ": no trace is set up");
+    if (!t.packed) return fail(NSK_E_INVALID, w + ": the rows are not bit-packed (some traced variable is not binary)");
+    if (nrows < 1) return fail(NSK_E_INVALID, w + ": at least 1 row is needed");
+    if (first_row < 0) return fail(NSK_E_INVALID, w + ": rows beyond those recorded");
+    if (npairs < 0 || (npairs > 0 && (!pairs || !out))) return fail(NSK_E_INVALID, w + ": null argument");
+    if (nrows > t.rows || first_row > t.rows - nrows) return fail(NSK_E_INVALID, w + ": rows beyond those recorded");
+    for (int64_t j = 0; j < 2 * npairs; j++)
+        if (pairs[j] < 0 || pairs[j] >= t.ncols) return fail(NSK_E_INDEX, w + ": column index out of range");
+    HIPCHECK(hipSetDevice(g->device));
+    HIPCHECK(hipStreamSynchronize(g->stream));
+    if (npairs == 0) return NSK_OK;
+    // the words the pairs touch, each transposed once
+    std::vector<int32_t> words((size_t)(2 * npairs));
+    for (int64_t j = 0; j < 2 * npairs; j++) words[(size_t)j] = (int32_t)(t.pos[(size_t)pairs[j]] >> 6);
+    std::sort(words.begin(), words.end());
+    words.erase(std::unique(words.begin(), words.end()), words.end());
+    // ... and the pairs as columns of T
+    std::vector<long long> tcols((size_t)(2 * npairs));
+    nsk::parallel_for(2 * npairs, [&](int64_t b0, int64_t b1, int) {
+        for (int64_t j = b0; j < b1; j++) {
+            const int64_t p = t.pos[(size_t)pairs[j]];
+            const int64_t slot = std::lower_bound(words.begin(), words.end(), (int32_t)(p >> 6)) - words.begin();
+            tcols[(size_t)j] = (long long)(slot * 64 + (p & 63));
+        }
+    });
+    TracePairsArgs a = {};
+    a.nwords = (long long)(t.row_bytes / 8);
+    a.chains = t.chains;
+    a.rows = (const unsigned long long *)t.buf + (size_t)first_row * (size_t)t.chains * (size_t)a.nwords;
+    a.nslots = (long long)words.size();
+    a.nrows = nrows;
+    a.nb = (nrows + 63) / 64;
+    a.bgroups = (a.nb + NSK_TRACEPAIRS_TBLKS - 1) / NSK_TRACEPAIRS_TBLKS;
+    a.npairs = npairs;
+    a.G = 1;
+    while (a.G < 64 && a.G < a.nb) a.G *= 2;
+    const double tiles = (double)words.size() * (double)a.chains * (double)a.nb, nres = 3.0 * (double)npairs * (double)a.chains;
+    const double bytes = 512.0 * tiles + 4.0 * (double)words.size() + 16.0 * (double)npairs + 8.0 * nres;
+    const long long sgroups = (a.nslots + NSK_TRACEPAIRS_TBLOCK / 64 - 1) / (NSK_TRACEPAIRS_TBLOCK / 64);
+    const double tgrid = (double)sgroups * (double)a.chains * (double)a.bgroups;
+    const long long pgrid = (npairs + NSK_TRACEPAIRS_PBLOCK / 64 - 1) / (NSK_TRACEPAIRS_PBLOCK / 64);
+    if (bytes >= 9.0e18 || tgrid >= 2147483648.0 || pgrid >= 2147483648ll) return tracestat_nomem("nsk_trace_pair_counts", bytes, "scratch and result");
+    const size_t nT = words.size() * 64 * (size_t)a.chains * (size_t)a.nb, nc = 3 * (size_t)npairs * (size_t)a.chains;
+    TraceStatBuffers buf(g);
+    int32_t *dwords = nullptr;
+    long long *dpairs = nullptr;
+    int rc = buf.alloc(&dwords, words.size());
+    if (!rc) rc = buf.alloc(&dpairs, tcols.size());
+    if (!rc) rc = buf.alloc(&a.T, nT);
+    if (!rc) rc = buf.alloc(&a.counts, nc);
+    if (rc) return rc == NSK_E_NOMEM ? tracestat_nomem("nsk_trace_pair_counts", bytes, "scratch and result") : rc;
+    HIPCHECK(hipMemcpyAsync(dwords, words.data(), words.size() * sizeof(int32_t), hipMemcpyHostToDevice, g->stream));
+    HIPCHECK(hipMemcpyAsync(dpairs, tcols.data(), tcols.size() * sizeof(long long), hipMemcpyHostToDevice, g->stream));
+    a.words = dwords;
+    a.pairs = dpairs;
+    k_trace_transpose<<<dim3((unsigned int)(sgroups * a.chains * a.bgroups)), dim3(NSK_TRACEPAIRS_TBLOCK), 0, g->stream>>>(a);
+    HIPCHECK(hipGetLastError());
+    k_trace_pair_counts<<<dim3((unsigned int)pgrid), dim3(NSK_TRACEPAIRS_PBLOCK), 0, g->stream>>>(a);
+    HIPCHECK(hipGetLastError());
+    static_assert(sizeof(long long) == sizeof(int64_t), "the counts go to the caller as they are");
+    HIPCHECK(hipMemcpyAsync(out, a.counts, nc * sizeof(long long), hipMemcpyDeviceToHost, g->stream));
+    HIPCHECK(hipStreamSynchronize(g->stream));
     return NSK_OK;
 }
 

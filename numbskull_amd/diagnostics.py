@@ -26,9 +26,18 @@ exact expectation): the log-likelihood gradient of weight learning, with its Mon
 a bit-packed trace (nsk_trace_ess): for 0 / 1 columns the estimator above is integer counts --
 exact in int64 -- and a short float64 epilogue, the lags cut at ``max_lag``.  With ``max_lag = n - 1`` it is the
 estimator of ``effective_sample_size``.
+
+``pair_counts`` restates what ``FactorGraph.pairwise`` counts on the device for pairs of 0 / 1 columns
+(nsk_trace_pair_counts), and ``pair_tables`` turns such counts -- the device's or numpy's -- into the 2 x 2 joint
+marginal, covariance, correlation and mutual information of every pair; ``factor_pairs`` lists the two ends of every
+pairwise factor of a graph.
 """
 
+import collections
+
 import numpy as np
+
+Pairwise = collections.namedtuple("Pairwise", ["joint", "cov", "corr", "mi", "counts", "samples"])
 
 _CHUNK = 256          # columns per FFT batch (memory: ~ 64 bytes x samples x chains x _CHUNK)
 
@@ -184,6 +193,108 @@ def ess_from_counts(n, H, A, S1, S2):
         mean = S1.astype(np.float64) / np.float64(H * n)
     truncated = (run & (L < n - 1)).astype(np.uint8)
     return mean, tau, rhat2, truncated
+
+
+def _pair_list(pairs, ncols, what):
+    p = np.asarray(pairs)
+    if p.size == 0 and p.ndim <= 2:
+        return np.zeros((0, 2), np.int64)
+    if p.ndim != 2 or p.shape[1] != 2 or p.dtype.kind not in "iu":
+        raise ValueError("%s: pairs have shape (npairs, 2) and an integer type, got %r %s" % (what, p.shape, p.dtype))
+    p = p.astype(np.int64)
+    if p.min() < 0 or p.max() >= ncols:
+        raise ValueError("%s: an index of a pair lies outside [0, %d)" % (what, ncols))
+    return p
+
+
+def pair_counts(trace, pairs):
+    """The integers of ``FactorGraph.pairwise`` from a downloaded 0 / 1 trace ``(rows, chains, columns)``: for every
+    pair ``(a, b)`` of ``pairs`` (``(npairs, 2)`` column indices; any order, repeats and ``a == b`` allowed) and every
+    chain ``r`` the number of rows where both columns are 1, where column ``a`` is and where column ``b`` is --
+    ``(n11, n1a, n1b)``, int64, shape ``(npairs, chains, 3)``.  ValueError on values other than 0 / 1, on a bad shape
+    and on an index outside the columns."""
+    x = np.asarray(trace)
+    if x.ndim != 3:
+        raise ValueError("a trace has shape (samples, chains, columns), got %r" % (x.shape,))
+    if x.size and not ((x == 0) | (x == 1)).all():
+        raise ValueError("the counts are defined for 0 / 1 columns")
+    p = _pair_list(pairs, x.shape[2], "pair_counts")
+    x = x.astype(np.int8)
+    out = np.zeros((len(p), x.shape[1], 3), np.int64)
+    n1 = x.sum(axis=0, dtype=np.int64)                                     # (chains, columns)
+    for j0 in range(0, len(p), _CHUNK):
+        a, b = p[j0:j0 + _CHUNK, 0], p[j0:j0 + _CHUNK, 1]
+        out[j0:j0 + _CHUNK, :, 0] = (x[:, :, a] & x[:, :, b]).sum(axis=0, dtype=np.int64).T
+        out[j0:j0 + _CHUNK, :, 1] = n1[:, a].T
+        out[j0:j0 + _CHUNK, :, 2] = n1[:, b].T
+    return out
+
+
+def pair_tables(counts, nrows):
+    """From the counts of ``pair_counts`` / nsk_trace_pair_counts -- ``(npairs, chains, 3)`` int64 over ``nrows`` rows a
+    chain -- the named tuple ``Pairwise(joint, cov, corr, mi, counts, samples)``, the chains pooled.  With
+    ``N = nrows x chains`` and the pooled integers ``n11, na, nb`` (sums over the chains, int64), every figure is an
+    exact integer expression converted to float64 once and then, in this order, one rounded float64 operation a step:
+
+        joint[j]  2 x 2, indexed [value of a][value of b]:  [1, 1] = n11 / N,  [1, 0] = (na - n11) / N,
+                  [0, 1] = (nb - n11) / N,  [0, 0] = (N - na - nb + n11) / N;
+        num = N n11 - na nb  (int64; ValueError when N >= 2^31, so that it fits);
+        cov = float(num) / float(N N);
+        corr = float(num) / sqrt(float(na (N - na)) x float(nb (N - nb))),  NaN when either column is constant;
+        mi (nats) = the cells c > 0 added in the order [0, 0], [0, 1], [1, 0], [1, 1] of
+                  (float(c) / N) x log(float(c N) / float(row total x column total)).
+
+    ``counts`` is the input as int64 and ``samples`` is ``N``.  With ``N = 0`` every float is NaN.  The device path
+    and the numpy path both go through this function: equal counts give equal floats."""
+    c = np.asarray(counts)
+    if c.ndim != 3 or c.shape[2] != 3 or (c.size and c.dtype.kind not in "iu"):
+        raise ValueError("counts have shape (npairs, chains, 3) and an integer type, got %r %s" % (c.shape, c.dtype))
+    c = c.astype(np.int64)
+    nrows = int(nrows)
+    if nrows < 0:
+        raise ValueError("nrows must not be negative")
+    N = nrows * c.shape[1]
+    if N >= 2 ** 31:
+        raise ValueError("rows x chains reaches 2^31: N n11 - na nb may not fit int64")
+    if c.size and (c.min() < 0 or c[:, :, 1:].max() > nrows or (c[:, :, :1] > c[:, :, 1:]).any()):
+        raise ValueError("not the counts of %d rows a chain" % nrows)
+    n11, na, nb = (c[:, :, k].sum(axis=1) for k in range(3))
+    if ((na + nb - n11) > N).any():
+        raise ValueError("not the counts of %d rows a chain" % nrows)
+    cells = np.empty((len(c), 2, 2), np.int64)
+    cells[:, 0, 0] = N - na - nb + n11
+    cells[:, 0, 1] = nb - n11
+    cells[:, 1, 0] = na - n11
+    cells[:, 1, 1] = n11
+    rowtot = np.stack([N - na, na], axis=1)                                # by the value of a
+    coltot = np.stack([N - nb, nb], axis=1)                                # by the value of b
+    num = N * n11 - na * nb
+    fN = np.float64(N)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        joint = cells.astype(np.float64) / fN
+        cov = num.astype(np.float64) / np.float64(N * N)
+        va, vb = na * (N - na), nb * (N - nb)
+        corr = num.astype(np.float64) / np.sqrt(va.astype(np.float64) * vb.astype(np.float64))
+        corr[(va == 0) | (vb == 0)] = np.nan
+        mi = np.zeros(len(c), np.float64)
+        for i in (0, 1):
+            for k in (0, 1):
+                cc = cells[:, i, k]
+                term = (cc.astype(np.float64) / fN) * np.log((cc * N).astype(np.float64) / (rowtot[:, i] * coltot[:, k]).astype(np.float64))
+                mi = np.where(cc > 0, mi + term, mi)
+        if N == 0:
+            mi[:] = np.nan
+    return Pairwise(joint, cov, corr, mi, c, N)
+
+
+def factor_pairs(factor, fmap):
+    """The two member variable ids of every arity-2 factor of a graph, in factor order: int64 ``(nf2, 2)``, first and
+    second member as ``fmap`` lists them."""
+    factor, fmap = np.asarray(factor), np.asarray(fmap)
+    off = factor["ftv_offset"][factor["arity"] == 2].astype(np.int64)
+    if len(off) and (off.min() < 0 or off.max() + 1 >= len(fmap)):
+        raise ValueError("factor_pairs: a factor's members lie outside fmap")
+    return np.stack([fmap["vid"][off], fmap["vid"][off + 1]], axis=1).astype(np.int64).reshape(-1, 2)
 
 
 def best_sample(lp):

@@ -574,6 +574,62 @@ class FactorGraph(object):
         with np.errstate(invalid="ignore"):
             return Mixing(samples / tau, tau, np.sqrt(rhat2), mean, truncated, samples)
 
+    def pairwise(self, epochs, pairs, thin=1, burnin_epochs=0, sample_evidence=False):
+        """The joint marginal of pairs of variables, counted on the device from the trace and without downloading a
+        row: ``inference(burnin_epochs, epochs, sample_evidence, var_copy="all")`` -- one chain per row of
+        ``var_value``; one chain is fine -- under a trace of the distinct variables of ``pairs``, a row after every
+        ``thin``-th sweep, then nsk_trace_pair_counts over the ``epochs // thin`` rows.  ``pairs`` is an ``(npairs, 2)``
+        array of variable ids (binary variables; any order, repeats and ``a == b`` allowed) or the string
+        ``"factors"``: the two ends of every arity-2 factor of the graph, in factor order
+        (``diagnostics.factor_pairs``).  Returns ``diagnostics.pair_tables`` of the counts, the named tuple
+        ``Pairwise(joint, cov, corr, mi, counts, samples)``: per pair the 2 x 2 table ``joint[j][value of a][value of
+        b]``, covariance, correlation (NaN when a column is constant, an evidence variable for one) and mutual
+        information in nats, the chains pooled; the per-chain integers ``counts`` ``(npairs, chains, 3)`` = n11, n1(a),
+        n1(b); and ``samples = rows x chains``.  With zero rows or zero pairs the arrays are NaN or empty and no trace
+        is set up.  State, ``count``, ``chain_count``, ``marginals`` and ``rhat`` come out as ``inference`` leaves them;
+        the trace is torn down before the call returns.  ValueError when a variable of a pair is not binary, on
+        ``thin < 1`` and on a bad shape; IndexError on an id out of range."""
+        from .diagnostics import factor_pairs, pair_tables
+        epochs, thin = int(epochs), int(thin)
+        if thin < 1:
+            raise ValueError("thin must be at least 1")
+        if isinstance(pairs, str):
+            if pairs != "factors":
+                raise ValueError('pairwise: pairs is an (npairs, 2) array of variable ids or "factors"')
+            pairs = factor_pairs(self.factor, self.fmap)
+        pairs = np.asarray(pairs)
+        if pairs.size == 0 and pairs.ndim <= 2:
+            pairs = np.zeros((0, 2), np.int64)
+        if pairs.ndim != 2 or pairs.shape[1] != 2 or pairs.dtype.kind not in "iu":
+            raise ValueError("pairwise: pairs have shape (npairs, 2) and an integer type, got %r %s" % (pairs.shape, pairs.dtype))
+        pairs = pairs.astype(np.int64)
+        if len(pairs) and (pairs.min() < 0 or pairs.max() >= self.variable.shape[0]):
+            raise IndexError("pairwise: variable id out of range")
+        vids, cols = np.unique(pairs, return_inverse=True)
+        if (self.variable["cardinality"][vids] != 2).any():
+            raise ValueError("pairwise: every variable of a pair must be binary (cardinality 2)")
+        vids, cols = _lib.as_c(vids, np.int64), _lib.as_c(cols.reshape(-1, 2), np.int64)
+        L, h = _lib.lib(), self._engine()
+        if burnin_epochs > 0:
+            self.burnIn(burnin_epochs, sample_evidence, var_copy="all")
+        nchains = self._chains()
+        rows = epochs // thin
+        counts = np.zeros((len(pairs), nchains, 3), np.int64)
+        measured = rows > 0 and len(pairs) > 0
+        if measured:
+            _lib.check(L.nsk_trace_setup(h, _lib.ptr(vids), len(vids), thin, rows))
+        try:
+            self.inference(0, epochs, sample_evidence, var_copy="all")
+            if measured:
+                _lib.check(L.nsk_trace_pair_counts(h, 0, rows, _lib.ptr(cols), len(cols), _lib.ptr(counts)))
+        except BaseException:
+            if measured:
+                L.nsk_trace_setup(h, None, 0, 1, 0)     # (its status must not replace the exception under way)
+            raise
+        if measured:
+            _lib.check(L.nsk_trace_setup(h, None, 0, 1, 0))
+        return pair_tables(counts, rows)
+
     # ------------------------------------------------------------------ per-weight statistics
     def weight_statistics(self, var_copy=0, evidence_chain=False, feature_scaled=False):
         """The sufficient statistics of a state: for every weight the sum of the values of its factors (the
