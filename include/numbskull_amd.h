@@ -260,6 +260,44 @@ int nsk_trace_autocov_counts(nsk_graph *g, int64_t first_row, int64_t nrows, int
 int nsk_trace_pair_counts(nsk_graph *g, int64_t first_row, int64_t nrows, const int64_t *pairs /* npairs x 2 */,
                           int64_t npairs, int64_t *out /* npairs x chains x 3 */);
 
+/* The same statistics for CATEGORICAL variables (FactorGraph.mixing_values / contingency): a trace with one variable
+ * of cardinality above 2 keeps PLAIN rows, one element of value_bytes per column, and the three calls above refuse it.
+ * These serve it through INDICATORS: an indicator is a pair (column, value), and its series is the 0 / 1 sequence
+ * x(t) == value of that column.  sel[2 i], sel[2 i + 1] = column and value of indicator i; quads[4 j .. 4 j + 3] =
+ * column a, value a, column b, value b of pair j.  Columns are indices into the caller's columns of nsk_trace_setup (the
+ * numbering nsk_trace_autocov_counts takes); any order, repeats allowed.
+ * The outputs mean what those of nsk_trace_autocov_counts, nsk_trace_ess and nsk_trace_pair_counts mean with "column"
+ * read as "the indicator's series": out[i (L + 3) ..] = A(0 .. L), S1, S2 of indicator i, L = min(max_lag, n - 1);
+ * mean[i] is the marginal of the value, tau, rhat2 and truncated as above (nsel long each, any may be NULL);
+ * out[(j R + r) 3 + 0 .. 2] = n11, n1(a), n1(b) of pair j in chain r.  A recorded value outside its variable's domain
+ * (the handle allows that) matches no indicator.
+ * The host sorts the indicators by (device column, value) and drops repeats -- two caller columns that name one variable
+ * share a plane -- and scatters the results back in the caller's order.  k_trace_onehot writes the window's indicators
+ * as time-major bit words (planes: bit i of a word is x(64 blk + i) == value, 0 beyond the segment), a 64-row x 64-column
+ * tile of the trace at a time through LDS, every touched trace byte read once; for the counts and the summary the
+ * segments are the H = 2 R half-chains and k_trace_autocov_planes, lane = indicator, forms the integers and the epilogue
+ * of nsk_trace_ess word for word; for the pairs the segments are the R chains and k_trace_pair_counts runs unchanged on
+ * pairs of planes.  Integers throughout, no atomics: the results are those of numbskull_amd.diagnostics (autocov_counts,
+ * ess_from_counts, pair_counts) on diagnostics.indicators of the downloaded rows, exactly.
+ * The calls synchronise with the handle's stream, read the trace and change nothing (rows, values, tallies,
+ * sweeps_done, the lp and stats columns).  Their buffers -- the indicator list, 8 bytes an indicator, with 12 bytes a
+ * touched column tile and 24 a segment; the planes, 8 bytes per distinct indicator, segment and block of 64 rows; the
+ * pair list, 16 bytes a pair; the results -- are allocated for the call and freed before it returns:
+ * nsk_graph_info.device_bytes shows them only meanwhile; NSK_E_NOMEM names their size when they do not fit.
+ * nsk_profile_* keeps counting sweep-kernel launches only.
+ * Refused before any launch, in this order -- NSK_E_INVALID: null graph, no trace, BIT-PACKED rows (the message names
+ * the call above that serves them), nrows < 4 (pairs: < 1), max_lag outside [1, 63], first_row < 0, a negative count,
+ * sel / quads / out NULL with a positive count; NSK_E_RANGE: 4 H n^3 reaches 2^63 (counts and summary; decided before
+ * the rows recorded are looked at); NSK_E_INDEX: a column outside [0, ncols); NSK_E_RANGE: a value outside
+ * [0, cardinality of the column's variable); NSK_E_INVALID: rows beyond those recorded.  A count of 0 is NSK_OK with
+ * nothing done. */
+int nsk_trace_value_autocov_counts(nsk_graph *g, int64_t first_row, int64_t nrows, int64_t max_lag,
+                                   const int64_t *sel /* nsel x 2 */, int64_t nsel, int64_t *out /* nsel x (L + 3) */);
+int nsk_trace_value_ess(nsk_graph *g, int64_t first_row, int64_t nrows, int64_t max_lag, const int64_t *sel /* nsel x 2 */,
+                        int64_t nsel, double *mean /* nsel */, double *tau, double *rhat2, uint8_t *truncated);
+int nsk_trace_value_pair_counts(nsk_graph *g, int64_t first_row, int64_t nrows, const int64_t *quads /* npairs x 4 */,
+                                int64_t npairs, int64_t *out /* npairs x chains x 3 */);
+
 /* RNG: the chromatic scan draws from Philox4x32-10 keyed by `seed`.  A variable's generator id is
  * its position in the compiled layout (nsk_graph_get_layout), so samples are a function of the seed
  * AND the layout the library chose (device, flags and diagnostic switches being equal, a graph

@@ -76,6 +76,7 @@ struct NskTrace {
     int chains = 1;                    // the handle's chain count at set-up (nsk_set_chains refuses another while it lives)
     size_t row_bytes = 0;              // one chain's share of a row
     std::vector<int64_t> pos;          // the caller's column j is device column pos[j]
+    std::vector<int32_t> card;         // ... and its variable's cardinality (the domain nsk_trace_value_* hold a value to)
     std::vector<int64_t> sweep_index;  // per recorded row: the handle's sweep index it was taken after
     double *lp = nullptr;              // the lp column (nsk_trace_log_potential): capacity x chains log-potentials, or off
     double *ws = nullptr;              // the stats column (nsk_trace_weight_stats): capacity x chains x ws_plan.ncols sums, or off

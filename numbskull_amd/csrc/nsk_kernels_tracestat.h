@@ -13,6 +13,8 @@
 // in int64 (the host refuses a call whose 4 H n^3 could reach 2^63).  The lag loops are unrolled over the compile-time
 // bound LB (15 / 31 / 63: the accumulators stay in registers); lags beyond the call's L are computed and dropped.
 // The 8 waves of a workgroup take 8 neighbouring words: the 64-byte line a row's load touches is consumed whole.
+// The counting itself -- the lag products of a tile, the fold behind a half-chain, the epilogue -- is AutocovLane, which
+// k_trace_autocov_planes (nsk_kernels_tracevalues.h: lane = one value of a categorical column) shares.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -56,38 +58,25 @@ static __device__ __forceinline__ unsigned long long transpose64(unsigned long l
     return x;
 }
 
-template <int LB, bool SUMMARY>
-__global__ __launch_bounds__(NSK_TRACESTAT_BLOCK) void k_trace_autocov(const TraceStatArgs a) {
-    const long long slot = (long long)blockIdx.x * (NSK_TRACESTAT_BLOCK / 64) + (threadIdx.x >> 6);
-    if (slot >= a.nslots) return;                       // (whole waves)
-    const int lane = (int)(threadIdx.x & 63);
-    const long long w = a.words ? (long long)a.words[slot] : slot;
-    const long long n = a.n, nb = (n + 63) >> 6, H = 2 * a.chains, row_words = a.chains * a.nwords;
-    const int m = (int)(n - ((nb - 1) << 6));           // rows of the last block: 1 .. 64
-    const long long n2 = n * n;
-
+// The counting both estimator kernels share (k_trace_autocov here, k_trace_autocov_planes of nsk_kernels_tracevalues.h):
+// a lane's series goes by as time-major 64-row words, half-chain after half-chain; `tile` takes the next word, `fold`
+// closes a half-chain, `store` writes the integers or the summary.
+template <int LB>
+struct AutocovLane {
     long long A[LB + 1];
     unsigned int c[LB + 1];
+    long long S1, S2;
+    unsigned long long prev, first;
+
+    __device__ __forceinline__ void init() {
 #pragma unroll
-    for (int k = 0; k <= LB; k++) { A[k] = 0; c[k] = 0; }
-    long long S1 = 0, S2 = 0;
+        for (int k = 0; k <= LB; k++) { A[k] = 0; c[k] = 0; }
+        S1 = S2 = 0;
+        prev = first = 0;
+    }
 
-    // row t of half-chain h (h < R: the first half of chain h; else the second half of chain h - R)
-    const auto load = [&](long long h, long long blk) -> unsigned long long {
-        const long long t = (blk << 6) + lane;
-        if (t >= n) return 0ull;
-        const long long chain = h < a.chains ? h : h - a.chains, row = (h < a.chains ? 0 : a.second) + t;
-        return a.rows[row * row_words + chain * a.nwords + w];
-    };
-
-    unsigned long long next = load(0, 0), prev = 0, first = 0;
-    long long h = 0, blk = 0;
-    for (long long it = 0; it < H * nb; it++) {
-        const unsigned long long wd = next;
-        long long h1 = h, blk1 = blk + 1;
-        if (blk1 == nb) { blk1 = 0; h1++; }
-        if (h1 < H) next = load(h1, blk1);              // (in flight while this tile is counted)
-        const unsigned long long cur = transpose64(wd, lane);
+    // block `blk` of a half-chain of n rows in nb blocks, the last of them m rows: bit i of cur is x(64 blk + i), 0 beyond row n
+    __device__ __forceinline__ void tile(const unsigned long long cur, const long long blk, const long long nb, const int m, const long long n) {
         if (blk == 0) { first = cur; prev = 0; }
         c[0] += (unsigned int)__popcll(cur);
         // (cur << k | prev >> (64 - k)) & cur in 32-bit halves: one funnel shift a half over the words prev.lo, prev.hi, cur.lo, cur.hi
@@ -100,7 +89,7 @@ __global__ __launch_bounds__(NSK_TRACESTAT_BLOCK) void k_trace_autocov(const Tra
         }
         if (blk == nb - 1) {                            // the half-chain is through: fold it
             const unsigned long long last = m == 64 ? cur : ((cur << (64 - m)) | (prev >> m));     // rows n - 64 .. n - 1 (bit 63 the last)
-            const long long S = (long long)c[0], SS = S * S, nS = n * S;
+            const long long S = (long long)c[0], SS = S * S, nS = n * S, n2 = n * n;
             S1 += S; S2 += SS;
             A[0] += n2 * S - n * SS;                    // head(0) + tail(0) = 2 S
             c[0] = 0;
@@ -112,40 +101,77 @@ __global__ __launch_bounds__(NSK_TRACESTAT_BLOCK) void k_trace_autocov(const Tra
             }
         }
         prev = cur;
-        h = h1; blk = blk1;
     }
 
-    if (!SUMMARY) {
-        long long *o = a.counts + (slot * 64 + lane) * (long long)(a.L + 3);
+    // the integers to a.counts + at * (L + 3), or the summary to element `at` of the four arrays
+    template <bool SUMMARY>
+    __device__ __forceinline__ void store(const TraceStatArgs &a, const long long at) const {
+        if (!SUMMARY) {
+            long long *o = a.counts + at * (long long)(a.L + 3);
 #pragma unroll
-        for (int k = 0; k <= LB; k++)
-            if (k <= a.L) o[k] = A[k];
-        o[a.L + 1] = S1;
-        o[a.L + 2] = S2;
-        return;
-    }
-    // The epilogue (float64, one rounded operation a step, -ffp-contract=off; diagnostics.ess_from_counts restates it)
-    const double W = (double)A[0] / a.D;
-    const double B = (double)(H * S2 - S1 * S1) / a.Bden;
-    const double V = a.c1 * W + B;
-    const bool ok = V > 0.0;
-    bool run = ok;
-    double sum = 0.0;
-#pragma unroll
-    for (int j = 0; j < (LB + 1) / 2; j++)
-        if (2 * j + 1 <= a.L) {
-            const double r0 = 1.0 - ((double)(A[0] - A[2 * j]) / a.D) / V;
-            const double r1 = 1.0 - ((double)(A[0] - A[2 * j + 1]) / a.D) / V;
-            const double P = r0 + r1;
-            if (run && P > 0.0) sum = sum + P; else run = false;
+            for (int k = 0; k <= LB; k++)
+                if (k <= a.L) o[k] = A[k];
+            o[a.L + 1] = S1;
+            o[a.L + 2] = S2;
+            return;
         }
-    const double tau = -1.0 + 2.0 * sum;
-    const double nan = __longlong_as_double(0x7ff8000000000000ll);
-    const long long col = w * 64 + lane;
-    a.mean[col] = (double)S1 / a.Hn;
-    a.tau[col] = ok && tau > 0.0 ? tau : nan;
-    a.rhat2[col] = ok ? V / W : nan;
-    a.truncated[col] = run && (long long)a.L < n - 1 ? 1 : 0;
+        // The epilogue (float64, one rounded operation a step, -ffp-contract=off; diagnostics.ess_from_counts restates it)
+        const long long H = 2 * a.chains;
+        const double W = (double)A[0] / a.D;
+        const double B = (double)(H * S2 - S1 * S1) / a.Bden;
+        const double V = a.c1 * W + B;
+        const bool ok = V > 0.0;
+        bool run = ok;
+        double sum = 0.0;
+#pragma unroll
+        for (int j = 0; j < (LB + 1) / 2; j++)
+            if (2 * j + 1 <= a.L) {
+                const double r0 = 1.0 - ((double)(A[0] - A[2 * j]) / a.D) / V;
+                const double r1 = 1.0 - ((double)(A[0] - A[2 * j + 1]) / a.D) / V;
+                const double P = r0 + r1;
+                if (run && P > 0.0) sum = sum + P; else run = false;
+            }
+        const double tau = -1.0 + 2.0 * sum;
+        const double nan = __longlong_as_double(0x7ff8000000000000ll);
+        a.mean[at] = (double)S1 / a.Hn;
+        a.tau[at] = ok && tau > 0.0 ? tau : nan;
+        a.rhat2[at] = ok ? V / W : nan;
+        a.truncated[at] = run && (long long)a.L < a.n - 1 ? 1 : 0;
+    }
+};
+
+template <int LB, bool SUMMARY>
+__global__ __launch_bounds__(NSK_TRACESTAT_BLOCK) void k_trace_autocov(const TraceStatArgs a) {
+    const long long slot = (long long)blockIdx.x * (NSK_TRACESTAT_BLOCK / 64) + (threadIdx.x >> 6);
+    if (slot >= a.nslots) return;                       // (whole waves)
+    const int lane = (int)(threadIdx.x & 63);
+    const long long w = a.words ? (long long)a.words[slot] : slot;
+    const long long n = a.n, nb = (n + 63) >> 6, H = 2 * a.chains, row_words = a.chains * a.nwords;
+    const int m = (int)(n - ((nb - 1) << 6));           // rows of the last block: 1 .. 64
+
+    AutocovLane<LB> acc;
+    acc.init();
+
+    // row t of half-chain h (h < R: the first half of chain h; else the second half of chain h - R)
+    const auto load = [&](long long h, long long blk) -> unsigned long long {
+        const long long t = (blk << 6) + lane;
+        if (t >= n) return 0ull;
+        const long long chain = h < a.chains ? h : h - a.chains, row = (h < a.chains ? 0 : a.second) + t;
+        return a.rows[row * row_words + chain * a.nwords + w];
+    };
+
+    unsigned long long next = load(0, 0);
+    long long h = 0, blk = 0;
+    for (long long it = 0; it < H * nb; it++) {
+        const unsigned long long wd = next;
+        long long h1 = h, blk1 = blk + 1;
+        if (blk1 == nb) { blk1 = 0; h1++; }
+        if (h1 < H) next = load(h1, blk1);              // (in flight while this tile is counted)
+        acc.tile(transpose64(wd, lane), blk, nb, m, n);
+        h = h1; blk = blk1;
+    }
+    if (SUMMARY) acc.template store<true>(a, w * 64 + lane);
+    else acc.template store<false>(a, slot * 64 + lane);
 }
 
 }  // namespace nsk

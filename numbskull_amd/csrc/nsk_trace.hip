@@ -51,11 +51,13 @@ int nsk_trace_setup(nsk_graph *g, const int64_t *vids, int64_t nvids, int64_t ev
     t.chains = g->nchains;
     t.packed = true;
     t.pos.resize((size_t)t.ncols);
+    t.card.resize((size_t)t.ncols);
     std::vector<int32_t> cols;
     if (vids) {
         for (int64_t j = 0; j < nvids; j++) {
             if (vids[j] < 0 || vids[j] >= c.nvar) return fail(NSK_E_INDEX, "nsk_trace_setup: variable id out of range");
             t.packed = t.packed && c.v_card[(size_t)vids[j]] == 2;
+            t.card[(size_t)j] = c.v_card[(size_t)vids[j]];
             cols.push_back(c.iid[(size_t)vids[j]]);
         }
         std::sort(cols.begin(), cols.end());            // a full-state trace reads the value array front to back
@@ -64,7 +66,7 @@ int nsk_trace_setup(nsk_graph *g, const int64_t *vids, int64_t nvids, int64_t ev
             t.pos[(size_t)j] = std::lower_bound(cols.begin(), cols.end(), c.iid[(size_t)vids[j]]) - cols.begin();
         t.ndev = (int64_t)cols.size();
     } else {                                            // every variable: the device records every internal id, no index list
-        for (int64_t v = 0; v < c.nvar; v++) { t.packed = t.packed && c.v_card[(size_t)v] == 2; t.pos[(size_t)v] = c.iid[(size_t)v]; }
+        for (int64_t v = 0; v < c.nvar; v++) { t.packed = t.packed && c.v_card[(size_t)v] == 2; t.pos[(size_t)v] = c.iid[(size_t)v]; t.card[(size_t)v] = c.v_card[(size_t)v]; }
         t.ndev = c.nid;
     }
     t.row_bytes = t.packed ? (size_t)((t.ndev + 63) / 64) * 8 : (size_t)t.ndev * (size_t)c.vbytes;

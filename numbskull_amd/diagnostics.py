@@ -31,6 +31,12 @@ estimator of ``effective_sample_size``.
 (nsk_trace_pair_counts), and ``pair_tables`` turns such counts -- the device's or numpy's -- into the 2 x 2 joint
 marginal, covariance, correlation and mutual information of every pair; ``factor_pairs`` lists the two ends of every
 pairwise factor of a graph.
+
+Categorical columns go through indicators: ``indicators(trace, sel)`` is the 0 / 1 trace of ``trace[..., column] ==
+value`` for every (column, value) of ``sel``, to which ``autocov_counts``, ``ess_from_counts`` and ``pair_counts`` apply
+unchanged -- the numpy side of ``FactorGraph.mixing_values`` and ``FactorGraph.contingency`` (nsk_trace_value_ess,
+nsk_trace_value_pair_counts) -- and ``contingency_tables`` turns the co-occurrence counts of all cells of a pair into its
+``K_a x K_b`` joint table and mutual information.
 """
 
 import collections
@@ -38,6 +44,7 @@ import collections
 import numpy as np
 
 Pairwise = collections.namedtuple("Pairwise", ["joint", "cov", "corr", "mi", "counts", "samples"])
+Contingency = collections.namedtuple("Contingency", ["joint", "mi", "counts", "samples"])
 
 _CHUNK = 256          # columns per FFT batch (memory: ~ 64 bytes x samples x chains x _CHUNK)
 
@@ -285,6 +292,91 @@ def pair_tables(counts, nrows):
         if N == 0:
             mi[:] = np.nan
     return Pairwise(joint, cov, corr, mi, c, N)
+
+
+def indicators(trace, sel):
+    """The 0 / 1 series of a categorical trace: for a ``(rows, chains, columns)`` integer array and ``sel`` of shape
+    ``(nsel, 2)`` -- (column, value) pairs; any order, repeats allowed -- the uint8 array ``(rows, chains, nsel)`` of
+    ``trace[..., column] == value``.  ``autocov_counts``, ``ess_from_counts`` and ``pair_counts`` apply to it as to any
+    0 / 1 trace: it is what nsk_trace_value_autocov_counts, nsk_trace_value_ess and nsk_trace_value_pair_counts count
+    on the device.  A value no row holds gives a column of zeros.  ValueError on a bad shape or a non-integer array,
+    IndexError on a column outside the trace."""
+    x = np.asarray(trace)
+    if x.ndim != 3 or (x.size and x.dtype.kind not in "iu"):
+        raise ValueError("a trace has shape (samples, chains, columns) and an integer type, got %r %s" % (x.shape, x.dtype))
+    s = np.asarray(sel)
+    if s.size == 0 and s.ndim <= 2:
+        return np.zeros(x.shape[:2] + (0,), np.uint8)
+    if s.ndim != 2 or s.shape[1] != 2 or s.dtype.kind not in "iu":
+        raise ValueError("indicators: sel has shape (nsel, 2) and an integer type, got %r %s" % (s.shape, s.dtype))
+    s = s.astype(np.int64)
+    if s[:, 0].min() < 0 or s[:, 0].max() >= x.shape[2]:
+        raise IndexError("indicators: a column lies outside [0, %d)" % x.shape[2])
+    return (x[:, :, s[:, 0]] == s[:, 1]).astype(np.uint8)
+
+
+def contingency_tables(counts, shapes, nrows):
+    """From the co-occurrence counts of all cells of all pairs the named tuple ``Contingency(joint, mi, counts,
+    samples)``.  ``shapes`` is ``(npairs, 2)``: the cardinalities ``(K_a, K_b)`` of every pair; ``counts`` is int64
+    ``(ncells, chains)``, the per-chain ``n11`` of the cells -- pair after pair, a pair's ``K_a x K_b`` cells in row-major
+    order (value of a, value of b), ``ncells`` the sum of ``K_a K_b`` -- over ``nrows`` rows a chain: column 0 of
+    ``pair_counts`` / nsk_trace_value_pair_counts on those cells.  With ``N = nrows x chains`` and the integers pooled
+    over the chains (int64), per pair:
+
+        joint   (K_a, K_b) float64:  float(cell) / float(N), one division a cell;
+        mi (nats):  row and column totals are int64 sums of the cells; the cells c > 0 in row-major order add
+                    (float(c) / float(N)) x log(float(c N) / float(row total x column total)) -- both products int64,
+                    one conversion each, then one rounded operation a step, the sum from 0.0 in that order
+                    (0 log 0 = 0: an empty cell adds nothing);
+        counts  the per-chain integers as (chains, K_a, K_b).
+
+    ``joint`` and ``counts`` are lists (the pairs need not share a shape), ``mi`` is an array ``(npairs,)`` and
+    ``samples`` is ``N``.  With ``N = 0`` every float is NaN.  ValueError on a bad shape, on negative counts, when a
+    pair's cells do not sum to ``nrows`` in every chain, and when ``N >= 2^31`` (``c N`` must fit int64).  The device
+    path and the numpy path both go through this function: equal counts give equal floats."""
+    c = np.asarray(counts)
+    sh = np.asarray(shapes)
+    if sh.size == 0 and sh.ndim <= 2:
+        sh = np.zeros((0, 2), np.int64)
+    if sh.ndim != 2 or sh.shape[1] != 2 or sh.dtype.kind not in "iu" or (sh.size and sh.min() < 1):
+        raise ValueError("shapes are (npairs, 2) positive integers, got %r %s" % (sh.shape, sh.dtype))
+    sh = sh.astype(np.int64)
+    ncells = int((sh[:, 0] * sh[:, 1]).sum())
+    if c.ndim != 2 or c.shape[0] != ncells or (c.size and c.dtype.kind not in "iu"):
+        raise ValueError("counts have shape (ncells, chains) = (%d, chains) and an integer type, got %r %s" % (ncells, c.shape, c.dtype))
+    c = c.astype(np.int64)
+    nrows = int(nrows)
+    if nrows < 0:
+        raise ValueError("nrows must not be negative")
+    nchains = c.shape[1]
+    N = nrows * nchains
+    if N >= 2 ** 31:
+        raise ValueError("rows x chains reaches 2^31: cell x N may not fit int64")
+    if c.size and c.min() < 0:
+        raise ValueError("not the counts of %d rows a chain" % nrows)
+    fN = np.float64(N)
+    joint, per_chain = [], []
+    mi = np.zeros(len(sh), np.float64)
+    at = 0
+    for j, (ka, kb) in enumerate(sh):
+        ka, kb = int(ka), int(kb)
+        cells = c[at:at + ka * kb].T.reshape(nchains, ka, kb)
+        at += ka * kb
+        if (cells.sum(axis=(1, 2)) != nrows).any():
+            raise ValueError("pair %d: not the counts of %d rows a chain" % (j, nrows))
+        pooled = cells.sum(axis=0)
+        rowtot, coltot = pooled.sum(axis=1), pooled.sum(axis=0)
+        with np.errstate(divide="ignore", invalid="ignore"):
+            joint.append(pooled.astype(np.float64) / fN)
+            total = np.float64(0.0)
+            for va in range(ka):
+                for vb in range(kb):
+                    cc = pooled[va, vb]
+                    if cc > 0:
+                        total = total + (np.float64(cc) / fN) * np.log(np.float64(cc * N) / np.float64(rowtot[va] * coltot[vb]))
+        mi[j] = total if N > 0 else np.nan
+        per_chain.append(cells.copy())
+    return Contingency(joint, mi, per_chain, N)
 
 
 def factor_pairs(factor, fmap):

@@ -31,6 +31,8 @@ def _all_copies(var_copy):
 
 # what FactorGraph.mixing returns, one entry per selected variable (samples: the samples the figures rest on)
 Mixing = collections.namedtuple("Mixing", ["ess", "tau", "rhat", "mean", "truncated", "samples"])
+# what FactorGraph.mixing_values returns, one entry per indicator (variable id, value)
+MixingValues = collections.namedtuple("MixingValues", ["ess", "tau", "rhat", "mean", "truncated", "samples", "var", "value", "offset"])
 
 
 def split_rhat(half_counts, n):
@@ -629,6 +631,147 @@ class FactorGraph(object):
         if measured:
             _lib.check(L.nsk_trace_setup(h, None, 0, 1, 0))
         return pair_tables(counts, rows)
+
+    def mixing_values(self, epochs, var_ids=None, indicators=None, thin=1, burnin_epochs=0, sample_evidence=False, max_lag=63):
+        """``mixing`` for categorical variables: how well every selected VALUE of every selected variable has mixed,
+        computed on the device from the trace and without downloading a row.  An indicator is a pair (variable id,
+        value); its series is the 0 / 1 sequence ``x == value``, and the figures are those of ``mixing`` for that
+        series (nsk_trace_value_ess; ``mean`` is the marginal of the value).  ``indicators`` is an ``(nind, 2)`` array
+        of (variable id, value) -- any order, repeats allowed -- or None for every value ``0 .. cardinality - 1`` of
+        every variable of ``var_ids`` in order (None = all variables); with ``indicators`` given ``var_ids`` is
+        ignored.  Runs ``inference(burnin_epochs, epochs, sample_evidence, var_copy="all")`` under a trace of the
+        distinct variables, a row after every ``thin``-th sweep.  Returns the named tuple ``MixingValues(ess, tau,
+        rhat, mean, truncated, samples, var, value, offset)``: the first five are arrays of length ``nind``,
+        ``var[i]`` and ``value[i]`` name indicator ``i``, and with ``indicators=None`` ``offset`` (length
+        ``nvars + 1``) brackets each variable's run -- variable ``j`` of the selection is indicators
+        ``offset[j] .. offset[j + 1] - 1`` -- else it is None.  NaN as in ``mixing``: one chain, fewer than 4 rows, a
+        series that never changes (a value an evidence variable holds, or one no row holds).  State, ``count``,
+        ``chain_count``, ``marginals`` and ``rhat`` come out as ``inference`` leaves them; the trace is torn down before
+        the call returns.  ValueError when every traced variable is binary (the trace would be bit-packed: ``mixing``
+        serves it), on ``thin < 1``, ``max_lag`` outside [1, 63], a bad shape and a value outside its variable's
+        domain; IndexError on a variable id out of range."""
+        epochs, thin, max_lag = int(epochs), int(thin), int(max_lag)
+        if thin < 1:
+            raise ValueError("thin must be at least 1")
+        if max_lag < 1 or max_lag > 63:
+            raise ValueError("max_lag must lie in [1, 63]")
+        nvar = self.variable.shape[0]
+        card = self.variable["cardinality"].astype(np.int64)
+        offset = None
+        if indicators is None:
+            ids = np.arange(nvar, dtype=np.int64) if var_ids is None else np.asarray(var_ids).reshape(-1)
+            if ids.size and ids.dtype.kind not in "iu":
+                raise ValueError("mixing_values: var_ids are integers")
+            ids = ids.astype(np.int64)
+            if len(ids) and (ids.min() < 0 or ids.max() >= nvar):
+                raise IndexError("mixing_values: variable id out of range")
+            offset = np.concatenate([[0], np.cumsum(card[ids])]).astype(np.int64)
+            var = np.repeat(ids, card[ids])
+            value = np.arange(offset[-1], dtype=np.int64) - np.repeat(offset[:-1], card[ids])
+        else:
+            ind = np.asarray(indicators)
+            if ind.size == 0 and ind.ndim <= 2:
+                ind = np.zeros((0, 2), np.int64)
+            if ind.ndim != 2 or ind.shape[1] != 2 or ind.dtype.kind not in "iu":
+                raise ValueError("mixing_values: indicators have shape (nind, 2) and an integer type, got %r %s" % (ind.shape, ind.dtype))
+            var, value = ind[:, 0].astype(np.int64), ind[:, 1].astype(np.int64)
+            if len(var) and (var.min() < 0 or var.max() >= nvar):
+                raise IndexError("mixing_values: variable id out of range")
+            if ((value < 0) | (value >= card[var])).any():
+                raise ValueError("mixing_values: a value lies outside its variable's domain")
+        vids, cols = np.unique(var, return_inverse=True)
+        if len(vids) and (card[vids] == 2).all():
+            raise ValueError("mixing_values: every traced variable is binary (cardinality 2): the trace would be bit-packed, use mixing")
+        nind = len(var)
+        sel = _lib.as_c(np.stack([cols.reshape(-1), value], axis=1).reshape(-1, 2), np.int64)
+        vids = _lib.as_c(vids, np.int64)
+        L, h = _lib.lib(), self._engine()
+        if burnin_epochs > 0:
+            self.burnIn(burnin_epochs, sample_evidence, var_copy="all")
+        nchains = self._chains()
+        rows = epochs // thin
+        mean, tau, rhat2 = (np.full(nind, np.nan) for _ in range(3))
+        truncated = np.zeros(nind, np.uint8)
+        measured = nchains >= 2 and rows >= 4 and nind > 0
+        if measured:
+            _lib.check(L.nsk_trace_setup(h, _lib.ptr(vids), len(vids), thin, rows))
+        try:
+            self.inference(0, epochs, sample_evidence, var_copy="all")
+            if measured:
+                _lib.check(L.nsk_trace_value_ess(h, 0, rows, max_lag, _lib.ptr(sel), nind, _lib.ptr(mean), _lib.ptr(tau), _lib.ptr(rhat2),
+                                                 _lib.ptr(truncated)))
+        except BaseException:
+            if measured:
+                L.nsk_trace_setup(h, None, 0, 1, 0)     # (its status must not replace the exception under way)
+            raise
+        if measured:
+            _lib.check(L.nsk_trace_setup(h, None, 0, 1, 0))
+        samples = 2 * (rows // 2) * nchains
+        with np.errstate(invalid="ignore"):
+            return MixingValues(samples / tau, tau, np.sqrt(rhat2), mean, truncated, samples, var, value, offset)
+
+    def contingency(self, epochs, pairs, thin=1, burnin_epochs=0, sample_evidence=False):
+        """``pairwise`` for categorical variables: the ``K_a x K_b`` joint table of pairs of variables, counted on the
+        device from the trace and without downloading a row.  ``pairs`` is as in ``pairwise``: an ``(npairs, 2)`` array
+        of variable ids (any order, repeats and ``a == b`` allowed) or ``"factors"``.  Runs
+        ``inference(burnin_epochs, epochs, sample_evidence, var_copy="all")`` under a trace of the distinct variables, a
+        row after every ``thin``-th sweep, then nsk_trace_value_pair_counts on all ``K_a x K_b`` cells of every pair
+        over the ``epochs // thin`` rows.  Returns ``diagnostics.contingency_tables`` of the counts, the named tuple
+        ``Contingency(joint, mi, counts, samples)``: per pair the table ``joint[j][value of a][value of b]`` (a list;
+        chains pooled), mutual information in nats, the per-chain integers ``(chains, K_a, K_b)`` and
+        ``samples = rows x chains``.  With zero rows or zero pairs no trace is set up.  State, ``count``,
+        ``chain_count``, ``marginals`` and ``rhat`` come out as ``inference`` leaves them; the trace is torn down before
+        the call returns.  ValueError when every variable involved is binary (the trace would be bit-packed:
+        ``pairwise`` serves it), on ``thin < 1`` and on a bad shape; IndexError on an id out of range."""
+        from .diagnostics import contingency_tables, factor_pairs
+        epochs, thin = int(epochs), int(thin)
+        if thin < 1:
+            raise ValueError("thin must be at least 1")
+        if isinstance(pairs, str):
+            if pairs != "factors":
+                raise ValueError('contingency: pairs is an (npairs, 2) array of variable ids or "factors"')
+            pairs = factor_pairs(self.factor, self.fmap)
+        pairs = np.asarray(pairs)
+        if pairs.size == 0 and pairs.ndim <= 2:
+            pairs = np.zeros((0, 2), np.int64)
+        if pairs.ndim != 2 or pairs.shape[1] != 2 or pairs.dtype.kind not in "iu":
+            raise ValueError("contingency: pairs have shape (npairs, 2) and an integer type, got %r %s" % (pairs.shape, pairs.dtype))
+        pairs = pairs.astype(np.int64)
+        if len(pairs) and (pairs.min() < 0 or pairs.max() >= self.variable.shape[0]):
+            raise IndexError("contingency: variable id out of range")
+        card = self.variable["cardinality"].astype(np.int64)
+        vids, cols = np.unique(pairs, return_inverse=True)
+        if len(vids) and (card[vids] == 2).all():
+            raise ValueError("contingency: every variable involved is binary (cardinality 2): the trace would be bit-packed, use pairwise")
+        cols = cols.reshape(-1, 2)
+        shapes = card[pairs].reshape(-1, 2)
+        # all cells of every pair, a pair's in row-major order (value of a, value of b)
+        ncell = shapes[:, 0] * shapes[:, 1]
+        pair_of = np.repeat(np.arange(len(pairs)), ncell)
+        within = np.arange(int(ncell.sum()), dtype=np.int64) - np.repeat(np.cumsum(ncell) - ncell, ncell)
+        kb = shapes[pair_of, 1]
+        quads = _lib.as_c(np.stack([cols[pair_of, 0], within // kb, cols[pair_of, 1], within % kb], axis=1).reshape(-1, 4), np.int64)
+        vids = _lib.as_c(vids, np.int64)
+        L, h = _lib.lib(), self._engine()
+        if burnin_epochs > 0:
+            self.burnIn(burnin_epochs, sample_evidence, var_copy="all")
+        nchains = self._chains()
+        rows = epochs // thin
+        counts = np.zeros((len(quads), nchains, 3), np.int64)
+        measured = rows > 0 and len(quads) > 0
+        if measured:
+            _lib.check(L.nsk_trace_setup(h, _lib.ptr(vids), len(vids), thin, rows))
+        try:
+            self.inference(0, epochs, sample_evidence, var_copy="all")
+            if measured:
+                _lib.check(L.nsk_trace_value_pair_counts(h, 0, rows, _lib.ptr(quads), len(quads), _lib.ptr(counts)))
+        except BaseException:
+            if measured:
+                L.nsk_trace_setup(h, None, 0, 1, 0)     # (its status must not replace the exception under way)
+            raise
+        if measured:
+            _lib.check(L.nsk_trace_setup(h, None, 0, 1, 0))
+        return contingency_tables(counts[:, :, 0], shapes, rows)
 
     # ------------------------------------------------------------------ per-weight statistics
     def weight_statistics(self, var_copy=0, evidence_chain=False, feature_scaled=False):
