@@ -453,7 +453,7 @@ static inline int nsk_tab_grid(int vtiles) {
 static inline int nsk_tabw_grid(int vtiles) {
     const int nquads = vtiles / 4, ntrips = nquads + 8;                     // (+ 8: every XCD's share rounds up)
     const int need = std::max(8, 8 * ((((ntrips + 3) / 4) + 7) / 8));
-    const char *cap_env = nsk::diag_env("NSK_TABW_GRID_CAP");               // (diagnostic)
+    const char *cap_env = nsk::diag_env("NSK_TABW_GRID_CAP");               // (diagnostic; read per launch so that tests can set it)
     const int cap = cap_env ? std::max(8, std::abs(atoi(cap_env)) & ~7) : 256 * NSK_TABW_PER_CU;
     return std::min(cap, need);
 }
@@ -495,7 +495,7 @@ static inline int nsk_tabw_front_blocks(uint32_t nrest) { return (int)((nrest + 
 static inline int nsk_learn_tabw_grid(int vtiles) {
     const int nquads = vtiles / 4 + 8;
     const int need = std::max(8, 8 * ((((nquads + 3) / 4) + 7) / 8));
-    const char *cap_env = nsk::diag_env("NSK_LEARN_TABW_GRID_CAP");         // (diagnostic)
+    const char *cap_env = nsk::diag_env("NSK_LEARN_TABW_GRID_CAP");         // (diagnostic; read per launch so that tests can set it)
     const int cap = cap_env ? std::max(8, std::abs(atoi(cap_env)) & ~7) : (nquads >= 40000 ? 2048 : 1024);
     return std::min(cap, need);
 }
