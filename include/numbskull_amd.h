@@ -130,7 +130,8 @@ int nsk_chains_download(nsk_graph *g, int64_t *var_value, int64_t *count);
  * elements of value_bytes (int8_t or int32_t, as NSK_BUF_VALUE) in the caller's column order, unpacked;
  * sweep_index[i] (may be NULL) = the handle's sweep index after which row first_row + i was taken.  Rows beyond
  * those recorded: NSK_E_INVALID.
- * nsk_trace_clear: rows and the count of sweeps since the last row back to 0; the buffer stays.
+ * nsk_trace_clear: rows and the count of sweeps since the last row back to 0; the buffer stays (and the accumulators of
+ * nsk_trace_conditionals are zeroed).
  * A handle with a trace refuses, before it enqueues anything: a nsk_gibbs_sweeps call that needs more rows than
  * are left (NSK_E_RANGE; state and sweeps_done untouched), sweeps while values lie outside their domains and the
  * rows are bit-packed (NSK_E_RANGE), and with NSK_E_INVALID nsk_learn_sweeps, sweeps under the sequential scan,
@@ -203,6 +204,46 @@ int nsk_weight_stats(nsk_graph *g, int which, int64_t first_chain, int64_t nchai
 int nsk_trace_weight_stats(nsk_graph *g, const int64_t *wids, int64_t nwids, int scaled);
 int nsk_trace_download_weight_stats(nsk_graph *g, int64_t first_row, int64_t nrows,
                                     double *out /* nrows x chains x nwids */);
+
+/* Per-variable conditionals (FactorGraph.conditionals / log_pseudo_likelihood / rao_blackwell): the distribution the
+ * sampler draws variable v from, P(x_v = k | every other variable), for the variables of a selection.  For a variable
+ * of cardinality C that has a position in the compiled layout (every owned variable with isEvidence != 4) and a state x:
+ *   potentials     p_k = potential(v, k, x), k = 0 .. C - 1: the reference's potential() with v hypothetically at k --
+ *                  the walk of the factor list of (v, k) (one list for dataType 0), every term one rounded product
+ *                  weight * eval_factor, added in list order, head quirks as the sampler sees them; the doubles the
+ *                  sweep kernels exponentiate;
+ *   probabilities  e_k = exp(p_k) by the library's specified exp, unshifted; Z the running sum
+ *                  e_0, Z + e_1, ... in k order; P_k = e_k / Z, one IEEE float64 division.  Where Z is 0, infinite or
+ *                  NaN the result is whatever IEEE gives: the sampler's own degenerate case.
+ * Layout ("full"): selected variable i owns C_i consecutive doubles at off_i = the sum of C_j over j < i, in the
+ * caller's order (a binary variable owns 2); total = the sum of all C_i.  A variable without a position reads NaN in all
+ * its slots.  vids = the caller's variable ids, any order, repeats allowed; NULL with nvids = 0 = all nvar variables;
+ * an id outside [0, nvar) is NSK_E_INDEX; NULL with another count, or a negative count: NSK_E_INVALID.
+ * One lane per selected variable (the host sorts the selection by position and drops repeats, and scatters the results
+ * back into the caller's order); every double is a function of graph, weights and state only.
+ * nsk_conditionals: out[i * total + off_j + k] for chain first_chain + i; what = 0 potentials, 1 probabilities, anything
+ * else NSK_E_INVALID.  `which`, the chains, the handles refused (NSK_E_INVALID) and reading without changing anything
+ * follow nsk_log_potential rule for rule; the sequential scan is fine.  nvids == 0 with a list, or total == 0, is NSK_OK
+ * with nothing done.  The first call uploads what potential() reads and the handle's kernels do not: the lists (4 bytes a
+ * position, 4 a list slot + 4, 4 a list entry) and the records nsk_log_potential shares (16 bytes a factor, 8 an edge,
+ * 4 a variable, 4 more with literal heads) -- kept, in nsk_graph_info.device_bytes; the selection (12 bytes a
+ * variable) and chains x total doubles live for the call only.  NSK_E_NOMEM names the size of what does not fit.  A
+ * handle that never calls them allocates and launches nothing for them.
+ * nsk_trace_conditionals: Rao-Blackwell accumulators.  Valid while a trace is set up (NSK_E_INVALID otherwise);
+ * allocates the selection and chains x total doubles, zeroed, and from then on every record launch is followed on the
+ * stream by ONE launch that adds the probabilities of the state just recorded to them, S = S + P_k, every chain,
+ * whatever columns the trace keeps: one lane owns a sum and adds once per row, in row order, so a sum equals the
+ * sequential sum of the per-row probabilities bit for bit.  Calling it again replaces the selection and zeroes the
+ * sums (a call refused for its arguments leaves the old ones); nvids < 0 switches it off and frees them;
+ * nsk_trace_setup (replace or tear down) resets it to off; nsk_trace_clear ZEROES the sums and their row count -- unlike
+ * the lp and stats columns, which it keeps: those are per row and have nothing to zero.
+ * nsk_trace_download_conditionals: synchronises, then writes chains x total sums in the caller's order and *rows (may
+ * be NULL) = the rows added since the selection was set or cleared; sums / rows estimates the marginals.
+ * NSK_E_INVALID without a selection.  nsk_profile_* keeps counting sweep-kernel launches only. */
+int nsk_conditionals(nsk_graph *g, int which, int64_t first_chain, int64_t nchains, const int64_t *vids, int64_t nvids,
+                     int what, double *out /* nchains x total */);
+int nsk_trace_conditionals(nsk_graph *g, const int64_t *vids, int64_t nvids);
+int nsk_trace_download_conditionals(nsk_graph *g, double *sums /* chains x total */, int64_t *rows);
 
 /* Effective sample size from the trace, on the device (FactorGraph.mixing): per column of a BIT-PACKED trace, the
  * split-chain estimator of numbskull_amd.diagnostics.effective_sample_size with the lags cut at max_lag, in one

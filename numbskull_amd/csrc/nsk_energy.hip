@@ -107,6 +107,34 @@ static int64_t energy_check_factors(const nsk_graph *g, bool *literal_out) {
     return bad;
 }
 
+// The factor and member records, the cardinalities and -- `literal`: a factor the caller evaluates reads its head at the
+// literal edge index -- the internal ids, each where the handle lacks it (nsk_ensure_generic uploads the same arrays and
+// takes these when it runs later); all of them or none
+int nsk_records_ensure(nsk_graph *g, bool literal, const char *what) {
+    Compiled &c = g->c;
+    uint32_t *f_rec = nullptr;
+    int32_t *m_rec = nullptr, *v_card = nullptr, *iid = nullptr;
+    NskRollback rb(g->mem, nsk_free_raw);
+    int rc = NSK_OK;
+    if (!g->f_rec) rc = dev_upload(g, &f_rec, c.f_rec);
+    if (!rc && !g->m_rec) rc = dev_upload(g, &m_rec, c.m_rec);
+    if (!rc && !g->v_card) rc = dev_upload(g, &v_card, c.v_card_i);
+    if (!rc && literal && !g->iid_of_vid && !g->xfer_iid) rc = dev_upload(g, &iid, c.iid);
+    if (!rc && hipStreamSynchronize(g->stream) != hipSuccess) rc = fail(NSK_E_DEVICE, "hipStreamSynchronize failed");
+    if (rc) {
+        if (rc != NSK_E_NOMEM) return rc;
+        const double mb = ((double)c.f_rec.size() * 4 + (double)c.m_rec.size() * 4 + (double)c.v_card_i.size() * 4) / 1048576.0;
+        return fail(NSK_E_NOMEM, std::string(what) + ": the factor and member records the evaluation reads (" +
+                                 std::to_string((long long)mb) + " MB) do not fit on the device");
+    }
+    rb.commit();
+    if (f_rec) g->f_rec = f_rec;
+    if (m_rec) g->m_rec = m_rec;
+    if (v_card) g->v_card = v_card;
+    if (literal && !g->iid_of_vid) g->iid_of_vid = iid ? iid : g->xfer_iid;     // (the state transfers hold the same table)
+    return NSK_OK;
+}
+
 // The arrays of the walk and the partial sums for `chains` chains, at the first use (and when more chains ask)
 int energy_ensure(nsk_graph *g, int chains, const char *what) {
     NskEnergy &en = g->energy;
@@ -118,26 +146,7 @@ int energy_ensure(nsk_graph *g, int chains, const char *what) {
         if (bad >= 0)
             return fail(NSK_E_INVALID, std::string(what) + ": factor " + std::to_string(bad) + ", which no sampled variable reaches, cannot be "
                                        "evaluated (unknown function, or a weight, member or head index outside the arrays)");
-        uint32_t *f_rec = nullptr;
-        int32_t *m_rec = nullptr, *v_card = nullptr, *iid = nullptr;
-        NskRollback rb(g->mem, nsk_free_raw);
-        int rc = NSK_OK;
-        if (!g->f_rec) rc = dev_upload(g, &f_rec, c.f_rec);
-        if (!rc && !g->m_rec) rc = dev_upload(g, &m_rec, c.m_rec);
-        if (!rc && !g->v_card) rc = dev_upload(g, &v_card, c.v_card_i);
-        if (!rc && literal && !g->iid_of_vid && !g->xfer_iid) rc = dev_upload(g, &iid, c.iid);
-        if (!rc && hipStreamSynchronize(g->stream) != hipSuccess) rc = fail(NSK_E_DEVICE, "hipStreamSynchronize failed");
-        if (rc) {
-            if (rc != NSK_E_NOMEM) return rc;
-            const double mb = ((double)c.f_rec.size() * 4 + (double)c.m_rec.size() * 4 + (double)c.v_card_i.size() * 4) / 1048576.0;
-            return fail(NSK_E_NOMEM, std::string(what) + ": the factor and member records the evaluation reads (" +
-                                     std::to_string((long long)mb) + " MB) do not fit on the device");
-        }
-        rb.commit();
-        if (f_rec) g->f_rec = f_rec;
-        if (m_rec) g->m_rec = m_rec;
-        if (v_card) g->v_card = v_card;
-        if (literal && !g->iid_of_vid) g->iid_of_vid = iid ? iid : g->xfer_iid;     // (the state transfers hold the same table)
+        if (int rc = nsk_records_ensure(g, literal, what)) return rc;
         en.ready = true;
     }
     if (chains > en.chains) {

@@ -1,7 +1,7 @@
 // nsk_internal.h -- host-side state of a compiled graph handle, shared by the translation units of
 // the library (nsk_api.hip: C-ABI, state sync; nsk_exchange.hip: the multi-GPU boundary exchange; nsk_gibbs.hip /
-// nsk_learn.hip: the sweep drivers of numbskull/factorgraph.py:141,163,202; nsk_trace.hip, nsk_energy.hip, nsk_wstats.hip:
-// the diagnostics).
+// nsk_learn.hip: the sweep drivers of numbskull/factorgraph.py:141,163,202; nsk_trace.hip, nsk_energy.hip, nsk_wstats.hip,
+// nsk_cond.hip: the diagnostics).
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -62,6 +62,23 @@ struct NskWstats {
     int result_chains = 0;
 };
 
+// A selection of variables for the conditionals (nsk_conditionals / nsk_trace_conditionals; nsk_cond.hip): the caller's
+// columns in the caller's order ("full" layout: column j owns card[j] doubles at off[j]) and the device's -- the
+// positions of the selected variables that have one, ascending, without repeats; device column i owns the doubles
+// [doff[i], doff[i + 1]) of a chain's device output.  col[j] = the device column of caller column j, -1: the variable
+// has no position (it reads NaN).
+struct NskCondSel {
+    std::vector<int64_t> off, col;     // [ncols + 1], [ncols]
+    std::vector<int32_t> sel;          // [ndev] positions
+    std::vector<long long> doff;       // [ndev + 1]
+    int32_t *d_sel = nullptr;          // device copies of sel and doff (nsk_cond_sel_upload)
+    long long *d_off = nullptr;
+    int64_t ncols() const { return (int64_t)col.size(); }
+    int64_t total() const { return off.empty() ? 0 : off.back(); }
+    int64_t ndev() const { return (int64_t)sel.size(); }
+    int64_t dtotal() const { return doff.empty() ? 0 : (int64_t)doff.back(); }
+};
+
 // Sample trace (nsk_trace_setup): thinned joint samples recorded on the device.  After every `every`-th tallied sweep
 // one k_trace_record_* launch appends a row: for every chain the values of the traced variables, in DEVICE column order
 // (sorted by internal id; every internal id when cols == nullptr, "all variables") -- bit-packed, ceil(ndev / 64) words a
@@ -82,6 +99,9 @@ struct NskTrace {
     double *ws = nullptr;              // the stats column (nsk_trace_weight_stats): capacity x chains x ws_plan.ncols sums, or off
     NskWstatsPlan ws_plan;             // ... the work list of its selection
     bool ws_scaled = false;
+    double *cond = nullptr;            // the accumulators (nsk_trace_conditionals): chains x cond_sel.dtotal() sums of probabilities, or off
+    NskCondSel cond_sel;               // ... their selection
+    int64_t cond_rows = 0;             // ... and the rows added to them since the selection was set or cleared
 };
 
 // Log-potential (nsk_log_potential / nsk_factor_values / the trace's lp column): the factor walk of nsk_kernels_energy.h
@@ -531,6 +551,11 @@ void wstats_plan_free(nsk_graph *g, NskWstatsPlan &plan);      // nsk_wstats.hip
 // the handles the diagnostics serve (whole graph, no exchange); the arrays of the factor walk at the first use (nsk_energy.hip)
 int energy_whole_graph(const nsk_graph *g, const char *what);
 int energy_ensure(nsk_graph *g, int chains, const char *what);
+// ... its part that the conditionals share: f_rec, m_rec, v_card and, with `literal`, iid_of_vid, where the handle lacks them
+int nsk_records_ensure(nsk_graph *g, bool literal, const char *what);
+// the accumulators of a sample trace: sums[r * sel.dtotal() + ..] += the conditionals of chain r at `val`, one launch (nsk_cond.hip)
+int nsk_cond_accumulate(nsk_graph *g, const NskCondSel &sel, const void *val, int nchains, bool packed_bytes, double *sums);
+void nsk_cond_sel_free(nsk_graph *g, NskCondSel &sel);      // the device copies of a selection (the trace's goes with the trace)
 namespace nsk { struct EnergyArgs; }
 nsk::EnergyArgs energy_args(const nsk_graph *g);
 // the log-potential of `nchains` chains from `val` on / every factor's value, enqueued on the handle's stream (nsk_energy.hip)

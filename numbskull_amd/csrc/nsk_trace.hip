@@ -1,5 +1,6 @@
 // nsk_trace.hip -- the sample trace (nsk_internal.h NskTrace): set-up, the record launch behind a tallied sweep (called by
-// nsk_gibbs_sweeps where a row is due), download.  Its lp column lives in nsk_energy.hip, its stats column in nsk_wstats.hip.
+// nsk_gibbs_sweeps where a row is due), download.  Its lp column lives in nsk_energy.hip, its stats column in nsk_wstats.hip,
+// its accumulators of conditionals in nsk_cond.hip.
 #include <hip/hip_runtime.h>
 
 #include "nsk_internal.h"
@@ -30,6 +31,8 @@ static void trace_free(nsk_graph *g) {
     dev_free(g, t.lp);
     dev_free(g, t.ws);
     wstats_plan_free(g, t.ws_plan);
+    dev_free(g, t.cond);
+    nsk_cond_sel_free(g, t.cond_sel);
     t = NskTrace();
 }
 
@@ -104,6 +107,11 @@ int nsk_trace_clear(nsk_graph *g) {
     if (g->trace.capacity == 0) return fail(NSK_E_INVALID, "nsk_trace_clear: no trace is set up");
     g->trace.rows = g->trace.phase = 0;
     g->trace.sweep_index.clear();
+    if (g->trace.cond) {    // the accumulators start over (behind the launches that still add to them)
+        HIPCHECK(hipSetDevice(g->device));
+        HIPCHECK(hipMemsetAsync(g->trace.cond, 0, std::max<size_t>(1, (size_t)g->trace.chains * (size_t)g->trace.cond_sel.dtotal()) * sizeof(double), g->stream));
+        g->trace.cond_rows = 0;
+    }
     return NSK_OK;
 }
 
@@ -162,6 +170,11 @@ int nsk_trace_record(nsk_graph *g) {
         const size_t row = (size_t)t.chains * (size_t)t.ws_plan.ncols;
         int rc = nsk_wstats_enqueue(g, t.ws_plan, g->val, t.chains, g->packed_sweeps > 0, t.ws_scaled, t.ws + (size_t)t.rows * row, t.ws_plan.ncols);
         if (rc) return rc;
+    }
+    if (t.cond) {   // the accumulators: likewise, the conditionals of their selection added to the sums
+        int rc = nsk_cond_accumulate(g, t.cond_sel, g->val, t.chains, g->packed_sweeps > 0, t.cond);
+        if (rc) return rc;
+        t.cond_rows++;
     }
     t.sweep_index.push_back((int64_t)g->sweep);
     t.rows++;

@@ -37,6 +37,12 @@ value`` for every (column, value) of ``sel``, to which ``autocov_counts``, ``ess
 unchanged -- the numpy side of ``FactorGraph.mixing_values`` and ``FactorGraph.contingency`` (nsk_trace_value_ess,
 nsk_trace_value_pair_counts) -- and ``contingency_tables`` turns the co-occurrence counts of all cells of a pair into its
 ``K_a x K_b`` joint table and mutual information.
+
+``conditional_probabilities`` restates what ``FactorGraph.conditionals`` computes on the device from the potentials of
+every value of a variable (nsk_conditionals), ``log_pseudo_likelihood`` sums the logs of those
+conditionals at a state's own values, and ``tally_layout`` brings the "full" layout of both (every variable owns
+``cardinality`` slots) to the layout of ``count`` / ``marginals`` (a binary variable owns one), so that the Rao-Blackwell
+marginals of ``FactorGraph.rao_blackwell`` can be compared with the tally's.
 """
 
 import collections
@@ -420,3 +426,76 @@ def moment_gap(stats, target):
         mcse = sd / np.sqrt(ess)
     mcse[~(sd > 0)] = np.nan
     return gap, mcse
+
+
+def _full_layout(offsets, x, what):
+    off = np.asarray(offsets)
+    if off.ndim != 1 or len(off) < 1 or off.dtype.kind not in "iu" or off[0] != 0 or (np.diff(off) < 1).any():
+        raise ValueError("%s: offsets are int64 (nsel + 1,), start at 0 and grow by each variable's cardinality" % what)
+    off = off.astype(np.int64)
+    x = np.asarray(x, np.float64)
+    if x.ndim < 1 or x.shape[-1] != off[-1]:
+        raise ValueError("%s: the last axis has offsets[-1] = %d entries, got shape %r" % (what, off[-1], x.shape))
+    return off, x
+
+
+def conditional_probabilities(offsets, potentials, exp=np.exp):
+    """The conditionals of ``FactorGraph.conditionals(potentials=True)`` output: ``potentials`` (..., total) holds, for
+    selected variable ``i``, the potentials ``p_k`` of its values ``k`` at ``offsets[i] + k``.  ``e_k = exp(p_k)``,
+    unshifted; ``Z`` is the running sum ``e_0, Z + e_1, ...`` in ``k`` order; ``P_k = e_k / Z`` -- the operations of the
+    device, one rounded float64 operation each, so with ``exp`` the library's specified exponential (the oracle's
+    ``exp_det``) the result equals ``FactorGraph.conditionals()`` bit for bit; ``np.exp`` may differ in the last place.
+    Where ``Z`` is 0, infinite or NaN the result is what IEEE gives (the sampler's own degenerate case), and the NaN
+    slots of a variable without a position stay NaN."""
+    off, p = _full_layout(offsets, potentials, "conditional_probabilities")
+    card = np.diff(off)
+    e = np.asarray(exp(p), np.float64).reshape(p.shape)
+    z = np.zeros(p.shape[:-1] + (len(card),))
+    for k in range(int(card.max()) if len(card) else 0):
+        m = card > k
+        ek = e[..., off[:-1][m] + k]
+        z[..., m] = ek if k == 0 else z[..., m] + ek
+    with np.errstate(divide="ignore", invalid="ignore"):
+        return e / np.repeat(z, card, axis=-1)
+
+
+def log_pseudo_likelihood(offsets, potentials, values):
+    """The log-pseudo-likelihood of a state from the potentials of ``FactorGraph.conditionals(potentials=True)``: the
+    sum over the selected variables ``v`` of ``log P(x_v | the others) = p_{x_v} - m_v - log(sum_k exp(p_k - m_v))``,
+    ``m_v`` the variable's largest potential (the shift keeps the sum finite where the unshifted conditional
+    overflows).  ``values`` (..., nsel) holds each selected variable's own value; ``potentials`` is (..., total).  Returns
+    a float, or an array over the leading axes.  NaN when a selected variable has no position (its potentials are NaN);
+    ValueError when a value lies outside its variable's domain."""
+    off, p = _full_layout(offsets, potentials, "log_pseudo_likelihood")
+    card = np.diff(off)
+    x = np.asarray(values)
+    if x.ndim < 1 or x.shape[-1] != len(card) or (x.size and x.dtype.kind not in "iu"):
+        raise ValueError("log_pseudo_likelihood: values are integers (..., nsel) = (..., %d), got %r %s" % (len(card), x.shape, x.dtype))
+    x = x.astype(np.int64)
+    if ((x < 0) | (x >= card)).any():
+        raise ValueError("log_pseudo_likelihood: a value lies outside its variable's domain")
+    lead = np.broadcast_shapes(p.shape[:-1], x.shape[:-1])
+    p = np.broadcast_to(p, lead + p.shape[-1:])
+    x = np.broadcast_to(x, lead + x.shape[-1:])
+    if len(card) == 0:
+        out = np.zeros(lead)
+    else:
+        m = np.maximum.reduceat(p, off[:-1], axis=-1)
+        with np.errstate(invalid="ignore"):
+            s = np.add.reduceat(np.exp(p - np.repeat(m, card, axis=-1)), off[:-1], axis=-1)
+            own = np.take_along_axis(p, off[:-1] + x, axis=-1)
+            out = (own - m - np.log(s)).sum(axis=-1)
+    return float(out) if out.ndim == 0 else out
+
+
+def tally_layout(offsets, values):
+    """``(tally_offsets, tally_values)``: the "full" layout of ``FactorGraph.conditionals`` / ``rao_blackwell`` (every
+    variable owns ``cardinality`` slots) brought to the layout of ``count`` / ``marginals`` / ``cstart``: the value-0 slot
+    of every binary variable dropped, so that it owns ONE slot, the probability of value 1.  With ``var_ids=None``
+    ``tally_offsets`` equals ``FactorGraph.cstart`` and ``tally_values`` lines up with ``count``."""
+    off, v = _full_layout(offsets, values, "tally_layout")
+    card = np.diff(off)
+    keep = np.ones(int(off[-1]), bool)
+    keep[off[:-1][card == 2]] = False
+    toff = np.concatenate([[0], np.cumsum(np.where(card == 2, 1, card))]).astype(np.int64)
+    return toff, v[..., keep]

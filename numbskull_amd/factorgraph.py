@@ -773,6 +773,124 @@ class FactorGraph(object):
             _lib.check(L.nsk_trace_setup(h, None, 0, 1, 0))
         return contingency_tables(counts[:, :, 0], shapes, rows)
 
+    # ------------------------------------------------------------------ conditionals
+    def _cond_selection(self, var_ids, default, what):
+        """(ids or None for all variables, offsets of the "full" layout); argument errors before any device work."""
+        nvar = self.variable.shape[0]
+        card = self.variable["cardinality"].astype(np.int64)
+        if var_ids is None and default is None:
+            return None, np.concatenate([[0], np.cumsum(card)]).astype(np.int64)
+        ids = np.asarray(default if var_ids is None else var_ids)
+        if ids.ndim != 1 or (ids.size and ids.dtype.kind not in "iu"):
+            raise ValueError("%s: var_ids is a one-dimensional list of integer variable ids, got %r %s" % (what, ids.shape, ids.dtype))
+        ids = _lib.as_c(ids, np.int64)
+        if len(ids) and (ids.min() < 0 or ids.max() >= nvar):
+            raise IndexError("%s: variable id out of range" % what)
+        return ids, np.concatenate([[0], np.cumsum(card[ids])]).astype(np.int64)
+
+    def conditionals(self, var_ids=None, var_copy=0, weight_copy=0, evidence_chain=False, potentials=False):
+        """The distribution the sampler draws each selected variable from, ``P(x_v = k | every other variable)``, evaluated
+        on the device (nsk_conditionals).  ``var_ids``: variable ids, any order, repeats allowed; None = all.  Returns
+        ``(offsets, values)``: int64 ``(nsel + 1,)`` and float64 ``(total,)`` -- selected variable ``i`` owns the
+        ``cardinality`` entries ``values[offsets[i] : offsets[i + 1]]``, one per value (a binary variable owns 2;
+        ``diagnostics.tally_layout`` converts to the layout of ``count``).  ``potentials=True`` returns the potentials
+        ``p_k`` the sampler exponentiates instead of the probabilities ``exp(p_k) / sum_j exp(p_j)``
+        (``diagnostics.conditional_probabilities`` turns one into the other).  The state is ``var_value[var_copy]`` --
+        ``var_value_evid[var_copy]`` with ``evidence_chain=True`` -- under ``weight_value[weight_copy]``, pushed as
+        ``log_potential`` pushes them; ``var_copy="all"`` gives ``(chains, total)``.  A variable this handle does not
+        sample (``isEvidence == 4``) reads NaN.  The sums are unshifted, as the sampler's: potentials beyond exp's range
+        give what IEEE gives (inf / inf = NaN)."""
+        ids, offsets = self._cond_selection(var_ids, None, "conditionals")
+        if _all_copies(var_copy) and evidence_chain:
+            raise ValueError('the evidence chain exists once: var_copy="all" is for the free chains')
+        total = int(offsets[-1])
+        if total == 0:
+            return offsets, np.zeros((self.var_value.shape[0], 0) if _all_copies(var_copy) else 0, np.float64)
+        L, h = _lib.lib(), self._engine()
+        what = 0 if potentials else 1
+        nsel = 0 if ids is None else len(ids)
+        if _all_copies(var_copy):
+            nchains = self._push_chains(weight_copy, count=False)
+            out = np.zeros((nchains, total), np.float64)
+            _lib.check(L.nsk_conditionals(h, _lib.BUF_VALUE, 0, nchains, _lib.ptr(ids), nsel, what, _lib.ptr(out)))
+            return offsets, out
+        self._push(var_copy, weight_copy)
+        out = np.zeros(total, np.float64)
+        _lib.check(L.nsk_conditionals(h, _lib.BUF_VALUE_EVID if evidence_chain else _lib.BUF_VALUE, 0, 1, _lib.ptr(ids), nsel, what,
+                                      _lib.ptr(out)))
+        return offsets, out
+
+    def log_pseudo_likelihood(self, var_ids=None, var_copy=0, weight_copy=0, evidence_chain=False):
+        """The log-pseudo-likelihood of a state: the sum over the selected variables (None = those with
+        ``isEvidence == 0``) of ``log P(x_v | every other variable)`` at the variable's own value -- the usual cheap score
+        for comparing weight vectors where no enumeration reaches.  The potentials come from the device
+        (``conditionals(potentials=True)``); the logarithms are taken on the host
+        (``diagnostics.log_pseudo_likelihood``, shifted by each variable's largest potential).  Returns a float;
+        ``var_copy="all"`` a float64 array with one entry per row of ``var_value``."""
+        default = np.nonzero(self.variable["isEvidence"] == 0)[0] if var_ids is None else None
+        ids, _ = self._cond_selection(var_ids, default, "log_pseudo_likelihood")
+        if _all_copies(var_copy) and evidence_chain:
+            raise ValueError('the evidence chain exists once: var_copy="all" is for the free chains')
+        from .diagnostics import log_pseudo_likelihood
+        offsets, pot = self.conditionals(ids, var_copy, weight_copy, evidence_chain, potentials=True)
+        if _all_copies(var_copy):
+            values = np.asarray(self.var_value)[:, ids]
+        else:
+            values = np.asarray((self.var_value_evid if evidence_chain else self.var_value)[var_copy])[ids]
+        return log_pseudo_likelihood(offsets, pot, values.astype(np.int64))
+
+    def rao_blackwell(self, epochs, var_ids=None, thin=1, burnin_epochs=0, sample_evidence=False):
+        """Rao-Blackwellised marginals: ``inference(burnin_epochs, epochs, sample_evidence, var_copy="all")`` -- one chain
+        per row of ``var_value``; one chain is fine -- during which, after every ``thin``-th tallied sweep, the device adds
+        the conditionals ``P(x_v = k | the others)`` of every selected variable in every chain's state to running sums
+        (nsk_trace_conditionals; no row leaves the device).  Their average estimates the same marginals as
+        ``count / epochs`` at lower variance for the same sweeps.  ``var_ids``: variable ids, any order, repeats allowed;
+        None = the variables the call samples.  Returns a dict: ``offsets`` (the layout of ``conditionals``),
+        ``per_chain`` ``(chains, total)`` = sums / rows, ``marginals`` ``(total,)`` their mean over chains, ``stderr`` the
+        standard deviation over chains divided by ``sqrt(chains)`` (NaN with one chain), ``rows = epochs // thin``.
+        With zero rows or an empty selection the figures are NaN and no trace is set up.  State, ``count``,
+        ``chain_count``, ``marginals`` and ``rhat`` come out as ``inference`` leaves them; the trace is torn down before
+        the call returns."""
+        epochs, thin = int(epochs), int(thin)
+        if thin < 1:
+            raise ValueError("thin must be at least 1")
+        if epochs < 0:
+            raise ValueError("epochs must not be negative")
+        default = None
+        if var_ids is None:
+            ev = self.variable["isEvidence"]
+            default = np.nonzero((ev != 4) if sample_evidence else (ev == 0))[0]
+        ids, offsets = self._cond_selection(var_ids, default, "rao_blackwell")
+        total = int(offsets[-1])
+        L, h = _lib.lib(), self._engine()
+        if burnin_epochs > 0:
+            self.burnIn(burnin_epochs, sample_evidence, var_copy="all")
+        nchains = self._chains()
+        rows = epochs // thin
+        sums = np.full((nchains, total), np.nan)
+        got = C.c_int64(0)
+        measured = rows > 0 and total > 0
+        if measured:
+            first = _lib.as_c(np.zeros(1), np.int64)            # the accumulators ride on a one-column trace
+            _lib.check(L.nsk_trace_setup(h, _lib.ptr(first), 1, thin, rows))
+        try:
+            if measured:
+                _lib.check(L.nsk_trace_conditionals(h, _lib.ptr(ids), len(ids)))
+            self.inference(0, epochs, sample_evidence, var_copy="all")
+            if measured:
+                _lib.check(L.nsk_trace_download_conditionals(h, _lib.ptr(sums), C.byref(got)))
+        except BaseException:
+            if measured:
+                L.nsk_trace_setup(h, None, 0, 1, 0)     # (its status must not replace the exception under way)
+            raise
+        if measured:
+            _lib.check(L.nsk_trace_setup(h, None, 0, 1, 0))
+        per_chain = sums / float(got.value) if measured else sums
+        with np.errstate(invalid="ignore"):
+            stderr = per_chain.std(axis=0, ddof=1) / np.sqrt(nchains) if nchains > 1 else np.full(total, np.nan)
+        return {"offsets": offsets, "per_chain": per_chain, "marginals": per_chain.mean(axis=0), "stderr": stderr,
+                "rows": int(got.value)}
+
     # ------------------------------------------------------------------ per-weight statistics
     def weight_statistics(self, var_copy=0, evidence_chain=False, feature_scaled=False):
         """The sufficient statistics of a state: for every weight the sum of the values of its factors (the
