@@ -436,6 +436,18 @@ typedef struct {
     int64_t hubs_block;               /* ... of those the ones a whole workgroup evaluates (more than 128 entries in a
                                          colour laid out as entry-parallel groups); the other hubs_ep - hubs_block
                                          take one wave each                                                          */
+    /* tiles (64 consecutive positions of a colour's fast range that hold at least one variable) and groups by the
+       kernel family that walks them -- see "Routes" below for the per-variable view */
+    int64_t tiles_shape;              /* shape tiles: one word layout for the 64 lanes, per-lane functions and weights */
+    int64_t tiles_shape_padded;       /* ... of them those whose stream holds at least one null member word (a lane's
+                                         entry has fewer members than the tile's layout)                            */
+    int64_t tiles_lane;               /* tiles with per-lane headers (every lane parses its own words)              */
+    int64_t tiles_general;            /* general tiles walked one lane per variable (E entries of 2 + M words)      */
+    int64_t tiles_general_roles;      /* ... of them those of member width M >= 4, walked by the role program
+                                         (general_walk_roles) instead of the layouts specialised on M <= 3          */
+    int64_t ep_groups;                /* entry-parallel groups: 256 positions of general-tile variables, one lane per
+                                         list entry                                                                 */
+    int64_t ep_groups_two_pass;       /* ... of them those with a variable of more than 8 entries: a second LDS pass */
 } nsk_graph_info;
 int nsk_graph_get_info(nsk_graph *g, nsk_graph_info *info);
 int nsk_graph_get_colors(nsk_graph *g, int32_t *color /* nvar, -1 for ghosts */);
@@ -470,6 +482,47 @@ int nsk_graph_get_weight_slots(nsk_graph *g, int64_t *slot);
 int nsk_graph_plan(const nsk_graph_desc *desc, int32_t *color, nsk_graph_info *info);
 /* Host-only twin of nsk_ghost_needs (vids == NULL: query the count). */
 int nsk_graph_plan_needs(const nsk_graph_desc *desc, int64_t *count, int32_t *vids);
+
+/* Routes: which kernel family samples every variable, read back from the compiled layout -- one word per variable
+ * (nvar entries), from a handle or host-only from a plan (both filled by the same function).  What tests and tools
+ * use to see that a graph built for a routing edge landed on the side it was built for.
+ *   bits 0-3   NSK_ROUTE_KIND: one of the NSK_ROUTE_* kinds below
+ *   GENERAL and GROUP:
+ *   bits 4-8   NSK_ROUTE_OWN_ENTRIES: list entries of the variable itself (a dataType-1 variable: over all its lists)
+ *   bits 9-11  NSK_ROUTE_OWN_WIDTH: most other members of one of its entries
+ *   GENERAL:
+ *   bits 12-16 NSK_ROUTE_TILE_ENTRIES: entries E per lane of its tile -- the most any lane has, padded to a multiple
+ *              of the walk's super-group (2, 4, 1, 4 entries for M = 0, 1, 2, 3; lanes with fewer carry padding entries)
+ *   bits 17-19 NSK_ROUTE_TILE_WIDTH: member width M of its tile (M >= 4: the role-program walk)
+ *   GROUP:
+ *   bits 12-16 NSK_ROUTE_TILE_ENTRIES: most entries of a variable of its group
+ *   bit  20    NSK_ROUTE_TWO_PASS: its group takes a second LDS pass (a variable of the group has more than 8 entries)
+ *   SHAPE:
+ *   bit  21    NSK_ROUTE_NULL_WORD: the lane's stream holds a null member word (its entry has fewer members than the
+ *              tile's layout: padded shapes)
+ *   HUB:
+ *   bit  22    NSK_ROUTE_HUB_EP: the hub has an entry-parallel stream;  bit 23  NSK_ROUTE_HUB_BLOCK: ... evaluated by
+ *              a whole workgroup (nsk_graph_info.hubs_ep / hubs_block count these) */
+#define NSK_ROUTE_NONE 0        /* not sampled by this handle                                                   */
+#define NSK_ROUTE_TABLE 1       /* uniform tile inside a segment with a draw table                              */
+#define NSK_ROUTE_UNIFORM 2     /* uniform tile on the exp path (segment without a table, or a rest tile)       */
+#define NSK_ROUTE_SHAPE 3       /* shape tile                                                                   */
+#define NSK_ROUTE_LANE 4        /* tile with per-lane headers                                                   */
+#define NSK_ROUTE_GENERAL 5     /* general tile, walked one lane per variable                                   */
+#define NSK_ROUTE_GROUP 6       /* entry-parallel group                                                         */
+#define NSK_ROUTE_HUB 7         /* a wave or a workgroup per variable                                           */
+#define NSK_ROUTE_GENERIC 8     /* one-lane generic kernel                                                      */
+#define NSK_ROUTE_KIND(r) ((r) & 15)
+#define NSK_ROUTE_OWN_ENTRIES(r) (((r) >> 4) & 31)
+#define NSK_ROUTE_OWN_WIDTH(r) (((r) >> 9) & 7)
+#define NSK_ROUTE_TILE_ENTRIES(r) (((r) >> 12) & 31)
+#define NSK_ROUTE_TILE_WIDTH(r) (((r) >> 17) & 7)
+#define NSK_ROUTE_TWO_PASS(r) (((r) >> 20) & 1)
+#define NSK_ROUTE_NULL_WORD(r) (((r) >> 21) & 1)
+#define NSK_ROUTE_HUB_EP(r) (((r) >> 22) & 1)
+#define NSK_ROUTE_HUB_BLOCK(r) (((r) >> 23) & 1)
+int nsk_graph_plan_routes(const nsk_graph_desc *desc, int32_t *route /* nvar */);
+int nsk_graph_get_routes(nsk_graph *g, int32_t *route /* nvar */);
 
 /* HIP-event bracket on the library's stream: elapsed ms and number of sweep-kernel launches
  * between begin and end (bench.py's roofline leg). */

@@ -23,7 +23,7 @@ BUF_VALUE, BUF_VALUE_EVID, BUF_WEIGHT, BUF_SEND, BUF_RECV, BUF_SEND_EVID, BUF_RE
 SYMBOLS = (
     "nsk_graph_create", "nsk_graph_destroy", "nsk_state_upload", "nsk_state_download",
     "nsk_set_seed", "nsk_set_rng_tag", "nsk_set_scan", "nsk_set_learn_cap", "nsk_set_learn_lag", "nsk_gibbs_sweeps", "nsk_learn_sweeps", "nsk_graph_get_info",
-    "nsk_graph_get_colors", "nsk_graph_get_layout", "nsk_graph_get_generators", "nsk_graph_get_weight_slots", "nsk_graph_plan", "nsk_graph_plan_needs", "nsk_profile_begin", "nsk_profile_end", "nsk_device_buffer",
+    "nsk_graph_get_colors", "nsk_graph_get_layout", "nsk_graph_get_generators", "nsk_graph_get_weight_slots", "nsk_graph_plan", "nsk_graph_plan_needs", "nsk_graph_plan_routes", "nsk_graph_get_routes", "nsk_profile_begin", "nsk_profile_end", "nsk_device_buffer",
     "nsk_set_stream", "nsk_synchronize", "nsk_ghost_needs", "nsk_exchange_setup", "nsk_exchange_pack",
     "nsk_exchange_unpack", "nsk_comm_unique_id", "nsk_comm_init", "nsk_gibbs_sweeps_exchange",
     "nsk_learn_sweeps_exchange", "nsk_pf_setup", "nsk_p2p_setup", "nsk_p2p_export", "nsk_p2p_import", "nsk_p2p_import_local",
@@ -60,7 +60,21 @@ class GraphInfo(C.Structure):
                 ("acc_copies", C.c_int64), ("learn_lag", C.c_int64), ("direct_weights", C.c_int64),
                 ("weight_slots", C.c_int64), ("layout_hash", C.c_int64), ("p2p_fused", C.c_int64),
                 ("tab_quads", C.c_int64), ("wide_quads", C.c_int64),
-                ("hubs", C.c_int64), ("hubs_ep", C.c_int64), ("hubs_block", C.c_int64)]
+                ("hubs", C.c_int64), ("hubs_ep", C.c_int64), ("hubs_block", C.c_int64),
+                ("tiles_shape", C.c_int64), ("tiles_shape_padded", C.c_int64), ("tiles_lane", C.c_int64),
+                ("tiles_general", C.c_int64), ("tiles_general_roles", C.c_int64),
+                ("ep_groups", C.c_int64), ("ep_groups_two_pass", C.c_int64)]
+
+
+# the route word of nsk_graph_plan_routes / nsk_graph_get_routes (include/numbskull_amd.h "Routes")
+ROUTE_NONE, ROUTE_TABLE, ROUTE_UNIFORM, ROUTE_SHAPE, ROUTE_LANE, ROUTE_GENERAL, ROUTE_GROUP, ROUTE_HUB, ROUTE_GENERIC = range(9)
+
+
+def route_fields(r):
+    """The fields of route words (an int or an array of them), by name."""
+    return {"kind": r & 15, "own_entries": (r >> 4) & 31, "own_width": (r >> 9) & 7, "tile_entries": (r >> 12) & 31,
+            "tile_width": (r >> 17) & 7, "two_pass": (r >> 20) & 1, "null_word": (r >> 21) & 1,
+            "hub_ep": (r >> 22) & 1, "hub_block": (r >> 23) & 1}
 
 
 _lib = None
@@ -130,6 +144,8 @@ def lib():
         L.nsk_graph_get_weight_slots.argtypes = [C.c_void_p, C.c_void_p]
         L.nsk_graph_plan.argtypes = [C.POINTER(GraphDesc), C.c_void_p, C.POINTER(GraphInfo)]
         L.nsk_graph_plan_needs.argtypes = [C.POINTER(GraphDesc), C.POINTER(C.c_int64), C.c_void_p]
+        L.nsk_graph_plan_routes.argtypes = [C.POINTER(GraphDesc), C.c_void_p]
+        L.nsk_graph_get_routes.argtypes = [C.c_void_p, C.c_void_p]
         L.nsk_profile_begin.argtypes = [C.c_void_p]
         L.nsk_profile_end.argtypes = [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_int64)]
         L.nsk_device_buffer.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_void_p),

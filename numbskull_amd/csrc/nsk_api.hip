@@ -792,7 +792,8 @@ int nsk_chains_download(nsk_graph *g, int64_t *var_value, int64_t *count) {
     return NSK_OK;
 }
 
-static void fill_info(const Compiled &c, nsk_graph_info *info) {
+// (have: the tile / group counters when the caller has counted them already, else they are counted here)
+static void fill_info(const Compiled &c, nsk_graph_info *info, const RouteCounts *have = nullptr) {
     info->nvar = c.nvar;
     info->nowned = c.nsampled;
     info->ncolors = (int64_t)c.phase_start.size() - 1;
@@ -823,11 +824,22 @@ static void fill_info(const Compiled &c, nsk_graph_info *info) {
         for (int64_t p = c.phase_fast_end[k]; p < c.phase_heavy_end[k]; p++) info->hubs += c.p_vid[(size_t)p] >= 0;
     info->hubs_ep = c.nhub_ep;
     info->hubs_block = c.phase_bighub_base.empty() ? 0 : c.phase_bighub_base.back();   // (bighub_pos is padded when empty)
+    RouteCounts rc;
+    if (have) rc = *have;
+    else compiled_routes(c, nullptr, &rc);
+    info->tiles_shape = rc.tiles_shape;
+    info->tiles_shape_padded = rc.tiles_shape_padded;
+    info->tiles_lane = rc.tiles_lane;
+    info->tiles_general = rc.tiles_general;
+    info->tiles_general_roles = rc.tiles_general_roles;
+    info->ep_groups = rc.ep_groups;
+    info->ep_groups_two_pass = rc.ep_groups_two_pass;
 }
 
 int nsk_graph_get_info(nsk_graph *g, nsk_graph_info *info) {
     if (!g || !info) return fail(NSK_E_INVALID, "null argument");
-    fill_info(g->c, info);
+    if (!g->have_route_counts) { compiled_routes(g->c, nullptr, &g->route_counts); g->have_route_counts = true; }
+    fill_info(g->c, info, &g->route_counts);
     info->device_bytes = g->mem.total;
     info->sweeps_done = g->sweeps_done;
     info->learn_cap = g->learn_cap;
@@ -852,6 +864,22 @@ int nsk_graph_plan(const nsk_graph_desc *desc, int32_t *color, nsk_graph_info *i
     if (rc) return fail(rc, err);
     if (color && c.nvar) memcpy(color, c.color.data(), (size_t)c.nvar * sizeof(int32_t));
     if (info) fill_info(c, info);
+    return NSK_OK;
+}
+
+int nsk_graph_plan_routes(const nsk_graph_desc *desc, int32_t *route) {
+    if (!desc || (!route && desc->nvar)) return fail(NSK_E_INVALID, "null argument");
+    Compiled c;
+    std::string err;
+    int rc = compile_graph(desc, c, err);
+    if (rc) return fail(rc, err);
+    compiled_routes(c, route, nullptr);
+    return NSK_OK;
+}
+
+int nsk_graph_get_routes(nsk_graph *g, int32_t *route) {
+    if (!g || (!route && g->c.nvar)) return fail(NSK_E_INVALID, "null argument");
+    compiled_routes(g->c, route, nullptr);
     return NSK_OK;
 }
 

@@ -251,6 +251,11 @@ int compile_graph(const nsk_graph_desc *d, Compiled &out, std::string &err);
 // 64-bit hash of every data member of a compiled layout (nsk_graph_info.layout_hash with NSK_LAYOUT_HASH=1)
 int64_t layout_hash(const Compiled &c);
 
+// Route word of every variable (route[nvar], may be null; include/numbskull_amd.h NSK_ROUTE_*) and the tile / group
+// counters of nsk_graph_info, both read back from the finished layout (nsk_routes.cpp)
+struct RouteCounts { int64_t tiles_shape, tiles_shape_padded, tiles_lane, tiles_general, tiles_general_roles, ep_groups, ep_groups_two_pass; };
+void compiled_routes(const Compiled &c, int32_t *route, RouteCounts *counts);
+
 // true for function ids of inference.py:74-143
 bool known_function(int fn);
 

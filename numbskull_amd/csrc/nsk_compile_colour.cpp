@@ -212,8 +212,7 @@ void CompileCtx::colour_sampled() {
     lap("greedy colouring");
     // the greedy pass assumes reads are symmetric (true for compute_var_map output); verify, and
     // repair with explicit reverse-read lists when a raw index is asymmetric
-    bool conflict = false;
-    {
+    auto has_conflict = [&]() {
         std::vector<uint8_t> bad((size_t)compile_threads(), 0);
         parallel_for(nvar, [&](int64_t b0, int64_t b1, int t) {
             for (int64_t v = b0; v < b1 && !bad[(size_t)t]; v++) {
@@ -223,9 +222,11 @@ void CompileCtx::colour_sampled() {
                 });
             }
         });
-        for (uint8_t x : bad) conflict = conflict || x;
-    }
-    if (conflict) {
+        bool any = false;
+        for (uint8_t x : bad) any = any || x;
+        return any;
+    };
+    auto repair = [&]() {
         std::vector<int64_t> rcount(nvar + 1, 0);
         for (int64_t v = 0; v < nvar; v++)
             if (sampled[v]) for_each_read(v, [&](int64_t b) { if (b != v) rcount[b + 1]++; });
@@ -249,7 +250,9 @@ void CompileCtx::colour_sampled() {
             }
             c.color[v] = pick(v);
         }
-    }
+    };
+    bool conflict = has_conflict();
+    if (conflict) repair();
 
     lap("symmetry check");
     // fewer classes: iterated greedy (Culberson) -- recolour first fit with the vertices taken class
@@ -334,6 +337,11 @@ void CompileCtx::colour_sampled() {
                 if (best != cur) { load[cur]--; load[best]++; c.color[v] = best; }
             }
     }
+    // Greedy in id order hides an asymmetric read whenever the variable that is read comes first: a literal head index
+    // (inference.py:243) that names a variable of no factor in common, say.  The two passes above take the variables
+    // in other orders and may then put reader and read into one class.  Checked once more; such a graph gets the
+    // repaired greedy colours and neither pass.
+    if (!conflict && ncolors > 2 && !(knobs.no_recolour && knobs.no_balance) && has_conflict()) repair();
 }
 
 // Ghosts: variables outside the owned range read by a sampled variable (c.ghost_needs, sorted).

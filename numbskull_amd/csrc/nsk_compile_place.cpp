@@ -336,7 +336,9 @@ int CompileCtx::place_variables() {
     });
     lap("positions: lane sizes");
     // entry-parallel groups (nsk_compile.h ep_desc) serve a colour whose general variables all
-    // have entries of at most 3 other members and at most 16 entries (ordinal: 5 bits, LDS slots)
+    // have entries of at most 3 other members and at most 16 entries (ordinal: 5 bits, LDS slots).  (With the default
+    // gen_max_entries of 16 the second half never decides: a variable of 17 entries is no general-tile variable at all,
+    // it takes a wave of its own and its colour keeps its groups; only NSK_GEN_MAX_ENTRIES above 16 lets it count.)
     c.phase_ep.assign((size_t)ncolors, 0);
     c.phase_ep_emax.assign((size_t)ncolors, 0);
     if (!knobs.no_ep && nw < ((int64_t)1 << 27)) {

@@ -243,6 +243,8 @@ struct nsk_graph {
                                         // table kernels index with the neighbours' low bits
     bool chain_regular[2] = {true, true};   // ... per chain (var_value, var_value_evid)
     double compile_seconds = 0;
+    nsk::RouteCounts route_counts = {0, 0, 0, 0, 0, 0, 0};   // nsk_graph_info's tile / group counters, counted once (nsk_graph_get_info)
+    bool have_route_counts = false;
     uint32_t *dyn_tiles = nullptr, *rest_tiles = nullptr, *learn_rest_tiles = nullptr;
     int acc_copies = 1;                // copies of the global learning accumulators (one per XCD, or 1)
     int bins_xcd = 0;                  // SMALLW bins private to XCDs (close_sink)

@@ -148,6 +148,20 @@ class FactorGraph(object):
         _lib.check(_lib.lib().nsk_graph_plan(C.byref(desc), _lib.ptr(color), C.byref(inf)))
         return color, {k: getattr(inf, k) for k, _ in inf._fields_}
 
+    def plan_routes(self):
+        """Host-only: the route word of every variable (which kernel family would sample it, with the sizes of its
+        tile or group: nsk_graph_plan_routes; ``_lib.route_fields`` names the fields)."""
+        desc, keep = self._descriptor()
+        out = np.zeros(self.variable.shape[0], np.int32)
+        _lib.check(_lib.lib().nsk_graph_plan_routes(C.byref(desc), _lib.ptr(out)))
+        return out
+
+    def routes(self):
+        """The route word of every variable on this handle's compiled layout (nsk_graph_get_routes)."""
+        out = np.zeros(self.variable.shape[0], np.int32)
+        _lib.check(_lib.lib().nsk_graph_get_routes(self._engine(), _lib.ptr(out)))
+        return out
+
     def ghost_needs(self, host_only=False):
         """Sorted ids of the variables outside ``own_range`` that this partition's variables read
         (what the boundary exchange must deliver).  ``host_only`` plans without touching a GPU."""
