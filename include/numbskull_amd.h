@@ -245,6 +245,38 @@ int nsk_conditionals(nsk_graph *g, int which, int64_t first_chain, int64_t nchai
 int nsk_trace_conditionals(nsk_graph *g, const int64_t *vids, int64_t nvids);
 int nsk_trace_download_conditionals(nsk_graph *g, double *sums /* chains x total */, int64_t *rows);
 
+/* Greedy MAP search: iterated conditional modes (FactorGraph.icm / map_estimate).  Deterministic coordinate ascent on the
+ * potentials above: no random numbers, no exponential.  One ICM sweep visits the colour classes in colour order, as the
+ * chromatic scan does; inside a class every eligible variable is decided in parallel, which equals the sequential
+ * decision because a variable reads none of its own class.  Eligible: a variable with a position and isEvidence == 0, or
+ * any variable with a position when sample_evidence != 0 (the sweep kernels' test).  For an eligible variable of
+ * cardinality C with current value cur and p_k = potential(v, k, x) -- the doubles nsk_conditionals(what = 0) returns:
+ *   best = cur, best_p = p_cur when 0 <= cur < C, else best = 0, best_p = p_0;
+ *   for k = 0 .. C - 1: if (p_k > best_p) { best = k; best_p = p_k; }
+ * A move happens on strict improvement only, the smallest k wins among several maxima, and a NaN potential never wins.
+ * The variable takes `best`; a value that differs from cur counts as one change.
+ * nsk_icm runs up to max_sweeps sweeps on chains first_chain .. first_chain + nchains - 1, every chain on its own:
+ *   sweeps[i]  = the sweeps chain first_chain + i ran up to and including its first sweep without a change (its fixed
+ *                point: later sweeps could change nothing), or -max_sweeps when every sweep changed something -- the
+ *                chain has NOT converged.  With the literal head lookup potential() is not the gradient of one energy,
+ *                so cycles are possible; the negative count is how they are reported;
+ *   changed    (may be NULL) [i * max_sweeps + s] = the changes of sweep s; 0 from the fixed point on.
+ * All max_sweeps x ncolors launches are enqueued on the handle's stream without returning to the host; a chain that has
+ * reached its fixed point ends its later launches on the device after one load.  The counters are integers: the result
+ * does not depend on any order of execution.
+ * `which`, the chains and the handles refused (NSK_E_INVALID) follow nsk_log_potential rule for rule; the sequential scan
+ * is fine (the sweep is the chromatic one either way).  max_sweeps outside [1, 4096] and sweeps == NULL are
+ * NSK_E_INVALID.  A handle with partial factors (nsk_pf_setup) is served: that set-up caches nothing that depends on the
+ * values -- the aggregates are recomputed from the values at every exchange, before they are pushed.  A handle with a
+ * sample trace is served; its rows and columns are untouched.
+ * The call changes the values of the chains named and nothing else: tallies (a tally kept in the value bytes is first
+ * brought back to its array, as before a state download), sweeps_done, the generator state and the weights stay.  The
+ * first call uploads what nsk_conditionals uploads, or finds it in place; the counters (8 bytes x max_sweeps x nchains)
+ * live for the call only; NSK_E_NOMEM names the size of what does not fit.  nsk_profile_* keeps counting sweep-kernel
+ * launches only. */
+int nsk_icm(nsk_graph *g, int which, int64_t first_chain, int64_t nchains, int64_t max_sweeps, int sample_evidence,
+            int64_t *sweeps /* nchains */, int64_t *changed /* nchains x max_sweeps, may be NULL */);
+
 /* Effective sample size from the trace, on the device (FactorGraph.mixing): per column of a BIT-PACKED trace, the
  * split-chain estimator of numbskull_amd.diagnostics.effective_sample_size with the lags cut at max_lag, in one
  * streaming pass over the packed rows -- no row is unpacked or leaves the device.  Rows first_row .. first_row +

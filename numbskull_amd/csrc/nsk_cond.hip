@@ -16,7 +16,7 @@ using namespace nsk;
 // it shares with the log-potential (nsk_records_ensure).  Not gstream / gs_off / f_feat, and generic_uploaded stays
 // nsk_ensure_generic's: it uploads what is still missing when it runs later, and this finds everything in place when
 // it ran before.  Every factor of a positioned variable's list was validated at nsk_graph_create.
-static int cond_ensure(nsk_graph *g, const char *what) {
+int cond_ensure(nsk_graph *g, const char *what) {
     Compiled &c = g->c;
     HIPCHECK(hipSetDevice(g->device));
     if (int rc = nsk_records_ensure(g, c.literal_heads, what)) return rc;

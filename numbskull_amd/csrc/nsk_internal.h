@@ -1,7 +1,7 @@
 // nsk_internal.h -- host-side state of a compiled graph handle, shared by the translation units of
 // the library (nsk_api.hip: C-ABI, state sync; nsk_exchange.hip: the multi-GPU boundary exchange; nsk_gibbs.hip /
 // nsk_learn.hip: the sweep drivers of numbskull/factorgraph.py:141,163,202; nsk_trace.hip, nsk_energy.hip, nsk_wstats.hip,
-// nsk_cond.hip: the diagnostics).
+// nsk_cond.hip: the diagnostics; nsk_icm.hip: the greedy MAP search).
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -555,6 +555,8 @@ int energy_whole_graph(const nsk_graph *g, const char *what);
 int energy_ensure(nsk_graph *g, int chains, const char *what);
 // ... its part that the conditionals share: f_rec, m_rec, v_card and, with `literal`, iid_of_vid, where the handle lacks them
 int nsk_records_ensure(nsk_graph *g, bool literal, const char *what);
+// the arrays potential() reads, each where the handle lacks it (nsk_cond.hip; nsk_icm walks the same lists)
+int cond_ensure(nsk_graph *g, const char *what);
 // the accumulators of a sample trace: sums[r * sel.dtotal() + ..] += the conditionals of chain r at `val`, one launch (nsk_cond.hip)
 int nsk_cond_accumulate(nsk_graph *g, const NskCondSel &sel, const void *val, int nchains, bool packed_bytes, double *sums);
 void nsk_cond_sel_free(nsk_graph *g, NskCondSel &sel);      // the device copies of a selection (the trace's goes with the trace)

@@ -43,6 +43,9 @@ every value of a variable (nsk_conditionals), ``log_pseudo_
 conditionals at a state's own values, and ``tally_layout`` brings the "full" layout of both (every variable owns
 ``cardinality`` slots) to the layout of ``count`` / ``marginals`` (a binary variable owns one), so that the Rao-Blackwell
 marginals of ``FactorGraph.rao_blackwell`` can be compared with the tally's.
+
+``icm_choice`` restates the rule by which ``FactorGraph.icm`` (nsk_icm) picks a variable's new value
+from the same potentials: greedy coordinate ascent towards a MAP estimate.
 """
 
 import collections
@@ -486,6 +489,36 @@ def log_pseudo_likelihood(offsets, potentials, values):
             own = np.take_along_axis(p, off[:-1] + x, axis=-1)
             out = (own - m - np.log(s)).sum(axis=-1)
     return float(out) if out.ndim == 0 else out
+
+
+def icm_choice(offsets, potentials, values):
+    """The decision of one iterated-conditional-modes visit (``FactorGraph.icm``, nsk_icm), for every selected variable at
+    once: ``potentials`` (..., total) is the "full" layout of ``FactorGraph.conditionals(potentials=True)``, ``values``
+    (..., nsel) each selected variable's current value.  Per variable of cardinality ``C``: ``best = cur`` when
+    ``0 <= cur < C``, else 0; then for ``k`` ascending ``if p_k > p_best: best = k``.  So a move needs a strict
+    improvement, the smallest ``k`` wins among several maxima, a NaN potential never wins (and a NaN incumbent is never
+    left).  Returns the new values, int64 (..., nsel).  The potentials must be those of the state the values come from
+    with every OTHER variable as it is: decide one colour class at a time."""
+    off, p = _full_layout(offsets, potentials, "icm_choice")
+    card = np.diff(off)
+    x = np.asarray(values)
+    if x.ndim < 1 or x.shape[-1] != len(card) or (x.size and x.dtype.kind not in "iu"):
+        raise ValueError("icm_choice: values are integers (..., nsel) = (..., %d), got %r %s" % (len(card), x.shape, x.dtype))
+    x = x.astype(np.int64)
+    lead = np.broadcast_shapes(p.shape[:-1], x.shape[:-1])
+    p = np.broadcast_to(p, lead + p.shape[-1:])
+    x = np.broadcast_to(x, lead + x.shape[-1:])
+    best = np.where((x >= 0) & (x < card), x, 0)
+    if len(card) == 0:
+        return best
+    best_p = np.take_along_axis(p, off[:-1] + best, axis=-1)
+    for k in range(int(card.max())):
+        m = card > k
+        pk = p[..., off[:-1][m] + k]
+        better = pk > best_p[..., m]            # (False wherever either side is NaN)
+        best[..., m] = np.where(better, k, best[..., m])
+        best_p[..., m] = np.where(better, pk, best_p[..., m])
+    return best
 
 
 def tally_layout(offsets, values):

@@ -905,6 +905,70 @@ class FactorGraph(object):
         return {"offsets": offsets, "per_chain": per_chain, "marginals": per_chain.mean(axis=0), "stderr": stderr,
                 "rows": int(got.value)}
 
+    # ------------------------------------------------------------------ greedy MAP search
+    def icm(self, max_sweeps=100, var_copy=0, weight_copy=0, evidence_chain=False, sample_evidence=False):
+        """Iterated conditional modes on the device (nsk_icm): greedy coordinate ascent from ``var_value[var_copy]`` --
+        ``var_value_evid[var_copy]`` with ``evidence_chain=True`` -- under ``weight_value[weight_copy]``, pushed as
+        ``log_potential`` pushes them.  A sweep visits the colour classes in the chromatic scan's order; every variable
+        with ``isEvidence == 0`` (every sampled variable with ``sample_evidence``) takes the value of largest potential
+        given the others -- moving on strict improvement only, the smallest value among several maxima
+        (``diagnostics.icm_choice`` is the rule in numpy).  Deterministic: no random numbers are drawn.  Up to
+        ``max_sweeps`` (1 .. 4096) sweeps; the state reached replaces the row it started from, and nothing else changes
+        (``count``, weights, the generator).  ``var_copy="all"`` polishes every row of ``var_value``, each on its own.
+        Returns a dict: ``sweeps`` -- the sweeps run up to and including the first without a change, ``max_sweeps`` when
+        every sweep changed something; ``converged`` -- whether a sweep without a change was reached (with the
+        reference's literal head lookup the potentials are not the gradient of one energy, and cycles are possible);
+        ``changed`` -- int64 ``(max_sweeps,)``, the changes of every sweep, 0 from the fixed point on.  For one copy an
+        int, a bool and that array; for ``"all"`` arrays ``(chains,)``, ``(chains,)`` and ``(chains, max_sweeps)``."""
+        max_sweeps = int(max_sweeps)
+        if max_sweeps < 1 or max_sweeps > 4096:
+            raise ValueError("icm: max_sweeps must lie in [1, 4096]")
+        if _all_copies(var_copy) and evidence_chain:
+            raise ValueError('the evidence chain exists once: var_copy="all" is for the free chains')
+        L, h = _lib.lib(), self._engine()
+        ev = int(bool(sample_evidence))
+        if _all_copies(var_copy):
+            nchains = self._push_chains(weight_copy, count=False)
+            sweeps, changed = np.zeros(nchains, np.int64), np.zeros((nchains, max_sweeps), np.int64)
+            _lib.check(L.nsk_icm(h, _lib.BUF_VALUE, 0, nchains, max_sweeps, ev, _lib.ptr(sweeps), _lib.ptr(changed)))
+            self._pull_chains(count=False)
+            return {"sweeps": np.abs(sweeps), "converged": sweeps > 0, "changed": changed}
+        self._push(var_copy, weight_copy)
+        sweeps, changed = np.zeros(1, np.int64), np.zeros(max_sweeps, np.int64)
+        _lib.check(L.nsk_icm(h, _lib.BUF_VALUE_EVID if evidence_chain else _lib.BUF_VALUE, 0, 1, max_sweeps, ev, _lib.ptr(sweeps),
+                             _lib.ptr(changed)))
+        self._pull(var_copy, weight_copy, weights=False, count=False)
+        return {"sweeps": abs(int(sweeps[0])), "converged": bool(sweeps[0] > 0), "changed": changed}
+
+    def map_estimate(self, epochs, thin=1, burnin_epochs=0, sample_evidence=False, max_sweeps=100):
+        """A MAP estimate: the most probable labelling the chains can find.  Runs ``sample(epochs, thin=thin,
+        burnin_epochs=burnin_epochs, sample_evidence=sample_evidence, var_copy="all", log_potential=True)`` -- one chain
+        per row of ``var_value``, all variables recorded -- takes every chain's best recorded row
+        (``diagnostics.best_sample``), loads those rows as the chains' states, polishes them with ``icm(max_sweeps,
+        var_copy="all")`` and evaluates ``log_potential(var_copy="all")``.  Returns a dict for the best polished chain:
+        ``values`` (its state, int64 ``(nvar,)``), ``log_potential``, ``chain``, ``sampled_log_potential`` (that of the
+        chain's best recorded row, before polishing), ``sweeps`` and ``converged`` (as ``icm``); and for all chains the
+        arrays ``log_potentials`` and ``sampled_log_potentials``.  ``var_value`` is left holding the polished states;
+        ``count``, ``chain_count``, ``marginals`` and ``rhat`` come out as ``inference`` leaves them.  ValueError when
+        ``epochs // thin`` is 0: there is no recorded row to start from."""
+        from .diagnostics import best_sample
+        epochs, thin = int(epochs), int(thin)
+        if thin < 1:
+            raise ValueError("thin must be at least 1")
+        if epochs // thin < 1:
+            raise ValueError("map_estimate: epochs // thin must be at least 1 (no row would be recorded)")
+        samples, lp = self.sample(epochs, None, thin, burnin_epochs, sample_evidence, var_copy="all", log_potential=True)
+        nchains = samples.shape[1]
+        rows = np.array([best_sample(lp[:, r:r + 1])[0] for r in range(nchains)])
+        sampled = lp[rows, np.arange(nchains)]
+        self.var_value[:] = samples[rows, np.arange(nchains)]
+        res = self.icm(max_sweeps, var_copy="all", sample_evidence=sample_evidence)
+        after = self.log_potential(var_copy="all")
+        chain = int(np.argmax(after))
+        return {"values": np.array(self.var_value[chain], np.int64), "log_potential": float(after[chain]), "chain": chain,
+                "sampled_log_potential": float(sampled[chain]), "sweeps": int(res["sweeps"][chain]),
+                "converged": bool(res["converged"][chain]), "log_potentials": after, "sampled_log_potentials": sampled}
+
     # ------------------------------------------------------------------ per-weight statistics
     def weight_statistics(self, var_copy=0, evidence_chain=False, feature_scaled=False):
         """The sufficient statistics of a state: for every weight the sum of the values of its factors (the
