@@ -136,8 +136,7 @@ int nsk_graph_destroy(nsk_graph *g) {
     for (const NskLedger::Entry &e : g->mem.entries) nsk_free_raw(e.raw);
     for (int k = 0; k < 2; k++) if (g->xfer_host[k]) (void)hipHostFree(g->xfer_host[k]);
     if (g->cnt_host) (void)hipHostFree(g->cnt_host);
-    if (g->sweep_graph) (void)hipGraphExecDestroy(g->sweep_graph);
-    if (g->sweep_graph_big) (void)hipGraphExecDestroy(g->sweep_graph_big);
+    nsk_drop_sweep_graph(g);
     if (g->ev0) (void)hipEventDestroy(g->ev0);
     if (g->ev1) (void)hipEventDestroy(g->ev1);
     if (g->own_stream && g->stream) (void)hipStreamDestroy(g->stream);

@@ -28,9 +28,6 @@ struct RcclApi {
 };
 static RcclApi g_rccl;
 
-// F<int8_t>(...) or F<int32_t>(...) by the handle's value type
-#define NSK_BY_VT(G, F, ...) ((G)->c.vbytes == 1 ? F<int8_t>(__VA_ARGS__) : F<int32_t>(__VA_ARGS__))
-
 // w_start / w_delta serve the weight merge of both paths: allocated by whichever set-up comes first
 static int ensure_w_start(nsk_graph *g) {
     int rc;

@@ -5,6 +5,7 @@
 #include <cstring>
 #include <vector>
 
+#include "nsk_class_plan.h"
 #include "nsk_internal.h"
 #include "nsk_kernels_misc.h"
 
@@ -242,6 +243,54 @@ static bool chains_batched(nsk_graph *g, int sample_evidence) {
     return true;
 }
 
+// ---- the launches of a class plan (nsk_class_plan.h), one routine per kernel family ----
+static_assert(PLAN_BLOCK == NSK_BLOCK, "nsk_class_plan.h copies the kernels' block size");
+
+// what the launches of one eager sweep share
+template <typename VT>
+struct EagerSweep { nsk_graph *g; DevGraph<VT> d; int sample_evidence, burnin; CounterSrc src; };
+#define NSK_SWEEP_TAIL(W) (W).sample_evidence, (W).burnin, (W).src.K0, (W).src.K1, (W).src.S0, (W).src.S1
+
+// hubs (one wave per variable) + general tiles + the class's rest tiles
+template <typename VT, int MAXC>
+static void launch_general(const EagerSweep<VT> &w, const ClassShape &s, const GeneralLaunch &L, hipStream_t st) {
+    k_gibbs_general<VT, MAXC><<<dim3(L.grid), dim3(NSK_BLOCK), 0, st>>>(
+        w.d, s.fb, s.fe, s.wb_base, L.tile0, L.ntiles, L.nblocks, s.fe, s.he, L.hblocks, s.hub0,
+        w.g->rest_tiles + s.rest0, L.nrest, NSK_SWEEP_TAIL(w));
+}
+// entry-parallel groups: hubs, the class's general tiles and its rest tiles
+template <typename VT>
+static void launch_ep(const EagerSweep<VT> &w, const ClassShape &s, const GeneralLaunch &L, hipStream_t st) {
+#define NSK_EP(K, MAXC) K<VT, MAXC><<<dim3(L.grid), dim3(NSK_BLOCK), 0, st>>>(                                                       \
+        w.d, s.fb, s.fe, s.wb_base, L.tile0, L.ntiles, s.ngroups, s.group0, L.gblocks, s.fe, s.he, L.hblocks, s.hub0, s.nbh, s.bh0, \
+        w.g->rest_tiles + s.rest0, L.nrest, NSK_SWEEP_TAIL(w))
+    if (L.capped) NSK_EP(k_gibbs_ep_w5, 8); else if (L.maxc == 8) NSK_EP(k_gibbs_ep, 8); else NSK_EP(k_gibbs_ep, 2);
+#undef NSK_EP
+}
+// generic CSR kernel, one lane per variable
+template <typename VT>
+static void launch_generic(const EagerSweep<VT> &w, const ClassShape &s, const SimpleLaunch &L, hipStream_t st) {
+    k_gibbs_phase<VT><<<dim3(L.grid), dim3(NSK_BLOCK), 0, st>>>(w.d, s.he, s.e, NSK_SWEEP_TAIL(w));
+}
+// a prepared segment launch without a draw table: the inlined-adjacency kernel of its kind
+template <typename VT>
+static void launch_seg(const EagerSweep<VT> &w, const NskSegPlan &pl) {
+    const int nb = (pl.tab.ntiles + 3) / 4;
+    const dim3 grid(8 * ((nb + 7) / 8));
+#define NSK_SEG(NCH, KIND) k_gibbs_seg<VT, KIND, NCH><<<grid, dim3(NSK_BLOCK), 0, w.g->stream>>>(w.d, pl.tab, nb, w.burnin, w.src.K0, w.src.K1, w.src.S0, w.src.S1)
+    if (pl.kind == 4) NSK_BY_NCH(NSK_SEG, 4);
+    else if (pl.kind == 2) NSK_BY_NCH(NSK_SEG, 2);
+    else if (pl.kind == 0) NSK_BY_NCH(NSK_SEG, 0);
+    else NSK_BY_NCH(NSK_SEG, 3);
+#undef NSK_SEG
+}
+// the rest tiles no general launch took: descriptor-driven kernel
+template <typename VT>
+static void launch_fast(const EagerSweep<VT> &w, const ClassShape &s, const SimpleLaunch &L) {
+    k_gibbs_fast<VT><<<dim3(L.grid), dim3(NSK_BLOCK), 0, w.g->stream>>>(
+        w.d, s.fb, s.fe, s.wb_base, plan_quarter(L.n), w.g->rest_tiles + s.rest0, L.n, NSK_SWEEP_TAIL(w));
+}
+
 template <typename VT>
 static int gibbs_impl(nsk_graph *g, int64_t nsweeps, int sample_evidence, int burnin) {
     DevGraph<VT> d = view<VT>(g);
@@ -255,123 +304,42 @@ static int gibbs_impl(nsk_graph *g, int64_t nsweeps, int sample_evidence, int bu
         const size_t nphase = g->c.phase_start.size() - 1;
         nsk_refresh_prog_weights(g);
         nsk_ensure_seg_plans(g, sample_evidence);
+        // every class's plan, once per call: cheap, and nothing a sweep changes enters it
+        std::vector<ClassShape> shapes(nphase);
+        std::vector<GibbsClassPlan> plans(nphase);
+        PlanOpts opts;
+        opts.overlap = !g->no_overlap;
+        opts.value_bytes = (size_t)g->c.nid * (size_t)g->c.vbytes;
+        for (size_t ph = 0; ph < nphase; ph++) {
+            shapes[ph] = class_shape(g->c, ph);
+            if (shapes[ph].ep && shapes[ph].fe > shapes[ph].fb)
+                opts.ep_per_cu = plan_per_cu(nsk::diag_env("NSK_EP_PER_CU"));        // (diagnostic: workgroups per CU)
+            plans[ph] = plan_gibbs_class(shapes[ph], opts);
+        }
         for (int64_t s = 0; s < nsweeps; s++) {
             if (g->pack_now && !burnin && g->packed_sweeps >= 127) (void)nsk_unpack_tally(g);       // 7 tally bits per value byte
             if (g->p2p.fused_now) ++g->p2p.tag;            // the exchange rides in this sweep's table launches
+            const EagerSweep<VT> w{g, d, sample_evidence, burnin, CounterSrc::eager(g)};
             for (size_t ph = 0; ph < nphase; ph++) {
-                const int fb = (int)g->c.phase_start[ph], fe = (int)g->c.phase_fast_end[ph];
-                const int e = (int)g->c.phase_end[ph];
-                const int he = (int)g->c.phase_heavy_end[ph];
+                const ClassShape &cl = shapes[ph];
+                const GibbsClassPlan &p = plans[ph];
                 ColourStreams cs(g, !g->no_overlap);
-                bool rest_in_general = false;       // the colour's rest tiles were given to a general launch
-                const bool ep = fe > fb && g->c.phase_ep[ph];
-                if (ep) {   // entry-parallel groups: hubs, the colour's general tiles and its rest tiles in one launch
-                    const int gt0 = (int)g->c.phase_gen_tile[ph];
-                    const int ngt = (int)(g->c.phase_wb_base[ph + 1] - g->c.phase_wb_base[ph]) - gt0;
-                    const int ngroups = (int)(g->c.phase_ep_base[ph + 1] - g->c.phase_ep_base[ph]);
-                    const int nbh = (int)(g->c.phase_bighub_base[ph + 1] - g->c.phase_bighub_base[ph]);   // a block per long-list hub
-                    const int hblocks = nbh + (he - fe + 3) / 4;
-                    const int nrest_all = (int)(g->c.phase_rest_base[ph + 1] - g->c.phase_rest_base[ph]);
-                    rest_in_general = nrest_all > 0;
-                    const int rblocks = (nrest_all + 3) / 4;
-                    // grid: 7 workgroups per CU, whole rounds of XCDs.  Five of them are resident (90 / 86 vector
-                    // registers since the wave index is a scalar; the categorical kernel had 101 and four until round 5); the
-                    // others start as those end, which deals the
-                    // groups' uneven costs out dynamically -- per class on the 5M LR graph (NSK_EP_PER_CU):
-                    // 3 workgroups per CU 68.4 us, 4 58.6, 5 65.6, 6 66.8, 7 58.3
-                    const bool cat8 = g->c.phase_gen_bin_tile[ph] > gt0;
-                    const char *pcu_env = nsk::diag_env("NSK_EP_PER_CU");        // (diagnostic: workgroups per CU)
-                    const int pcu = pcu_env ? std::max(1, std::min(32, atoi(pcu_env))) : 7;
-                    const int gblocks = 8 * ((std::min(ngroups, 256 * pcu) + 7) / 8);
-                    const dim3 grid(hblocks + gblocks + rblocks);
-#define NSK_EP_ARGS d, fb, fe, (int)g->c.phase_wb_base[ph], gt0, ngt, ngroups, (int)g->c.phase_ep_base[ph], gblocks, fe, he, hblocks, \
-                    (int)g->c.phase_hub_base[ph], nbh, (int)g->c.phase_bighub_base[ph], g->rest_tiles + g->c.phase_rest_base[ph], nrest_all, sample_evidence, burnin, \
-                    (uint32_t)g->seed, (uint32_t)(g->seed >> 32), (uint32_t)g->sweep, nsk_sweep_hi(g)
-                    // (value array within the L2s: the register-capped twin with a fifth wave per SIMD)
-                    const bool in_l2 = (size_t)g->c.nid * (size_t)g->c.vbytes <= ((size_t)24 << 20);
-                    if (cat8 && in_l2) k_gibbs_ep_w5<VT, 8><<<grid, dim3(NSK_BLOCK), 0, g->stream>>>(NSK_EP_ARGS);
-                    else if (cat8) k_gibbs_ep<VT, 8><<<grid, dim3(NSK_BLOCK), 0, g->stream>>>(NSK_EP_ARGS);
-                    else k_gibbs_ep<VT, 2><<<grid, dim3(NSK_BLOCK), 0, g->stream>>>(NSK_EP_ARGS);
-#undef NSK_EP_ARGS
+                const GeneralLaunch &L = p.general;
+                // (the all-binary launch, and only it, goes behind the generic kernel's fork: L.behind_generic)
+                if (L.on && !L.behind_generic) {
+                    if (L.ep) launch_ep<VT>(w, cl, L, cs.of(L.stream));
+                    else launch_general<VT, 8>(w, cl, L, cs.of(L.stream));
                     g->launches++;
                 }
-                if (!ep) {   // hubs (one wave per variable) + general tiles with categorical lanes: one launch
-                    const int gt0 = fe > fb ? (int)g->c.phase_gen_tile[ph] : 0;
-                    int gtb = fe > fb ? (int)g->c.phase_gen_bin_tile[ph] : 0;
-                    // a class with categorical tiles walks ALL its general tiles in this launch, on
-                    // the main stream: the fork / join events of a side stream cost more (~20 us per
-                    // class) than the binary tiles lose by running the 8-candidate code
-                    const bool one_general = gtb > gt0;
-                    if (one_general) gtb = (int)(g->c.phase_wb_base[ph + 1] - g->c.phase_wb_base[ph]);
-                    // without categorical tiles the hubs ride in the binary launch on the main stream
-                    // (no side stream, no fork / join events for this class)
-                    const bool hubs_with_binary = gtb == gt0 && fe > fb &&
-                        (int)(g->c.phase_wb_base[ph + 1] - g->c.phase_wb_base[ph]) > gtb;
-                    const int nblocks = (gtb - gt0 + 3) / 4, hblocks = hubs_with_binary ? 0 : (he - fe + 3) / 4;
-                    // the colour's other tiles outside segments ride in the general launch too
-                    const int nrest_all = fe > fb ? (int)(g->c.phase_rest_base[ph + 1] - g->c.phase_rest_base[ph]) : 0;
-                    const bool rest_here = one_general && nrest_all > 0;
-                    rest_in_general = rest_here;
-                    const int rblocks = rest_here ? (nrest_all + 3) / 4 : 0;
-                    if (nblocks + hblocks > 0) {
-                        k_gibbs_general<VT, 8><<<dim3(hblocks + 8 * ((nblocks + 7) / 8) + rblocks), dim3(NSK_BLOCK), 0, one_general ? g->stream : cs.side(0)>>>(
-                            d, fb, fe, (int)g->c.phase_wb_base[ph], gt0, gtb - gt0, nblocks, fe, he, hblocks, (int)g->c.phase_hub_base[ph],
-                            g->rest_tiles + g->c.phase_rest_base[ph], rest_here ? nrest_all : 0,
-                            sample_evidence, burnin, (uint32_t)g->seed, (uint32_t)(g->seed >> 32),
-                            (uint32_t)g->sweep, nsk_sweep_hi(g));
-                        g->launches++;
-                    }
-                }
-                if (e > he) {       // generic CSR kernel, one lane per variable
-                    k_gibbs_phase<VT><<<dim3((e - he + NSK_BLOCK - 1) / NSK_BLOCK), dim3(NSK_BLOCK), 0, cs.side(1)>>>(
-                        d, he, e, sample_evidence, burnin, (uint32_t)g->seed, (uint32_t)(g->seed >> 32),
-                        (uint32_t)g->sweep, nsk_sweep_hi(g));
-                    g->launches++;
-                }
-                if (fe > fb) {      // inlined-adjacency kernels
-                    const CounterSrc src = CounterSrc::eager(g);
-                    const uint32_t K0 = src.K0, K1 = src.K1, S0 = src.S0, S1 = src.S1;
-                    const int gt0 = (int)g->c.phase_gen_tile[ph];
-                    const int ngt = (int)(g->c.phase_wb_base[ph + 1] - g->c.phase_wb_base[ph]) - gt0;
-                    int gtb = (int)g->c.phase_gen_bin_tile[ph];
-                    if (gtb > gt0) gtb = gt0 + ngt;     // walked by the launch above
-                    if (gt0 + ngt > gtb && !ep) {   // all-binary general tiles (IMPLY_MLN, mixed tails)
-                        const int nblocks = (gt0 + ngt - gtb + 3) / 4;
-                        const int hbl = gtb == gt0 ? (he - fe + 3) / 4 : 0;     // see above
-                        const int nrest_all = (int)(g->c.phase_rest_base[ph + 1] - g->c.phase_rest_base[ph]);
-                        rest_in_general = gtb == gt0 && nrest_all > 0;
-                        const int rblocks = rest_in_general ? (nrest_all + 3) / 4 : 0;
-                        k_gibbs_general<VT, 2><<<dim3(hbl + 8 * ((nblocks + 7) / 8) + rblocks), dim3(NSK_BLOCK), 0, g->stream>>>(
-                            d, fb, fe, (int)g->c.phase_wb_base[ph], gtb, gt0 + ngt - gtb, nblocks, fe, he, hbl, (int)g->c.phase_hub_base[ph],
-                            g->rest_tiles + g->c.phase_rest_base[ph], rest_in_general ? nrest_all : 0,
-                            sample_evidence, burnin, K0, K1, S0, S1);
-                        g->launches++;
-                    }
-                    // segments of this colour: the launches prepared before the sweep loop
+                if (p.generic.on) { launch_generic<VT>(w, cl, p.generic, cs.of(p.generic.stream)); g->launches++; }
+                if (L.on && L.behind_generic) { launch_general<VT, 2>(w, cl, L, g->stream); g->launches++; }
+                if (p.segments)         // the launches prepared before the sweep loop
                     for (const NskSegPlan &pl : g->seg_plans[ph]) {
-                        if (pl.kind >= 8) launch_table<VT>(g, pl, (int)ph, burnin, src);
-                        else {
-                            const int nb = (pl.tab.ntiles + 3) / 4;
-                            const dim3 grid(8 * ((nb + 7) / 8));
-#define NSK_SEG(NCH, KIND) k_gibbs_seg<VT, KIND, NCH><<<grid, dim3(NSK_BLOCK), 0, g->stream>>>(d, pl.tab, nb, burnin, K0, K1, S0, S1)
-                            if (pl.kind == 4) NSK_BY_NCH(NSK_SEG, 4);
-                            else if (pl.kind == 2) NSK_BY_NCH(NSK_SEG, 2);
-                            else if (pl.kind == 0) NSK_BY_NCH(NSK_SEG, 0);
-                            else NSK_BY_NCH(NSK_SEG, 3);
-#undef NSK_SEG
-                        }
+                        if (pl.kind >= 8) launch_table<VT>(g, pl, (int)ph, burnin, w.src);
+                        else launch_seg<VT>(w, pl);
                         g->launches++;
                     }
-                    const int nrest = (int)(g->c.phase_rest_base[ph + 1] - g->c.phase_rest_base[ph]);
-                    if (nrest > 0 && !rest_in_general) {
-                        const int nblocks = (nrest + 3) / 4;
-                        k_gibbs_fast<VT><<<dim3(8 * ((nblocks + 7) / 8)), dim3(NSK_BLOCK), 0, g->stream>>>(
-                            d, fb, fe, (int)g->c.phase_wb_base[ph], nblocks,
-                            g->rest_tiles + g->c.phase_rest_base[ph], nrest, sample_evidence, burnin,
-                            K0, K1, S0, S1);
-                        g->launches++;
-                    }
-                }
+                if (p.fast.on) { launch_fast<VT>(w, cl, p.fast); g->launches++; }
                 cs.join();
             }
             g->sweep++;
@@ -393,8 +361,7 @@ extern "C" int nsk_debug_dump(unsigned long long *out, int n) {
 #endif
 
 static int gibbs_eager(nsk_graph *g, int64_t nsweeps, int sample_evidence, int burnin) {
-    return g->c.vbytes == 1 ? gibbs_impl<int8_t>(g, nsweeps, sample_evidence, burnin)
-                            : gibbs_impl<int32_t>(g, nsweeps, sample_evidence, burnin);
+    return NSK_BY_VT(g, gibbs_impl, g, nsweeps, sample_evidence, burnin);
 }
 
 // ---- captured sweep sequences (hipGraph) -------------------------------------------------------------
@@ -406,10 +373,10 @@ bool nsk_tables_only(const nsk_graph *g) {
     const size_t nphase = c.phase_start.size() - 1;
     if (g->scan != NSK_SCAN_CHROMATIC || nphase == 0) return false;
     for (size_t ph = 0; ph < nphase; ph++) {
-        const int64_t ntiles = c.phase_wb_base[ph + 1] - c.phase_wb_base[ph];
-        if (c.phase_end[ph] > c.phase_fast_end[ph]) return false;                    // generic-path variables / hubs
-        if (ntiles > c.phase_gen_tile[ph]) return false;                             // general tiles
-        if (c.phase_rest_base[ph + 1] > c.phase_rest_base[ph]) return false;         // tiles outside segments
+        const ClassShape s = class_shape(c, ph);
+        if (s.e > s.fe) return false;                    // generic-path variables / hubs
+        if (s.ntiles > s.gt0) return false;              // general tiles
+        if (s.nrest > 0) return false;                   // tiles outside segments
     }
     for (const nsk::Compiled::Segment &sg : c.segments) if (sg.ztab < 0) return false;
     return true;
@@ -417,10 +384,10 @@ bool nsk_tables_only(const nsk_graph *g) {
 
 // the captured sweep sequences bake array addresses and exchange pointers: dropped when those change
 void nsk_drop_sweep_graph(nsk_graph *g) {
-    if (g->sweep_graph) { (void)hipGraphExecDestroy(g->sweep_graph); g->sweep_graph = nullptr; }
-    g->sweep_graph_key = -1;
-    if (g->sweep_graph_big) { (void)hipGraphExecDestroy(g->sweep_graph_big); g->sweep_graph_big = nullptr; }
-    g->sweep_graph_big_key = -1;
+    for (SweepGraph &sg : g->sweep_graphs) {
+        if (sg.exec) { (void)hipGraphExecDestroy(sg.exec); sg.exec = nullptr; }
+        sg.key = -1;
+    }
 }
 
 // NSK_GRAPH_SWEEPS sweeps -- class launches, peer-to-peer push and wait/unpack -- are captured once into
@@ -440,13 +407,11 @@ static bool graph_eligible(const nsk_graph *g, bool p2p) {
 }
 
 template <typename VT>
-static int graph_build(nsk_graph *g, int burnin, bool p2p, int key, bool big) {
-    hipGraphExec_t &exec = big ? g->sweep_graph_big : g->sweep_graph;
-    int &exec_key = big ? g->sweep_graph_big_key : g->sweep_graph_key;
-    int &exec_launches = big ? g->sweep_graph_big_launches : g->sweep_graph_launches;
-    const int nsw = big ? NSK_GRAPH_SWEEPS_BIG : NSK_GRAPH_SWEEPS;
+static int graph_build(nsk_graph *g, int burnin, bool p2p, int key, SweepGraph &sg) {
+    hipGraphExec_t &exec = sg.exec;
+    const int nsw = sg.nsweeps;
     if (exec) { (void)hipGraphExecDestroy(exec); exec = nullptr; }
-    exec_key = -1;
+    sg.key = -1;
     hipGraph_t graph = nullptr;
     // (the legacy default stream cannot be captured: a caller that pointed the library at it -- torch's
     // current stream in a process without its own streams -- keeps the eager loop)
@@ -470,8 +435,8 @@ static int graph_build(nsk_graph *g, int burnin, bool p2p, int key, bool big) {
     e = hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0);
     (void)hipGraphDestroy(graph);
     if (e != hipSuccess) { exec = nullptr; return nsk::fail(NSK_E_DEVICE, std::string("hipGraphInstantiate: ") + hipGetErrorString(e)); }
-    exec_key = key;
-    exec_launches = launches;
+    sg.key = key;
+    sg.launches = launches;
     return NSK_OK;
 }
 
@@ -518,13 +483,11 @@ int nsk_gibbs_run(nsk_graph *g, int64_t nsweeps, int sample_evidence, int burnin
         if (g->seg_plans_all_tab && left >= NSK_GRAPH_SWEEPS) {
             // two sizes: NSK_GRAPH_SWEEPS_BIG sweeps per replay while the call is long enough, NSK_GRAPH_SWEEPS for what is left
             for (int big = (left >= NSK_GRAPH_SWEEPS_BIG && !nsk::diag_env("NSK_NO_BIG_GRAPH")) ? 1 : 0; big >= 0; big--) {
-                const int nsw = big ? NSK_GRAPH_SWEEPS_BIG : NSK_GRAPH_SWEEPS;
-                hipGraphExec_t &exec = big ? g->sweep_graph_big : g->sweep_graph;
-                int &exec_key = big ? g->sweep_graph_big_key : g->sweep_graph_key;
+                SweepGraph &sg = g->sweep_graphs[big];
+                const int nsw = sg.nsweeps;
                 if (left < nsw || g->sweep_graph_off) continue;
-                if (exec_key != key) {
-                    rc = g->c.vbytes == 1 ? graph_build<int8_t>(g, burnin, p2p, key, big != 0)
-                                          : graph_build<int32_t>(g, burnin, p2p, key, big != 0);
+                if (sg.key != key) {
+                    rc = NSK_BY_VT(g, graph_build, g, burnin, p2p, key, sg);
                     if (rc) {               // capture is an optimisation: without it the eager loop runs
                         g->sweep_graph_off = true;
                         (void)hipGetLastError();
@@ -532,15 +495,15 @@ int nsk_gibbs_run(nsk_graph *g, int64_t nsweeps, int sample_evidence, int burnin
                     }
                 }
                 k_graph_counters<<<dim3(1), dim3(1), 0, g->stream>>>(g->d_counters, g->sweep, g->p2p.tag, 1, g->seed, g->rng_tag);
-                while (left >= nsw && exec_key == key) {
+                while (left >= nsw && sg.key == key) {
                     if (!burnin && g->pos_tally_sweeps + nsw > 255) nsk_fold_position_tally(g);   // uint8 tally
                     if (g->pack_now && g->packed_sweeps + nsw > 127) (void)nsk_unpack_tally(g);   // 7 bits in a value byte
-                    HIPCHECK(hipGraphLaunch(exec, g->stream));
+                    HIPCHECK(hipGraphLaunch(sg.exec, g->stream));
                     g->sweep += (uint64_t)nsw;
                     if (p2p) g->p2p.tag += (unsigned int)nsw;
                     if (!burnin) { g->pos_tally_sweeps += nsw; g->cnt_dirty = true; if (g->pack_now) g->packed_sweeps += nsw; }
                     g->sweeps_done += nsw;
-                    g->launches += big ? g->sweep_graph_big_launches : g->sweep_graph_launches;
+                    g->launches += sg.launches;
                     left -= nsw;
                 }
             }

@@ -176,6 +176,15 @@ static inline unsigned int nsk_energy_blocks(long long nfactor) {
     return (unsigned int)(need < 8 ? 8 : (need >= NSK_ENERGY_MAX_BLOCKS ? NSK_ENERGY_MAX_BLOCKS : (need + 7) / 8 * 8));
 }
 
+// one captured sweep sequence (nsk_gibbs.hip graph_build): the executable graph, what it was captured for (-1: nothing),
+// the kernel launches of one replay and its sweeps
+#define NSK_GRAPH_SWEEPS 16
+#define NSK_GRAPH_SWEEPS_BIG 64
+struct SweepGraph { hipGraphExec_t exec; int key, launches, nsweeps; };
+
+// F<VT>(...) with the value type of the handle G
+#define NSK_BY_VT(G, F, ...) ((G)->c.vbytes == 1 ? F<int8_t>(__VA_ARGS__) : F<int32_t>(__VA_ARGS__))
+
 struct nsk_graph {
     nsk::Compiled c;
     NskTrace trace;
@@ -187,14 +196,11 @@ struct nsk_graph {
     std::vector<std::vector<NskSegPlan>> seg_plans;
     int seg_plans_key = -1;
     bool seg_plans_all_tab = false, seg_plans_all_wide = false;   // every plan is a table launch (kind 8); ... a wide one (they live with the key)
-    // captured sweep sequence (hipGraph): NSK_GRAPH_SWEEPS inference sweeps of a handle whose sweep is
-    // table launches only (+ the peer-to-peer exchange), replayed with the sweep index in device memory
-    hipGraphExec_t sweep_graph = nullptr;
-    int sweep_graph_key = -1, sweep_graph_launches = 0;
-    // ... and NSK_GRAPH_SWEEPS_BIG of them for long calls (the one-thread kernel that advances the counters and the
+    // captured sweep sequences (hipGraph): [0] NSK_GRAPH_SWEEPS inference sweeps of a handle whose sweep is
+    // table launches only (+ the peer-to-peer exchange), replayed with the sweep index in device memory;
+    // [1] NSK_GRAPH_SWEEPS_BIG of them for long calls (the one-thread kernel that advances the counters and the
     // replay's own latency are ~5 us per replay: 4 % of a 16-sweep replay of the 1M grid)
-    hipGraphExec_t sweep_graph_big = nullptr;
-    int sweep_graph_big_key = -1, sweep_graph_big_launches = 0;
+    SweepGraph sweep_graphs[2] = {{nullptr, -1, 0, NSK_GRAPH_SWEEPS}, {nullptr, -1, 0, NSK_GRAPH_SWEEPS_BIG}};
     bool sweep_graph_off = false;                  // capture failed once (e.g. the legacy default stream): eager from then on
     unsigned long long *d_counters = nullptr;      // [0] sweep index, [1] exchange tag, [2] Philox key, [3] shard tag
     int device = 0;
@@ -425,6 +431,7 @@ struct ColourStreams {
         if (!forked[i]) { (void)hipStreamWaitEvent(g->side[i], g->ev_fork, 0); forked[i] = true; }
         return g->side[i];
     }
+    hipStream_t of(int i) { return i < 0 ? g->stream : side(i); }      // a class plan's stream (nsk_class_plan.h PlanStream)
     void join() {
         for (int i = 0; i < 3; i++)
             if (forked[i]) {
@@ -529,8 +536,6 @@ static inline int nsk_learn_seg_grid(const nsk::Compiled::SegLaunch &sl, int nwe
 
 extern "C" int nsk_ensure_generic(nsk_graph *g);       // internal (not in the public header)
 int nsk_ensure_lag_sets(nsk_graph *g);                 // second set of weights / tables / accumulators (nsk_api.hip)
-#define NSK_GRAPH_SWEEPS 16
-#define NSK_GRAPH_SWEEPS_BIG 64
 // one peer-to-peer exchange on the library's stream; tag_base != null: a captured launch whose tag is
 // the device counter + tag_off; learn: both chains + the weight deltas; part 0 = all of it, 1 = the
 // pushes only, 2 = wait + unpack (+ the owner's half of the weight merge), 3 = the closing half of the

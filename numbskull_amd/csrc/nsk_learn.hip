@@ -4,11 +4,16 @@
 #include <cstdlib>
 #include <cstring>
 
+#include "nsk_class_plan.h"
 #include "nsk_internal.h"
 #include "nsk_kernels_learn.h"
 #include "nsk_kernels_misc.h"
 
 using namespace nsk;
+
+static_assert(PLAN_BLOCK == NSK_BLOCK && PLAN_LEARN_FAST_BLOCKS == NSK_LEARN_FAST_BLOCKS && PLAN_LEARN_LIST_BLOCKS == NSK_LEARN_LIST_BLOCKS &&
+              PLAN_LEARN_GEN_BLOCKS == NSK_LEARN_GEN_BLOCKS && PLAN_LEARN_HEAVY_BLOCKS == NSK_LEARN_HEAVY_BLOCKS &&
+              PLAN_LEARN_GENERAL_BLOCKS == NSK_LEARN_GENERAL_BLOCKS, "nsk_class_plan.h copies the kernels' block size and grid caps");
 
 #ifndef NSK_LEARN_TPW
 #define NSK_LEARN_TPW 2          // tiles per trip of the learning table kernel (1: 41.6 us, 2: 41.6 us, 4: 46.7 us
@@ -183,22 +188,34 @@ int nsk_learn_chromatic(nsk_graph *g, int64_t nsweeps, double step, double decay
     };
     ApplyArgs no_update;
     memset(&no_update, 0, sizeof(no_update));
+    // every class's plan (nsk_class_plan.h) and its segment launches, once per call: nothing a sweep changes enters them
+    struct LearnClass { ClassShape s; LearnClassPlan p; std::vector<const Compiled::SegLaunch *> segs; };
+    std::vector<LearnClass> classes(nphase);
+    PlanOpts opts;
+    opts.overlap = !g->no_overlap;
+    opts.smallw = SMALLW; opts.nweight = nw; opts.has_kstat = dv[0].ep_kstat != nullptr; opts.regularization = regularization;
+    for (size_t ph = 0; ph < nphase; ph++) {
+        LearnClass &c = classes[ph];
+        c.s = class_shape(g->c, ph);
+        opts.seg_tiles = 0;
+        for (const Compiled::SegLaunch &sl : g->c.learn_seg)
+            if (sl.phase == (int)ph) { c.segs.push_back(&sl); opts.seg_tiles += sl.tile_start[sl.n]; }
+        if (c.s.ep && c.s.e > c.s.fb) opts.ep_per_cu = plan_per_cu(nsk::diag_env("NSK_EP_PER_CU"));    // (diagnostic: workgroups per CU)
+        c.p = plan_learn_class(c.s, opts);
+    }
     for (int64_t s = 0; s < nsweeps; s++) {
         lp.s0 = (uint32_t)g->sweep; lp.s1 = nsk_sweep_hi(g);
         for (size_t ph = 0; ph < nphase; ph++) {
-            const int fb = (int)g->c.phase_start[ph], fe = (int)g->c.phase_fast_end[ph];
-            const int e = (int)g->c.phase_end[ph];
-            if (e <= fb) continue;
+            const ClassShape &cl = classes[ph].s;
+            const LearnClassPlan &p = classes[ph].p;
+            if (p.skip) continue;
             const int set = lag ? (int)(cls & 1) : 0;
             DevGraph<VT> d = dv[set];
             // the parameters of this class's update, for the weights the kernels update in place (w_direct)
             d.upd_step = step; d.upd_regularization = regularization; d.upd_reg_param = reg_param;
             d.upd_truncation = (double)truncation; d.upd_cap = g->learn_cap;
             d.upd_a1 = 1.0 / (1.0 + reg_param * step);
-            lp.hub0 = (int)g->c.phase_hub_base[ph];
-            const int ntiles = (int)(g->c.phase_wb_base[ph + 1] - g->c.phase_wb_base[ph]);
-            const int ndyn = (int)(g->c.phase_dyn_base[ph + 1] - g->c.phase_dyn_base[ph]);
-            const int he = (int)g->c.phase_heavy_end[ph];
+            lp.hub0 = cl.hub0;
             ColourStreams cs(g, !g->no_overlap);
             // the weight update of the class (SMALLW): arguments of k_apply_bins
             const bool tabs_here = g->c.nfast > 0 && g->c.nztab <= 2048;
@@ -211,91 +228,38 @@ int nsk_learn_chromatic(nsk_graph *g, int64_t nsweeps, double step, double decay
             aa.nprog = g->c.nfast > 0 ? (int)g->c.tile_hdr.size() : 0; aa.zp = g->zprogs;
             aa.nzp = tabs_here ? (int)g->c.zprogs.size() : 0; aa.nztab = tabs_here ? (int)g->c.nztab : 0;
             aa.ztab = const_cast<uint4 *>(d.ztab); aa.cap = g->learn_cap; aa.clipped = g->clip_count; aa.grad_inv = d.grad_inv;
-            if (e > he) {               // variables outside the fast path: generic kernel, range mode
-                const int nitems = (e - he + 63) / 64;
-                const int grid = std::min(NSK_LEARN_GEN_BLOCKS, (nitems + 3) / 4);
-                k_learn_phase<VT, SMALLW, true><<<dim3(grid), dim3(NSK_BLOCK), shmem, cs.side(1)>>>(
-                    d, he, e, nullptr, nitems, lp);
+            if (p.generic.on) {         // variables outside the fast path: generic kernel, range mode
+                k_learn_phase<VT, SMALLW, true><<<dim3(p.generic.grid), dim3(NSK_BLOCK), shmem, cs.of(p.generic.stream)>>>(
+                    d, cl.he, cl.e, nullptr, p.generic.n, lp);
                 g->launches++;
             }
-            const int gt0 = (int)g->c.phase_gen_tile[ph];
-            const int gtb = (int)g->c.phase_gen_bin_tile[ph];
-            // hubs ride as extra blocks of a general-tile launch when the class has one
-            const bool hubs_in_general = (gtb > gt0 || ntiles > gtb) && he > fe;
-            const int hbl = hubs_in_general ? std::min(NSK_LEARN_HEAVY_BLOCKS, (he - fe + 3) / 4) : 0;
-            if (he > fe && !hubs_in_general) {   // hubs: one wave per variable
-                const int grid = std::min(NSK_LEARN_HEAVY_BLOCKS, (he - fe + 3) / 4);
-                k_learn_heavy<VT, SMALLW><<<dim3(grid), dim3(NSK_BLOCK), shmem, cs.side(2)>>>(d, fe, he, lp);
+            if (p.heavy.on) {           // hubs no general launch carries: one wave per variable
+                k_learn_heavy<VT, SMALLW><<<dim3(p.heavy.grid), dim3(NSK_BLOCK), shmem, cs.of(p.heavy.stream)>>>(d, cl.fe, cl.he, lp);
                 g->launches++;
             }
-            // the colour's uniform / shape tiles outside segment launches ride in the general launch
-            const int nlrest = (int)(g->c.phase_learn_rest_base[ph + 1] - g->c.phase_learn_rest_base[ph]);
-            const bool rest_in_general = ntiles > gt0 && nlrest > 0;
-            const uint32_t *lrest = g->learn_rest_tiles + g->c.phase_learn_rest_base[ph];
-            // a class with a lot of both general tiles and other tiles runs the two groups side by side
-            // (side stream 0); smaller ones are not worth the fork / join events
-            int other_tiles = rest_in_general ? 0 : nlrest;
-            for (const Compiled::SegLaunch &sl : g->c.learn_seg) if (sl.phase == (int)ph) other_tiles += sl.tile_start[sl.n];
-            const bool general_aside = ntiles - gt0 >= 2048 && other_tiles >= 2048 && !g->no_overlap;
-            // as in inference: a class with categorical tiles walks all its general tiles in one
-            // launch of the 8-candidate kernel on the main stream (+10 % over two concurrent launches)
-            const bool one_lg = gtb > gt0;
-            const bool ep = fe > fb && g->c.phase_ep[ph] && ntiles > gt0;
-            // structural visit counts: the entry-parallel launch skips zero-gradient visits of dataType-0
-            // variables and the weight update adds their counts (not with L1: its truncation coins are
-            // counted per visit)
-            const bool kstat_here = ep && !SMALLW && d.ep_kstat != nullptr && regularization != 1;
-            lp.kstat = kstat_here ? 1 : 0;
-            if (ep) {                   // entry-parallel groups: hubs, the general tiles and the rest tiles
-                const int ngroups = (int)(g->c.phase_ep_base[ph + 1] - g->c.phase_ep_base[ph]);
-                // grid: 10 workgroups per CU (4 are resident -- 128 with the cap of k_learn_ep_w4 / 114 vector registers; 153 / 111 and 3 or 4 until round 5 --, the others
-                // start as those end: dynamic dealing of uneven groups).  Per class (NSK_EP_PER_CU), 5M LR graph:
-                // 3 workgroups per CU 142.4 us, 4 149.2, 5 139.5, 6 135.4, 7 134.2, 8 132.9, 10 134.7, 16 135.6;
-                // 50M LR graph: 4 1362 us, 7 1247, 10 1189
-                const char *pcu_env = nsk::diag_env("NSK_EP_PER_CU");            // (diagnostic: workgroups per CU)
-                // -- and at 5M, twice each (tools/sessions/history/r4_s26.sh): 10 per CU 4.95 / 4.97e9 updates/s, 7 per CU
-                // 5.04 / 5.06e9.  Hence 10 when a workgroup walks four groups or more, 7 otherwise (the shards
-                // of an 8-rank run of the 50M graph are of the second kind).
-                const int per_cu = pcu_env ? std::max(1, std::min(32, atoi(pcu_env))) : (ngroups >= 4 * 2560 ? 10 : 7);
-                const int gblocks = 8 * ((std::min(256 * per_cu, ngroups) + 7) / 8);
-                const int nbh = (int)(g->c.phase_bighub_base[ph + 1] - g->c.phase_bighub_base[ph]);   // a block per long-list hub
-                const int hbl_ep = nbh + hbl;
-                // the colour's rest tiles (shape tiles: graphs with individual weights) are walked by all of these
-                // workgroups, one wave per tile: when the groups alone bring too few, more workgroups (they skip the
-                // group walk) -- the weighted boolean graph has 750 groups and 7 000 rest tiles per colour
-                const int nrest_here = rest_in_general ? nlrest : 0;
-                const int rblocks = std::max(0, 8 * ((std::min(2560, (nrest_here + 3) / 4) + 7) / 8) - gblocks);
-                const int grid = gblocks + rblocks + hbl_ep;
-                hipStream_t st = general_aside ? cs.side(0) : g->stream;
-#define NSK_LEP(KERNEL, MAXC) KERNEL<VT, SMALLW, MAXC><<<dim3(grid), dim3(NSK_BLOCK), shmem, st>>>( \
-                    d, fb, fe, (int)g->c.phase_wb_base[ph], gt0, ntiles - gt0, ngroups, (int)g->c.phase_ep_base[ph], gblocks, \
-                    fe, he, hbl_ep, nbh, (int)g->c.phase_bighub_base[ph], lrest, rest_in_general ? nlrest : 0, lp)
+            lp.kstat = p.kstat ? 1 : 0;
+            if (p.general.on) {         // hubs, general tiles (as entry-parallel groups: L.ep) and the class's rest tiles
+                const GeneralLaunch &L = p.general;
+                const uint32_t *lrest = g->learn_rest_tiles + cl.lrest0;
+                hipStream_t st = cs.of(L.stream);
+#define NSK_LEP(KERNEL, MAXC) KERNEL<VT, SMALLW, MAXC><<<dim3(L.grid), dim3(NSK_BLOCK), shmem, st>>>( \
+                    d, cl.fb, cl.fe, cl.wb_base, L.tile0, L.ntiles, cl.ngroups, cl.group0, L.gblocks, \
+                    cl.fe, cl.he, L.hblocks, cl.nbh, cl.bh0, lrest, L.nrest, lp)
+#define NSK_LGEN(MAXC) k_learn_general<VT, SMALLW, MAXC><<<dim3(L.grid), dim3(NSK_BLOCK), shmem, st>>>( \
+                    d, cl.fb, cl.fe, cl.wb_base, L.tile0, L.ntiles, cl.fe, cl.he, L.hblocks, lrest, L.nrest, lp)
                 // (a colour's all-binary groups -- its tail: categorical lanes come first -- in a launch of their own with the
                 // two-candidate kernel, 114 vector registers and four waves per SIMD instead of 152 and three: 50M LR graph
                 // 5.57 -> 5.73e9 updates/s, 5M 5.13 -> 4.17e9 with the split forced (two tails per class); inference, 86 / 5
                 // against 102 / 4: 1.540 / 1.540e10 -- tools/sessions/r5_s24.sh; not kept)
-                if (one_lg) NSK_LEP(k_learn_ep_w4, 8); else NSK_LEP(k_learn_ep, 2);
+                if (L.ep) { if (L.capped) NSK_LEP(k_learn_ep_w4, 8); else NSK_LEP(k_learn_ep, 2); }
+                else if (L.maxc == 8) NSK_LGEN(8);
+                else NSK_LGEN(2);
+#undef NSK_LGEN
 #undef NSK_LEP
                 g->launches++;
             }
-            if (gtb > gt0 && !ep) {            // general tiles with categorical lanes
-                const int nt8 = one_lg ? ntiles - gt0 : gtb - gt0;
-                const int grid = 8 * ((std::min(NSK_LEARN_GENERAL_BLOCKS / 2, (nt8 + 3) / 4) + 7) / 8) + hbl;   // whole rounds of XCDs
-                k_learn_general<VT, SMALLW, 8><<<dim3(grid), dim3(NSK_BLOCK), shmem, (one_lg && !general_aside) ? g->stream : cs.side(0)>>>(
-                    d, fb, fe, (int)g->c.phase_wb_base[ph], gt0, nt8, fe, he, hbl, lrest,
-                    (rest_in_general && one_lg) ? nlrest : 0, lp);
-                g->launches++;
-            }
-            if (ntiles > gtb && !one_lg && !ep) {   // all-binary general tiles
-                const int hb2 = gtb > gt0 ? 0 : hbl;        // no categorical launch: the hubs come here
-                const int grid = 8 * ((std::min(NSK_LEARN_GENERAL_BLOCKS / 2, (ntiles - gtb + 3) / 4) + 7) / 8) + hb2;
-                k_learn_general<VT, SMALLW, 2><<<dim3(grid), dim3(NSK_BLOCK), shmem, general_aside ? cs.side(0) : g->stream>>>(
-                    d, fb, fe, (int)g->c.phase_wb_base[ph], gtb, ntiles - gtb, fe, he, hb2, lrest,
-                    (rest_in_general && !(one_lg)) ? nlrest : 0, lp);
-                g->launches++;
-            }
-            for (const Compiled::SegLaunch &sl : g->c.learn_seg) {       // homogeneous segments
-                if (sl.phase != (int)ph) continue;
+            for (const Compiled::SegLaunch *slp : classes[ph].segs) {       // homogeneous segments
+                const Compiled::SegLaunch &sl = *slp;
                 const bool use_tab = sl.tab && g->values_regular;
                 const NskLearnSegPlan &pl = learn_seg_plan(g, sl, use_tab, sizeof(VT) == 1);
                 const SegTable &tab = pl.tab;
@@ -330,24 +294,21 @@ int nsk_learn_chromatic(nsk_graph *g, int64_t nsweeps, double step, double decay
                 if (fuse) pend.valid = false;
                 g->launches++;
             }
-            if (nlrest > 0 && !rest_in_general) {   // the other uniform and shape tiles: descriptor-driven kernel
-                const int grid = std::min(NSK_LEARN_FAST_BLOCKS, (nlrest + 3) / 4);
-                k_learn_fast<VT, SMALLW><<<dim3(grid), dim3(NSK_BLOCK), shmem, g->stream>>>(
-                    d, fb, fe, (int)g->c.phase_wb_base[ph], g->learn_rest_tiles + g->c.phase_learn_rest_base[ph],
-                    nlrest, lp);
+            if (p.fast.on) {            // the other uniform and shape tiles: descriptor-driven kernel
+                k_learn_fast<VT, SMALLW><<<dim3(p.fast.grid), dim3(NSK_BLOCK), shmem, g->stream>>>(
+                    d, cl.fb, cl.fe, cl.wb_base, g->learn_rest_tiles + cl.lrest0, cl.nlrest, lp);
                 g->launches++;
             }
-            if (ndyn > 0) {             // tiles with per-lane headers: generic kernel, list mode
-                const int grid = std::min(NSK_LEARN_LIST_BLOCKS, (ndyn + 3) / 4);
-                k_learn_phase<VT, SMALLW, false><<<dim3(grid), dim3(NSK_BLOCK), shmem, g->stream>>>(
-                    d, fb, fe, g->dyn_tiles + g->c.phase_dyn_base[ph], ndyn, lp);
+            if (p.dyn.on) {             // tiles with per-lane headers: generic kernel, list mode
+                k_learn_phase<VT, SMALLW, false><<<dim3(p.dyn.grid), dim3(NSK_BLOCK), shmem, g->stream>>>(
+                    d, cl.fb, cl.fe, g->dyn_tiles + cl.dyn0, cl.ndyn, lp);
                 g->launches++;
             }
             cs.join();
-            if (nw > 0) {
+            if (p.update) {
                 if (pend.valid) { launch_update(pend); pend.valid = false; }     // the previous class's, not fused above
                 Pending u;
-                u.valid = true; u.set = set; u.tabs_here = tabs_here; u.kstat = kstat_here; u.ph = ph; u.step = step; u.aa = aa;
+                u.valid = true; u.set = set; u.tabs_here = tabs_here; u.kstat = p.kstat; u.ph = ph; u.step = step; u.aa = aa;
                 if (lag) pend = u;              // behind the next class
                 else launch_update(u);
             }
@@ -419,8 +380,6 @@ extern "C" int nsk_learn_sweeps(nsk_graph *g, int64_t nsweeps, double step, doub
                                  "use the sequential scan");
     HIPCHECK(hipSetDevice(g->device));
     { int frc = nsk_p2p_flush(g); if (frc) return frc; }
-    return g->c.vbytes == 1
-               ? learn_impl<int8_t>(g, nsweeps, step, decay, regularization, reg_param, truncation, learn_non_evidence)
-               : learn_impl<int32_t>(g, nsweeps, step, decay, regularization, reg_param, truncation, learn_non_evidence);
+    return NSK_BY_VT(g, learn_impl, g, nsweeps, step, decay, regularization, reg_param, truncation, learn_non_evidence);
 }
 #endif

@@ -173,6 +173,10 @@ def _small_graphs(golden):
         "gencat4": (_general_tile_graph(maxarity=4), False),
         "gencat4_vid": (_general_tile_graph(maxarity=4), True),
         "gencat4_i32": (_general_tile_graph(wide_values=True, maxarity=4), True),
+        # the two kinds of colour class no graph above has (tests/test_class_launches_gpu.py): hubs in the launch of
+        # all-binary general tiles; one-lane generic kernels
+        "boolw_hub": (_boolw_hub(), False),
+        "generic_lanes": (_generic_lane_graph(), False),
     }
 
 
@@ -268,6 +272,49 @@ def _boolw():
     return tuple(g)
 
 
+def _boolw_hub():
+    """the weighted boolean graph (all-binary general tiles) with one hub: variable 0 under 40 more EQUAL factors -- a
+    colour class whose hubs ride in the launch of its binary general tiles"""
+    from numbskull_amd.numbskulltypes import Weight, Factor, FactorToVar
+    w, var, fac, fm, dm, nedge = _boolw()
+    nhub = 40
+    factor = np.zeros(len(fac) + nhub, Factor)
+    factor[:len(fac)] = fac
+    fmap = np.zeros(nedge + 2 * nhub, FactorToVar)
+    fmap[:nedge] = fm
+    for i in range(nhub):
+        factor[len(fac) + i] = (3, len(w) + i % 5, 1.0, 2, nedge + 2 * i)
+        fmap["vid"][nedge + 2 * i:nedge + 2 * i + 2] = (0, 1000 + 7 * i)
+    weight = np.zeros(len(w) + 5, Weight)
+    weight[:len(w)] = w
+    weight["initialValue"][len(w):] = (0.1, -0.2, 0.15, 0.05, -0.1)
+    return weight, var, factor, fmap, dm, nedge + 2 * nhub
+
+
+def _generic_lane_graph():
+    """one colour of more variables than get a wave each (32768), of a cardinality beyond the general tiles: the
+    one-lane generic kernels.  Every variable under one EQUAL-to-a-value prior; 3 free weights"""
+    from numbskull_amd.numbskulltypes import Weight, Variable, Factor, FactorToVar
+    rng = np.random.default_rng(31)
+    nvar = 32768 + 64
+    variable = np.zeros(nvar, Variable)
+    variable["cardinality"] = 12
+    variable["isEvidence"] = rng.random(nvar) < 0.5
+    variable["initialValue"] = rng.integers(0, 12, nvar)
+    factor = np.zeros(nvar, Factor)
+    factor["factorFunction"] = 4
+    factor["weightId"] = np.arange(nvar) % 3
+    factor["featureValue"] = 1.0
+    factor["arity"] = 1
+    factor["ftv_offset"] = np.arange(nvar)
+    fmap = np.zeros(nvar, FactorToVar)
+    fmap["vid"] = np.arange(nvar)
+    fmap["dense_equal_to"] = rng.integers(0, 12, nvar)
+    weight = np.zeros(3, Weight)
+    weight["initialValue"] = (0.3, -0.2, 0.1)
+    return weight, variable, factor, fmap, np.zeros(nvar, np.bool_), nvar
+
+
 def _pairs_many_weights():
     """pair model with one weight per pair for the EQUAL factors (600 weights): uniform tiles are
     impossible (every lane has its own weight id) -> per-lane-header tiles in learning"""
@@ -303,9 +350,10 @@ def _big_cardinality_graph():
 GRAPHS = ["grid4x5", "grid32", "mixed", "lf", "headquirk", "headquirk_vid", "pairs", "grid57x33",
           "lr3000", "lr_bigcard", "lr_manyw", "pairs_manyw", "boolw", "hubs", "gencat", "gencat_vid",
           "gencat_bigw", "gencat_i32", "lr_selfdup", "gencat4", "gencat4_vid", "gencat4_i32"]
+CLASS_GRAPHS = ["boolw_hub", "generic_lanes"]      # (beside GRAPHS: the per-feature suites that walk GRAPHS stay as they are)
 
 
-@pytest.mark.parametrize("name", GRAPHS)
+@pytest.mark.parametrize("name", GRAPHS + CLASS_GRAPHS)
 @pytest.mark.parametrize("sample_evidence", [True, False])
 def test_chromatic_inference_equals_oracle(golden, name, sample_evidence):
     g, hbv = _small_graphs(golden)[name]
@@ -333,7 +381,7 @@ def test_chromatic_inference_equals_oracle(golden, name, sample_evidence):
 @pytest.mark.parametrize("name", ["mixed", "lf", "pairs", "grid32", "lr3000", "lr_bigcard",
                                   "headquirk", "lr_manyw", "pairs_manyw", "boolw", "hubs", "gencat",
                                   "gencat_vid", "gencat_i32", "lr_selfdup", "gencat4", "gencat4_vid",
-                                  "gencat4_i32"])
+                                  "gencat4_i32"] + CLASS_GRAPHS)
 @pytest.mark.parametrize("reg,trunc", [(0, 1), (1, 1), (1, 3), (2, 1)])
 @pytest.mark.parametrize("lne", [False, True])
 def test_chromatic_learning_equals_oracle(golden, name, reg, trunc, lne):
