@@ -317,6 +317,9 @@ static int gibbs_impl(nsk_graph *g, int64_t nsweeps, int sample_evidence, int bu
             plans[ph] = plan_gibbs_class(shapes[ph], opts);
         }
         for (int64_t s = 0; s < nsweeps; s++) {
+            // uint8 tally: folded BEFORE the sweep that would take a byte past 255, whatever left the residue -- sweeps of
+            // this loop or, from an earlier call, replays that stopped at 255 exactly (nsk_gibbs_run folds the same way)
+            if (!burnin && g->pos_tally_sweeps >= 255) nsk_fold_position_tally(g);
             if (g->pack_now && !burnin && g->packed_sweeps >= 127) (void)nsk_unpack_tally(g);       // 7 tally bits per value byte
             if (g->p2p.fused_now) ++g->p2p.tag;            // the exchange rides in this sweep's table launches
             const EagerSweep<VT> w{g, d, sample_evidence, burnin, CounterSrc::eager(g)};
@@ -344,7 +347,7 @@ static int gibbs_impl(nsk_graph *g, int64_t nsweeps, int sample_evidence, int bu
             }
             g->sweep++;
             if (!burnin && g->pack_now) g->packed_sweeps++;
-            if (!burnin && ++g->pos_tally_sweeps == 255) nsk_fold_position_tally(g);   // uint8 tally is full
+            if (!burnin) g->pos_tally_sweeps++;
         }
         HIPCHECK(hipGetLastError());
     }

@@ -1755,7 +1755,7 @@ __device__ __forceinline__ void wide_finish(const DevGraph<signed char> &g, uint
     if (MODE == 2) *vq = (t.tally & 0xFEFEFEFEu) + 3u * out;
     else {
         *vq = out;
-        if (MODE == 0) *(uint32_t *)((char *)g.cnt_pos + ((uint32_t)p0 + 4u * (uint32_t)lane)) = t.tally + out;   // (four byte tallies: folded before one reaches 255)
+        if (MODE == 0) *(uint32_t *)((char *)g.cnt_pos + ((uint32_t)p0 + 4u * (uint32_t)lane)) = t.tally + out;   // (four byte tallies: folded before one would pass 255, so no add carries)
     }
     }
 }
