@@ -556,6 +556,73 @@ int nsk_graph_plan_needs(const nsk_graph_desc *desc, int64_t *count, int32_t *vi
 int nsk_graph_plan_routes(const nsk_graph_desc *desc, int32_t *route /* nvar */);
 int nsk_graph_get_routes(nsk_graph *g, int32_t *route /* nvar */);
 
+/* Class plans: the launches a sweep would give every colour class, host-only from a plan -- one record of NSK_CLASS_REC
+ * int32 per class, filled from the functions the sweep drivers launch from (csrc/nsk_class_plan.h) under the options
+ * they would pass.  `learning` != 0: the learning sweep under `regularization`, else the inference sweep.  `grid_cap`
+ * is what the drivers read from NSK_CLASS_GRID_CAP (NSK_DIAG=1): 0 none, else at most that many blocks (whole rounds of
+ * XCDs where the launch has them) for every persistent grid whose waves walk their items in trips -- taken as an
+ * argument, not from the environment; the other diagnostic switches (NSK_NO_OVERLAP, NSK_EP_PER_CU) count as in a sweep.
+ * `rec` may be NULL (query): *nclass gets the number of classes either way.  A launch that is off leaves its fields 0.
+ *   [NSK_CLS_SKIP]     learning: an empty class (no launch, no update)
+ *   the general launch, k_gibbs_general / k_gibbs_ep* or k_learn_general / k_learn_ep*:
+ *   [NSK_CLS_GEN_ON] [NSK_CLS_GEN_ITEMS] groups (entry-parallel) or general tiles  [NSK_CLS_GEN_GRID]
+ *   [NSK_CLS_GEN_STREAM] -1 the handle's stream, 0 .. 2 a side stream  [NSK_CLS_GEN_EP] entry-parallel kernels
+ *   [NSK_CLS_GEN_MAXC] 8 or 2 candidate values  [NSK_CLS_GEN_CAPPED] the register-capped twin
+ *   [NSK_CLS_GEN_TILE0] [NSK_CLS_GEN_NTILES] its general tiles, relative to the class's first tile
+ *   [NSK_CLS_GEN_HBLOCKS] hub blocks in front (long-list hubs first)  [NSK_CLS_GEN_GBLOCKS] tile / group blocks
+ *   [NSK_CLS_GEN_RBLOCKS] blocks behind them for rest tiles only  [NSK_CLS_GEN_NREST] rest tiles the launch samples
+ *   [NSK_CLS_GEN_BEHIND] enqueued behind the generic kernel's fork  [NSK_CLS_GEN_NBLOCKS] blocks the tiles need, 4 each
+ *   the simple launches, four fields each -- on, items, grid, stream -- from:
+ *   [NSK_CLS_GENERIC]  generic lanes: positions (inference), items of 64 positions (learning, k_learn_phase range mode)
+ *   [NSK_CLS_HEAVY]    learning: hubs in a launch of their own (k_learn_heavy)
+ *   [NSK_CLS_FAST]     rest tiles (k_gibbs_fast) / learn-rest tiles (k_learn_fast) no general launch took
+ *   [NSK_CLS_DYN]      learning: tiles with per-lane headers (k_learn_phase list mode)
+ *   the shape of the class:
+ *   [NSK_CLS_NHUB] hubs  [NSK_CLS_NBH] of them long-list  [NSK_CLS_NGROUPS]  [NSK_CLS_NDYN]  [NSK_CLS_NLREST] learn-rest
+ *   tiles  [NSK_CLS_NREST] rest tiles (inference)  [NSK_CLS_NGENERIC] generic positions  [NSK_CLS_NTILES] tiles
+ *   [NSK_CLS_FB] [NSK_CLS_FE] [NSK_CLS_HE] [NSK_CLS_E] positions: tiles [fb, fe), hubs [fe, he), generic lanes [he, e)
+ *   [NSK_CLS_KSTAT] learning: structural visit counts  [NSK_CLS_UPDATE] learning: a weight update follows
+ *   [NSK_CLS_SEGMENTS] the class has segment launches  [NSK_CLS_SEG_TILES] learning: tiles in them */
+#define NSK_CLASS_REC 48
+#define NSK_CLS_SKIP 0
+#define NSK_CLS_GEN_ON 1
+#define NSK_CLS_GEN_ITEMS 2
+#define NSK_CLS_GEN_GRID 3
+#define NSK_CLS_GEN_STREAM 4
+#define NSK_CLS_GEN_EP 5
+#define NSK_CLS_GEN_MAXC 6
+#define NSK_CLS_GEN_CAPPED 7
+#define NSK_CLS_GEN_TILE0 8
+#define NSK_CLS_GEN_NTILES 9
+#define NSK_CLS_GEN_HBLOCKS 10
+#define NSK_CLS_GEN_GBLOCKS 11
+#define NSK_CLS_GEN_RBLOCKS 12
+#define NSK_CLS_GEN_NREST 13
+#define NSK_CLS_GEN_BEHIND 14
+#define NSK_CLS_GEN_NBLOCKS 15
+#define NSK_CLS_GENERIC 16
+#define NSK_CLS_HEAVY 20
+#define NSK_CLS_FAST 24
+#define NSK_CLS_DYN 28
+#define NSK_CLS_NHUB 32
+#define NSK_CLS_NBH 33
+#define NSK_CLS_NGROUPS 34
+#define NSK_CLS_NDYN 35
+#define NSK_CLS_NLREST 36
+#define NSK_CLS_NREST 37
+#define NSK_CLS_NGENERIC 38
+#define NSK_CLS_NTILES 39
+#define NSK_CLS_FB 40
+#define NSK_CLS_FE 41
+#define NSK_CLS_HE 42
+#define NSK_CLS_E 43
+#define NSK_CLS_KSTAT 44
+#define NSK_CLS_UPDATE 45
+#define NSK_CLS_SEGMENTS 46
+#define NSK_CLS_SEG_TILES 47
+int nsk_graph_plan_classes(const nsk_graph_desc *desc, int learning, int regularization, int grid_cap,
+                           int32_t *rec /* NSK_CLASS_REC * classes */, int64_t *nclass);
+
 /* HIP-event bracket on the library's stream: elapsed ms and number of sweep-kernel launches
  * between begin and end (bench.py's roofline leg). */
 int nsk_profile_begin(nsk_graph *g);

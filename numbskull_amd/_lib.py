@@ -23,7 +23,7 @@ BUF_VALUE, BUF_VALUE_EVID, BUF_WEIGHT, BUF_SEND, BUF_RECV, BUF_SEND_EVID, BUF_RE
 SYMBOLS = (
     "nsk_graph_create", "nsk_graph_destroy", "nsk_state_upload", "nsk_state_download",
     "nsk_set_seed", "nsk_set_rng_tag", "nsk_set_scan", "nsk_set_learn_cap", "nsk_set_learn_lag", "nsk_gibbs_sweeps", "nsk_learn_sweeps", "nsk_graph_get_info",
-    "nsk_graph_get_colors", "nsk_graph_get_layout", "nsk_graph_get_generators", "nsk_graph_get_weight_slots", "nsk_graph_plan", "nsk_graph_plan_needs", "nsk_graph_plan_routes", "nsk_graph_get_routes", "nsk_profile_begin", "nsk_profile_end", "nsk_device_buffer",
+    "nsk_graph_get_colors", "nsk_graph_get_layout", "nsk_graph_get_generators", "nsk_graph_get_weight_slots", "nsk_graph_plan", "nsk_graph_plan_needs", "nsk_graph_plan_routes", "nsk_graph_get_routes", "nsk_graph_plan_classes", "nsk_profile_begin", "nsk_profile_end", "nsk_device_buffer",
     "nsk_set_stream", "nsk_synchronize", "nsk_ghost_needs", "nsk_exchange_setup", "nsk_exchange_pack",
     "nsk_exchange_unpack", "nsk_comm_unique_id", "nsk_comm_init", "nsk_gibbs_sweeps_exchange",
     "nsk_learn_sweeps_exchange", "nsk_pf_setup", "nsk_p2p_setup", "nsk_p2p_export", "nsk_p2p_import", "nsk_p2p_import_local",
@@ -75,6 +75,23 @@ def route_fields(r):
     return {"kind": r & 15, "own_entries": (r >> 4) & 31, "own_width": (r >> 9) & 7, "tile_entries": (r >> 12) & 31,
             "tile_width": (r >> 17) & 7, "two_pass": (r >> 20) & 1, "null_word": (r >> 21) & 1,
             "hub_ep": (r >> 22) & 1, "hub_block": (r >> 23) & 1}
+
+
+# the class record of nsk_graph_plan_classes (include/numbskull_amd.h "Class plans"): CLASS_REC int32 per colour class
+CLASS_REC = 48
+CLASS_FIELDS = ("skip", "gen_on", "gen_items", "gen_grid", "gen_stream", "gen_ep", "gen_maxc", "gen_capped", "gen_tile0",
+                "gen_ntiles", "gen_hblocks", "gen_gblocks", "gen_rblocks", "gen_nrest", "gen_behind", "gen_nblocks",
+                "generic_on", "generic_n", "generic_grid", "generic_stream", "heavy_on", "heavy_n", "heavy_grid", "heavy_stream",
+                "fast_on", "fast_n", "fast_grid", "fast_stream", "dyn_on", "dyn_n", "dyn_grid", "dyn_stream",
+                "nhub", "nbh", "ngroups", "ndyn", "nlrest", "nrest", "ngeneric", "ntiles", "fb", "fe", "he", "e",
+                "kstat", "update", "segments", "seg_tiles")
+assert len(CLASS_FIELDS) == CLASS_REC
+
+
+def class_fields(rec):
+    """The fields of class records (one record, or an array of them: the last axis), by name."""
+    rec = np.asarray(rec)
+    return {k: rec[..., i] for i, k in enumerate(CLASS_FIELDS)}
 
 
 _lib = None
@@ -147,6 +164,7 @@ def lib():
         L.nsk_graph_plan_needs.argtypes = [C.POINTER(GraphDesc), C.POINTER(C.c_int64), C.c_void_p]
         L.nsk_graph_plan_routes.argtypes = [C.POINTER(GraphDesc), C.c_void_p]
         L.nsk_graph_get_routes.argtypes = [C.c_void_p, C.c_void_p]
+        L.nsk_graph_plan_classes.argtypes = [C.POINTER(GraphDesc), C.c_int, C.c_int, C.c_int, C.c_void_p, C.POINTER(C.c_int64)]
         L.nsk_profile_begin.argtypes = [C.c_void_p]
         L.nsk_profile_end.argtypes = [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_int64)]
         L.nsk_device_buffer.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_void_p),

@@ -18,6 +18,7 @@
 #include <vector>
 
 #include "nsk_internal.h"
+#include "nsk_class_plan.h"
 #include "nsk_kernels_learn.h"
 #include "nsk_kernels_misc.h"
 
@@ -873,6 +874,31 @@ int nsk_graph_plan_routes(const nsk_graph_desc *desc, int32_t *route) {
     int rc = compile_graph(desc, c, err);
     if (rc) return fail(rc, err);
     compiled_routes(c, route, nullptr);
+    return NSK_OK;
+}
+
+int nsk_graph_plan_classes(const nsk_graph_desc *desc, int learning, int regularization, int grid_cap, int32_t *rec, int64_t *nclass) {
+    if (!desc || !nclass || grid_cap < 0) return fail(NSK_E_INVALID, "null argument or negative grid cap");
+    Compiled c;
+    std::string err;
+    int rc = compile_graph(desc, c, err);
+    if (rc) return fail(rc, err);
+    *nclass = c.phase_start.empty() ? 0 : (int64_t)c.phase_start.size() - 1;
+    if (!rec) return NSK_OK;
+    // what gibbs_impl / nsk_learn_chromatic put into the options (nsk_gibbs.hip, nsk_learn.hip), from the layout alone
+    PlanOpts opts;
+    opts.overlap = nsk::diag_env("NSK_NO_OVERLAP") == nullptr;
+    opts.ep_per_cu = plan_per_cu(nsk::diag_env("NSK_EP_PER_CU"));
+    opts.grid_cap = std::min(grid_cap, 1 << 20);
+    if (learning) {
+        opts.smallw = c.nweight > 0 && c.nweight <= NSK_SMALLW;
+        opts.nweight = c.nweight;
+        opts.has_kstat = !c.ep_kstat.empty();
+        opts.regularization = regularization;
+    } else {
+        opts.value_bytes = (size_t)c.nid * (size_t)c.vbytes;
+    }
+    compiled_class_records(c, learning != 0, opts, rec);
     return NSK_OK;
 }
 

@@ -68,8 +68,14 @@ struct PlanOpts {
     bool has_kstat = false;         // the layout has structural visit counts (ep_kstat)
     int regularization = 0;
     int seg_tiles = 0;              // tiles of the class's segment launches (Compiled::learn_seg)
+    // diagnostic (NSK_CLASS_GRID_CAP): the limit of every persistent grid that walks its items in trips is at most this
+    // many blocks (rounded up to whole rounds of XCDs where the launch is), 0: no cap.  The grid is no part of the
+    // semantics: small classes then take the later trips that only very large ones take otherwise (tests/class_trips.py)
+    int grid_cap = 0;
 };
 static inline int plan_per_cu(const char *env) { return env ? std::max(1, std::min(32, atoi(env))) : 0; }
+static inline int plan_grid_cap(const char *env) { return env ? std::max(1, std::min(1 << 20, atoi(env))) : 0; }
+static inline int plan_cap(const PlanOpts &o, int limit) { return o.grid_cap > 0 ? std::min(o.grid_cap, limit) : limit; }
 
 // One launch of a general-tile family -- k_gibbs_general / k_gibbs_ep*, k_learn_general / k_learn_ep*: the general tiles
 // [tile0, tile0 + ntiles) of the class; in front of them `hblocks` blocks for its hubs (0: not in this launch), behind
@@ -115,7 +121,7 @@ static inline GibbsClassPlan plan_gibbs_class(const ClassShape &s, const PlanOpt
         L.capped = L.maxc == 8 && o.value_bytes <= ((size_t)24 << 20);
         L.tile0 = s.gt0; L.ntiles = s.ntiles - s.gt0;
         L.hblocks = s.nbh + hubs;
-        L.gblocks = plan_rounds(std::min(s.ngroups, 256 * (o.ep_per_cu ? o.ep_per_cu : 7)));
+        L.gblocks = plan_rounds(std::min(s.ngroups, plan_cap(o, 256 * (o.ep_per_cu ? o.ep_per_cu : 7))));
         L.nrest = s.nrest;
     } else if (tiles && s.gtb > s.gt0) {
         // a class with categorical tiles walks ALL its general tiles in one launch of the 8-candidate kernel, on the
@@ -180,10 +186,10 @@ static inline LearnClassPlan plan_learn_class(const ClassShape &s, const PlanOpt
         p.generic.on = true;
         p.generic.stream = plan_stream(o, PLAN_SIDE1);
         p.generic.n = (s.e - s.he + 63) / 64;
-        p.generic.grid = std::min(PLAN_LEARN_GEN_BLOCKS, plan_quarter(p.generic.n));
+        p.generic.grid = std::min(plan_cap(o, PLAN_LEARN_GEN_BLOCKS), plan_quarter(p.generic.n));
     }
     // hubs ride as extra blocks of a general-tile launch when the class has one
-    const int hubs = std::min(PLAN_LEARN_HEAVY_BLOCKS, plan_quarter(s.he - s.fe));
+    const int hubs = std::min(plan_cap(o, PLAN_LEARN_HEAVY_BLOCKS), plan_quarter(s.he - s.fe));
     const bool hubs_in_general = (s.gtb > s.gt0 || s.ntiles > s.gtb) && s.he > s.fe;
     if (s.he > s.fe && !hubs_in_general) {      // ... else one wave per variable in a launch of their own
         p.heavy.on = true;
@@ -219,14 +225,14 @@ static inline LearnClassPlan plan_learn_class(const ClassShape &s, const PlanOpt
             // the 50M graph are of the second kind).
             const int per_cu = o.ep_per_cu ? o.ep_per_cu : (s.ngroups >= 4 * 2560 ? 10 : 7);
             L.capped = L.maxc == 8;
-            L.gblocks = plan_rounds(std::min(256 * per_cu, s.ngroups));
+            L.gblocks = plan_rounds(std::min(plan_cap(o, 256 * per_cu), s.ngroups));
             L.hblocks += s.nbh;             // a block per long-list hub
             // the rest tiles (shape tiles: graphs with individual weights) are walked by all of these workgroups, one
             // wave per tile: when the groups alone bring too few, more workgroups (they skip the group walk) -- the
             // weighted boolean graph has 750 groups and 7 000 rest tiles per colour
-            L.rblocks = std::max(0, plan_rounds(std::min(2560, plan_quarter(L.nrest))) - L.gblocks);
+            L.rblocks = std::max(0, plan_rounds(std::min(plan_cap(o, 2560), plan_quarter(L.nrest))) - L.gblocks);
         } else {
-            L.gblocks = plan_rounds(std::min(PLAN_LEARN_GENERAL_BLOCKS / 2, L.nblocks));
+            L.gblocks = plan_rounds(std::min(plan_cap(o, PLAN_LEARN_GENERAL_BLOCKS / 2), L.nblocks));
         }
         L.grid = L.hblocks + L.gblocks + L.rblocks;
     }
@@ -235,15 +241,20 @@ static inline LearnClassPlan plan_learn_class(const ClassShape &s, const PlanOpt
     if (s.nlrest > 0 && !rest_in_general) {     // the other uniform and shape tiles: descriptor-driven kernel
         p.fast.on = true;
         p.fast.n = s.nlrest;
-        p.fast.grid = std::min(PLAN_LEARN_FAST_BLOCKS, plan_quarter(s.nlrest));
+        p.fast.grid = std::min(plan_cap(o, PLAN_LEARN_FAST_BLOCKS), plan_quarter(s.nlrest));
     }
     if (s.ndyn > 0) {
         p.dyn.on = true;
         p.dyn.n = s.ndyn;
-        p.dyn.grid = std::min(PLAN_LEARN_LIST_BLOCKS, plan_quarter(s.ndyn));
+        p.dyn.grid = std::min(plan_cap(o, PLAN_LEARN_LIST_BLOCKS), plan_quarter(s.ndyn));
     }
     p.update = o.nweight > 0;
     return p;
 }
+
+// The plans of every class as the int32 records of nsk_graph_plan_classes (nsk_class_records.cpp): `opts` as a sweep
+// driver fills them but for what it sets per class (seg_tiles; ep_per_cu, which counts from the first class laid out as
+// groups on); rec[NSK_CLASS_REC * classes].
+void compiled_class_records(const Compiled &c, bool learning, const PlanOpts &opts, int32_t *rec);
 
 }  // namespace nsk

@@ -310,6 +310,7 @@ static int gibbs_impl(nsk_graph *g, int64_t nsweeps, int sample_evidence, int bu
         PlanOpts opts;
         opts.overlap = !g->no_overlap;
         opts.value_bytes = (size_t)g->c.nid * (size_t)g->c.vbytes;
+        opts.grid_cap = plan_grid_cap(nsk::diag_env("NSK_CLASS_GRID_CAP"));     // (diagnostic: a small group grid, later trips)
         for (size_t ph = 0; ph < nphase; ph++) {
             shapes[ph] = class_shape(g->c, ph);
             if (shapes[ph].ep && shapes[ph].fe > shapes[ph].fb)

@@ -194,6 +194,7 @@ int nsk_learn_chromatic(nsk_graph *g, int64_t nsweeps, double step, double decay
     PlanOpts opts;
     opts.overlap = !g->no_overlap;
     opts.smallw = SMALLW; opts.nweight = nw; opts.has_kstat = dv[0].ep_kstat != nullptr; opts.regularization = regularization;
+    opts.grid_cap = plan_grid_cap(nsk::diag_env("NSK_CLASS_GRID_CAP"));     // (diagnostic: small persistent grids, later trips)
     for (size_t ph = 0; ph < nphase; ph++) {
         LearnClass &c = classes[ph];
         c.s = class_shape(g->c, ph);

@@ -156,6 +156,19 @@ class FactorGraph(object):
         _lib.check(_lib.lib().nsk_graph_plan_routes(C.byref(desc), _lib.ptr(out)))
         return out
 
+    def plan_classes(self, learning, regularization=2, grid_cap=0):
+        """Host-only: the launches a sweep would give every colour class (nsk_graph_plan_classes), one int32 record per
+        class -- ``_lib.class_fields`` names the fields.  ``learning``: the learning sweep under ``regularization``, else
+        the inference sweep; ``grid_cap``: what a sweep reads from NSK_CLASS_GRID_CAP (0: none)."""
+        desc, keep = self._descriptor()
+        n = C.c_int64()
+        L = _lib.lib()
+        _lib.check(L.nsk_graph_plan_classes(C.byref(desc), int(bool(learning)), int(regularization), int(grid_cap), None, C.byref(n)))
+        out = np.zeros((n.value, _lib.CLASS_REC), np.int32)
+        _lib.check(L.nsk_graph_plan_classes(C.byref(desc), int(bool(learning)), int(regularization), int(grid_cap),
+                                            _lib.ptr(out), C.byref(n)))
+        return out
+
     def routes(self):
         """The route word of every variable on this handle's compiled layout (nsk_graph_get_routes)."""
         out = np.zeros(self.variable.shape[0], np.int32)

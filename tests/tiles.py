@@ -58,9 +58,11 @@ def cyc(n, others, card=3, fns=None, **kw):
     return tuple(ent(fns[i % len(fns)], oth[i], **kw) for i in range(n))
 
 
-def tile_graph(families, nweight=30, wide=False, pad_front=0, seed=0):
+def tile_graph(families, nweight=30, wide=False, pad_front=0, seed=0, max_vars=4200):
     """families: [(size, Target)].  ``pad_front``: isolated binary evidence variables in front of everything (the
-    literal head lookup reads var_value[edge index]: the case that uses it keeps every edge index among them)."""
+    literal head lookup reads var_value[edge index]: the case that uses it keeps every edge index among them).
+    ``max_vars``: what the graph may not outgrow -- the cases of this module stay small; tests/class_trips.py builds
+    whole colour classes of tiles with the same builder."""
     rng = np.random.default_rng(seed)
     cards, dtypes, evid = [2] * pad_front, [0] * pad_front, [1] * pad_front
     fn_, members_, deos_ = [], [], []
@@ -120,7 +122,7 @@ def tile_graph(families, nweight=30, wide=False, pad_front=0, seed=0):
     weight = np.zeros(nw, Weight)
     weight["initialValue"] = rng.normal(0, 0.3, nw)
     weight["isFixed"][::5] = True
-    assert nvar <= 4200, nvar
+    assert nvar <= max_vars, nvar
     assert pad_front == 0 or nedge <= pad_front, (nedge, pad_front)
     return (weight, variable, factor, fmap, np.zeros(nvar, np.bool_), nedge), targets
 
@@ -317,16 +319,18 @@ def learn_cfgs(name):
     return "ABCDEF"
 
 
-def build_case(name, nweight=None, learn=None):
+def build_case(name, nweight=None, learn=None, case=None, max_vars=4200):
     """((weight, ...), targets per family).  ``nweight``: overrides the case's weights (shared weights drawn in turn
     make no exact class of 64 either, so a shape case keeps its shape tiles: check_case says so each time).  ``learn``: None, or the learn_non_evidence flag of a learning test -- every other
     target of a family becomes evidence (both halves of the structural visit counts; without learn_non_evidence only
     the evidence half is visited).  A shape class is keyed by the evidence flag, so a case with shape tiles makes every
-    target evidence without learn_non_evidence and none with it."""
-    cs = CASES[name]
+    target evidence without learn_non_evidence and none with it.  ``case``: a Case of the caller's own, seeded by
+    ``name`` (tests/class_trips.py)."""
+    cs = CASES[name] if case is None else case
     seed = sum(ord(ch) * (i + 1) for i, ch in enumerate(name)) + SALT
     nw = cs.nweight if nweight is None else nweight
-    g, targets = tile_graph([(s, t) for s, t, _ in cs.families], nweight=nw, wide=cs.wide, pad_front=cs.pad_front, seed=seed)
+    g, targets = tile_graph([(s, t) for s, t, _ in cs.families], nweight=nw, wide=cs.wide, pad_front=cs.pad_front, seed=seed,
+                            max_vars=max_vars)
     if learn is not None:
         shapes = any(e.get("kind") == SHAPE for _, _, e in cs.families)
         for fam in targets:
