@@ -720,7 +720,7 @@ int nsk_set_chains(nsk_graph *g, int nchains) {
     g->values_regular = g->chain_regular[0] && g->chain_regular[1] && g->chains_regular;
     g->pos_tally_sweeps = 0;
     g->cnt_dirty = false;
-    g->seg_plans_key = -1;                  // (the plans check the arrays' offsets from the value array)
+    g->seg_plans_valid = false;                  // (the plans check the arrays' offsets from the value array)
     nsk_drop_sweep_graph(g);                // (captured launches hold the old arrays' addresses)
     return NSK_OK;
 }

@@ -2,6 +2,8 @@
 // class's plan and issue its launches; the decisions -- kernel variant, tile range, hub / group / rest blocks, grid,
 // stream -- are made here, once per call, from the layout and a handful of options.  Host only and pure: no HIP type, no
 // environment variable, nothing of the handle (tests/test_class_plan_cpu.py pins the plans down without a GPU).
+// The segment launches of a class -- which segments share one, their tables and grids -- are planned beside this, by the
+// same rule: nsk_seg_plan.h.
 // Invariant: every hub, general tile, rest tile, generic position (and, in learning, learn-rest and per-lane-header
 // tile) of a class is sampled by exactly one launch of its plan, and every grid is the sum of its parts.
 #pragma once
@@ -101,7 +103,7 @@ static inline int plan_stream(const PlanOpts &o, PlanStream side) { return o.ove
 struct GibbsClassPlan {
     GeneralLaunch general;          // k_gibbs_ep* (general.ep) or k_gibbs_general<maxc>
     SimpleLaunch generic;           // k_gibbs_phase over positions [he, e)
-    bool segments = false;          // the class's prepared segment launches (nsk_graph::seg_plans), main stream
+    bool segments = false;          // the class's segment launches (nsk_seg_plan.h plan_segments), main stream
     SimpleLaunch fast;              // k_gibbs_fast over the rest tiles no general launch took
 };
 

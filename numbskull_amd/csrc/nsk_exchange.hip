@@ -389,7 +389,7 @@ static int p2p_fuse_plan(nsk_graph *g) {
     g->p2p.border_tiles.swap(tiles);
     g->p2p.ghost_lo = ghost_lo;
     g->p2p.fused = true;
-    g->seg_plans_key = -1;          // the segment plans split at the border tiles
+    g->seg_plans_valid = false;          // the segment plans split at the border tiles
     return NSK_OK;
 }
 
@@ -638,7 +638,7 @@ int nsk_p2p_fuse(nsk_graph *g, int on) {
     } else if (g->p2p.fused) {
         g->p2p.fused = false;
         g->p2p.border_tiles.clear();
-        g->seg_plans_key = -1;
+        g->seg_plans_valid = false;
     }
     nsk_drop_sweep_graph(g);
     return g->p2p.fused ? 1 : 0;

@@ -11,157 +11,47 @@
 
 using namespace nsk;
 
-// hot arguments of k_gibbs_seg_tabw (nsk_kernels_gibbs.h NSK_TABW_HOT): the other arrays as 256-byte units from `val`
-static inline int tabw_delta(const void *p, const void *base) {
-    const long long d = (const char *)p - (const char *)base;
-    return (int)(d / 256);            // (device allocations are 256-byte aligned: checked once in nsk_ensure_seg_plans)
+// The arrays the wide-quad kernels address as 256-byte units from `val` (nsk_kernels_gibbs.h NSK_TABW_HOT): does p lie
+// whole units from it that fit 32 bits -- `shift` units further down for the last chain of a batched launch?  (Device
+// allocations are 256-byte aligned.)
+static inline long long val_units(const nsk_graph *g, const void *p) { return ((const char *)p - (const char *)g->val) / 256; }
+static bool val_offset_fits(const nsk_graph *g, const void *p, long long shift = 0) {
+    const long long u = val_units(g, p) - shift;
+    return ((const char *)p - (const char *)g->val) % 256 == 0 && u > -(1ll << 31) && u < (1ll << 31);
 }
-#define NSK_TABW_HOT_ARGS(G, T, NB, NF, SB) (signed char *)(G)->val, tabw_delta((G)->cnt_pos, (G)->val), tabw_delta((G)->seg_wide, (G)->val),            \
-        tabw_delta((G)->ztab, (G)->val), (T).e[1].tile_start, (T).e[0].ntiles_lead, (T).e[0].pos0, (T).e[0].wide_off, (T).e[0].zoff,             \
+#define NSK_TABW_HOT_ARGS(G, T, NB, NF, SB) (signed char *)(G)->val, (int)val_units(G, (G)->cnt_pos), (int)val_units(G, (G)->seg_wide),            \
+        (int)val_units(G, (G)->ztab), (T).e[1].tile_start, (T).e[0].ntiles_lead, (T).e[0].pos0, (T).e[0].wide_off, (T).e[0].zoff,                \
         (uint32_t)(T).ntiles | ((uint32_t)((T).n - 1) << 28),                                                                                    \
         ((T).e[0].zmask_ev & 0xFFu) | ((uint32_t)(((NB) >> 3) * (NSK_BLOCK / 64)) << 8) | ((uint32_t)(NF) << 24),                                \
         (const unsigned long long *)(SB)
 
-// The segment launches of every colour, prepared once and kept in the handle (a small graph's sweep is two
-// 4 us kernels: rebuilding the tables per sweep made the host the bottleneck): segments batched by (kind,
-// chunks) into tables of <= NSK_SEG_MAX; kind 8 = segments with draw tables (any function: the table encodes
-// it).  A handle that exchanges its boundary inside the table launches (p2p_fused) gets its segments split
-// into runs of border tiles (SegEntry.push_off = their first row in the push map) and runs of interior tiles.
-void nsk_ensure_seg_plans(nsk_graph *g, int sample_evidence) {
-    const size_t nphase = g->c.phase_start.size() - 1;
-    std::vector<std::vector<NskSegPlan>> &seg_plans = g->seg_plans;
-    const int plans_key = (sample_evidence ? 1 : 0) | (g->values_regular ? 2 : 0) | (g->p2p.fused ? 4 : 0);
-    if (g->seg_plans_key == plans_key) return;
-    g->seg_plans_key = plans_key;
-    seg_plans.assign(nphase, std::vector<NskSegPlan>());
-    const bool use_tab = g->values_regular;
-    struct Run { const Compiled::Segment *sg; int t0, nt; uint32_t push_off; };
-    const std::vector<int32_t> &bt = g->p2p.border_tiles;
-    uint32_t border_total = 0;
-    bool border_all = true;
-    if (g->p2p.fused)          // border tiles of segments this call does not sample: the fused exchange cannot run
-        for (const Compiled::Segment &sg : g->c.segments)
-            if (!(sg.ev == 0 || sample_evidence)) {
-                const int32_t f = (int32_t)(sg.pos0 / 64);
-                const auto it = std::lower_bound(bt.begin(), bt.end(), f);
-                if (it != bt.end() && *it < f + sg.ntiles) border_all = false;
-            }
-    int first_phase = -1;            // the first class with sampled segments
-    for (const Compiled::Segment &sg : g->c.segments)
-        if ((sg.ev == 0 || sample_evidence) && (first_phase < 0 || sg.phase < first_phase)) first_phase = sg.phase;
-    g->p2p.first_phase = first_phase;
-    for (size_t ph = 0; ph < nphase; ph++)
-        for (int kind = 0; kind <= 8; kind++) {
-            if (kind == 1 || (kind > 4 && kind < 8)) continue;   // IMPLY_NATURAL shares the AND step (3)
-            for (int nch = 1; nch <= 2; nch++) {
-                SegTable tab;
-                memset(&tab, 0, sizeof(tab));
-                auto flush = [&]() {
-                    if (tab.n == 0) return;
-                    for (int i = tab.n; i < NSK_SEG_MAX; i++) tab.e[i].tile_start = tab.ntiles;
-                    // the wide-quad kernel takes the launch when at least half of its quads are wide ones (it samples
-                    // the others one tile at a time)
-                    const auto fits = [&](const void *p) {         // (the kernel's hot arguments: 256-byte units from val in 32 bits)
-                        const long long d = (const char *)p - (const char *)g->val;
-                        return d % 256 == 0 && d / 256 > -(1ll << 31) && d / 256 < (1ll << 31);
-                    };
-                    tab.wide = (kind >= 8 && 8 * tab.wide >= tab.ntiles && tab.ntiles < (1 << 28) && fits(g->cnt_pos) && fits(g->seg_wide) &&
-                                fits(g->ztab) && !nsk::diag_env("NSK_NO_WIDE_KERNEL")) ? 1 : 0;
-                    NskSegPlan pl{kind, nch, tab};
-                    if (tab.wide) nsk_tabw_rest_list(g->c, pl.tab, pl.nch, pl.nrest, pl.rest);
-                    seg_plans[ph].push_back(pl);
-                    memset(&tab, 0, sizeof(tab));
-                };
-                // largest segments first: the kernels find a tile's segment with a scan
-                // whose first probe is the table's first entry
-                std::vector<Run> mine;
-                for (const Compiled::Segment &sg : g->c.segments) {
-                    if (sg.phase != (int)ph) continue;
-                    const int k3 = (use_tab && sg.ztab >= 0) ? 8 : sg.kind == 1 ? 3 : (int)sg.kind;
-                    if (k3 != kind || (sg.nslots > 4 ? 2 : 1) != nch) continue;
-                    if (!(sg.ev == 0 || sample_evidence)) continue;      // inference.py:24
-                    if (!g->p2p.fused || kind < 8) { mine.push_back(Run{&sg, 0, sg.ntiles, NSK_NO_STREAM}); continue; }
-                    // runs of border / interior tiles (a tile's rank among the border tiles = its push-map row)
-                    const int32_t f = (int32_t)(sg.pos0 / 64);
-                    size_t bi = (size_t)(std::lower_bound(bt.begin(), bt.end(), f) - bt.begin());
-                    for (int t = 0; t < sg.ntiles;) {
-                        const bool isb = bi < bt.size() && bt[bi] == f + t;
-                        int e = t + 1;
-                        if (isb) { while (e < sg.ntiles && bi + (size_t)(e - t) < bt.size() && bt[bi + (size_t)(e - t)] == f + e) e++; }
-                        else e = (bi < bt.size() && bt[bi] < f + sg.ntiles) ? bt[bi] - f : sg.ntiles;
-                        mine.push_back(Run{&sg, t, e - t, isb ? (uint32_t)bi : NSK_NO_STREAM});
-                        if (isb) { bi += (size_t)(e - t); border_total += (uint32_t)(e - t); }
-                        t = e;
-                    }
-                }
-                // largest first -- but, for a shard that exchanges inside its launches, the border runs in front: their
-                // chain (flag, system-coherent ghost loads, pushes, acknowledgement, counter) is twice a trip long and
-                // overlaps the interior trips when it starts first; behind them it was a tail of every launch (a
-                // border wave that waits for a peer holds one of 6144 wave slots, nothing else)
-                std::stable_sort(mine.begin(), mine.end(), [&](const Run &a, const Run &b) {
-                    const bool ba = a.push_off != NSK_NO_STREAM, bb = b.push_off != NSK_NO_STREAM;
-                    if (ba != bb) return ba;
-                    return a.nt > b.nt; });
-                for (const Run &rn : mine) {
-                    const Compiled::Segment &sg = *rn.sg;
-                    SegEntry &en = tab.e[tab.n];
-                    const int64_t pos0 = sg.pos0 + 64 * (int64_t)rn.t0;
-                    // table launches number their tiles virtually: a segment starts on a quad
-                    // boundary (positions 256 m), with up to three dead tiles in front
-                    const int lead = kind >= 8 ? (int)((pos0 / 64) & 3) : 0;
-                    const int vtiles = kind >= 8 ? ((rn.nt + lead + 3) & ~3) : rn.nt;
-                    en.ntiles_lead = (uint32_t)rn.nt | ((uint32_t)lead << 30);
-                    en.tile_start = tab.ntiles;
-                    en.pos0 = (int)pos0;
-                    en.adj_off = sg.adj_off + (uint32_t)rn.t0 * 64u * (uint32_t)nch;
-                    en.prog = sg.prog;
-                    en.zoff = sg.ztab >= 0 ? (uint32_t)sg.ztab : 0u;
-                    // (bit 16: the positions of a segment with a draw table draw from the quad
-                    // scheme whichever kernel samples them, nsk_device.h quad_block)
-                    en.zmask_ev = ((1u << sg.nslots) - 1u) | (((uint32_t)sg.ev & 0xFFu) << 8) | (sg.ztab >= 0 ? 1u << 16 : 0u);
-                    en.aff_off = (kind >= 8 && sg.aff >= 0) ? (uint32_t)sg.aff + (uint32_t)rn.t0 * (uint32_t)nch : NSK_NO_STREAM;
-                    en.push_off = rn.push_off;
-                    // quad descriptors (nsk_compile.h seg_wide) from the quad of the run's first position on; NCH of the
-                    // descriptors = the segment's own chunk count = this launch's
-                    en.wide_off = (sg.ztab >= 0 && sg.wide >= 0)
-                        ? (uint32_t)(sg.wide + ((pos0 >> 8) - (sg.pos0 >> 8)) * NSK_WIDE_STRIDE(nch)) : NSK_NO_STREAM;
-                    if (en.wide_off != NSK_NO_STREAM) {      // the wide quads the run touches; those it holds whole (SegTable.wide, flush)
-                        const int stride = NSK_WIDE_STRIDE(nch);
-                        int touched = 0;
-                        for (int64_t P = pos0 & ~(int64_t)255; P < pos0 + 64 * (int64_t)rn.nt; P += 256)
-                            if (g->c.seg_wide[(size_t)sg.wide + (size_t)((P >> 8) - (sg.pos0 >> 8)) * stride] != 0xFFFFFFFFu) {
-                                touched++;
-                                if (kind >= 8 && P >= pos0 && P + 256 <= pos0 + 64 * (int64_t)rn.nt) tab.wide++;
-                            }
-                        if (!touched) en.wide_off = NSK_NO_STREAM;       // (none: the kernels need not look)
-                    }
-                    tab.ntiles += vtiles;
-                    if (++tab.n == NSK_SEG_MAX) flush();
-                }
-                flush();
-            }
-        }
-    // The border waves of the sweep's first class THAT HAS BORDER TILES wait for the peers' flags of the previous
-    // exchange (later classes find them raised: the stream is in order).  Not simply the first class with sampled
-    // segments: a cut whose boundary variables all have the other colour (a chain, a bipartite cut) has no border tile
-    // there, and then nothing in the sweep would wait -- ghosts read before they arrived, pushes over a block a peer
-    // still reads.
-    if (g->p2p.fused) {
-        int first_border = -1;
-        for (size_t ph = 0; ph < nphase && first_border < 0; ph++)
-            for (const NskSegPlan &pl : seg_plans[ph])
-                for (int i = 0; i < pl.tab.n && first_border < 0; i++)
-                    if (pl.tab.e[i].push_off != NSK_NO_STREAM) first_border = (int)ph;
-        if (first_border >= 0) g->p2p.first_phase = first_border;
-    }
-    g->p2p.border_total = border_total;
-    g->p2p.border_all = border_all && border_total == (uint32_t)bt.size();
-    g->seg_plans_all_tab = g->seg_plans_all_wide = true;
-    for (const auto &v : seg_plans)
-        for (const NskSegPlan &pl : v) {
-            g->seg_plans_all_tab = g->seg_plans_all_tab && pl.kind >= 8;
-            g->seg_plans_all_wide = g->seg_plans_all_wide && pl.kind >= 8 && pl.tab.wide;
-        }
+// The segment launches of every colour (nsk_seg_plan.h plan_segments), planned once and kept in the handle (a small
+// graph's sweep is two 4 us kernels: rebuilding the tables per sweep made the host the bottleneck).  The switches and the
+// addresses are read here, once per call; the plans are rebuilt when the options differ from the ones they were made for
+// -- and then the captured sweep sequences go, so that no replay carries a table or a grid of other options.
+static void ensure_seg_plans(nsk_graph *g, int sample_evidence) {
+    SegPlanOpts o;
+    o.sample_evidence = sample_evidence != 0;
+    o.use_tab = g->values_regular;
+    o.byte_values = g->c.vbytes == 1;
+    o.offsets_fit = val_offset_fits(g, g->cnt_pos) && val_offset_fits(g, g->seg_wide) && val_offset_fits(g, g->ztab);
+    o.fused = g->p2p.fused;
+    o.border_tiles = &g->p2p.border_tiles;
+    o.no_wide_kernel = nsk::diag_env("NSK_NO_WIDE_KERNEL") != nullptr;
+    o.no_tabw_rest = nsk::diag_env("NSK_NO_TABW_REST") != nullptr;
+    o.tab_grid_cap = seg_cap_rounds(nsk::diag_env("NSK_TAB_GRID_CAP"));
+    o.tabw_grid_cap = seg_cap_rounds(nsk::diag_env("NSK_TABW_GRID_CAP"));
+    if (g->seg_plans_valid && o == g->seg_opts) return;
+    SegPlans r = plan_segments(g->c, o);
+    g->seg_plans.swap(r.by_class);
+    g->seg_opts = o;
+    g->seg_plans_valid = true;
+    g->p2p.first_phase = r.first_phase;
+    g->p2p.border_total = r.border_total;
+    g->p2p.border_all = r.border_all;
+    g->seg_plans_all_tab = r.all_tab;
+    g->seg_plans_all_wide = r.all_wide;
+    nsk_drop_sweep_graph(g);
 }
 
 // Where a table launch gets its counters.  An eager launch carries the Philox key, the sweep index and the exchange tag
@@ -182,10 +72,10 @@ struct CounterSrc {
 
 // The wide-quad launch of a plan (four positions to a lane) -- chains: for every chain of the handle, over as many copies
 // of the one-chain grid
-static void launch_tabw(nsk_graph *g, const NskSegPlan &pl, int burnin, const CounterSrc &src, bool chains) {
+static void launch_tabw(nsk_graph *g, const SegLaunchPlan &pl, int burnin, const CounterSrc &src, bool chains) {
     TabwCold cold{src.K0, src.K1, src.S0, src.S1, src.sweep_off, 0u, view<signed char>(g), pl.tab, pl.nrest, {}};
     memcpy(cold.rest, pl.rest, sizeof(cold.rest));
-    const int nbw = nsk_tabw_grid(pl.tab.ntiles), nf = nsk_tabw_front_blocks(pl.nrest);
+    const int nbw = pl.wide_grid, nf = pl.front;
     const dim3 grid((chains ? (unsigned)g->nchains : 1u) * (unsigned)(nf + nbw));     // (the kernel derives nf + nbw from its hot arguments)
 #define NSK_TABW(NCH, K, MODE) K<NCH, MODE><<<grid, dim3(NSK_BLOCK), 0, g->stream>>>(NSK_TABW_HOT_ARGS(g, pl.tab, nbw, nf, src.sweep_base), cold)
     if (chains) { if (burnin) NSK_BY_NCH(NSK_TABW, k_gibbs_seg_tabw_chains, 1); else NSK_BY_NCH(NSK_TABW, k_gibbs_seg_tabw_chains, 0); }
@@ -199,13 +89,13 @@ static void launch_tabw(nsk_graph *g, const NskSegPlan &pl, int burnin, const Co
 // of a handle with several in one launch (chains_batched; R copies of the one-chain grid), else the boundary exchange
 // inside the launch, else (mostly) wide quads, else a wave per tile pair.
 template <typename VT>
-static void launch_table(nsk_graph *g, const NskSegPlan &pl, int ph, int burnin, const CounterSrc &src) {
+static void launch_table(nsk_graph *g, const SegLaunchPlan &pl, int ph, int burnin, const CounterSrc &src) {
     // (under a ChainSwap the one-chain launches sample the one chain.  The capture needs no such test, and this one is the
     // same there: only nsk_gibbs_run captures, and chains_run sweeps a swapped handle through gibbs_eager alone.)
     const bool chains = g->nchains > 1 && !g->chain_swapped;
     const bool wide = sizeof(VT) == 1 && pl.tab.wide;
     // a wave per tile pair while that fits the resident grid, else its waves loop over quads
-    const unsigned nbp = (unsigned)nsk_tab_grid(pl.tab.ntiles);
+    const unsigned nbp = (unsigned)pl.grid;
 #define NSK_TAB_ARGS view<VT>(g), pl.tab, burnin, src.K0, src.K1, src.S0, src.S1, src.sweep_base, src.sweep_off
 #define NSK_TAB(NCH, K, NB, ...) K<VT, NCH><<<dim3(NB), dim3(NSK_BLOCK), 0, g->stream>>>(__VA_ARGS__)
     if (chains) {
@@ -229,16 +119,12 @@ static bool chains_batched(nsk_graph *g, int sample_evidence) {
     if (g->nchains < 2 || g->chain_swapped || g->scan != NSK_SCAN_CHROMATIC || !g->values_regular || !nsk_tables_only(g) ||
         nsk::diag_env("NSK_NO_CHAIN_BATCH"))
         return false;
-    nsk_ensure_seg_plans(g, sample_evidence);
-    const long long shift = (long long)(g->nchains - 1) * (long long)(g->chain_stride / 256);
-    const auto fits = [&](const void *p) {
-        const long long d = ((const char *)p - (const char *)g->val) / 256 - shift;
-        return d > -(1ll << 31) && d < (1ll << 31);
-    };
+    ensure_seg_plans(g, sample_evidence);
     if (!g->seg_plans_all_tab) return false;
-    if (g->c.vbytes == 1 && !(fits(g->seg_wide) && fits(g->ztab)))
+    const long long shift = (long long)(g->nchains - 1) * (long long)(g->chain_stride / 256);
+    if (g->c.vbytes == 1 && !(val_offset_fits(g, g->seg_wide, shift) && val_offset_fits(g, g->ztab, shift)))
         for (const auto &v : g->seg_plans)
-            for (const NskSegPlan &pl : v)
+            for (const SegLaunchPlan &pl : v)
                 if (pl.tab.wide) return false;
     return true;
 }
@@ -274,9 +160,9 @@ static void launch_generic(const EagerSweep<VT> &w, const ClassShape &s, const S
 }
 // a prepared segment launch without a draw table: the inlined-adjacency kernel of its kind
 template <typename VT>
-static void launch_seg(const EagerSweep<VT> &w, const NskSegPlan &pl) {
-    const int nb = (pl.tab.ntiles + 3) / 4;
-    const dim3 grid(8 * ((nb + 7) / 8));
+static void launch_seg(const EagerSweep<VT> &w, const SegLaunchPlan &pl) {
+    const int nb = (pl.tab.ntiles + 3) / 4;         // a wave per tile
+    const dim3 grid(pl.grid);
 #define NSK_SEG(NCH, KIND) k_gibbs_seg<VT, KIND, NCH><<<grid, dim3(NSK_BLOCK), 0, w.g->stream>>>(w.d, pl.tab, nb, w.burnin, w.src.K0, w.src.K1, w.src.S0, w.src.S1)
     if (pl.kind == 4) NSK_BY_NCH(NSK_SEG, 4);
     else if (pl.kind == 2) NSK_BY_NCH(NSK_SEG, 2);
@@ -303,7 +189,7 @@ static int gibbs_impl(nsk_graph *g, int64_t nsweeps, int sample_evidence, int bu
     } else {
         const size_t nphase = g->c.phase_start.size() - 1;
         nsk_refresh_prog_weights(g);
-        nsk_ensure_seg_plans(g, sample_evidence);
+        ensure_seg_plans(g, sample_evidence);
         // every class's plan, once per call: cheap, and nothing a sweep changes enters it
         std::vector<ClassShape> shapes(nphase);
         std::vector<GibbsClassPlan> plans(nphase);
@@ -338,7 +224,7 @@ static int gibbs_impl(nsk_graph *g, int64_t nsweeps, int sample_evidence, int bu
                 if (p.generic.on) { launch_generic<VT>(w, cl, p.generic, cs.of(p.generic.stream)); g->launches++; }
                 if (L.on && L.behind_generic) { launch_general<VT, 2>(w, cl, L, g->stream); g->launches++; }
                 if (p.segments)         // the launches prepared before the sweep loop
-                    for (const NskSegPlan &pl : g->seg_plans[ph]) {
+                    for (const SegLaunchPlan &pl : g->seg_plans[ph]) {
                         if (pl.kind >= 8) launch_table<VT>(g, pl, (int)ph, burnin, w.src);
                         else launch_seg<VT>(w, pl);
                         g->launches++;
@@ -424,7 +310,7 @@ static int graph_build(nsk_graph *g, int burnin, bool p2p, int key, SweepGraph &
     int launches = 0;
     for (int i = 0; i < nsw; i++) {
         for (size_t ph = 0; ph < g->seg_plans.size(); ph++)
-            for (const NskSegPlan &pl : g->seg_plans[ph]) {
+            for (const SegLaunchPlan &pl : g->seg_plans[ph]) {
                 launch_table<VT>(g, pl, (int)ph, burnin, CounterSrc::captured(g, i));     // (the exchange tag of sweep i: counter + i + 1)
                 launches++;
             }
@@ -453,7 +339,7 @@ int nsk_gibbs_run(nsk_graph *g, int64_t nsweeps, int sample_evidence, int burnin
     // the unpack into the value array are enqueued lazily (nsk_p2p_flush)
     bool fuse = false;
     if (p2p && g->p2p.fused && g->scan == NSK_SCAN_CHROMATIC && g->values_regular && nsweeps > 0) {
-        nsk_ensure_seg_plans(g, sample_evidence);
+        ensure_seg_plans(g, sample_evidence);
         fuse = g->p2p.border_all && g->seg_plans_all_tab;
         // (a fused call right behind a fused call continues it: the receive block already holds what the first
         // sweep reads -- nothing to unpack into the value array and pack back)
@@ -470,7 +356,7 @@ int nsk_gibbs_run(nsk_graph *g, int64_t nsweeps, int sample_evidence, int burnin
     g->pack_now = false;
     if (!p2p && !burnin && g->nchains == 1 && g->scan == NSK_SCAN_CHROMATIC && g->values_regular && g->c.vbytes == 1 && nsweeps > 0 &&
         nsk_tables_only(g) && !nsk::diag_env("NSK_NO_PACK_TALLY")) {
-        nsk_ensure_seg_plans(g, sample_evidence);
+        ensure_seg_plans(g, sample_evidence);
         g->pack_now = g->seg_plans_all_wide;
     }
     struct Done { nsk_graph *g; bool fuse, keep; ~Done() { g->p2p.fused_now = false; if (fuse) g->p2p.close_pending = true;
@@ -482,8 +368,9 @@ int nsk_gibbs_run(nsk_graph *g, int64_t nsweeps, int sample_evidence, int burnin
         // 16 sweeps outside them -- this one and the 15 that 399 leaves over)
         int rc = NSK_OK;
         nsk_refresh_prog_weights(g);
-        nsk_ensure_seg_plans(g, sample_evidence);
-        const int key = g->seg_plans_key | (burnin ? 8 : 0) | (p2p ? 16 : 0) | (fuse ? 32 : 0) | (g->pack_now ? 64 : 0);
+        ensure_seg_plans(g, sample_evidence);
+        // (what a sequence was captured for, beside the plans: planning again drops every sequence)
+        const int key = (burnin ? 8 : 0) | (p2p ? 16 : 0) | (fuse ? 32 : 0) | (g->pack_now ? 64 : 0);
         if (g->seg_plans_all_tab && left >= NSK_GRAPH_SWEEPS) {
             // two sizes: NSK_GRAPH_SWEEPS_BIG sweeps per replay while the call is long enough, NSK_GRAPH_SWEEPS for what is left
             for (int big = (left >= NSK_GRAPH_SWEEPS_BIG && !nsk::diag_env("NSK_NO_BIG_GRAPH")) ? 1 : 0; big >= 0; big--) {

@@ -16,6 +16,7 @@
 #include "nsk_compile.h"
 #include "nsk_device.h"
 #include "nsk_kernels_gibbs.h"
+#include "nsk_seg_plan.h"
 
 namespace nsk {
 int fail(int code, const std::string &msg);       // records nsk_last_error, returns code
@@ -27,13 +28,6 @@ int fail(int code, const std::string &msg);       // records nsk_last_error, ret
         if (e_ != hipSuccess)                                                                   \
             return nsk::fail(NSK_E_DEVICE, std::string(#expr) + ": " + hipGetErrorString(e_));  \
     } while (0)
-
-struct NskSegPlan { int kind, nch; nsk::SegTable tab;         // one prepared segment launch (nsk_gibbs.hip)
-                    uint32_t nrest = 0, rest[NSK_TABW_REST_MAX] = {}; };      // wide launches: the quads that are not wide (TabwCold.rest)
-
-// one prepared learning segment launch (nsk_learn.hip), built for key = its draw tables are usable: the segment table -- in
-// whole quads, with the quads that are not wide ones, when the wide kernel takes the launch (wide); tile by tile otherwise
-struct NskLearnSegPlan { int key = -1; bool wide = false; nsk::SegTable tab; uint32_t nrest = 0, rest[NSK_TABW_REST_MAX] = {}; };
 
 // Per-weight statistics (nsk_weight_stats / the trace's stats column; nsk_kernels_wstats.h).  A PLAN is the device work
 // list of a selection of weights: one lane per short weight, one wave per piece of a longer one, a second launch for
@@ -190,12 +184,16 @@ struct nsk_graph {
     NskTrace trace;
     NskEnergy energy;
     NskWstats wstats;
-    std::vector<NskLearnSegPlan> learn_seg_plans;        // per Compiled::learn_seg entry
-    // the inference sweep's segment launches per colour, kept across calls (the N-rank loops sweep one
-    // epoch per call); key = sample_evidence | draw tables usable << 1
-    std::vector<std::vector<NskSegPlan>> seg_plans;
-    int seg_plans_key = -1;
-    bool seg_plans_all_tab = false, seg_plans_all_wide = false;   // every plan is a table launch (kind 8); ... a wide one (they live with the key)
+    // The segment launches (nsk_seg_plan.h), kept across calls (the N-rank loops sweep one epoch per call) together with
+    // the options they were planned for; a call whose options differ plans again.  Learning: per Compiled::learn_seg entry.
+    std::vector<nsk::LearnSegPlan> learn_seg_plans;
+    nsk::SegPlanOpts learn_seg_opts;
+    // Inference: per colour.  seg_plans_valid is also cleared where something the options only point at changes (the
+    // border tiles, the arrays' addresses); planning again drops the captured sweep sequences.
+    std::vector<std::vector<nsk::SegLaunchPlan>> seg_plans;
+    nsk::SegPlanOpts seg_opts;
+    bool seg_plans_valid = false;
+    bool seg_plans_all_tab = false, seg_plans_all_wide = false;   // every plan is a table launch (kind 8); ... a wide one
     // captured sweep sequences (hipGraph): [0] NSK_GRAPH_SWEEPS inference sweeps of a handle whose sweep is
     // table launches only (+ the peer-to-peer exchange), replayed with the sweep index in device memory;
     // [1] NSK_GRAPH_SWEEPS_BIG of them for long calls (the one-thread kernel that advances the counters and the
@@ -444,96 +442,6 @@ struct ColourStreams {
 
 // the fast path reads weights through prog_w (and the draw tables): rebuilt whenever weights may
 // have changed (nsk_api.hip)
-// Grid of a table-driven learning segment launch: resident -- the waves loop over their XCD's trips
-// with the next trip's loads in flight (k_learn_seg_tab) -- and smaller when a block's flush of its
-// LDS sums (a few atomics per weight) would rival its tile traffic
-static inline int nsk_learn_tab_grid(int ntiles, int nweight, bool smallw) {
-    const int blocks = (ntiles + 7) / 8;                            // 4 waves x 2 tiles
-    const int trips = smallw ? std::max(1, (nweight * 16 * 16 + 14847) / 14848) : 1;
-    // Six blocks per CU.  The kernel holds 7 waves per SIMD (112 scalar registers), so 2048 blocks are
-    // not all resident, and whole blocks per CU beat fractions (measured on the 10M grid, per class with
-    // the update launch: 1024 blocks 31.2 us, 1280 30.1, 1408 31.1, 1536 29.6, 1664 31.2, 1792 32.2,
-    // 1920 32.5, 2048 31.4, 3072 31.3, 4096 31.7; the 1M grid is indifferent: 14.1-14.3)
-    const char *cap_env = nsk::diag_env("NSK_LEARN_GRID_CAP");              // (diagnostic; read per launch so that tests can set it)
-    // (SMALLW launches carry 8 service blocks in front, k_learn_seg_tab: they count towards the six per CU)
-    const int cap = cap_env ? atoi(cap_env) : (smallw ? 1528 : 1536);
-    return 8 * ((std::max(1, std::min(cap, (blocks + trips - 1) / trips)) + 7) / 8);     // whole rounds of XCDs
-}
-// Grid of a table-driven inference segment launch (k_gibbs_seg_tab) over `vtiles` virtual tiles (a multiple
-// of 4): one wave per tile PAIR while that fits the resident grid, else the resident grid -- 6 blocks per CU,
-// whole rounds of XCDs -- whose waves loop over QUADS (the kernel deals whole rounds of quads, then pairs).
-// Six, not the seven the compiler's occupancy and the occupancy API report: the kernel holds 106 scalar
-// registers and the hardware admits min(8, 800 / (ceil(sgpr / 16) * 16 + 16)) blocks of 256 threads per CU
-// (MI355X_MICROARCH.md); capping the registers for a seventh or eighth block was slower.  A grid beyond the resident one runs a tail round as long as
-// the first: per 10M-grid class 1024 blocks 15.2 us, 1280 14.3, 1536 12.7, 1632 16.2, 1792 14.1, 2048 14.3
-// (NSK_TAB_GRID_CAP); the 1M grid (1954 blocks of pairs) is indifferent (4.2 us).
-static inline int nsk_tab_grid(int vtiles) {
-    const int npairs = vtiles / 2;
-    const int need = std::max(8, 8 * ((((npairs + 3) / 4) + 7) / 8));
-    const char *cap_env = nsk::diag_env("NSK_TAB_GRID_CAP");                // (diagnostic)
-    const int cap = cap_env ? std::max(8, std::abs(atoi(cap_env)) & ~7) : (need <= 2048 ? 2048 : 1536);
-    return std::min(cap, need);        // (a launch that needs fewer blocks than 2048 runs in pairs: one trip per wave)
-}
-// Grid of a wide-quad table launch (k_gibbs_seg_tabw) over `vtiles` virtual tiles: a wave per quad while that fits the
-// resident grid (NSK_TABW_PER_CU blocks per CU), else the resident grid, whole rounds of XCDs
-#ifndef NSK_TABW_PER_CU
-#define NSK_TABW_PER_CU 6
-#endif
-static inline int nsk_tabw_grid(int vtiles) {
-    const int nquads = vtiles / 4, ntrips = nquads + 8;                     // (+ 8: every XCD's share rounds up)
-    const int need = std::max(8, 8 * ((((ntrips + 3) / 4) + 7) / 8));
-    const char *cap_env = nsk::diag_env("NSK_TABW_GRID_CAP");               // (diagnostic; read per launch so that tests can set it)
-    const int cap = cap_env ? std::max(8, std::abs(atoi(cap_env)) & ~7) : 256 * NSK_TABW_PER_CU;
-    return std::min(cap, need);
-}
-// The quads of a wide launch that are not wide ones (TabwCold.rest / TabwRest; the kernels' own tests of a quad, mirrored):
-// each gets a workgroup in front of the grid.  More than NSK_TABW_REST_MAX of them: none listed, the waves sample them in
-// line (NSK_DIAG=1 NSK_NO_TABW_REST=1: likewise).
-static inline void nsk_tabw_rest_list(const nsk::Compiled &c, const nsk::SegTable &tab, int nch, uint32_t &nrest, uint32_t *out) {
-    const int ST = NSK_WIDE_STRIDE(nch);
-    std::vector<uint32_t> rest;
-    for (int i = 0; i < tab.n; i++) {
-        const nsk::SegEntry &en = tab.e[i];
-        const int tend = i + 1 < NSK_SEG_MAX ? tab.e[i + 1].tile_start : tab.ntiles;
-        const int lead = (int)(en.ntiles_lead >> 30), nt = (int)(en.ntiles_lead & 0x3FFFFFFFu);
-        const int qs = en.tile_start >> 2, qin_lo = qs + (lead ? 1 : 0);
-        const uint32_t qin_n = (uint32_t)(qs + ((lead + nt) >> 2) - qin_lo);
-        const bool hasw = en.wide_off != NSK_NO_STREAM;
-        for (int Q = qs; Q < (tend >> 2); Q++) {
-            const bool flagged = hasw && c.seg_wide[(size_t)en.wide_off + (size_t)(Q - qs) * ST] != 0xFFFFFFFFu;
-            if (flagged && (uint32_t)(Q - qin_lo) < qin_n) continue;     // a wide quad
-            rest.push_back((uint32_t)Q | (flagged ? 0x80000000u : 0u));
-        }
-    }
-    nrest = 0;
-    if (rest.size() <= NSK_TABW_REST_MAX && !nsk::diag_env("NSK_NO_TABW_REST")) {
-        nrest = (uint32_t)rest.size();
-        for (size_t k = 0; k < rest.size(); k++) out[k] = rest[k];
-    }
-}
-static inline int nsk_tabw_front_blocks(uint32_t nrest) { return (int)((nrest + 7u) & ~7u); }     // whole rounds of XCDs
-
-// Grid of a wide-quad learning launch (k_learn_seg_tabw) over `vtiles` virtual tiles, whole rounds of XCDs (the service
-// and front blocks come on top).  One MI355X, us per learning sweep (tools/sessions/r6_s26.sh): 10M grid 45.6 / 45.6 / 40.3 /
-// 42.6 / 41.8 / 43.7 / 43.3 at 512 / 640 / 768 / 896 / 1024 / 1152 / 1280 blocks (45.5 tile by tile; 41.0 at 1024 and 43.0 at 1536 in
-// r6_s25.sh); 40M grid 120.8 / 117.7 / 117.4 / 111.6 at 768 / 1024 / 1536 / 2048 (146.6 tile by tile).  (While the waves whose
-// turn they were sampled the launch's few quads that are not wide in line, these figures jumped by a quarter from one
-// grid size to the next -- whichever waves drew those quads ended the launch: r6_s16.sh.)  On the 4M grid the
-// tile-by-tile kernel wins (24.3 against 27.5), hence NSK_WIDE_LEARN_MIN_QUADS.
-#define NSK_WIDE_LEARN_MIN_QUADS 12000
-static inline int nsk_learn_tabw_grid(int vtiles) {
-    const int nquads = vtiles / 4 + 8;
-    const int need = std::max(8, 8 * ((((nquads + 3) / 4) + 7) / 8));
-    const char *cap_env = nsk::diag_env("NSK_LEARN_TABW_GRID_CAP");         // (diagnostic; read per launch so that tests can set it)
-    const int cap = cap_env ? std::max(8, std::abs(atoi(cap_env)) & ~7) : (nquads >= 40000 ? 2048 : 1024);
-    return std::min(cap, need);
-}
-static inline int nsk_learn_seg_grid(const nsk::Compiled::SegLaunch &sl, int nweight, bool smallw, bool use_tab) {
-    const int ntiles = sl.tile_start[sl.n];
-    if (sl.tab && use_tab) return nsk_learn_tab_grid(ntiles, nweight, smallw);
-    return std::min(NSK_LEARN_SEG_BLOCKS, (ntiles + 3) / 4);
-}
-
 extern "C" int nsk_ensure_generic(nsk_graph *g);       // internal (not in the public header)
 int nsk_ensure_lag_sets(nsk_graph *g);                 // second set of weights / tables / accumulators (nsk_api.hip)
 // one peer-to-peer exchange on the library's stream; tag_base != null: a captured launch whose tag is
@@ -542,7 +450,6 @@ int nsk_ensure_lag_sets(nsk_graph *g);                 // second set of weights 
 // weight merge (nsk_exchange.hip)
 int nsk_p2p_enqueue(nsk_graph *g, const unsigned long long *tag_base, unsigned int tag_off, bool learn = false, int part = 0);
 bool nsk_tables_only(const nsk_graph *g);           // every sampled variable lives in a table segment (nsk_gibbs.hip)
-void nsk_ensure_seg_plans(nsk_graph *g, int sample_evidence);    // nsk_gibbs.hip
 int nsk_p2p_ghost_pack(nsk_graph *g);
 void nsk_exchange_release(nsk_graph *g);           // nsk_graph_destroy: the peers' hipIpc mappings and the RCCL communicator (nsk_exchange.hip)
 int nsk_p2p_flush(nsk_graph *g);                   // enqueue the pending closing wait + unpack of a fused sweep sequence, if any

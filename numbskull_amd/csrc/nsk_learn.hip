@@ -32,62 +32,30 @@ static void refresh_after_update(nsk_graph *g, int set, hipStream_t st) {
     }
 }
 
-// The segment launches of learning (Compiled::learn_seg), each prepared once per handle and per use_tab (its draw tables
-// are usable: the values lie in their domains) -- walking a launch's quad descriptors on the host for every launch of every
-// sweep cost more than the launch itself from a few million variables on.
-static void learn_seg_entry(SegEntry &en, const Compiled::SegLaunch &sl, int i, int nt, int lead, bool use_tab) {
-    en.ntiles_lead = (uint32_t)nt | ((uint32_t)lead << 30);
-    en.pos0 = sl.pos0[i]; en.adj_off = sl.adj_off[i]; en.prog = sl.prog[i]; en.zoff = sl.zoff[i];
-    en.zmask_ev = (sl.zmask[i] & 0xFFu) | (((uint32_t)sl.ev[i] & 0xFFu) << 8);
-    en.aff_off = use_tab ? sl.aff[i] : NSK_NO_STREAM;         // implicit adjacency (table kernels)
-}
-static const NskLearnSegPlan &learn_seg_plan(nsk_graph *g, const Compiled::SegLaunch &sl, bool use_tab, bool byte_values) {
-    if (g->learn_seg_plans.size() != g->c.learn_seg.size()) g->learn_seg_plans.assign(g->c.learn_seg.size(), NskLearnSegPlan());
-    NskLearnSegPlan &p = g->learn_seg_plans[(size_t)(&sl - g->c.learn_seg.data())];
-    if (p.key == (use_tab ? 1 : 0)) return p;
-    p = NskLearnSegPlan();
-    p.key = use_tab ? 1 : 0;
-    SegTable &tab = p.tab;
-    // (mostly) wide quads: the wide learning kernel, its tiles numbered in whole quads like the inference launches
-    // (lead = dead tiles in front of a segment that does not start on a quad boundary)
-    if (use_tab && byte_values) {
-        memset(&tab, 0, sizeof(tab));
-        tab.n = sl.n;
-        int nwide = 0;
-        for (int i = 0; i < NSK_SEG_MAX; i++) {
-            SegEntry &en = tab.e[i];
-            en.tile_start = tab.ntiles;
-            if (i >= sl.n) continue;
-            const int nt_i = sl.tile_start[i + 1] - sl.tile_start[i];
-            const int64_t pos0 = sl.pos0[i];
-            const int lead = (int)((pos0 / 64) & 3);
-            learn_seg_entry(en, sl, i, nt_i, lead, true);
-            en.push_off = NSK_NO_STREAM;
-            en.wide_off = sl.wide[i] >= 0 ? (uint32_t)sl.wide[i] : NSK_NO_STREAM;     // (the descriptors start at the quad of pos0)
-            if (sl.wide[i] >= 0) {
-                const int stride = NSK_WIDE_STRIDE(sl.nch);
-                for (int64_t P = (pos0 + 255) & ~(int64_t)255; P + 256 <= pos0 + 64 * (int64_t)nt_i; P += 256)
-                    if (g->c.seg_wide[(size_t)sl.wide[i] + (size_t)((P >> 8) - (pos0 >> 8)) * stride] != 0xFFFFFFFFu) nwide++;
-            }
-            tab.ntiles += (nt_i + lead + 3) & ~3;
-        }
-        const char *min_env = nsk::diag_env("NSK_WIDE_LEARN_MIN");                 // (diagnostic; the small-grid tests use 0)
-        const int min_quads = min_env ? atoi(min_env) : NSK_WIDE_LEARN_MIN_QUADS;
-        p.wide = 8 * nwide >= tab.ntiles && tab.ntiles > 0 && tab.ntiles / 4 >= min_quads && !nsk::diag_env("NSK_NO_WIDE_LEARN");
-        if (p.wide) { nsk_tabw_rest_list(g->c, tab, sl.nch, p.nrest, p.rest); return p; }
+static_assert(SEG_LEARN_TPW == NSK_LEARN_TPW && SEG_LEARN_SEG_BLOCKS == NSK_LEARN_SEG_BLOCKS && SEG_SERVICE_BLOCKS == NSK_SERVICE_BLOCKS,
+              "nsk_seg_plan.h copies the trip width and grid constants of the learning segment kernels");
+
+// The segment launches of learning (Compiled::learn_seg; nsk_seg_plan.h plan_learn_segment), planned once per handle and
+// set of options -- walking a launch's quad descriptors on the host for every launch of every sweep cost more than the
+// launch itself from a few million variables on.  The switches are read here, once per call.
+static const std::vector<LearnSegPlan> &learn_seg_plans(nsk_graph *g, bool smallw) {
+    SegPlanOpts o;
+    o.use_tab = g->values_regular;
+    o.byte_values = g->c.vbytes == 1;
+    o.no_tabw_rest = nsk::diag_env("NSK_NO_TABW_REST") != nullptr;
+    o.nweight = (int)g->c.nweight;
+    o.smallw = smallw;
+    const char *min_env = nsk::diag_env("NSK_WIDE_LEARN_MIN");                 // (the small-grid tests use 0)
+    if (min_env) o.wide_learn_min_quads = atoi(min_env);
+    o.no_wide_learn = nsk::diag_env("NSK_NO_WIDE_LEARN") != nullptr;
+    o.learn_grid_cap = seg_cap_blocks(nsk::diag_env("NSK_LEARN_GRID_CAP"));
+    o.learn_tabw_grid_cap = seg_cap_rounds(nsk::diag_env("NSK_LEARN_TABW_GRID_CAP"));
+    if (g->learn_seg_plans.size() != g->c.learn_seg.size() || !(o == g->learn_seg_opts)) {
+        g->learn_seg_plans.clear();
+        for (const Compiled::SegLaunch &sl : g->c.learn_seg) g->learn_seg_plans.push_back(plan_learn_segment(g->c, sl, o));
+        g->learn_seg_opts = o;
     }
-    // tile by tile; table launches number their tiles virtually: every segment is padded to whole trips
-    memset(&tab, 0, sizeof(tab));
-    tab.n = sl.n;
-    int vt = 0;
-    for (int i = 0; i < NSK_SEG_MAX; i++) {
-        const int nt_i = i < sl.n ? sl.tile_start[i + 1] - sl.tile_start[i] : 0;
-        tab.e[i].tile_start = use_tab ? vt : (i < sl.n ? sl.tile_start[i] : sl.tile_start[sl.n]);
-        vt += (nt_i + NSK_LEARN_TPW - 1) / NSK_LEARN_TPW * NSK_LEARN_TPW;
-        learn_seg_entry(tab.e[i], sl, i, nt_i, 0, use_tab);
-    }
-    tab.ntiles = use_tab ? vt : sl.tile_start[sl.n];
-    return p;
+    return g->learn_seg_plans;
 }
 
 // The chromatic learning sweep is instantiated four times (value type x accumulator flavour) and every
@@ -189,7 +157,9 @@ int nsk_learn_chromatic(nsk_graph *g, int64_t nsweeps, double step, double decay
     ApplyArgs no_update;
     memset(&no_update, 0, sizeof(no_update));
     // every class's plan (nsk_class_plan.h) and its segment launches, once per call: nothing a sweep changes enters them
-    struct LearnClass { ClassShape s; LearnClassPlan p; std::vector<const Compiled::SegLaunch *> segs; };
+    struct LearnSeg { const Compiled::SegLaunch *sl; const LearnSegPlan *pl; };
+    struct LearnClass { ClassShape s; LearnClassPlan p; std::vector<LearnSeg> segs; };
+    const std::vector<LearnSegPlan> &seg_plans = learn_seg_plans(g, SMALLW);
     std::vector<LearnClass> classes(nphase);
     PlanOpts opts;
     opts.overlap = !g->no_overlap;
@@ -199,8 +169,10 @@ int nsk_learn_chromatic(nsk_graph *g, int64_t nsweeps, double step, double decay
         LearnClass &c = classes[ph];
         c.s = class_shape(g->c, ph);
         opts.seg_tiles = 0;
-        for (const Compiled::SegLaunch &sl : g->c.learn_seg)
-            if (sl.phase == (int)ph) { c.segs.push_back(&sl); opts.seg_tiles += sl.tile_start[sl.n]; }
+        for (size_t i = 0; i < g->c.learn_seg.size(); i++) {
+            const Compiled::SegLaunch &sl = g->c.learn_seg[i];
+            if (sl.phase == (int)ph) { c.segs.push_back(LearnSeg{&sl, &seg_plans[i]}); opts.seg_tiles += sl.tile_start[sl.n]; }
+        }
         if (c.s.ep && c.s.e > c.s.fb) opts.ep_per_cu = plan_per_cu(nsk::diag_env("NSK_EP_PER_CU"));    // (diagnostic: workgroups per CU)
         c.p = plan_learn_class(c.s, opts);
     }
@@ -259,28 +231,27 @@ int nsk_learn_chromatic(nsk_graph *g, int64_t nsweeps, double step, double decay
 #undef NSK_LEP
                 g->launches++;
             }
-            for (const Compiled::SegLaunch *slp : classes[ph].segs) {       // homogeneous segments
-                const Compiled::SegLaunch &sl = *slp;
+            for (const LearnSeg &ls : classes[ph].segs) {       // homogeneous segments, from their plans
+                const Compiled::SegLaunch &sl = *ls.sl;
+                const LearnSegPlan &pl = *ls.pl;
                 const bool use_tab = sl.tab && g->values_regular;
-                const NskLearnSegPlan &pl = learn_seg_plan(g, sl, use_tab, sizeof(VT) == 1);
                 const SegTable &tab = pl.tab;
+                const int grid = pl.grid;
                 // the previous class's update rides in a table launch (block 0 of the service blocks in front)
                 const bool fuse = use_tab && SMALLW && pend.valid && pend.tabs_here;
                 const ApplyArgs &prev = fuse ? pend.aa : no_update;
                 const int service = SMALLW ? NSK_SERVICE_BLOCKS : 0;
 #define NSK_LSEG(KIND, NCH) k_learn_seg<VT, SMALLW, KIND, NCH><<<dim3(grid), dim3(NSK_BLOCK), shmem, g->stream>>>(d, tab, lp)
 #define NSK_LTAB(NCH) k_learn_seg_tab<VT, SMALLW, NCH, NSK_LEARN_TPW><<<dim3(grid + service), dim3(NSK_BLOCK), shmem, g->stream>>>(d, tab, lp, prev)
-#define NSK_LTABW(NCH) k_learn_seg_tabw<SMALLW, NCH><<<dim3(grid), dim3(NSK_BLOCK), shmem, g->stream>>>(d, tab, lp, prev, rest)
+#define NSK_LTABW(NCH) k_learn_seg_tabw<SMALLW, NCH><<<dim3(grid + service), dim3(NSK_BLOCK), shmem, g->stream>>>(d, tab, lp, prev, rest)
                 if (pl.wide) {
                     if constexpr (sizeof(VT) == 1) {        // (only a plan over byte values is wide)
                         TabwRest rest;
                         rest.n = pl.nrest;
                         memcpy(rest.q, pl.rest, sizeof(rest.q));
-                        const int grid = nsk_learn_tabw_grid(tab.ntiles) + service + nsk_tabw_front_blocks(rest.n);
                         if (sl.nch == 1) NSK_LTABW(1); else NSK_LTABW(2);
                     }
                 } else {
-                    const int grid = nsk_learn_seg_grid(sl, nw, SMALLW, g->values_regular);
                     if (use_tab) { if (sl.nch == 1) NSK_LTAB(1); else NSK_LTAB(2); }
                     else if (sl.tab) { if (sl.nch == 1) NSK_LSEG(0, 1); else NSK_LSEG(0, 2); }   // tables unusable: the
                                                                            // generic slot algebra serves every function
