@@ -277,6 +277,54 @@ int nsk_trace_download_conditionals(nsk_graph *g, double *sums /* chains x total
 int nsk_icm(nsk_graph *g, int which, int64_t first_chain, int64_t nchains, int64_t max_sweeps, int sample_evidence,
             int64_t *sweeps /* nchains */, int64_t *changed /* nchains x max_sweeps, may be NULL */);
 
+/* Tempered sweep schedules (FactorGraph.tempered_sweeps / log_partition / log_evidence / anneal): sweeps at an inverse
+ * temperature beta, driven by a schedule.  potential() is linear in the weights, so sampling from exp(beta U) / Z_beta,
+ * U the log-potential above, IS sampling under the weight table beta * w: one beta per step, shared by every chain,
+ * needs no other sweep kernel, draw table, plan or captured sequence.  The call acts on ALL chains of the handle (R =
+ * nsk_get_chains).  With w_base the device weight table as it stands when the call begins, slot by slot, for
+ * t = 0 .. nsteps - 1, in this order on the handle's stream and without a host wait between steps:
+ *   1. scale  w[s] = betas[t] * w_base[s] for every slot, fixed weights included: one rounded float64 product;
+ *   2. sweep  exactly what nsk_gibbs_sweeps(g, sweeps_per_step, sample_evidence, 1) enqueues under those weights -- the
+ *             same sweep indices, generators, plans and captured sequences, the tables derived from the weights
+ *             rebuilt first; nothing is tallied, no trace row is recorded or counted; sweeps_done and the sweep index
+ *             advance by sweeps_per_step;
+ *   3. score  U_t[r] = the log-potential of chain r's state under w_base (NOT the scaled table), with the very bits
+ *             nsk_log_potential returns for that state and those weights; lp[t * R + r] = U_t[r];
+ *   4. fold   if t + 1 < nsteps: log_weight[r] = log_weight[r] + (betas[t + 1] - betas[t]) * U_t[r] -- one rounded
+ *             difference, one rounded product, one rounded addition, from 0.0, in t order, one lane per chain.  With a
+ *             schedule from 0 to 1 these are the log importance weights of annealed importance sampling: log Z =
+ *             log Z_0 + log mean_r exp(log_weight[r]), Z_0 the number of states of the variables the sweeps sample
+ *             (numbskull_amd.diagnostics.ais_estimate);
+ *   5. best   only when best_values or best_lp is asked for: at step 0 chain r's state and U_0[r] are kept
+ *             unconditionally; afterwards the state replaces the kept one when U_t[r] > best strictly -- the earliest
+ *             maximum wins, a NaN never wins.  The copy is device to device, decided on the device per chain.
+ * Then w = w_base again, bit for bit (a copy, no division), the handle is marked so that a following sweep call rebuilds
+ * the tables under the base weights, and the call synchronises ONCE and downloads what was asked for: log_weight
+ * (R), lp (nsteps x R), best_lp (R), and best_values (R x nvar) through the gather of nsk_chains_download -- the
+ * caller's variable ids, int64.  Each of the four may be NULL.  The values of the chains are left as the last step's
+ * sweeps leave them; tallies, trace rows and columns, and the evidence chain are untouched (a handle with a sample trace
+ * is served; a tally kept in the value bytes is first brought back to its array, as in nsk_icm).  If anything fails after
+ * the first scale, the base weights are still restored before the error is returned.  While the call runs, a pointer
+ * from nsk_device_buffer(NSK_BUF_WEIGHT) sees the SCALED table.
+ * exp is unshifted, as in the sampler: a beta that overflows it is the sampler's own degenerate case.  With the literal
+ * head lookup (IMPLY_MLN-type functions without NSK_FLAG_HEAD_BY_VID) potential() is not the gradient of one energy, the
+ * sampler's stationary law is not exp(U) / Z, and the estimate has no meaning for such graphs (the limit nsk_icm states).
+ * NSK_E_INVALID, before anything is enqueued and with values, weights, sweeps_done and the generator untouched: a null
+ * graph or betas == NULL; nsteps outside [1, 65536]; sweeps_per_step < 1 or nsteps * sweeps_per_step > INT32_MAX; a beta
+ * that is NaN, infinite or negative (the order is free: annealing goes past 1, a reverse run goes down); the
+ * sequential scan; the handles nsk_log_potential refuses (own_range / NSK_FLAG_PARTITION, a boundary exchange).
+ * Memory: the first call uploads what nsk_log_potential uploads, or finds it in place, and that stays; a call that asks
+ * for best_values sets up the staging buffers of the state transfers where no transfer has yet, and they stay too.  The
+ * copy of the base weights (8 bytes a weight), lp, log_weight, the flags and best log-potentials (12 bytes a chain) and
+ * the best states (R x the bytes of a chain's values, rounded up to 16; only with best_values) live for the call only:
+ * nsk_graph_info.device_bytes is afterwards what it was.  NSK_E_NOMEM names the size of what does not fit.
+ * nsk_profile_* keeps counting sweep-kernel launches only. */
+int nsk_tempered_sweeps(nsk_graph *g, const double *betas /* nsteps */, int64_t nsteps, int64_t sweeps_per_step,
+                        int sample_evidence, double *log_weight /* chains, may be NULL */,
+                        double *lp /* nsteps x chains, may be NULL */,
+                        int64_t *best_values /* chains x nvar, the caller's ids, may be NULL */,
+                        double *best_lp /* chains, may be NULL */);
+
 /* Effective sample size from the trace, on the device (FactorGraph.mixing): per column of a BIT-PACKED trace, the
  * split-chain estimator of numbskull_amd.diagnostics.effective_sample_size with the lags cut at max_lag, in one
  * streaming pass over the packed rows -- no row is unpacked or leaves the device.  Rows first_row .. first_row +

@@ -582,8 +582,9 @@ int nsk_state_upload(nsk_graph *g, const int64_t *var_value, const int64_t *var_
 }
 
 // device values of one chain -> the caller's int64 array: gather into the caller's order on the device, one
-// narrow copy over PCIe, widened by the host threads
-static int download_values(nsk_graph *g, const void *src, int64_t *dst, int k) {
+// narrow copy over PCIe, widened by the host threads (internal, not in the public header: nsk_temper.hip downloads its
+// kept states through it)
+int nsk_download_values(nsk_graph *g, const void *src, int64_t *dst, int k) {
     const int64_t nvar = g->c.nvar;
     if (!nvar) return NSK_OK;
     int rc = xfer_ensure(g);
@@ -608,8 +609,8 @@ int nsk_state_download(nsk_graph *g, int64_t *var_value, int64_t *var_value_evid
     HIPCHECK(hipSetDevice(g->device));
     { int frc = nsk_p2p_flush(g); if (frc) return frc; }
     int rc;
-    if (var_value && (rc = download_values(g, g->val, var_value, 0))) return rc;
-    if (var_value_evid && (rc = download_values(g, g->val_evid, var_value_evid, 1))) return rc;
+    if (var_value && (rc = nsk_download_values(g, g->val, var_value, 0))) return rc;
+    if (var_value_evid && (rc = nsk_download_values(g, g->val_evid, var_value_evid, 1))) return rc;
     if (weight_value && g->c.nweight) {
         if (!g->c.wuser.empty()) {      // slot order on the device, the caller's order in `weight_value`
             g->w_stage.resize((size_t)g->c.nweight);
@@ -783,7 +784,7 @@ int nsk_chains_download(nsk_graph *g, int64_t *var_value, int64_t *count) {
     int rc;
     if (var_value)
         for (size_t r = 0; r < R; r++)
-            if ((rc = download_values(g, (const char *)g->val + r * g->chain_stride, var_value + r * nvar, 0))) return rc;
+            if ((rc = nsk_download_values(g, (const char *)g->val + r * g->chain_stride, var_value + r * nvar, 0))) return rc;
     if (count && nc) {
         if ((rc = fold_counts(g))) return rc;
         HIPCHECK(hipMemcpyAsync(count, g->cnt_total, R * nc * sizeof(int64_t), hipMemcpyDeviceToHost, g->stream));

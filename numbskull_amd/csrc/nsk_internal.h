@@ -1,7 +1,7 @@
 // nsk_internal.h -- host-side state of a compiled graph handle, shared by the translation units of
 // the library (nsk_api.hip: C-ABI, state sync; nsk_exchange.hip: the multi-GPU boundary exchange; nsk_gibbs.hip /
 // nsk_learn.hip: the sweep drivers of numbskull/factorgraph.py:141,163,202; nsk_trace.hip, nsk_energy.hip, nsk_wstats.hip,
-// nsk_cond.hip: the diagnostics; nsk_icm.hip: the greedy MAP search).
+// nsk_cond.hip: the diagnostics; nsk_icm.hip: the greedy MAP search; nsk_temper.hip: tempered sweep schedules).
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -443,6 +443,8 @@ struct ColourStreams {
 // the fast path reads weights through prog_w (and the draw tables): rebuilt whenever weights may
 // have changed (nsk_api.hip)
 extern "C" int nsk_ensure_generic(nsk_graph *g);       // internal (not in the public header)
+// one chain's device values at `src` -> the caller's ids, int64, through staging buffer k; synchronises (nsk_api.hip)
+extern "C" int nsk_download_values(nsk_graph *g, const void *src, int64_t *dst, int k);
 int nsk_ensure_lag_sets(nsk_graph *g);                 // second set of weights / tables / accumulators (nsk_api.hip)
 // one peer-to-peer exchange on the library's stream; tag_base != null: a captured launch whose tag is
 // the device counter + tag_off; learn: both chains + the weight deltas; part 0 = all of it, 1 = the

@@ -46,6 +46,11 @@ marginals of ``FactorGraph.rao_blackwell`` can be compared with the tally's.
 
 ``icm_choice`` restates the rule by which ``FactorGraph.icm`` (nsk_icm) picks a variable's new value
 from the same potentials: greedy coordinate ascent towards a MAP estimate.
+
+``ais_log_weights``, ``log_mean_exp``, ``ais_estimate`` and ``thermodynamic_integral`` are the host side of
+``FactorGraph.tempered_sweeps`` / ``log_partition`` (nsk_tempered_sweeps): the device runs the
+sweeps under a schedule of inverse temperatures and hands back every step's log-potentials; the fold of the importance
+weights restated with the device's roundings, and the estimators of log Z, which need a ``log`` and live here.
 """
 
 import collections
@@ -532,3 +537,65 @@ def tally_layout(offsets, values):
     keep[off[:-1][card == 2]] = False
     toff = np.concatenate([[0], np.cumsum(np.where(card == 2, 1, card))]).astype(np.int64)
     return toff, v[..., keep]
+
+
+def _schedule(betas, lp, what):
+    b = np.asarray(betas, np.float64)
+    u = np.asarray(lp, np.float64)
+    if b.ndim != 1 or u.ndim != 2 or u.shape[0] != len(b) or len(b) < 1:
+        raise ValueError("%s: betas (T,) and log-potentials (T, chains), got %r and %r" % (what, b.shape, u.shape))
+    return b, u
+
+
+def ais_log_weights(betas, lp):
+    """The log importance weights of annealed importance sampling (Neal, "Annealed importance sampling", Statistics and
+    Computing 11, 2001) as nsk_tempered_sweeps folds them: ``betas`` (T,) the schedule, ``lp`` (T, chains) the
+    log-potential of every chain after the sweeps of every step.  Per chain, from 0.0 and in step order,
+    ``logw = logw + (betas[t + 1] - betas[t]) * lp[t]`` for ``t + 1 < T`` -- one rounded difference, one rounded product,
+    one rounded addition, a plain loop: fed the device's ``lp`` it returns the device's ``log_weights`` bit for bit."""
+    b, u = _schedule(betas, lp, "ais_log_weights")
+    logw = np.zeros(u.shape[1], np.float64)
+    for t in range(len(b) - 1):
+        d = b[t + 1] - b[t]
+        term = d * u[t]
+        logw = logw + term
+    return logw
+
+
+def log_mean_exp(x):
+    """``log(mean(exp(x)))`` of a 1-d array, shifted by its maximum so that nothing overflows; -inf when every entry is
+    -inf, NaN for an empty array."""
+    x = np.asarray(x, np.float64).ravel()
+    if x.size == 0:
+        return float("nan")
+    m = float(x.max())
+    if not np.isfinite(m):
+        return m
+    return m + float(np.log(np.mean(np.exp(x - m))))
+
+
+def ais_estimate(log_weights, log_z0):
+    """``(log_z, stderr, ess)`` from the AIS log-weights of R chains and ``log_z0``, the log of the number of states at
+    beta = 0.  With ``w = exp(logw - max)``: ``log_z = log_z0 + max + log(mean w)``; ``stderr = std(w, ddof=1) / (mean(w)
+    sqrt(R))``, the delta-method standard error of ``log_z`` (NaN for R = 1); ``ess = (sum w)^2 / sum w^2``, the
+    effective number of chains behind the mean (between 1 and R)."""
+    lw = np.asarray(log_weights, np.float64).ravel()
+    n = lw.size
+    if n < 1:
+        raise ValueError("ais_estimate: no log-weights")
+    m = float(lw.max())
+    w = np.exp(lw - m)
+    mean = float(w.mean())
+    log_z = float(log_z0) + m + float(np.log(mean))
+    stderr = float(np.std(w, ddof=1) / (mean * np.sqrt(n))) if n > 1 else float("nan")
+    ess = float(w.sum() ** 2 / (w * w).sum())
+    return log_z, stderr, ess
+
+
+def thermodynamic_integral(betas, lp, log_z0):
+    """``log_z0`` plus the trapezoid over beta of the chain-mean of ``lp``: d log Z_beta / d beta = E_beta[U], so the
+    integral from 0 to 1 is log Z - log Z_0.  An independent cross-check of ``ais_estimate`` from the same numbers; its
+    bias is the trapezoid's and the chains' lag behind the schedule, and it comes without an error bar."""
+    b, u = _schedule(betas, lp, "thermodynamic_integral")
+    mean = u.mean(axis=1)
+    return float(log_z0) + float(np.sum(np.diff(b) * 0.5 * (mean[1:] + mean[:-1])))

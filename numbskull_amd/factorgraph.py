@@ -982,6 +982,110 @@ class FactorGraph(object):
                 "sampled_log_potential": float(sampled[chain]), "sweeps": int(res["sweeps"][chain]),
                 "converged": bool(res["converged"][chain]), "log_potentials": after, "sampled_log_potentials": sampled}
 
+    # ------------------------------------------------------------------ tempered schedules: log Z, annealing
+    @staticmethod
+    def _schedule(betas, what):
+        b = np.ascontiguousarray(betas, np.float64)
+        if b.ndim != 1 or len(b) < 1:
+            raise ValueError("%s: betas is a 1-d schedule of at least one inverse temperature" % what)
+        if not (np.isfinite(b).all() and (b >= 0).all()):
+            raise ValueError("%s: an inverse temperature is negative, infinite or NaN" % what)
+        return b
+
+    def tempered_sweeps(self, betas, sweeps=1, sample_evidence=False, weight_copy=0, best=False):
+        """Sweeps under a schedule of inverse temperatures, driven on the device (nsk_tempered_sweeps): for every
+        ``betas[t]`` in turn the weights are scaled by it, ``sweeps`` burn-in sweeps run on every chain -- one chain per
+        row of ``var_value``, pushed and pulled as ``icm(var_copy="all")`` does, under ``weight_value[weight_copy]`` --
+        and every chain's log-potential under the UNSCALED weights is taken.  Sampling at beta is sampling under the weight
+        table beta x w, so step t draws from ``exp(betas[t] U) / Z``; nothing is tallied (``count`` stays) and the weights
+        come back as they were.  Returns a dict: ``log_potentials`` float64 ``(T, chains)``, the log-potential after
+        every step, with the bits ``log_potential`` gives for that state; ``log_weights`` ``(chains,)``, the sum over
+        ``t + 1 < T`` of ``(betas[t + 1] - betas[t]) * log_potentials[t]`` (``diagnostics.ais_log_weights``: with a
+        schedule from 0 to 1 the log importance weights of annealed importance sampling); with ``best=True`` also
+        ``best_values`` int64 ``(chains, nvar)`` and ``best_log_potentials`` ``(chains,)``, each chain's state of largest
+        log-potential over the steps (the earliest among equals), kept on the device.  ``var_value`` is left holding the
+        final states.  The schedule's order is free: annealing goes past 1."""
+        b = self._schedule(betas, "tempered_sweeps")
+        sweeps = int(sweeps)
+        if sweeps < 1:
+            raise ValueError("tempered_sweeps: sweeps must be at least 1")
+        L, h = _lib.lib(), self._engine()
+        nchains = self._push_chains(weight_copy, count=False)
+        lp, logw = np.zeros((len(b), nchains), np.float64), np.zeros(nchains, np.float64)
+        bv = np.zeros((nchains, self.variable.shape[0]), np.int64) if best else None
+        bu = np.zeros(nchains, np.float64) if best else None
+        _lib.check(L.nsk_tempered_sweeps(h, _lib.ptr(b), len(b), sweeps, int(bool(sample_evidence)), _lib.ptr(logw), _lib.ptr(lp),
+                                         _lib.ptr(bv), _lib.ptr(bu)))
+        self._pull_chains(count=False)
+        out = {"log_weights": logw, "log_potentials": lp}
+        if best:
+            out["best_values"], out["best_log_potentials"] = bv, bu
+        return out
+
+    def log_partition(self, steps=100, betas=None, sweeps=1, sample_evidence=False, weight_copy=0):
+        """log Z by annealed importance sampling (Neal 2001), the chains of ``var_value`` as the particles:
+        ``tempered_sweeps`` along ``betas`` -- ``np.linspace(0, 1, steps + 1)`` unless given; a schedule must start at 0.0
+        and end at 1.0 (ValueError, raised before the device is touched) -- and ``diagnostics.ais_estimate`` of the
+        log-weights.  The first step's sweeps, at beta = 0, draw every sampled variable uniformly, so the rows of
+        ``var_value`` need no preparation.  With ``sample_evidence=False`` Z is the partition function with the evidence
+        variables clamped at their current values, with ``True`` the free one.  Returns a dict: ``log_z``; ``stderr``
+        (NaN for one chain) and ``ess``, the effective number of chains behind the estimate (``diagnostics.ais_estimate``);
+        ``log_z0`` = the sum of log(cardinality) over the variables the sweeps sample; ``log_weights``; ``log_z_ti``, the
+        thermodynamic integral of the same log-potentials, an independent cross-check; ``betas``.  ``log Z -
+        log_potential`` of a state is its negative log-likelihood.  Meaningless where ``potential()`` is not the gradient
+        of one energy: the reference's literal head lookup of IMPLY_MLN-type functions (see ``icm``)."""
+        from .diagnostics import ais_estimate, thermodynamic_integral
+        if betas is None:
+            steps = int(steps)
+            if steps < 1:
+                raise ValueError("log_partition: steps must be at least 1")
+            b = np.linspace(0.0, 1.0, steps + 1)
+        else:
+            b = self._schedule(betas, "log_partition")
+            if len(b) < 2 or b[0] != 0.0 or b[-1] != 1.0:
+                raise ValueError("log_partition: the schedule must start at 0.0 and end at 1.0")
+        res = self.tempered_sweeps(b, sweeps, sample_evidence, weight_copy)
+        sampled = self.colors() >= 0
+        if not sample_evidence:
+            sampled &= np.asarray(self.variable["isEvidence"]) == 0
+        log_z0 = float(np.log(np.asarray(self.variable["cardinality"], np.float64)[sampled]).sum())
+        log_z, stderr, ess = ais_estimate(res["log_weights"], log_z0)
+        return {"log_z": log_z, "stderr": stderr, "ess": ess, "log_z0": log_z0, "log_weights": res["log_weights"],
+                "log_z_ti": thermodynamic_integral(b, res["log_potentials"], log_z0), "betas": b}
+
+    def log_evidence(self, steps=100, betas=None, sweeps=1, weight_copy=0):
+        """log P(the evidence variables hold their values in ``var_value``) = log Z with the evidence clamped minus log Z
+        with every variable free: two ``log_partition`` runs from the same rows.  Every row of ``var_value`` must hold
+        the same evidence values (the clamped Z is one number).  Returns a dict: ``log_evidence``; ``stderr``, the root of
+        the two squared errors; ``clamped`` and ``free``, the two ``log_partition`` results.  ``var_value`` is restored to
+        what it held before the call."""
+        keep = np.array(self.var_value, np.int64)
+        try:
+            clamped = self.log_partition(steps, betas, sweeps, False, weight_copy)
+            self.var_value[:] = keep
+            free = self.log_partition(steps, betas, sweeps, True, weight_copy)
+        finally:
+            self.var_value[:] = keep
+        return {"log_evidence": clamped["log_z"] - free["log_z"],
+                "stderr": float(np.sqrt(clamped["stderr"] ** 2 + free["stderr"] ** 2)), "clamped": clamped, "free": free}
+
+    def anneal(self, betas, sweeps=1, sample_evidence=False, max_sweeps=100):
+        """A MAP search that can leave a basin: simulated annealing with the best state tracked on the device.  Runs
+        ``tempered_sweeps(betas, sweeps, sample_evidence, best=True)`` -- a schedule that rises past 1 cools the chains --
+        loads every chain's best state, polishes it with ``icm(max_sweeps, var_copy="all")`` and evaluates
+        ``log_potential(var_copy="all")``.  No trace is set up: nothing but the best states is kept.  Returns the dict
+        ``map_estimate`` returns; ``sampled_log_potential(s)`` are the best ones kept on the device, before polishing.
+        ``var_value`` is left holding the polished states; ``count`` is untouched."""
+        res = self.tempered_sweeps(betas, sweeps, sample_evidence, best=True)
+        sampled = res["best_log_potentials"]
+        self.var_value[:] = res["best_values"]
+        pol = self.icm(max_sweeps, var_copy="all", sample_evidence=sample_evidence)
+        after = self.log_potential(var_copy="all")
+        chain = int(np.argmax(after))
+        return {"values": np.array(self.var_value[chain], np.int64), "log_potential": float(after[chain]), "chain": chain,
+                "sampled_log_potential": float(sampled[chain]), "sweeps": int(pol["sweeps"][chain]),
+                "converged": bool(pol["converged"][chain]), "log_potentials": after, "sampled_log_potentials": sampled}
+
     # ------------------------------------------------------------------ per-weight statistics
     def weight_statistics(self, var_copy=0, evidence_chain=False, feature_scaled=False):
         """The sufficient statistics of a state: for every weight the sum of the values of its factors (the
