@@ -277,6 +277,61 @@ int nsk_trace_download_conditionals(nsk_graph *g, double *sums /* chains x total
 int nsk_icm(nsk_graph *g, int which, int64_t first_chain, int64_t nchains, int64_t max_sweeps, int sample_evidence,
             int64_t *sweeps /* nchains */, int64_t *changed /* nchains x max_sweeps, may be NULL */);
 
+/* Pseudo-likelihood gradient and maximum pseudo-likelihood learning (FactorGraph.pl_gradient / learn_mple): the
+ * derivative of sum_v log P(x_v | every other variable) over a selection of variables with respect to every weight, and
+ * the deterministic, sampling-free learner built on it.  No random number is drawn and no logarithm is taken on the
+ * device.  For a state x, the weight table w and a selected variable v that has a position, of cardinality C and own
+ * value cur = x_v: P_k, k = 0 .. C - 1, are the very bits nsk_conditionals(what = 1) returns for v.  The variable is
+ * SKIPPED when cur lies outside [0, C) or Z is not a finite positive number: it contributes nothing and adds one to the
+ * chain's `skipped`.  Otherwise, for k = 0 .. C - 1 and every entry f of the factor list of (v, k) (one list for
+ * dataType 0):
+ *   c_k = (k == cur ? 1.0 : 0.0) - P_k        one rounded subtraction
+ *   e   = eval_factor(f, v, k, x)             as potential() calls it, head quirks included
+ *   t   = c_k * e                             one rounded product
+ *   q   = t * 2^32 rounded to the nearest int64, ties to even (numpy: np.rint(t * 2.0**32).astype(np.int64))
+ *   G[weight of f] += q                       int64
+ * G_w * 2^-32 is the derivative with respect to weight w, to within 2^-33 per term.  The sums are integers, so no order
+ * of execution changes a bit (numbskull_amd.diagnostics.pl_gradient_counts is the rule in numpy).  Fixed weights get
+ * their sum like any other; featureValue plays no part, as in potential().  With the literal head lookup (IMPLY_MLN-type
+ * functions without NSK_FLAG_HEAD_BY_VID) this is the derivative of the sum of the SAMPLER'S OWN conditionals, which is
+ * then not the derivative of the pseudo-likelihood of one joint energy -- the limit nsk_icm states.
+ * vids = the caller's variable ids in any order, NULL with nvids = 0 for all nvar variables; an id outside [0, nvar) is
+ * NSK_E_INDEX, a repeated id NSK_E_INVALID (the selection is a set); a variable without a position contributes nothing
+ * and is not counted in N below.  `which`, the chains and the handles refused (NSK_E_INVALID) follow nsk_conditionals /
+ * nsk_log_potential rule for rule; the sequential scan is fine, several chains are served, a handle with a sample trace
+ * is served and its rows and columns are untouched; a tally kept in the value bytes is first brought back to its array,
+ * as in nsk_icm.
+ * Range, decided before any launch from the graph and the selection alone: with B_w = the sum over the selected
+ * variables' list entries naming weight w of m * vmax(f) -- m = 2 for an entry of a dataType-0 list, 1 for a dataType-1
+ * one; vmax = arity for LINEAR, log(arity + 1) for RATIO, 1e6 for UFO, 1 otherwise -- the call is NSK_E_RANGE when
+ * B_w * nchains >= 2^30 for some w.
+ * nsk_pl_gradient: grad_q[i * nweight + w] = G_w of chain first_chain + i, in the caller's weight ids (slots are mapped
+ * back as nsk_state_download maps the weights); grad = (double)grad_q * 2^-32; skipped[i] = the chain's skips.  Each of
+ * the three may be NULL.  It changes nothing.
+ * nsk_mple_steps: nsteps gradient-ascent steps on the mean log-pseudo-likelihood of the chains named, every chain one
+ * training example.  N = (selected variables with a position) * nchains.  For t = 0 .. nsteps - 1, on the handle's
+ * stream and without a host wait: zero G; the gradient launch above; then per weight slot, with S = the int64 sum of G
+ * over the chains (exact) and step_0 = step, step_{t+1} = step_t * decay (the products formed on the host in t order):
+ *   gbar = ((double)S * 2^-32) / N            one conversion, an exact scaling, one rounded division
+ *   a = reg_param * w;  b = gbar - a;  c = step_t * b;  w = w + c      one rounded operation each
+ * -- not for a fixed weight, which stays -- and gmax[t] = the largest |S| over the weights that are not fixed,
+ * skipped[t] = the skips of step t summed over the chains (numbskull_amd.diagnostics.mple_step is the update in numpy).
+ * The call synchronises once and downloads gmax and skipped (each may be NULL).  It leaves the new weights in the
+ * device table, marked so that the next sweep call rebuilds what derives from them, and changes nothing else: values,
+ * tallies, sweeps_done, the generator state and the trace stay.  nsteps outside [1, 65536], a step, decay or reg_param
+ * that is not finite, or reg_param < 0: NSK_E_INVALID.  N == 0 is NSK_OK with nothing done.
+ * Memory: the first call uploads what nsk_conditionals uploads, or finds it in place; the selection (4 bytes a
+ * variable), chains x (nweight + 1) int64 and the per-step outputs (16 bytes a step) live for the call only, so
+ * nsk_graph_info.device_bytes is afterwards what a nsk_conditionals call leaves.  NSK_E_NOMEM names the size of what
+ * does not fit.  nsk_profile_* keeps counting sweep-kernel launches only.  A handle that never calls these allocates
+ * and launches nothing for them. */
+int nsk_pl_gradient(nsk_graph *g, int which, int64_t first_chain, int64_t nchains, const int64_t *vids, int64_t nvids,
+                    int64_t *grad_q /* nchains x nweight, may be NULL */, double *grad /* same shape, may be NULL */,
+                    int64_t *skipped /* nchains, may be NULL */);
+int nsk_mple_steps(nsk_graph *g, int which, int64_t first_chain, int64_t nchains, const int64_t *vids, int64_t nvids,
+                   int64_t nsteps, double step, double decay, double reg_param,
+                   int64_t *gmax /* nsteps, may be NULL */, int64_t *skipped /* nsteps, may be NULL */);
+
 /* Tempered sweep schedules (FactorGraph.tempered_sweeps / log_partition / log_evidence / anneal): sweeps at an inverse
  * temperature beta, driven by a schedule.  potential() is linear in the weights, so sampling from exp(beta U) / Z_beta,
  * U the log-potential above, IS sampling under the weight table beta * w: one beta per step, shared by every chain,

@@ -33,6 +33,7 @@ SYMBOLS = (
     "nsk_log_potential", "nsk_factor_values", "nsk_trace_log_potential", "nsk_trace_download_log_potential",
     "nsk_weight_stats", "nsk_trace_weight_stats", "nsk_trace_download_weight_stats",
     "nsk_conditionals", "nsk_trace_conditionals", "nsk_trace_download_conditionals", "nsk_icm", "nsk_tempered_sweeps",
+    "nsk_pl_gradient", "nsk_mple_steps",
     "nsk_trace_ess", "nsk_trace_autocov_counts", "nsk_trace_pair_counts",
     "nsk_trace_value_autocov_counts", "nsk_trace_value_ess", "nsk_trace_value_pair_counts",
     "nsk_selftest_exp", "nsk_selftest_philox", "nsk_selftest_stream", "nsk_device_count", "nsk_last_error", "nsk_version",
@@ -64,6 +65,20 @@ class GraphInfo(C.Structure):
                 ("tiles_shape", C.c_int64), ("tiles_shape_padded", C.c_int64), ("tiles_lane", C.c_int64),
                 ("tiles_general", C.c_int64), ("tiles_general_roles", C.c_int64),
                 ("ep_groups", C.c_int64), ("ep_groups_two_pass", C.c_int64)]
+
+
+# the launch of nsk_pl_gradient / nsk_mple_steps (csrc/nsk_kernels_plgrad.h nsk_plgrad_blocks): blocks of PLGRAD_BLOCK lanes
+# per chain; one selected variable per lane up to PLGRAD_CU_BLOCKS blocks, then two per lane before the grid grows, at
+# most PLGRAD_MAX_BLOCKS blocks -- a longer selection loops further; LDS bins up to PLGRAD_BINS weights
+PLGRAD_BLOCK, PLGRAD_CU_BLOCKS, PLGRAD_MAX_BLOCKS, PLGRAD_BINS = 256, 256, 2048, 256
+
+
+def plgrad_blocks(nsel):
+    """Blocks per chain of the gradient launch for a selection of ``nsel`` variables with a position."""
+    one = (int(nsel) + PLGRAD_BLOCK - 1) // PLGRAD_BLOCK
+    if one <= PLGRAD_CU_BLOCKS:
+        return max(1, one)
+    return max(PLGRAD_CU_BLOCKS, min(PLGRAD_MAX_BLOCKS, (one + 1) // 2))
 
 
 # the route word of nsk_graph_plan_routes / nsk_graph_get_routes (include/numbskull_amd.h "Routes")
@@ -147,6 +162,9 @@ def lib():
         L.nsk_trace_conditionals.argtypes = [C.c_void_p, C.c_void_p, C.c_int64]
         L.nsk_trace_download_conditionals.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(C.c_int64)]
         L.nsk_icm.argtypes = [C.c_void_p, C.c_int, C.c_int64, C.c_int64, C.c_int64, C.c_int, C.c_void_p, C.c_void_p]
+        L.nsk_pl_gradient.argtypes = [C.c_void_p, C.c_int, C.c_int64, C.c_int64, C.c_void_p, C.c_int64] + [C.c_void_p] * 3
+        L.nsk_mple_steps.argtypes = [C.c_void_p, C.c_int, C.c_int64, C.c_int64, C.c_void_p, C.c_int64, C.c_int64,
+                                     C.c_double, C.c_double, C.c_double, C.c_void_p, C.c_void_p]
         L.nsk_tempered_sweeps.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int] + [C.c_void_p] * 4
         L.nsk_trace_ess.argtypes = [C.c_void_p, C.c_int64, C.c_int64, C.c_int64] + [C.c_void_p] * 4
         L.nsk_trace_autocov_counts.argtypes = [C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p]

@@ -51,6 +51,10 @@ from the same potentials: greedy coordinate ascent towards a MAP estimate.
 ``FactorGraph.tempered_sweeps`` / ``log_partition`` (nsk_tempered_sweeps): the device runs the
 sweeps under a schedule of inverse temperatures and hands back every step's log-potentials; the fold of the importance
 weights restated with the device's roundings, and the estimators of log Z, which need a ``log`` and live here.
+
+``pl_gradient_counts`` and ``mple_step`` restate ``FactorGraph.pl_gradient`` / ``learn_mple`` (nsk_pl_gradient,
+nsk_mple_steps): the gradient of the log-pseudo-likelihood as int64 sums of quantised terms -- exact,
+whatever the order -- and the weight update of maximum pseudo-likelihood learning, one rounded operation each.
 """
 
 import collections
@@ -537,6 +541,71 @@ def tally_layout(offsets, values):
     keep[off[:-1][card == 2]] = False
     toff = np.concatenate([[0], np.cumsum(np.where(card == 2, 1, card))]).astype(np.int64)
     return toff, v[..., keep]
+
+
+def pl_gradient_counts(offsets, probabilities, values, entry_var, entry_k, entry_weight, entry_eval, nweight):
+    """The gradient of the log-pseudo-likelihood with respect to the weights, as ``FactorGraph.pl_gradient(counts=True)``
+    sums it on the device (nsk_pl_gradient), for ONE state.  ``offsets`` / ``probabilities`` are the "full" layout of
+    ``FactorGraph.conditionals()`` for the selection (``P_k`` of selected variable ``i`` at ``offsets[i] + k``), ``values``
+    (nsel,) each selected variable's own value.  The entries are the walk: entry ``j`` says that the factor list of
+    (selected variable ``entry_var[j]`` -- an index into the selection --, value ``entry_k[j]``) holds a factor of weight
+    ``entry_weight[j]`` whose value with the variable at ``entry_k[j]`` is ``entry_eval[j]``; a factor of a dataType-0
+    list appears once per value.  Per entry, with ``cur`` the variable's own value::
+
+        c = (k == cur ? 1.0 : 0.0) - P_k;  t = c * e;  q = np.rint(t * 2.0**32).astype(np.int64);  counts[weight] += q
+
+    A variable is SKIPPED -- no entry of it counts -- when its value lies outside its domain or its ``Z`` is not a finite
+    positive number, which its probabilities show: one of them is NaN (``Z`` is 0, NaN, or infinite through an infinite
+    term), or none is positive (a finite sum that overflowed).  Returns ``(counts, skipped)``: int64 ``(nweight,)`` and
+    the number of skipped variables.  ``counts * 2.0**-32`` is the derivative, to within ``2**-33`` per entry; the sums
+    are integers, so their order does not matter."""
+    off, p = _full_layout(offsets, probabilities, "pl_gradient_counts")
+    if p.ndim != 1:
+        raise ValueError("pl_gradient_counts: one state at a time: probabilities are (total,), got %r" % (p.shape,))
+    card = np.diff(off)
+    x = np.asarray(values)
+    if x.shape != (len(card),) or (x.size and x.dtype.kind not in "iu"):
+        raise ValueError("pl_gradient_counts: values are integers (nsel,) = (%d,), got %r %s" % (len(card), x.shape, x.dtype))
+    x = x.astype(np.int64)
+    ev, ek = np.asarray(entry_var, np.int64), np.asarray(entry_k, np.int64)
+    ew, ee = np.asarray(entry_weight, np.int64), np.asarray(entry_eval, np.float64)
+    if not (ev.ndim == 1 and ev.shape == ek.shape == ew.shape == ee.shape):
+        raise ValueError("pl_gradient_counts: the four entry arrays are one-dimensional and equally long")
+    counts = np.zeros(int(nweight), np.int64)
+    if len(card) == 0:
+        return counts, 0
+    if len(ev) and (ev.min() < 0 or ev.max() >= len(card) or ek.min() < 0 or (ek >= card[ev]).any()
+                    or ew.min() < 0 or ew.max() >= nweight):
+        raise IndexError("pl_gradient_counts: an entry names a variable, value or weight out of range")
+    nan = np.isnan(p)
+    skip = (x < 0) | (x >= card) | (np.add.reduceat(nan.astype(np.int64), off[:-1]) > 0) \
+        | ~(np.maximum.reduceat(np.where(nan, 0.0, p), off[:-1]) > 0)
+    keep = ~skip[ev]
+    ev, ek, ew, ee = ev[keep], ek[keep], ew[keep], ee[keep]
+    c = (ek == x[ev]).astype(np.float64) - p[off[ev] + ek]
+    t = c * ee
+    q = np.rint(t * 2.0 ** 32).astype(np.int64)
+    np.add.at(counts, ew, q)
+    return counts, int(skip.sum())
+
+
+def mple_step(w, fixed, counts_sum, n, step, reg_param):
+    """One step of maximum pseudo-likelihood learning as ``FactorGraph.learn_mple`` takes it on the device
+    (nsk_mple_steps): ``counts_sum`` (nweight,) is the int64 sum of ``pl_gradient_counts`` over the training examples,
+    ``n`` = selected variables x examples.  One rounded float64 operation each::
+
+        gbar = (float(S) * 2.0**-32) / n;  a = reg_param * w;  b = gbar - a;  c = step * b;  w = w + c
+
+    Weights with ``fixed`` set stay as they are.  Returns the new weights (a new array)."""
+    w = np.asarray(w, np.float64)
+    s = np.asarray(counts_sum)
+    if s.dtype.kind not in "iu" or s.shape != w.shape:
+        raise ValueError("mple_step: counts_sum is int64 with the shape of w")
+    gbar = (s.astype(np.float64) * 2.0 ** -32) / np.float64(n)
+    a = np.float64(reg_param) * w
+    b = gbar - a
+    c = np.float64(step) * b
+    return np.where(np.asarray(fixed).astype(bool), w, w + c)
 
 
 def _schedule(betas, lp, what):

@@ -866,6 +866,85 @@ class FactorGraph(object):
             values = np.asarray((self.var_value_evid if evidence_chain else self.var_value)[var_copy])[ids]
         return log_pseudo_likelihood(offsets, pot, values.astype(np.int64))
 
+    # ------------------------------------------------------------------ pseudo-likelihood gradient, MPLE learning
+    def _pl_selection(self, var_ids, var_copy, evidence_chain, what):
+        """The selection of ``log_pseudo_likelihood`` (None = the variables with ``isEvidence == 0``), as a set; argument
+        errors before any device work."""
+        default = np.nonzero(self.variable["isEvidence"] == 0)[0] if var_ids is None else None
+        ids, _ = self._cond_selection(var_ids, default, what)
+        if len(np.unique(ids)) != len(ids):
+            raise ValueError("%s: a variable id is repeated (the selection is a set)" % what)
+        if _all_copies(var_copy) and evidence_chain:
+            raise ValueError('the evidence chain exists once: var_copy="all" is for the free chains')
+        return ids
+
+    def pl_gradient(self, var_ids=None, var_copy=0, weight_copy=0, evidence_chain=False, counts=False):
+        """The gradient of ``log_pseudo_likelihood`` with respect to the weights, summed on the device
+        (nsk_pl_gradient): for every weight the sum, over the selected variables ``v`` (None = those with
+        ``isEvidence == 0``), their values ``k`` and the factors ``f`` of the weight in the list of ``(v, k)``, of
+        ``((k == x_v) - P(x_v = k | the others)) * f(x with v at k)``.  Every term is rounded to a multiple of ``2**-32``
+        and the terms are added as int64, so the result is exact to within ``2**-33`` per term and does not depend on the
+        order of execution (``diagnostics.pl_gradient_counts`` is the rule in numpy).  State and weights are pushed as
+        ``conditionals`` pushes them.  Returns float64 ``(nweight,)`` in the order of ``weight`` -- fixed weights
+        included; ``var_copy="all"`` gives ``(chains, nweight)``, one row per row of ``var_value``.  ``counts=True``
+        returns ``(int64 sums, skipped)`` instead: the raw sums (gradient ``= sums * 2.0**-32``) and the number of
+        selected variables skipped because their value lies outside its domain or their normaliser is not a finite
+        positive number (an array per chain for ``"all"``).  Repeated ids raise ValueError: the selection is a set.
+        With the reference's literal head lookup this is the derivative of the sum of the sampler's own conditionals,
+        which are then not those of one joint distribution."""
+        ids = self._pl_selection(var_ids, var_copy, evidence_chain, "pl_gradient")
+        L, h = _lib.lib(), self._engine()
+        nw = self.weight.shape[0]
+        if _all_copies(var_copy):
+            nchains = self._push_chains(weight_copy, count=False)
+            which, shape = _lib.BUF_VALUE, (nchains, nw)
+        else:
+            self._push(var_copy, weight_copy)
+            nchains, which, shape = 1, (_lib.BUF_VALUE_EVID if evidence_chain else _lib.BUF_VALUE), (nw,)
+        gq, skipped = np.zeros(shape, np.int64), np.zeros(nchains, np.int64)
+        if len(ids):
+            _lib.check(L.nsk_pl_gradient(h, which, 0, nchains, _lib.ptr(ids), len(ids), _lib.ptr(gq), None, _lib.ptr(skipped)))
+        if counts:
+            return gq, (skipped if _all_copies(var_copy) else int(skipped[0]))
+        return gq.astype(np.float64) * 2.0 ** -32
+
+    def learn_mple(self, epochs, stepsize, decay=1.0, reg_param=0.0, var_ids=None, var_copy=0, weight_copy=0,
+                   evidence_chain=False):
+        """Maximum pseudo-likelihood learning on the device (nsk_mple_steps): ``epochs`` steps of gradient ascent on the
+        mean log-pseudo-likelihood of fully observed data, ``w += step * (pl_gradient / n - reg_param * w)`` with
+        ``step = stepsize * decay**t`` -- deterministic, no sampling, every chain an example.  The data are
+        ``var_value[var_copy]`` (``var_value_evid[var_copy]`` with ``evidence_chain=True``); ``var_copy="all"`` makes
+        every row of ``var_value`` a training example.  ``var_ids`` selects the variables whose conditionals count
+        (None = those with ``isEvidence == 0``; repeats raise ValueError).  State and weights are pushed as
+        ``conditionals`` pushes them; all steps run on the device without returning to the host, and the learned weights
+        are pulled back into ``weight_value[weight_copy]``, as ``learn`` does.  Fixed weights stay.  Nothing else
+        changes: values, ``count`` and the generator are as before.  Returns a dict: ``grad_max`` -- float64
+        ``(epochs,)``, the largest magnitude of the mean gradient over the weights that are not fixed at the weights
+        each step started from (without the penalty); ``skipped`` -- int64 ``(epochs,)``, the variables skipped in each
+        step, summed over the examples (see ``pl_gradient``); ``n`` -- selected variables with a position x examples
+        (``diagnostics.mple_step`` is the update in numpy)."""
+        epochs = int(epochs)
+        if epochs < 1 or epochs > 65536:
+            raise ValueError("learn_mple: epochs must lie in [1, 65536]")
+        stepsize, decay, reg_param = float(stepsize), float(decay), float(reg_param)
+        if not (np.isfinite(stepsize) and np.isfinite(decay) and np.isfinite(reg_param)) or reg_param < 0:
+            raise ValueError("learn_mple: stepsize, decay and reg_param must be finite, reg_param not negative")
+        ids = self._pl_selection(var_ids, var_copy, evidence_chain, "learn_mple")
+        L, h = _lib.lib(), self._engine()
+        if _all_copies(var_copy):
+            nchains, which = self._push_chains(weight_copy, count=False), _lib.BUF_VALUE
+        else:
+            self._push(var_copy, weight_copy)
+            nchains, which = 1, (_lib.BUF_VALUE_EVID if evidence_chain else _lib.BUF_VALUE)
+        n = int(np.count_nonzero(self.variable["isEvidence"][ids] != 4)) * nchains
+        gmax, skipped = np.zeros(epochs, np.int64), np.zeros(epochs, np.int64)
+        if n > 0:
+            _lib.check(L.nsk_mple_steps(h, which, 0, nchains, _lib.ptr(ids), len(ids), epochs, stepsize, decay, reg_param,
+                                        _lib.ptr(gmax), _lib.ptr(skipped)))
+            self._pull(0 if _all_copies(var_copy) else var_copy, weight_copy, values=False, count=False)
+        grad_max = gmax.astype(np.float64) * 2.0 ** -32 / n if n > 0 else np.zeros(epochs)
+        return {"grad_max": grad_max, "skipped": skipped, "n": n}
+
     def rao_blackwell(self, epochs, var_ids=None, thin=1, burnin_epochs=0, sample_evidence=False):
         """Rao-Blackwellised marginals: ``inference(burnin_epochs, epochs, sample_evidence, var_copy="all")`` -- one chain
         per row of ``var_value``; one chain is fine -- during which, after every ``thin``-th tallied sweep, the device adds
