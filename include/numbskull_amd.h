@@ -380,6 +380,57 @@ int nsk_tempered_sweeps(nsk_graph *g, const double *betas /* nsteps */, int64_t 
                         int64_t *best_values /* chains x nvar, the caller's ids, may be NULL */,
                         double *best_lp /* chains, may be NULL */);
 
+/* Population annealing (FactorGraph.smc_sweeps / log_partition(resample=...) / log_evidence(resample=...)): the tempered
+ * schedule above with the resampling step of sequential Monte Carlo between its steps.  Plain annealed importance
+ * sampling anneals every chain on its own and averages the weights at the end; where a few chains carry almost all the
+ * weight, the heavy chains are here duplicated over the light ones on the device and the run goes on with equal weights.
+ * The call acts on ALL chains of the handle (R = nsk_get_chains, at most 1024).  For t = 0 .. nsteps - 1, on the handle's
+ * stream and without a host wait, steps 1. - 4. of nsk_tempered_sweeps exactly as stated there -- scale, sweep, score under
+ * w_base, fold: the same kernels, launches, sweep indices and bits -- and then, if t + 1 < nsteps:
+ *   5. decide  logw_pre[t * R + r] = log_weight[r].  m = the maximum of the log_weight[r].  If a log_weight is NaN or m is
+ *              not finite, step t does not resample.  Otherwise w_r = exp(log_weight[r] - m), exp the library's specified
+ *              exponential (DESIGN.md "nsk_exp", the oracle's orc_exp_det bit for bit), and in chain order, sequentially,
+ *                c_0 = w_0, c_r = c_(r-1) + w_r;   q_0 = w_0 * w_0, q_r = q_(r-1) + w_r * w_r;   S = c_(R-1), Q = q_(R-1)
+ *              -- one rounded float64 operation each, the only arithmetic of the step whose order matters.  The step
+ *              resamples iff S * S < (threshold * (double)R) * Q, the product in brackets formed once by the host: the
+ *              effective sample size S^2 / Q of the population fell below threshold x R.  threshold = 0 never resamples,
+ *              R = 1 never does, equal weights never do.
+ *              A step that does not resample: resampled[t] = 0, ancestors[t * R + r] = r, log_weight stays.
+ *              A step that does: systematic resampling with the caller's uniform offsets[t].  step = S / (double)R;
+ *              target_i = ((double)i + offsets[t]) * step; a_i = the number of j with c_j <= target_i, at most R - 1;
+ *              chain j has n_j = #{i : a_i = j} offspring (they sum to R; n_j is floor or ceil of R w_j / S up to the
+ *              rounding of c and target).  The offspring are dealt to slots so that the copy is in place: a chain with
+ *              n_j >= 1 keeps its slot, ancestors[t * R + j] = j; the dead slots (n_j = 0) in ascending order take the
+ *              entries of the donor list in order, the list being j ascending with j repeated n_j - 1 times.
+ *              resampled[t] = 1, and log_weight[r] = 0.0 for every r: the fold of the following steps starts afresh.
+ *   6. copy    where ancestors[t * R + r] != r, the values of chain ancestors[t * R + r] replace those of chain r, device
+ *              to device.  Every source kept its own slot, so nothing is read that the step writes.  The sweep generators
+ *              are keyed by the slot r, so two copies of one state part ways at the next sweep.
+ * With a schedule from 0 to 1: log Z = log Z_0 + the sum over the resampling steps t of log mean_r exp(logw_pre[t][r]) +
+ * log mean_r exp(log_weight[r]) (numbskull_amd.diagnostics.smc_estimate; smc_resample is the rule of step 5 in numpy
+ * and returns the device's ancestors integer for integer when fed logw_pre and that exp).  There is no best-state
+ * tracking.  Then w = w_base again, bit for bit, the call synchronises ONCE and downloads what was asked for: log_weight
+ * (R, the fold since the last resampling), lp (nsteps x R), logw_pre ((nsteps - 1) x R), ancestors ((nsteps - 1) x R,
+ * int32), resampled (nsteps - 1, int32).  Each of the five may be NULL.  The values of the chains are left as the last
+ * step leaves them; tallies, trace rows and columns and the evidence chain are untouched, a tally kept in the value bytes
+ * is first brought back to its array, and an error after the first scale still restores the base weights -- all as in
+ * nsk_tempered_sweeps, whose limits on what the estimate means hold here too.
+ * NSK_E_INVALID, before anything is enqueued and with values, weights, sweeps_done and the generator untouched: what
+ * nsk_tempered_sweeps refuses; a threshold outside [0, 1] or NaN; an offset outside [0, 1) or NaN (offsets, when given,
+ * are nsteps - 1 doubles and all are checked); offsets == NULL while nsteps > 1 and threshold > 0.
+ * Memory: what nsk_tempered_sweeps keeps, stays.  The copy of the base weights, lp, log_weight, logw_pre, the ancestors
+ * and the flags live for the call only: nsk_graph_info.device_bytes is afterwards what it was.  NSK_E_NOMEM names the
+ * size of what does not fit.  The offsets travel as kernel arguments.  A copy can carry a value from any slot into any
+ * other, so after a call that may have copied the handle treats chain 0 and the chains behind it as lying in their domains
+ * only if all of them did (the table kernels index with values: uploading one chain afresh does not clear the others).
+ * nsk_profile_* keeps counting sweep-kernel launches only. */
+int nsk_smc_sweeps(nsk_graph *g, const double *betas /* nsteps */, int64_t nsteps, int64_t sweeps_per_step,
+                   int sample_evidence, double threshold, const double *offsets /* nsteps - 1, each in [0, 1) */,
+                   double *log_weight /* chains, may be NULL */, double *lp /* nsteps x chains, may be NULL */,
+                   double *logw_pre /* (nsteps - 1) x chains, may be NULL */,
+                   int32_t *ancestors /* (nsteps - 1) x chains, may be NULL */,
+                   int32_t *resampled /* nsteps - 1, may be NULL */);
+
 /* Effective sample size from the trace, on the device (FactorGraph.mixing): per column of a BIT-PACKED trace, the
  * split-chain estimator of numbskull_amd.diagnostics.effective_sample_size with the lags cut at max_lag, in one
  * streaming pass over the packed rows -- no row is unpacked or leaves the device.  Rows first_row .. first_row +

@@ -2,7 +2,7 @@
 // the library (nsk_api.hip: C-ABI, state sync; nsk_exchange.hip: the multi-GPU boundary exchange; nsk_gibbs.hip /
 // nsk_learn.hip: the sweep drivers of numbskull/factorgraph.py:141,163,202; nsk_trace.hip, nsk_energy.hip, nsk_wstats.hip,
 // nsk_cond.hip: the diagnostics; nsk_icm.hip: the greedy MAP search; nsk_temper.hip: tempered sweep schedules;
-// nsk_plgrad.hip: the pseudo-likelihood gradient and MPLE learning).
+// nsk_smc.hip: population annealing on top of them; nsk_plgrad.hip: the pseudo-likelihood gradient and MPLE learning).
 #pragma once
 
 #include <hip/hip_runtime.h>

@@ -14,6 +14,7 @@
 //                   bytes with 16-byte loads and stores; block 0 copies the bytes behind the last whole 16.
 #pragma once
 
+#include "nsk_internal.h"
 #include "nsk_kernels_energy.h"
 
 namespace nsk {
@@ -69,3 +70,27 @@ static __global__ __launch_bounds__(NSK_BLOCK) void k_temper_keep(const unsigned
 }
 
 }  // namespace nsk
+
+// ------------------------------------------------------------------------------------------
+// the host side of a step that nsk_tempered_sweeps (nsk_temper.hip) and nsk_smc_sweeps (nsk_smc.hip) share: one place,
+// so that "the same launches, the same bits" holds by construction
+// ------------------------------------------------------------------------------------------
+// a buffer of one call through the ledger; NSK_E_NOMEM names the entry point `who` and the size of what does not fit
+template <typename T>
+static int temper_alloc(nsk_graph *g, T **ptr, size_t n, const char *who, const char *what) {
+    const int rc = dev_alloc(g, ptr, n);
+    if (rc != NSK_E_NOMEM) return rc;
+    return nsk::fail(NSK_E_NOMEM, std::string(who) + ": " + what + " (" + std::to_string((long long)((n ? n : 1) * sizeof(T))) +
+                                  " bytes) do not fit on the device");
+}
+
+// the log-potential of every chain under the weights `w`, folded behind the walk (nsk_energy_enqueue with k_temper_fold in
+// the place of k_energy_reduce: the same grid, the same partials, the same order)
+template <typename VT>
+static void temper_score(nsk_graph *g, const double *w, int nchains, const nsk::TemperFold &fold) {
+    nsk::EnergyArgs a = energy_args(g);
+    a.w = w;
+    const unsigned int nb = nsk_energy_blocks(a.nfactor);
+    nsk::k_energy_partial<VT><<<dim3(nb, (unsigned)nchains), dim3(NSK_BLOCK), 0, g->stream>>>(a, (const VT *)g->val, g->energy.partial);
+    nsk::k_temper_fold<<<dim3((unsigned)nchains), dim3(NSK_BLOCK), 0, g->stream>>>(g->energy.partial, (int)nb, fold);
+}

@@ -27,25 +27,6 @@ struct TemperBufs {
     }
 };
 
-template <typename T>
-int temper_alloc(nsk_graph *g, T **ptr, size_t n, const char *what) {
-    const int rc = dev_alloc(g, ptr, n);
-    if (rc != NSK_E_NOMEM) return rc;
-    return fail(NSK_E_NOMEM, std::string("nsk_tempered_sweeps: ") + what + " (" + std::to_string((long long)((n ? n : 1) * sizeof(T))) +
-                             " bytes) do not fit on the device");
-}
-
-// the log-potential of every chain under the weights `w`, folded behind the walk (nsk_energy_enqueue with k_temper_fold in
-// the place of k_energy_reduce: the same grid, the same partials, the same order)
-template <typename VT>
-void temper_score(nsk_graph *g, const double *w, int nchains, const TemperFold &fold) {
-    EnergyArgs a = energy_args(g);
-    a.w = w;
-    const unsigned int nb = nsk_energy_blocks(a.nfactor);
-    k_energy_partial<VT><<<dim3(nb, (unsigned)nchains), dim3(NSK_BLOCK), 0, g->stream>>>(a, (const VT *)g->val, g->energy.partial);
-    k_temper_fold<<<dim3((unsigned)nchains), dim3(NSK_BLOCK), 0, g->stream>>>(g->energy.partial, (int)nb, fold);
-}
-
 }  // namespace
 
 extern "C" int nsk_tempered_sweeps(nsk_graph *g, const double *betas, int64_t nsteps, int64_t sweeps_per_step, int sample_evidence,
@@ -74,13 +55,13 @@ extern "C" int nsk_tempered_sweeps(nsk_graph *g, const double *betas, int64_t ns
     // a 256-byte boundary)
     const size_t vbytes = (size_t)c.nid * (size_t)c.vbytes, bstride = (vbytes + 15) / 16 * 16;
     TemperBufs b(g);
-    if ((rc = temper_alloc(g, &b.base, nw, "the copy of the base weights"))) return rc;
-    if (lp && (rc = temper_alloc(g, &b.lp, T * (size_t)R, "the log-potentials, nsteps x chains float64"))) return rc;
-    if (log_weight && (rc = temper_alloc(g, &b.log_weight, (size_t)R, "the log-weights, one float64 a chain"))) return rc;
+    if ((rc = temper_alloc(g, &b.base, nw, "nsk_tempered_sweeps", "the copy of the base weights"))) return rc;
+    if (lp && (rc = temper_alloc(g, &b.lp, T * (size_t)R, "nsk_tempered_sweeps", "the log-potentials, nsteps x chains float64"))) return rc;
+    if (log_weight && (rc = temper_alloc(g, &b.log_weight, (size_t)R, "nsk_tempered_sweeps", "the log-weights, one float64 a chain"))) return rc;
     if (keep) {
-        if ((rc = temper_alloc(g, &b.best_u, (size_t)R, "the best log-potentials, one float64 a chain"))) return rc;
-        if ((rc = temper_alloc(g, &b.improved, (size_t)R, "the flags, one word a chain"))) return rc;
-        if (best_values && (rc = temper_alloc(g, &b.best, (size_t)R * bstride, "the best states, chains x the bytes of a chain's values"))) return rc;
+        if ((rc = temper_alloc(g, &b.best_u, (size_t)R, "nsk_tempered_sweeps", "the best log-potentials, one float64 a chain"))) return rc;
+        if ((rc = temper_alloc(g, &b.improved, (size_t)R, "nsk_tempered_sweeps", "the flags, one word a chain"))) return rc;
+        if (best_values && (rc = temper_alloc(g, &b.best, (size_t)R * bstride, "nsk_tempered_sweeps", "the best states, chains x the bytes of a chain's values"))) return rc;
     }
     if (b.log_weight) HIPCHECK(hipMemsetAsync(b.log_weight, 0, (size_t)R * sizeof(double), g->stream));
     if (nw) HIPCHECK(hipMemcpyAsync(b.base, g->w, nw * sizeof(double), hipMemcpyDeviceToDevice, g->stream));

@@ -52,6 +52,10 @@ from the same potentials: greedy coordinate ascent towards a MAP estimate.
 sweeps under a schedule of inverse temperatures and hands back every step's log-potentials; the fold of the importance
 weights restated with the device's roundings, and the estimators of log Z, which need a ``log`` and live here.
 
+``smc_resample`` and ``smc_estimate`` are the host side of ``FactorGraph.smc_sweeps`` / ``log_partition(resample=...)``
+(nsk_smc_sweeps): the device's resampling decision and ancestor choice restated operation by
+operation, and the estimate of log Z from a resampled population.
+
 ``pl_gradient_counts`` and ``mple_step`` restate ``FactorGraph.pl_gradient`` / ``learn_mple`` (nsk_pl_gradient,
 nsk_mple_steps): the gradient of the log-pseudo-likelihood as int64 sums of quantised terms -- exact,
 whatever the order -- and the weight update of maximum pseudo-likelihood learning, one rounded operation each.
@@ -659,6 +663,73 @@ def ais_estimate(log_weights, log_z0):
     stderr = float(np.std(w, ddof=1) / (mean * np.sqrt(n))) if n > 1 else float("nan")
     ess = float(w.sum() ** 2 / (w * w).sum())
     return log_z, stderr, ess
+
+
+def smc_resample(log_weights, u, threshold, exp=np.exp):
+    """The resampling decision and the ancestors of population annealing as nsk_smc_sweeps takes them behind the fold of a
+    step (include/numbskull_amd.h, step 5): ``log_weights`` (R,) the folded log-weights, ``u`` the step's uniform in
+    [0, 1), ``threshold`` in [0, 1].  Returns ``(resampled, ancestors, S, Q)``.  With ``m`` the largest log-weight,
+    ``w = exp(log_weights - m)``, ``c = cumsum(w)`` and ``q = cumsum(w * w)`` in chain order, ``S = c[-1]``, ``Q = q[-1]``:
+    the population is resampled iff ``S * S < (threshold * R) * Q`` -- its effective sample size fell below ``threshold x
+    R`` -- and then systematically: ``target[i] = (i + u) * (S / R)``, ``a[i]`` = the number of ``c[j] <= target[i]``, at
+    most ``R - 1``, chain j gets ``n[j] = #{i : a[i] = j}`` offspring.  A chain with offspring keeps its slot
+    (``ancestors[j] = j``); the slots without, ascending, take the chains with more than one, ascending, each repeated
+    ``n[j] - 1`` times -- so the copy ``x[r] = x[ancestors[r]]`` can run in place.  Without resampling the ancestors are
+    the identity; a NaN log-weight or a maximum that is not finite means no resampling (``S`` and ``Q`` are then NaN).
+    Every step is one rounded float64 operation, the two cumulative sums run in order: fed the device's ``logw_pre`` row
+    and the oracle's ``exp_det`` as ``exp`` it returns the device's ancestors integer for integer; ``np.exp`` may differ in
+    a last place and so, rarely, in an ancestor."""
+    lw = np.ascontiguousarray(log_weights, np.float64)
+    if lw.ndim != 1 or lw.size < 1:
+        raise ValueError("smc_resample: log_weights is a 1-d array of at least one chain, got %r" % (lw.shape,))
+    if not 0.0 <= threshold <= 1.0:
+        raise ValueError("smc_resample: the threshold lies in [0, 1]")
+    if not 0.0 <= u < 1.0:
+        raise ValueError("smc_resample: the uniform lies in [0, 1)")
+    R = lw.size
+    ident = np.arange(R, dtype=np.int32)
+    m = lw.max()                                            # (NaN if any entry is)
+    if not np.isfinite(m):
+        return False, ident, float("nan"), float("nan")
+    w = np.ascontiguousarray(exp(lw - m), np.float64)
+    c, q = np.cumsum(w), np.cumsum(w * w)                   # 1-d float64: sequential, one rounded addition an entry
+    S, Q = c[-1], q[-1]
+    if not S * S < (np.float64(threshold) * np.float64(R)) * Q:
+        return False, ident, float(S), float(Q)
+    step = S / np.float64(R)
+    target = (np.arange(R, dtype=np.float64) + np.float64(u)) * step
+    a = np.minimum(np.searchsorted(c, target, side="right"), R - 1)
+    n = np.bincount(a, minlength=R)
+    anc = ident.copy()
+    anc[n == 0] = np.repeat(ident, np.maximum(n - 1, 0))
+    return True, anc, float(S), float(Q)
+
+
+def smc_estimate(logw_pre, resampled, log_weights, log_z0):
+    """``(log_z, ess, resamplings)`` of one population-annealing run (``FactorGraph.smc_sweeps``): ``logw_pre`` (T - 1,
+    R) the log-weights in front of every decision, ``resampled`` (T - 1,) the decisions, ``log_weights`` (R,) the fold
+    since the last resampling, ``log_z0`` the log of the number of states at beta = 0.  Every resampling closes a stage
+    whose ratio of normalisers is the mean weight, so ``log_z = log_z0 + sum over resampled t of log_mean_exp(logw_pre[t])
+    + log_mean_exp(log_weights)``; ``ess = (sum w)^2 / sum w^2`` of the final weights; ``resamplings`` the number of
+    events.  Without an event this is ``ais_estimate``'s ``log_z``.  There is NO standard error: the chains of a
+    resampled population share ancestors, the spread of the final weights says nothing about the stages before, and one
+    run has no honest error bar -- repeat the run with other seeds and take the spread of ``exp(log_z)``."""
+    pre = np.asarray(logw_pre, np.float64)
+    lw = np.asarray(log_weights, np.float64).ravel()
+    flag = np.asarray(resampled).astype(bool).ravel()
+    if lw.size < 1:
+        raise ValueError("smc_estimate: no log-weights")
+    if pre.size == 0:
+        pre = pre.reshape(0, lw.size)
+    if pre.ndim != 2 or pre.shape != (flag.size, lw.size):
+        raise ValueError("smc_estimate: logw_pre (T - 1, R), resampled (T - 1,) and log_weights (R,), got %r, %r and %r" %
+                         (pre.shape, flag.shape, lw.shape))
+    log_z = float(log_z0)
+    for t in np.nonzero(flag)[0]:
+        log_z = log_z + log_mean_exp(pre[t])
+    log_z = log_z + log_mean_exp(lw)
+    w = np.exp(lw - lw.max())
+    return log_z, float(w.sum() ** 2 / (w * w).sum()), int(flag.sum())
 
 
 def thermodynamic_integral(betas, lp, log_z0):

@@ -1101,7 +1101,55 @@ class FactorGraph(object):
             out["best_values"], out["best_log_potentials"] = bv, bu
         return out
 
-    def log_partition(self, steps=100, betas=None, sweeps=1, sample_evidence=False, weight_copy=0):
+    def smc_sweeps(self, betas, sweeps=1, threshold=0.5, seed=0, sample_evidence=False, weight_copy=0):
+        """Population annealing, driven on the device (nsk_smc_sweeps): ``tempered_sweeps`` along ``betas`` with the
+        resampling step of sequential Monte Carlo behind the fold of every step but the last.  When the effective sample
+        size of the folded log-weights falls below ``threshold x chains`` the heavy chains are copied over the light ones
+        -- systematic resampling, decided, drawn and copied on the device -- and the log-weights start again from 0.
+        ``threshold`` lies in [0, 1]; 0 never resamples.  The one uniform a step needs comes from
+        ``np.random.default_rng(seed).random(T - 1)``.  Chains are pushed and pulled as ``tempered_sweeps`` does; nothing
+        is tallied, the weights come back as they were, ``var_value`` is left holding the final states.  Returns a dict:
+        ``log_potentials`` float64 ``(T, chains)``; ``log_weights`` ``(chains,)``, the fold since the last resampling;
+        ``logw_pre`` ``(T - 1, chains)``, the log-weights in front of every decision; ``ancestors`` int32 ``(T - 1,
+        chains)``, the chain whose state slot r holds after step t (itself where nothing was copied); ``resampled``
+        bool ``(T - 1,)``; ``offsets`` ``(T - 1,)``.  ``diagnostics.smc_resample`` restates the rule and
+        ``diagnostics.smc_estimate`` turns the result into log Z."""
+        b = self._schedule(betas, "smc_sweeps")
+        sweeps = int(sweeps)
+        if sweeps < 1:
+            raise ValueError("smc_sweeps: sweeps must be at least 1")
+        threshold = float(threshold)
+        if not 0.0 <= threshold <= 1.0:
+            raise ValueError("smc_sweeps: the threshold lies in [0, 1]")
+        T = len(b)
+        offsets = np.ascontiguousarray(np.random.default_rng(seed).random(T - 1), np.float64)
+        L, h = _lib.lib(), self._engine()
+        nchains = self._push_chains(weight_copy, count=False)
+        lp, logw = np.zeros((T, nchains), np.float64), np.zeros(nchains, np.float64)
+        pre = np.zeros((T - 1, nchains), np.float64)
+        anc, flag = np.zeros((T - 1, nchains), np.int32), np.zeros(T - 1, np.int32)
+        _lib.check(L.nsk_smc_sweeps(h, _lib.ptr(b), T, sweeps, int(bool(sample_evidence)), threshold, _lib.ptr(offsets),
+                                    _lib.ptr(logw), _lib.ptr(lp), _lib.ptr(pre), _lib.ptr(anc), _lib.ptr(flag)))
+        self._pull_chains(count=False)
+        return {"log_weights": logw, "log_potentials": lp, "logw_pre": pre, "ancestors": anc, "resampled": flag != 0,
+                "offsets": offsets}
+
+    def _log_z0(self, sample_evidence):
+        """the log of the number of states of the variables a sweep samples"""
+        sampled = self.colors() >= 0
+        if not sample_evidence:
+            sampled &= np.asarray(self.variable["isEvidence"]) == 0
+        return float(np.log(np.asarray(self.variable["cardinality"], np.float64)[sampled]).sum())
+
+    def _log_partition_smc(self, b, sweeps, sample_evidence, weight_copy, resample):
+        from .diagnostics import smc_estimate, thermodynamic_integral
+        res = self.smc_sweeps(b, sweeps, resample, 0, sample_evidence, weight_copy)
+        log_z0 = self._log_z0(sample_evidence)
+        log_z, ess, events = smc_estimate(res["logw_pre"], res["resampled"], res["log_weights"], log_z0)
+        return {"log_z": log_z, "stderr": float("nan"), "ess": ess, "log_z0": log_z0, "log_weights": res["log_weights"],
+                "log_z_ti": thermodynamic_integral(b, res["log_potentials"], log_z0), "betas": b, "resamplings": events}
+
+    def log_partition(self, steps=100, betas=None, sweeps=1, sample_evidence=False, weight_copy=0, resample=None):
         """log Z by annealed importance sampling (Neal 2001), the chains of ``var_value`` as the particles:
         ``tempered_sweeps`` along ``betas`` -- ``np.linspace(0, 1, steps + 1)`` unless given; a schedule must start at 0.0
         and end at 1.0 (ValueError, raised before the device is touched) -- and ``diagnostics.ais_estimate`` of the
@@ -1112,8 +1160,18 @@ class FactorGraph(object):
         ``log_z0`` = the sum of log(cardinality) over the variables the sweeps sample; ``log_weights``; ``log_z_ti``, the
         thermodynamic integral of the same log-potentials, an independent cross-check; ``betas``.  ``log Z -
         log_potential`` of a state is its negative log-likelihood.  Meaningless where ``potential()`` is not the gradient
-        of one energy: the reference's literal head lookup of IMPLY_MLN-type functions (see ``icm``)."""
+        of one energy: the reference's literal head lookup of IMPLY_MLN-type functions (see ``icm``).
+        ``resample``: ``None`` is plain AIS as above; a threshold in (0, 1] is population annealing -- ``smc_sweeps(betas,
+        sweeps, threshold=resample)`` and ``diagnostics.smc_estimate``: chains are resampled on the device whenever the
+        effective sample size falls below ``resample x chains``, which keeps the estimate from resting on one heavy
+        chain where the couplings are strong.  The dict then has the same keys with ``stderr`` NaN (one run of a
+        resampled population has no honest error bar; repeat it), ``ess`` and ``log_weights`` those of the last stage,
+        and ``resamplings``, the number of events."""
         from .diagnostics import ais_estimate, thermodynamic_integral
+        if resample is not None:
+            resample = float(resample)
+            if not 0.0 < resample <= 1.0:
+                raise ValueError("log_partition: resample is None or a threshold in (0, 1]")
         if betas is None:
             steps = int(steps)
             if steps < 1:
@@ -1123,26 +1181,25 @@ class FactorGraph(object):
             b = self._schedule(betas, "log_partition")
             if len(b) < 2 or b[0] != 0.0 or b[-1] != 1.0:
                 raise ValueError("log_partition: the schedule must start at 0.0 and end at 1.0")
+        if resample is not None:
+            return self._log_partition_smc(b, sweeps, sample_evidence, weight_copy, resample)
         res = self.tempered_sweeps(b, sweeps, sample_evidence, weight_copy)
-        sampled = self.colors() >= 0
-        if not sample_evidence:
-            sampled &= np.asarray(self.variable["isEvidence"]) == 0
-        log_z0 = float(np.log(np.asarray(self.variable["cardinality"], np.float64)[sampled]).sum())
+        log_z0 = self._log_z0(sample_evidence)
         log_z, stderr, ess = ais_estimate(res["log_weights"], log_z0)
         return {"log_z": log_z, "stderr": stderr, "ess": ess, "log_z0": log_z0, "log_weights": res["log_weights"],
                 "log_z_ti": thermodynamic_integral(b, res["log_potentials"], log_z0), "betas": b}
 
-    def log_evidence(self, steps=100, betas=None, sweeps=1, weight_copy=0):
+    def log_evidence(self, steps=100, betas=None, sweeps=1, weight_copy=0, resample=None):
         """log P(the evidence variables hold their values in ``var_value``) = log Z with the evidence clamped minus log Z
         with every variable free: two ``log_partition`` runs from the same rows.  Every row of ``var_value`` must hold
         the same evidence values (the clamped Z is one number).  Returns a dict: ``log_evidence``; ``stderr``, the root of
         the two squared errors; ``clamped`` and ``free``, the two ``log_partition`` results.  ``var_value`` is restored to
-        what it held before the call."""
+        what it held before the call.  ``resample``: as in ``log_partition``, for both runs (``stderr`` is then NaN)."""
         keep = np.array(self.var_value, np.int64)
         try:
-            clamped = self.log_partition(steps, betas, sweeps, False, weight_copy)
+            clamped = self.log_partition(steps, betas, sweeps, False, weight_copy, resample)
             self.var_value[:] = keep
-            free = self.log_partition(steps, betas, sweeps, True, weight_copy)
+            free = self.log_partition(steps, betas, sweeps, True, weight_copy, resample)
         finally:
             self.var_value[:] = keep
         return {"log_evidence": clamped["log_z"] - free["log_z"],
