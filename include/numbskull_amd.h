@@ -100,7 +100,8 @@ int nsk_state_download(nsk_graph *g, int64_t *var_value, int64_t *var_value_evid
  * nsk_set_chains: 1 <= nchains <= 1024.  Chain 0 keeps its values and tally (as do the chains both counts
  * have); new chains start as nsk_graph_create leaves a handle: initialValue, tally 0.  NSK_E_NOMEM when the
  * state does not fit.  The value array moves: a pointer from nsk_device_buffer(NSK_BUF_VALUE) taken before is
- * stale.  With R > 1 only chromatic inference and burn-in sweeps serve the handle: learning, the sequential
+ * stale.  With R > 1 only chromatic inference and burn-in sweeps serve the handle (and what is built on
+ * them: nsk_pcd_steps learns from all R chains): the per-visit learning of nsk_learn_sweeps, the sequential
  * scan, own_range / NSK_FLAG_PARTITION handles, nsk_pf_setup and the exchange, RCCL and peer-to-peer entry
  * points return NSK_E_INVALID.
  * nsk_chains_upload / nsk_chains_download: var_value is R x nvar (row r = chain r, caller's variable ids),
@@ -331,6 +332,63 @@ int nsk_pl_gradient(nsk_graph *g, int which, int64_t first_chain, int64_t nchain
 int nsk_mple_steps(nsk_graph *g, int which, int64_t first_chain, int64_t nchains, const int64_t *vids, int64_t nvids,
                    int64_t nsteps, double step, double decay, double reg_param,
                    int64_t *gmax /* nsteps, may be NULL */, int64_t *skipped /* nsteps, may be NULL */);
+
+/* Chain-summed moments and persistent contrastive divergence (FactorGraph.weight_moments / learn_pcd): full-batch
+ * maximum-likelihood learning in which the handle's R chains (nsk_set_chains) are the persistent "fantasy particles".
+ * Fixed-point moments: for a state x and a factor f, e_f = eval_factor(f, x) exactly as nsk_log_potential asks every
+ * factor, as its first member sees it;
+ *   q_f = e_f * 2^32 rounded to the nearest int64, ties to even (numpy: np.rint(e * 2.0**32).astype(np.int64))
+ *   M_w = the sum over the chains named and over the factors f with weightId == w of q_f(x_chain)        int64
+ * featureValue plays no part, as in potential(); a weight without a factor reads 0.  The sums are integers, so no order
+ * of execution changes a bit (numbskull_amd.diagnostics.moment_counts is the rule in numpy), and ONE accumulator of
+ * nweight x 8 bytes serves any number of chains: nothing is allocated as chains x nweight.  One lane per weight of at
+ * most 16 factors, one wave per piece of at most 2048 factors of a longer one -- the cuts of nsk_weight_stats --, each
+ * over its share of the chains; a wave adds its lanes' integers and issues at most one 64-bit global atomic per weight it
+ * holds, a block's waves that end on the same weight one between them.
+ * Range, decided before any launch from the graph alone: with B_w = the sum over the factors of w of vmax(f) -- vmax as
+ * nsk_pl_gradient defines it: arity for LINEAR, log(arity + 1) for RATIO, 1e6 for UFO, 1 otherwise -- the call is
+ * NSK_E_RANGE when B_w * nchains >= 2^30 for some w.
+ * nsk_weight_moments: moments[w] = M_w over chains first_chain .. first_chain + nchains - 1, in the caller's weight ids.
+ * `which`, the chains, the handles refused (NSK_E_INVALID) and reading without changing anything follow nsk_weight_stats
+ * rule for rule; it is not a sweep, so the sequential scan is fine; a tally kept in the value bytes is first brought back
+ * to its array, as in nsk_icm.
+ * nsk_pcd_steps: nsteps steps over ALL chains of the handle, R = nsk_get_chains.  For t = 0 .. nsteps - 1, on the handle's
+ * stream and without a host wait:
+ *   1. what nsk_gibbs_sweeps(g, sweeps_per_step, sample_evidence, burnin = 1) enqueues -- it rebuilds what derives from
+ *      the weights first, which every step leaves marked;
+ *   2. zero M, then the moment launches over all R chains;
+ *   3. one update launch, per weight slot that is not fixed, every line ONE rounded IEEE operation:
+ *        m = ((double)M * 2^-32) / R              one conversion, an exact scaling, one division
+ *        g = target_w - m
+ *        if (normalize) g = g / n_w               n_w = the factors of w (a weight without a factor: n_w = 1)
+ *        a = reg_param * w;  b = g - a;  c = step_t * b;  w = w + c
+ *      with step_0 = step, step_{t+1} = step_t * decay (the products formed on the host in t order).
+ * gmax[t] = the largest |g| over the weights that are not fixed, after the normalisation and before the penalty (0 when
+ * every weight is fixed); moments[t * nweight + w] = that step's M_w in the caller's weight ids
+ * (numbskull_amd.diagnostics.pcd_step is the update in numpy).  The fixed point of the iteration is where the model's
+ * mean statistics equal the target: the maximum-likelihood estimate when the target is the data's mean statistics.
+ * The call synchronises once and downloads gmax and moments (each may be NULL).  It leaves the new weights in the device
+ * table, marked so that the next sweep call rebuilds what derives from them; the chains where the last sweep left them;
+ * sweeps_done advanced by nsteps * sweeps_per_step.  Tallies are untouched (a tally kept in the value bytes is unpacked
+ * first, as in nsk_tempered_sweeps), and a sample trace keeps its rows and columns: burn-in sweeps record nothing.
+ * NSK_E_INVALID, before anything is enqueued and with the handle left as it was: a null graph or target; a target entry
+ * that is not finite; nsteps outside [1, 65536]; sweeps_per_step < 1 or nsteps * sweeps_per_step > 2^31 - 1; a step,
+ * decay or reg_param that is not finite, or reg_param < 0; normalize other than 0 or 1; the sequential scan; every
+ * handle nsk_log_potential refuses.  NSK_E_RANGE: the rule above with nchains = R.  nweight == 0 is NSK_OK with nothing
+ * done.
+ * Memory: the first call uploads what nsk_weight_stats(scaled = 0) uploads short of its work list and result, or finds
+ * it in place.  The accumulator (8 bytes a weight), the work list by weight slot (8 bytes a short weight, 16 a piece),
+ * the target and the factor counts (16 bytes a weight) and the per-step outputs (8 bytes a step, and 8 x nsteps x nweight
+ * only when moments is asked for) live for the call only, so nsk_graph_info.device_bytes is afterwards what a
+ * nsk_weight_stats call leaves.  NSK_E_NOMEM names the size of what does not fit.  nsk_profile_* keeps counting
+ * sweep-kernel launches only.  A handle that never calls these allocates and launches nothing for them. */
+int nsk_weight_moments(nsk_graph *g, int which, int64_t first_chain, int64_t nchains,
+                       int64_t *moments /* nweight, caller's weight ids */);
+int nsk_pcd_steps(nsk_graph *g, const double *target /* nweight, caller's weight ids */,
+                  int64_t nsteps, int64_t sweeps_per_step, int sample_evidence,
+                  double step, double decay, double reg_param, int normalize,
+                  double *gmax /* nsteps, may be NULL */,
+                  int64_t *moments /* nsteps x nweight, may be NULL */);
 
 /* Tempered sweep schedules (FactorGraph.tempered_sweeps / log_partition / log_evidence / anneal): sweeps at an inverse
  * temperature beta, driven by a schedule.  potential() is linear in the weights, so sampling from exp(beta U) / Z_beta,

@@ -33,7 +33,7 @@ SYMBOLS = (
     "nsk_log_potential", "nsk_factor_values", "nsk_trace_log_potential", "nsk_trace_download_log_potential",
     "nsk_weight_stats", "nsk_trace_weight_stats", "nsk_trace_download_weight_stats",
     "nsk_conditionals", "nsk_trace_conditionals", "nsk_trace_download_conditionals", "nsk_icm", "nsk_tempered_sweeps",
-    "nsk_smc_sweeps", "nsk_pl_gradient", "nsk_mple_steps",
+    "nsk_smc_sweeps", "nsk_pl_gradient", "nsk_mple_steps", "nsk_weight_moments", "nsk_pcd_steps",
     "nsk_trace_ess", "nsk_trace_autocov_counts", "nsk_trace_pair_counts",
     "nsk_trace_value_autocov_counts", "nsk_trace_value_ess", "nsk_trace_value_pair_counts",
     "nsk_selftest_exp", "nsk_selftest_philox", "nsk_selftest_stream", "nsk_device_count", "nsk_last_error", "nsk_version",
@@ -79,6 +79,26 @@ def plgrad_blocks(nsel):
     if one <= PLGRAD_CU_BLOCKS:
         return max(1, one)
     return max(PLGRAD_CU_BLOCKS, min(PLGRAD_MAX_BLOCKS, (one + 1) // 2))
+
+
+# the launches of nsk_weight_moments / nsk_pcd_steps (csrc/nsk_kernels_pcd.h nsk_moments_blocks): one weight of at most
+# MOMENTS_SHORT factors per lane, one piece of at most MOMENTS_PIECE factors of a longer one per wave, blocks of
+# MOMENTS_BLOCK lanes in whole rounds of 8, at most MOMENTS_MAX_BLOCKS -- or the diagnostic cap NSK_MOMENTS_GRID_CAP,
+# rounded down to a whole round but at least one; more items loop
+MOMENTS_BLOCK, MOMENTS_SHORT, MOMENTS_PIECE, MOMENTS_MAX_BLOCKS = 256, 16, 2048, 2048
+
+
+def moments_blocks(items, per_block, cap=0):
+    """Blocks of a moment launch over ``items`` lanes' or waves' items, ``per_block`` of them a block and trip."""
+    need = ((int(items) + per_block - 1) // per_block + 7) // 8 * 8
+    limit = max(8, min(MOMENTS_MAX_BLOCKS, int(cap) // 8 * 8)) if cap > 0 else MOMENTS_MAX_BLOCKS
+    return max(8, min(need, limit))
+
+
+def moments_trips(items, per_block, cap=0):
+    """Trips the lanes (``per_block`` = MOMENTS_BLOCK) or waves (MOMENTS_BLOCK // 64) of that launch make."""
+    per_trip = moments_blocks(items, per_block, cap) * per_block
+    return (int(items) + per_trip - 1) // per_trip
 
 
 # the route word of nsk_graph_plan_routes / nsk_graph_get_routes (include/numbskull_amd.h "Routes")
@@ -165,6 +185,9 @@ def lib():
         L.nsk_pl_gradient.argtypes = [C.c_void_p, C.c_int, C.c_int64, C.c_int64, C.c_void_p, C.c_int64] + [C.c_void_p] * 3
         L.nsk_mple_steps.argtypes = [C.c_void_p, C.c_int, C.c_int64, C.c_int64, C.c_void_p, C.c_int64, C.c_int64,
                                      C.c_double, C.c_double, C.c_double, C.c_void_p, C.c_void_p]
+        L.nsk_weight_moments.argtypes = [C.c_void_p, C.c_int, C.c_int64, C.c_int64, C.c_void_p]
+        L.nsk_pcd_steps.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int, C.c_double, C.c_double, C.c_double,
+                                    C.c_int, C.c_void_p, C.c_void_p]
         L.nsk_tempered_sweeps.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int] + [C.c_void_p] * 4
         L.nsk_smc_sweeps.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int, C.c_double] + [C.c_void_p] * 6
         L.nsk_trace_ess.argtypes = [C.c_void_p, C.c_int64, C.c_int64, C.c_int64] + [C.c_void_p] * 4

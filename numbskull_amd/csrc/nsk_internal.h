@@ -2,7 +2,8 @@
 // the library (nsk_api.hip: C-ABI, state sync; nsk_exchange.hip: the multi-GPU boundary exchange; nsk_gibbs.hip /
 // nsk_learn.hip: the sweep drivers of numbskull/factorgraph.py:141,163,202; nsk_trace.hip, nsk_energy.hip, nsk_wstats.hip,
 // nsk_cond.hip: the diagnostics; nsk_icm.hip: the greedy MAP search; nsk_temper.hip: tempered sweep schedules;
-// nsk_smc.hip: population annealing on top of them; nsk_plgrad.hip: the pseudo-likelihood gradient and MPLE learning).
+// nsk_smc.hip: population annealing on top of them; nsk_plgrad.hip: the pseudo-likelihood gradient and MPLE learning;
+// nsk_pcd.hip: the chain-summed moments and persistent contrastive divergence).
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -465,6 +466,7 @@ int nsk_fold_position_tally(nsk_graph *g);
 int nsk_unpack_tally(nsk_graph *g);
 int nsk_trace_record(nsk_graph *g);                 // one row of the sample trace behind what the stream holds (nsk_trace.hip)
 void wstats_plan_free(nsk_graph *g, NskWstatsPlan &plan);      // nsk_wstats.hip (the trace's stats column goes with the trace)
+int nsk_wstats_ensure(nsk_graph *g, bool scaled, const char *what);    // ... the by-weight list at the first use (after energy_ensure)
 // the handles the diagnostics serve (whole graph, no exchange); the arrays of the factor walk at the first use (nsk_energy.hip)
 int energy_whole_graph(const nsk_graph *g, const char *what);
 int energy_ensure(nsk_graph *g, int chains, const char *what);

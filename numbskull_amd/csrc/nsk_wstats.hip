@@ -49,8 +49,8 @@ int nsk_wstats_enqueue(nsk_graph *g, const NskWstatsPlan &plan, const void *val,
 
 // ---- per-weight statistics (nsk_internal.h NskWstats, nsk_kernels_wstats.h) -----------------------------------------
 // The by-weight index list at the first use (after energy_ensure: every factor's weight slot was checked), and the
-// feature values when a scaled sum asks for them
-static int wstats_ensure(nsk_graph *g, bool scaled, const char *what) {
+// feature values when a scaled sum asks for them (nsk_pcd.hip reads the list too)
+int nsk_wstats_ensure(nsk_graph *g, bool scaled, const char *what) {
     NskWstats &ws = g->wstats;
     Compiled &c = g->c;
     HIPCHECK(hipSetDevice(g->device));
@@ -172,7 +172,7 @@ int nsk_weight_stats(nsk_graph *g, int which, int64_t first_chain, int64_t nchai
     const Compiled &c = g->c;
     if (c.nweight == 0) return NSK_OK;
     if ((rc = energy_ensure(g, 0, "nsk_weight_stats"))) return rc;
-    if ((rc = wstats_ensure(g, scaled != 0, "nsk_weight_stats"))) return rc;
+    if ((rc = nsk_wstats_ensure(g, scaled != 0, "nsk_weight_stats"))) return rc;
     NskWstats &ws = g->wstats;
     if (!ws.all_ready) {
         std::vector<int32_t> slot((size_t)c.nweight);
@@ -214,7 +214,7 @@ int nsk_trace_weight_stats(nsk_graph *g, const int64_t *wids, int64_t nwids, int
     if (nwids >= 0) {       // (before the column that stands goes)
         if ((rc = energy_whole_graph(g, "nsk_trace_weight_stats"))) return rc;
         if ((rc = energy_ensure(g, 0, "nsk_trace_weight_stats"))) return rc;
-        if ((rc = wstats_ensure(g, scaled != 0, "nsk_trace_weight_stats"))) return rc;
+        if ((rc = nsk_wstats_ensure(g, scaled != 0, "nsk_trace_weight_stats"))) return rc;
     }
     dev_free(g, t.ws);
     t.ws = nullptr; t.ws_scaled = false;

@@ -59,6 +59,10 @@ operation, and the estimate of log Z from a resampled population.
 ``pl_gradient_counts`` and ``mple_step`` restate ``FactorGraph.pl_gradient`` / ``learn_mple`` (nsk_pl_gradient,
 nsk_mple_steps): the gradient of the log-pseudo-likelihood as int64 sums of quantised terms -- exact,
 whatever the order -- and the weight update of maximum pseudo-likelihood learning, one rounded operation each.
+
+``moment_counts`` and ``pcd_step`` restate ``FactorGraph.weight_moments`` / ``learn_pcd`` (nsk_weight_moments, nsk_pcd_steps;
+DESIGN.md section 4): the per-weight statistics summed over chains as int64 sums of quantised factor values, and the weight
+update of persistent contrastive divergence, one rounded operation each.
 """
 
 import collections
@@ -610,6 +614,61 @@ def mple_step(w, fixed, counts_sum, n, step, reg_param):
     b = gbar - a
     c = np.float64(step) * b
     return np.where(np.asarray(fixed).astype(bool), w, w + c)
+
+
+def moment_counts(values, weight_ids, nweight):
+    """The chain-summed per-weight moments as ``FactorGraph.weight_moments(counts=True)`` sums them on the device
+    (nsk_weight_moments): ``values`` ``(chains, nfactor)`` -- or ``(nfactor,)`` for one chain -- are the factors' values on
+    every chain's state (``FactorGraph.factor_values``), ``weight_ids`` ``(nfactor,)`` each factor's weight.  Per factor and
+    chain ``q = np.rint(e * 2.0**32).astype(np.int64)``, and ``M[w]`` is the int64 sum of ``q`` over the chains and the
+    factors of ``w``: integers, so their order does not matter.  A weight without a factor reads 0.  Returns int64
+    ``(nweight,)``; ``M * 2.0**-32 / chains`` are the mean statistics."""
+    e = np.asarray(values, np.float64)
+    if e.ndim == 1:
+        e = e[None, :]
+    wid = np.asarray(weight_ids)
+    if e.ndim != 2 or wid.shape != (e.shape[1],) or (wid.size and wid.dtype.kind not in "iu"):
+        raise ValueError("moment_counts: values are (chains, nfactor), weight_ids integers (nfactor,)")
+    wid = wid.astype(np.int64)
+    nweight = int(nweight)
+    if wid.size and (wid.min() < 0 or wid.max() >= nweight):
+        raise IndexError("moment_counts: a factor names a weight out of range")
+    if not np.isfinite(e).all() or (e.size and np.abs(e).max() >= 2.0 ** 30):
+        raise OverflowError("moment_counts: a factor value is not finite or does not fit the fixed point")
+    q = np.rint(e * 2.0 ** 32).astype(np.int64)
+    counts = np.zeros(nweight, np.int64)
+    np.add.at(counts, wid, q.sum(axis=0, dtype=np.int64))
+    return counts
+
+
+def pcd_step(w, fixed, M, R, target, n_w, step, reg_param, normalize):
+    """One step of persistent contrastive divergence as ``FactorGraph.learn_pcd`` takes it on the device (nsk_pcd_steps):
+    ``M`` (nweight,) is the int64 ``moment_counts`` of the ``R`` chains, ``target`` the statistics to match, ``n_w`` the
+    number of factors of every weight (a weight without a factor counts as 1).  One rounded float64 operation each::
+
+        m = (float(M) * 2.0**-32) / R;  g = target - m;  if normalize: g = g / n_w
+        a = reg_param * w;  b = g - a;  c = step * b;  w = w + c
+
+    Weights with ``fixed`` set stay as they are.  Returns ``(w_new, gmax)``: the new weights (a new array) and the largest
+    ``|g|`` over the weights that are not fixed (after the normalisation, before the penalty; 0.0 when all are fixed)."""
+    w = np.asarray(w, np.float64)
+    s = np.asarray(M)
+    t = np.asarray(target, np.float64)
+    if s.dtype.kind not in "iu" or s.shape != w.shape or t.shape != w.shape:
+        raise ValueError("pcd_step: M is int64 and target float64, both with the shape of w")
+    n = np.maximum(np.asarray(n_w, np.float64), 1.0)
+    if n.shape != w.shape:
+        raise ValueError("pcd_step: n_w has the shape of w")
+    free = ~np.asarray(fixed).astype(bool)
+    m = (s.astype(np.float64) * 2.0 ** -32) / np.float64(R)
+    g = t - m
+    if normalize:
+        g = g / n
+    a = np.float64(reg_param) * w
+    b = g - a
+    c = np.float64(step) * b
+    gmax = float(np.abs(g[free]).max()) if free.any() else 0.0
+    return np.where(free, w + c, w), gmax
 
 
 def _schedule(betas, lp, what):

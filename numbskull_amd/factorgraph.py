@@ -945,6 +945,84 @@ class FactorGraph(object):
         grad_max = gmax.astype(np.float64) * 2.0 ** -32 / n if n > 0 else np.zeros(epochs)
         return {"grad_max": grad_max, "skipped": skipped, "n": n}
 
+    # ------------------------------------------------------------------ chain-summed moments, PCD learning
+    def weight_moments(self, var_copy=0, evidence_chain=False, counts=False):
+        """The mean per-weight statistics of chains, summed on the device in fixed point (nsk_weight_moments): every
+        factor value is rounded to a multiple of ``2**-32`` and added as int64 into ONE sum per weight, whatever the
+        number of chains, so the result is exact to within ``2**-33`` per factor and does not depend on the order of
+        execution (``diagnostics.moment_counts`` is the rule in numpy).  The state is ``var_value[var_copy]`` --
+        ``var_value_evid[var_copy]`` with ``evidence_chain=True`` --, pushed as ``weight_statistics`` pushes it;
+        ``var_copy="all"`` sums over every row of ``var_value``.  Returns float64 ``(nweight,)`` in the order of
+        ``weight``: the sums ``* 2.0**-32 / chains``, equal to ``weight_statistics(...)`` averaged over the chains where the
+        factor values are integers.  ``counts=True`` returns ``(int64 sums, chains)`` instead.  A weight without a
+        factor reads 0; ``featureValue`` plays no part."""
+        if _all_copies(var_copy) and evidence_chain:
+            raise ValueError('the evidence chain exists once: var_copy="all" is for the free chains')
+        L, h = _lib.lib(), self._engine()
+        if _all_copies(var_copy):
+            nchains, which = self._push_chains(0, count=False), _lib.BUF_VALUE
+        else:
+            self._push(var_copy, 0)
+            nchains, which = 1, (_lib.BUF_VALUE_EVID if evidence_chain else _lib.BUF_VALUE)
+        m = np.zeros(self.weight.shape[0], np.int64)
+        _lib.check(L.nsk_weight_moments(h, which, 0, nchains, _lib.ptr(m)))
+        if counts:
+            return m, nchains
+        return m.astype(np.float64) * 2.0 ** -32 / np.float64(nchains)
+
+    def learn_pcd(self, epochs, stepsize, decay=1.0, reg_param=0.0, sweeps=1, sample_evidence=True, target=None,
+                  normalize=True, weight_copy=0, moments=False):
+        """Maximum-likelihood learning by persistent contrastive divergence on the device (nsk_pcd_steps).  The rows of
+        ``var_value`` are the persistent chains ("fantasy particles"); each of the ``epochs`` steps sweeps all of them
+        ``sweeps`` times under the current weights (burn-in sweeps: nothing is tallied), sums their per-weight statistics
+        exactly (``weight_moments``) and moves every weight that is not fixed along ``target - model mean``:
+        ``w += step * ((target - mean) / n_w - reg_param * w)`` with ``step = stepsize * decay**t`` and ``n_w`` the number
+        of factors of the weight (``normalize=False``: no division).  Nothing returns to the host between steps.  Its
+        fixed point is where the model's mean statistics equal the target -- the maximum-likelihood estimate when the
+        target is the data's mean statistics -- unlike ``learn_mple``, which maximises the pseudo-likelihood, and unlike
+        ``learn``, which takes one clipped SGD step per variable visit.
+
+        ``target`` (nweight,) are the statistics to match; None means those of the evidence chain,
+        ``weight_moments(evidence_chain=True)``, which is right for FULLY OBSERVED data.  With latent variables the
+        caller supplies the target -- for example the mean of the ``weight_statistics`` column of a clamped
+        ``sample(..., sample_evidence=False)`` run under the current weights; a clamped phase inside the call is out of
+        scope here.  ``sample_evidence=True`` lets the chains sample every variable (the free phase).
+
+        The chains are pushed as ``inference(var_copy="all")`` pushes them, without the tally; afterwards ``var_value``
+        holds every chain's state and ``weight_value[weight_copy]`` the learned weights.  ``count`` is untouched.
+        Returns a dict: ``grad_max`` -- float64 ``(epochs,)``, the largest ``|target - mean|`` (divided by ``n_w`` with
+        ``normalize``) over the weights that are not fixed, at the weights each step swept under; ``target``; ``chains``;
+        ``factors_per_weight`` -- int64 ``(nweight,)``; and with ``moments=True`` ``moments`` -- int64 ``(epochs,
+        nweight)``, every step's sums (``diagnostics.pcd_step`` is the update in numpy)."""
+        epochs, sweeps = int(epochs), int(sweeps)
+        if epochs < 1 or epochs > 65536:
+            raise ValueError("learn_pcd: epochs must lie in [1, 65536]")
+        if sweeps < 1 or epochs * sweeps > 2 ** 31 - 1:
+            raise ValueError("learn_pcd: sweeps must be at least 1 and epochs x sweeps at most 2**31 - 1")
+        stepsize, decay, reg_param = float(stepsize), float(decay), float(reg_param)
+        if not (np.isfinite(stepsize) and np.isfinite(decay) and np.isfinite(reg_param)) or reg_param < 0:
+            raise ValueError("learn_pcd: stepsize, decay and reg_param must be finite, reg_param not negative")
+        nw = self.weight.shape[0]
+        if target is not None:
+            target = np.ascontiguousarray(target, np.float64)
+            if target.shape != (nw,) or not np.isfinite(target).all():
+                raise ValueError("learn_pcd: target is finite float64 (nweight,) = (%d,)" % nw)
+        else:
+            target = self.weight_moments(evidence_chain=True)
+        L, h = _lib.lib(), self._engine()
+        nchains = self._push_chains(weight_copy, count=False)
+        gmax = np.zeros(epochs, np.float64)
+        rows = np.zeros((epochs, nw), np.int64) if moments else None
+        _lib.check(L.nsk_pcd_steps(h, _lib.ptr(target), epochs, sweeps, int(bool(sample_evidence)), stepsize, decay, reg_param,
+                                   int(bool(normalize)), _lib.ptr(gmax), _lib.ptr(rows)))
+        self._pull_chains(count=False)
+        self._pull(0, weight_copy, values=False, count=False)
+        out = {"grad_max": gmax, "target": target, "chains": nchains,
+               "factors_per_weight": np.bincount(self.factor["weightId"].astype(np.int64), minlength=nw).astype(np.int64)}
+        if moments:
+            out["moments"] = rows
+        return out
+
     def rao_blackwell(self, epochs, var_ids=None, thin=1, burnin_epochs=0, sample_evidence=False):
         """Rao-Blackwellised marginals: ``inference(burnin_epochs, epochs, sample_evidence, var_copy="all")`` -- one chain
         per row of ``var_value``; one chain is fine -- during which, after every ``thin``-th tallied sweep, the device adds
