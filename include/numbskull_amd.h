@@ -390,6 +390,52 @@ int nsk_pcd_steps(nsk_graph *g, const double *target /* nweight, caller's weight
                   double *gmax /* nsteps, may be NULL */,
                   int64_t *moments /* nsteps x nweight, may be NULL */);
 
+/* PCD with latent variables (FactorGraph.learn_pcd(clamped = K)): a clamped and a free population of chains on one handle.
+ * With latent variables the gradient of the log-likelihood of the evidence is E[S_w | evidence] - E[S_w], and BOTH
+ * expectations move with the weights; nsk_pcd_steps' constant target is right for fully observed data only.  With
+ * R = nsk_get_chains(g), K = nclamped and k = sweeps_per_step, chains [0, K) are the CLAMPED population -- they sample
+ * the latent variables with the evidence held -- and chains [K, R) the FREE one.
+ * clamp = 1: before the first step one launch writes initialValue into every variable with isEvidence 1, 2 or 3 of every
+ * clamped chain (a list of {internal id, value} pairs uploaded for the call).  clamp = 0: the rows are trusted as they
+ * are -- each clamped chain may hold the evidence of another training example.
+ * With s0 the handle's sweep index at the call, for t = 0 .. nsteps - 1, on the handle's stream and without a host wait:
+ *   1. clamped phase: what nsk_gibbs_sweeps(g, k, sample_evidence = 0, burnin = 1) enqueues on a handle that has the
+ *      chains [0, K) and no other, at sweep indices s0 + 2kt .. s0 + 2kt + k - 1; the tables derived from the weights are
+ *      rebuilt first, as every step leaves them marked;
+ *   2. free phase: what nsk_gibbs_sweeps(g, k, free_sample_evidence, 1) enqueues on a handle that has the chains [K, R)
+ *      and no other, at sweep indices s0 + 2kt + k .. s0 + 2k(t + 1) - 1;
+ *   3. zero Mc and Mf, then the moment launches of nsk_weight_moments over the clamped chains into Mc and over the free
+ *      chains into Mf: its rule, bit for bit, on two accumulators of nweight x 8 bytes;
+ *   4. one update launch, per weight slot that is not fixed, every line ONE rounded IEEE operation:
+ *        mc = ((double)Mc * 2^-32) / K
+ *        mf = ((double)Mf * 2^-32) / (R - K)
+ *        g  = mc - mf
+ *        if (normalize) g = g / n_w
+ *        a = reg_param * w;  b = g - a;  c = step_t * b;  w = w + c
+ *      with step_0 = step, step_{t+1} = step_t * decay (the products formed on the host in t order): nsk_pcd_steps' update
+ *      with target = mc and R - K chains (numbskull_amd.diagnostics.pcd_latent_step is the rule in numpy).
+ * Generators: within a phase, local chain i of its population (global chain i, or K + i) draws what a one-chain handle
+ * seeded seed ^ ((uint64_t)i << 32) draws at the phase's sweep indices -- what the sweep kernels make of the launch-local
+ * chain index, so no sweep kernel and no kernel argument knows of the populations.  Clamped chain i and free chain i
+ * share a key and never a sweep index, so they share no uniform.  Each phase takes the launches its population would
+ * take as a handle of its own: the chain-batched table launches, chain after chain otherwise, the one-chain launches for
+ * a population of one; never a captured sequence.  The phases plan their launches anew when their sample_evidence flags
+ * differ (host work only), which drops the captured sequences of later plain calls; they are captured again on demand.
+ * gmax[t] = the largest |g| over the weights that are not fixed, found as nsk_pcd_steps finds it; moments[(2 t) * nweight
+ * + w] = that step's Mc_w and moments[(2 t + 1) * nweight + w] = its Mf_w, in the caller's weight ids.
+ * The call synchronises once.  It leaves the new weights in the device table, marked so that the next sweep call rebuilds
+ * what derives from them; the chains where the last sweeps left them; sweeps_done and the sweep index advanced by
+ * 2 * k * nsteps.  Tallies are untouched (a tally kept in the value bytes is unpacked first), a sample trace keeps its
+ * rows and columns, and nsk_graph_info.device_bytes is afterwards what a nsk_weight_stats call leaves.
+ * NSK_E_INVALID, before anything is enqueued and with the handle left as it was: everything nsk_pcd_steps refuses (there
+ * is no target); nclamped outside [1, R - 1], so R >= 2; clamp or normalize other than 0 or 1; 2 * nsteps * k > 2^31 - 1.
+ * NSK_E_RANGE: the rule of nsk_weight_moments with nchains = max(K, R - K).  nweight == 0 is NSK_OK with nothing done. */
+int nsk_pcd_latent_steps(nsk_graph *g, int64_t nclamped, int clamp,
+                         int64_t nsteps, int64_t sweeps_per_step, int free_sample_evidence,
+                         double step, double decay, double reg_param, int normalize,
+                         double *gmax /* nsteps, may be NULL */,
+                         int64_t *moments /* nsteps x 2 x nweight, may be NULL */);
+
 /* Tempered sweep schedules (FactorGraph.tempered_sweeps / log_partition / log_evidence / anneal): sweeps at an inverse
  * temperature beta, driven by a schedule.  potential() is linear in the weights, so sampling from exp(beta U) / Z_beta,
  * U the log-potential above, IS sampling under the weight table beta * w: one beta per step, shared by every chain,

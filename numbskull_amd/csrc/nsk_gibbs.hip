@@ -362,7 +362,8 @@ int nsk_gibbs_run(nsk_graph *g, int64_t nsweeps, int sample_evidence, int burnin
     struct Done { nsk_graph *g; bool fuse, keep; ~Done() { g->p2p.fused_now = false; if (fuse) g->p2p.close_pending = true;
                                                             if (!keep) (void)nsk_unpack_tally(g);
                                                             g->pack_now = false; } } done{g, fuse, keep_packed};
-    if (left >= NSK_GRAPH_SWEEPS && graph_eligible(g, p2p)) {
+    // (under a ChainRange the sequences stay as they are: they hold the whole handle's pointers and chain count)
+    if (left >= NSK_GRAPH_SWEEPS && !g->chain_view && graph_eligible(g, p2p)) {
         // the plans of this (sample_evidence, tables) combination and the tables of the current weights (what an eager
         // sweep does in front of its launches; an eager sweep in front of the replays cost a 400-sweep call of the 1M grid
         // 16 sweeps outside them -- this one and the 15 that 399 leaves over)

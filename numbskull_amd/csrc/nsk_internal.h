@@ -3,7 +3,7 @@
 // nsk_learn.hip: the sweep drivers of numbskull/factorgraph.py:141,163,202; nsk_trace.hip, nsk_energy.hip, nsk_wstats.hip,
 // nsk_cond.hip: the diagnostics; nsk_icm.hip: the greedy MAP search; nsk_temper.hip: tempered sweep schedules;
 // nsk_smc.hip: population annealing on top of them; nsk_plgrad.hip: the pseudo-likelihood gradient and MPLE learning;
-// nsk_pcd.hip: the chain-summed moments and persistent contrastive divergence).
+// nsk_pcd.hip: the chain-summed moments and persistent contrastive divergence, fully observed and with latent variables).
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -308,6 +308,7 @@ struct nsk_graph {
     size_t chain_stride = 0;
     bool chains_regular = true;    // the values of chains 1 .. R - 1 lie in their domains (see values_regular)
     bool chain_swapped = false;    // a ChainSwap is active: the pointers are one chain's, the sweep samples that chain only
+    bool chain_view = false;       // a ChainRange is active: the pointers and nchains are a range's; no captured sequence runs
     // profiling bracket
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
     int64_t launches = 0, launches_at_begin = 0;
@@ -371,6 +372,25 @@ struct ChainSwap {
         g->seed = seed ^ ((uint64_t)(uint32_t)r << 32);
     }
     ~ChainSwap() { g->val = val; g->cnt_pos = cnt_pos; g->cnt = cnt; g->cnt_total = cnt_total; g->seed = seed; g->chain_swapped = false; }
+};
+// Points the handle at its chains [r0, r0 + n) while it lives: values and tallies are chain r0's and nchains == n, so
+// what nsk_gibbs_sweeps(.., burnin = 1) enqueues serves those n chains and no other -- the batched chain launches, the
+// ChainSwap loop (which nests: it offsets from the view's pointers) or, with n == 1, the one-chain launches.  The key
+// stays the handle's: local chain i (global chain r0 + i) draws what a one-chain handle seeded seed ^ (i << 32) draws,
+// which is what the kernels make of the launch-local chain index -- no kernel and no kernel argument knows of the view.
+// Captured sweep sequences bake the whole handle's pointers and chain count, so nsk_gibbs_run takes the eager path
+// under a view (chain_view) and leaves the sequences alone: they stay valid for the whole handle unless the plans are
+// made again, which drops them.  values_regular stays the conjunction over ALL chains of the handle.
+struct ChainRange {
+    nsk_graph *g;
+    void *val; uint8_t *cnt_pos; int32_t *cnt; long long *cnt_total; int nchains;
+    ChainRange(nsk_graph *g_, int r0, int n) : g(g_), val(g_->val), cnt_pos(g_->cnt_pos), cnt(g_->cnt), cnt_total(g_->cnt_total), nchains(g_->nchains) {
+        const size_t off = (size_t)r0 * g->chain_stride, nc = (size_t)r0 * (size_t)g->c.ncount;
+        g->val = (char *)val + off; g->cnt_pos = cnt_pos + off; g->cnt = cnt + nc; g->cnt_total = cnt_total + nc;
+        g->nchains = n;
+        g->chain_view = true;
+    }
+    ~ChainRange() { g->val = val; g->cnt_pos = cnt_pos; g->cnt = cnt; g->cnt_total = cnt_total; g->nchains = nchains; g->chain_view = false; }
 };
 
 // Philox counter word 3 of every sweep kernel (see rng_tag)

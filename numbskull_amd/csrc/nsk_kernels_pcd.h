@@ -29,6 +29,9 @@
 //   a = reg_param * w;  b = g - a;  c = step * b;  w = w + c
 // and gmax = the largest |g| over those weights: |g| is a non-negative finite double, whose bit pattern orders as an
 // unsigned integer -- a block maximum, then one 64-bit integer atomic max.  With `mout` the step's M is kept.
+//
+// Latent variables (nsk_pcd_latent_steps; at the end of the file): k_pcd_clamp writes the initial values of the evidence
+// variables into the clamped chains, k_pcd_latent_update is k_pcd_update with the clamped chains' mean as its target.
 #pragma once
 
 #include "nsk_internal.h"          // NSK_WSTATS_SHORT, NSK_WSTATS_PIECE
@@ -148,6 +151,59 @@ static __global__ __launch_bounds__(NSK_BLOCK) void k_pcd_update(const long long
         if (!w_fixed[s]) {
             const double m = ((double)S * (1.0 / NSK_GRAD_SCALE)) / nchains;
             double gr = target[s] - m;
+            if (normalize) gr = gr / nfac[s];
+            const double x = w[s];
+            const double a = reg_param * x;
+            const double b = gr - a;
+            const double c = step * b;
+            w[s] = x + c;
+            mag = (unsigned long long)__double_as_longlong(fabs(gr));
+        }
+    }
+#pragma unroll
+    for (int off = 1; off < 64; off <<= 1) { const unsigned long long o = __shfl_xor(mag, off, 64); mag = o > mag ? o : mag; }
+    if ((threadIdx.x & 63) == 0) lds[threadIdx.x >> 6] = mag;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        unsigned long long m = lds[0];
+#pragma unroll
+        for (int k = 1; k < NSK_BLOCK / 64; k++) m = lds[k] > m ? lds[k] : m;
+        if (m > 0ull) (void)__hip_atomic_fetch_max(gmax, m, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+}
+
+// ---- latent variables (nsk_pcd_latent_steps): a clamped and a free population of chains ----
+// The clamp: pairs = {internal id, value} of every variable with isEvidence 1, 2 or 3, built by the host for the call;
+// chain r < nchains of the chains that start at `val` gets every value written.  One lane per pair and chain group
+// (blockIdx.y, as the moment launches), more pairs loop.
+template <typename VT>
+__global__ __launch_bounds__(NSK_BLOCK) void k_pcd_clamp(VT *val, long long chain_stride, int nchains, const int2 *pairs, long long npairs) {
+    for (long long i = (long long)blockIdx.x * NSK_BLOCK + threadIdx.x; i < npairs; i += (long long)gridDim.x * NSK_BLOCK) {
+        const int2 p = pairs[i];
+        for (int r = (int)blockIdx.y; r < nchains; r += (int)gridDim.y)
+            ((VT *)((char *)val + (long long)r * chain_stride))[p.x] = (VT)p.y;
+    }
+}
+
+// One step's update with the target taken from the clamped chains: k_pcd_update with target = mc, every line one
+// rounded IEEE operation:
+//   mc = ((double)Mc * 2^-32) / K;  mf = ((double)Mf * 2^-32) / (R - K);  g = mc - mf;  if (normalize) g = g / n_w
+//   a = reg_param * w;  b = g - a;  c = step * b;  w = w + c
+// gmax as k_pcd_update finds it; mout (may be null): this step's two rows of the kept moments, Mc then Mf.
+static __global__ __launch_bounds__(NSK_BLOCK) void k_pcd_latent_update(const long long *Mc, const long long *Mf, const double *nfac,
+                                                                        double nclamped, double nfree, int nweight, double *w,
+                                                                        const uint8_t *w_fixed, int normalize, double step, double reg_param,
+                                                                        unsigned long long *gmax, long long *mout) {
+    __shared__ unsigned long long lds[NSK_BLOCK / 64];
+    const int s = (int)(blockIdx.x * NSK_BLOCK + threadIdx.x);
+    unsigned long long mag = 0ull;
+    if (s < nweight) {
+        const long long Sc = Mc[s], Sf = Mf[s];
+        if (mout) { mout[s] = Sc; mout[nweight + s] = Sf; }
+        if (!w_fixed[s]) {
+            const double mc = ((double)Sc * (1.0 / NSK_GRAD_SCALE)) / nclamped;
+            const double mf = ((double)Sf * (1.0 / NSK_GRAD_SCALE)) / nfree;
+            double gr = mc - mf;
             if (normalize) gr = gr / nfac[s];
             const double x = w[s];
             const double a = reg_param * x;

@@ -3,6 +3,8 @@
 // statistics (nsk_wstats.hip nsk_wstats_ensure); the work list, the int64 sums, the target, the factor counts and the
 // per-step outputs live for the call only.  nsk_pcd_steps enqueues (the burn-in sweeps of nsk_gibbs_sweeps, zero the sums,
 // the moment launches, k_pcd_update) per step on the handle's stream without a host wait and synchronises once.
+// nsk_pcd_latent_steps does the same for two populations of the handle's chains, clamped and free, each swept through a
+// ChainRange view (nsk_internal.h), each with its own sums, and k_pcd_latent_update takes its target from the clamped ones.
 #include <hip/hip_runtime.h>
 
 #include <cmath>
@@ -62,8 +64,11 @@ struct PcdBufs {
     unsigned long long *M = nullptr, *gmax = nullptr;
     double *target = nullptr, *nfac = nullptr;
     long long *rows = nullptr;
+    unsigned long long *Mf = nullptr;      // nsk_pcd_latent_steps: the free chains' sums (M holds the clamped chains')
+    int2 *pairs = nullptr;                 // ... and the clamp's {internal id, value} list
     explicit PcdBufs(nsk_graph *g_) : g(g_) {}
     ~PcdBufs() {
+        dev_free(g, pairs); dev_free(g, Mf);
         dev_free(g, rows); dev_free(g, nfac); dev_free(g, target); dev_free(g, gmax); dev_free(g, M); dev_free(g, pieces); dev_free(g, shorts);
     }
 };
@@ -252,6 +257,123 @@ int nsk_pcd_steps(nsk_graph *g, const double *target, int64_t nsteps, int64_t sw
     if (gmax) std::memcpy(gmax, hmax.data(), T * sizeof(double));
     if (moments)
         for (size_t t = 0; t < T; t++)
+            for (size_t i = 0; i < nw; i++) moments[t * nw + i] = (int64_t)hrows[t * nw + (wmap ? (size_t)wmap[i] : i)];
+    return NSK_OK;
+}
+
+int nsk_pcd_latent_steps(nsk_graph *g, int64_t nclamped, int clamp, int64_t nsteps, int64_t sweeps_per_step, int free_sample_evidence,
+                         double step, double decay, double reg_param, int normalize, double *gmax, int64_t *moments) {
+    const char *who = "nsk_pcd_latent_steps";
+    if (!g) return fail(NSK_E_INVALID, "null graph");
+    if (nsteps < 1 || nsteps > 65536) return fail(NSK_E_INVALID, "nsk_pcd_latent_steps: nsteps must lie in [1, 65536]");
+    if (sweeps_per_step < 1 || sweeps_per_step > INT32_MAX / (2 * nsteps))
+        return fail(NSK_E_INVALID, "nsk_pcd_latent_steps: sweeps_per_step must be at least 1 and 2 x nsteps x sweeps_per_step at most 2^31 - 1");
+    if (!std::isfinite(step) || !std::isfinite(decay) || !std::isfinite(reg_param) || reg_param < 0.0)
+        return fail(NSK_E_INVALID, "nsk_pcd_latent_steps: step, decay and reg_param must be finite, reg_param not negative");
+    if (normalize != 0 && normalize != 1) return fail(NSK_E_INVALID, "nsk_pcd_latent_steps: normalize must be 0 or 1");
+    if (clamp != 0 && clamp != 1) return fail(NSK_E_INVALID, "nsk_pcd_latent_steps: clamp must be 0 or 1");
+    if (g->scan != NSK_SCAN_CHROMATIC) return fail(NSK_E_INVALID, "nsk_pcd_latent_steps: the sequential scan is not served");
+    int rc = energy_whole_graph(g, who);
+    if (rc) return rc;
+    const int R = g->nchains;
+    if (nclamped < 1 || nclamped > R - 1)
+        return fail(NSK_E_INVALID, "nsk_pcd_latent_steps: nclamped must lie in [1, chains - 1]: a clamped and a free population, each of at least one "
+                                   "chain (nsk_set_chains)");
+    const Compiled &c = g->c;
+    const size_t nw = (size_t)c.nweight, T = (size_t)nsteps;
+    if (nw == 0) return NSK_OK;
+    const int K = (int)nclamped, F = R - K;
+    if ((rc = moments_range(g, std::max(K, F), who))) return rc;
+    HIPCHECK(hipSetDevice(g->device));
+    if ((rc = energy_ensure(g, 0, who))) return rc;
+    if ((rc = nsk_wstats_ensure(g, false, who))) return rc;
+    // a tally kept in bits 1-7 of the value bytes goes back to its array first, as in nsk_pcd_steps
+    if ((rc = nsk_unpack_tally(g))) return rc;
+
+    PcdBufs b(g);
+    MomentsArgs a;
+    PcdHost keep;
+    const NskWstats &ws = g->wstats;
+    const int32_t *wmap = c.wmap.empty() ? nullptr : c.wmap.data();
+    std::vector<double> nfac(nw);
+    for (size_t s = 0; s < nw; s++) { const uint32_t n = ws.wf_off[s + 1] - ws.wf_off[s]; nfac[s] = n ? (double)n : 1.0; }
+    // the clamp's list: every variable with isEvidence 1, 2 or 3 has a position (only isEvidence 4 has none), whose word
+    // names it; its internal id is where its value lies in a chain
+    std::vector<int2> pairs;
+    bool clamp_regular = true;
+    if (clamp)
+        for (size_t p = 0; p < (size_t)c.npos; p++) {
+            const int64_t v = c.p_vid[p];
+            const uint32_t ev = v >= 0 ? (c.p_info[p] & 0xFFu) : 0u;
+            if (ev < 1u || ev > 3u) continue;
+            const int32_t x = c.v_init[(size_t)v];
+            pairs.push_back(make_int2(c.iid[(size_t)v], x));
+            if (x < 0 || x >= c.v_card[(size_t)v]) clamp_regular = false;
+        }
+    rc = moments_plan(g, b, a, keep, K, who);
+    if (!rc) rc = pcd_alloc(g, &b.Mf, nw, who, "the free chains' int64 sums, 8 bytes a weight");
+    if (!rc) rc = pcd_alloc(g, &b.nfac, nw, who, "the factor counts, 8 bytes a weight");
+    if (!rc) rc = pcd_alloc(g, &b.gmax, T, who, "the largest gradients, 8 bytes a step");
+    if (!rc && moments) rc = pcd_alloc(g, &b.rows, T * 2 * nw, who, "the kept moments, nsteps x 2 x nweight int64");
+    if (!rc && !pairs.empty()) rc = pcd_alloc(g, &b.pairs, pairs.size(), who, "the clamp's list, 8 bytes an evidence variable");
+    hipError_t e = hipSuccess;
+    if (!rc) e = hipMemcpyAsync(b.nfac, nfac.data(), nw * sizeof(double), hipMemcpyHostToDevice, g->stream);
+    if (!rc && e == hipSuccess) e = hipMemsetAsync(b.gmax, 0, T * sizeof(unsigned long long), g->stream);
+    if (!rc && e == hipSuccess && b.pairs) e = hipMemcpyAsync(b.pairs, pairs.data(), pairs.size() * sizeof(int2), hipMemcpyHostToDevice, g->stream);
+    if (rc || e != hipSuccess) { (void)hipStreamSynchronize(g->stream); if (rc) return rc; HIPCHECK(e); }
+
+    // the clamp: one launch over the clamped chains; their values lie in their domains afterwards where they did before
+    // and every initial value written does
+    if (b.pairs) {
+        const long long np = (long long)pairs.size();
+        const unsigned nb = (unsigned)std::min<long long>(NSK_MOMENTS_MAX_BLOCKS, (np + NSK_BLOCK - 1) / NSK_BLOCK);
+        const dim3 grid(nb, nsk_moments_chain_groups(nb, K));
+        if (c.vbytes == 4) k_pcd_clamp<int32_t><<<grid, dim3(NSK_BLOCK), 0, g->stream>>>((int32_t *)g->val, (long long)g->chain_stride, K, b.pairs, np);
+        else k_pcd_clamp<int8_t><<<grid, dim3(NSK_BLOCK), 0, g->stream>>>((int8_t *)g->val, (long long)g->chain_stride, K, b.pairs, np);
+        e = hipGetLastError();
+        if (!clamp_regular) {
+            g->chain_regular[0] = false;
+            if (K > 1) g->chains_regular = false;
+            g->values_regular = false;
+        }
+    }
+
+    MomentsArgs af = a;             // the same work list over the free chains
+    af.nchains = F;
+    const char *val_free = (const char *)g->val + (size_t)K * g->chain_stride;
+    const int cap = moments_cap();
+    const unsigned wblocks = (unsigned)((nw + NSK_BLOCK - 1) / NSK_BLOCK);
+    double st = step;           // step_0 = step, step_{t+1} = step_t * decay: the products are formed here, in t order
+    for (size_t t = 0; t < T && !rc && e == hipSuccess; t++) {
+        // 1. the clamped phase: a burn-in call through the view [0, K); it refreshes what derives from the weights
+        { ChainRange view(g, 0, K); rc = nsk_gibbs_sweeps(g, sweeps_per_step, 0, 1); }
+        if (rc) break;
+        // 2. the free phase, through the view [K, R), at the sweep indices that follow
+        { ChainRange view(g, K, F); rc = nsk_gibbs_sweeps(g, sweeps_per_step, free_sample_evidence ? 1 : 0, 1); }
+        if (rc) break;
+        // 3. the moments of each population
+        if ((e = moments_enqueue(g, a, g->val, b.M, cap)) != hipSuccess) break;
+        if ((e = moments_enqueue(g, af, val_free, b.Mf, cap)) != hipSuccess) break;
+        // 4. the update
+        k_pcd_latent_update<<<dim3(wblocks), dim3(NSK_BLOCK), 0, g->stream>>>((const long long *)b.M, (const long long *)b.Mf, b.nfac, (double)K, (double)F,
+                                                                             (int)nw, g->w, g->w_fixed, normalize, st, reg_param, b.gmax + t,
+                                                                             b.rows ? b.rows + t * 2 * nw : nullptr);
+        e = hipGetLastError();
+        g->weights_dirty = true;            // the next sweep call rebuilds what derives from the weights
+        st = st * decay;
+    }
+    std::vector<unsigned long long> hmax(T);
+    std::vector<long long> hrows(b.rows ? T * 2 * nw : 0);
+    const bool ok = !rc && e == hipSuccess;
+    if (ok) e = hipMemcpyAsync(hmax.data(), b.gmax, T * sizeof(unsigned long long), hipMemcpyDeviceToHost, g->stream);
+    if (ok && b.rows && e == hipSuccess) e = hipMemcpyAsync(hrows.data(), b.rows, T * 2 * nw * sizeof(long long), hipMemcpyDeviceToHost, g->stream);
+    const hipError_t e2 = hipStreamSynchronize(g->stream);      // (also: the uploads read the host vectors)
+    if (rc) return rc;
+    HIPCHECK(e);
+    HIPCHECK(e2);
+    if (gmax) std::memcpy(gmax, hmax.data(), T * sizeof(double));
+    if (moments)
+        for (size_t t = 0; t < 2 * T; t++)
             for (size_t i = 0; i < nw; i++) moments[t * nw + i] = (int64_t)hrows[t * nw + (wmap ? (size_t)wmap[i] : i)];
     return NSK_OK;
 }

@@ -62,7 +62,8 @@ whatever the order -- and the weight update of maximum pseudo-likelihood learnin
 
 ``moment_counts`` and ``pcd_step`` restate ``FactorGraph.weight_moments`` / ``learn_pcd`` (nsk_weight_moments, nsk_pcd_steps;
 DESIGN.md section 4): the per-weight statistics summed over chains as int64 sums of quantised factor values, and the weight
-update of persistent contrastive divergence, one rounded operation each.
+update of persistent contrastive divergence, one rounded operation each; ``pcd_latent_step`` is the update of
+``learn_pcd(clamped=K)`` (nsk_pcd_latent_steps), whose target is the mean of a clamped population of chains.
 """
 
 import collections
@@ -669,6 +670,26 @@ def pcd_step(w, fixed, M, R, target, n_w, step, reg_param, normalize):
     c = np.float64(step) * b
     gmax = float(np.abs(g[free]).max()) if free.any() else 0.0
     return np.where(free, w + c, w), gmax
+
+
+def pcd_latent_step(w, fixed, Mc, K, Mf, Rf, n_w, step, reg_param, normalize):
+    """One step of PCD with latent variables as ``FactorGraph.learn_pcd(clamped=K)`` takes it on the device
+    (nsk_pcd_latent_steps): ``Mc`` (nweight,) is the int64 ``moment_counts`` of the ``K`` clamped chains, ``Mf`` that of the
+    ``Rf`` free chains.  One rounded float64 operation each::
+
+        mc = (float(Mc) * 2.0**-32) / K;  mf = (float(Mf) * 2.0**-32) / Rf;  g = mc - mf;  if normalize: g = g / n_w
+        a = reg_param * w;  b = g - a;  c = step * b;  w = w + c
+
+    which is ``pcd_step`` with ``target = mc`` and ``Rf`` chains.  Weights with ``fixed`` set stay as they are.  Returns
+    ``(w_new, gmax)`` as ``pcd_step`` does."""
+    w = np.asarray(w, np.float64)
+    sc = np.asarray(Mc)
+    if sc.dtype.kind not in "iu" or sc.shape != w.shape:
+        raise ValueError("pcd_latent_step: Mc and Mf are int64 with the shape of w")
+    if int(K) < 1 or int(Rf) < 1:
+        raise ValueError("pcd_latent_step: each population has at least one chain")
+    mc = (sc.astype(np.float64) * 2.0 ** -32) / np.float64(K)
+    return pcd_step(w, fixed, Mf, Rf, mc, n_w, step, reg_param, normalize)
 
 
 def _schedule(betas, lp, what):

@@ -946,7 +946,7 @@ class FactorGraph(object):
         return {"grad_max": grad_max, "skipped": skipped, "n": n}
 
     # ------------------------------------------------------------------ chain-summed moments, PCD learning
-    def weight_moments(self, var_copy=0, evidence_chain=False, counts=False):
+    def weight_moments(self, var_copy=0, evidence_chain=False, counts=False, chains=None):
         """The mean per-weight statistics of chains, summed on the device in fixed point (nsk_weight_moments): every
         factor value is rounded to a multiple of ``2**-32`` and added as int64 into ONE sum per weight, whatever the
         number of chains, so the result is exact to within ``2**-33`` per factor and does not depend on the order of
@@ -955,23 +955,34 @@ class FactorGraph(object):
         ``var_copy="all"`` sums over every row of ``var_value``.  Returns float64 ``(nweight,)`` in the order of
         ``weight``: the sums ``* 2.0**-32 / chains``, equal to ``weight_statistics(...)`` averaged over the chains where the
         factor values are integers.  ``counts=True`` returns ``(int64 sums, chains)`` instead.  A weight without a
-        factor reads 0; ``featureValue`` plays no part."""
+        factor reads 0; ``featureValue`` plays no part.  ``chains=(first, n)`` sums over the rows ``first .. first + n - 1``
+        of ``var_value`` alone (``var_copy`` is then not read): one population of ``learn_pcd(clamped=K)``."""
+        first = 0
+        if chains is not None:
+            if evidence_chain:
+                raise ValueError("the evidence chain exists once: chains=(first, n) names rows of var_value")
+            first, n = (int(x) for x in chains)
+            if first < 0 or n < 1 or first + n > int(self.var_value.shape[0]):
+                raise ValueError("weight_moments: chains=(first, n) must name rows of var_value, n at least 1")
+            var_copy = "all"
         if _all_copies(var_copy) and evidence_chain:
             raise ValueError('the evidence chain exists once: var_copy="all" is for the free chains')
         L, h = _lib.lib(), self._engine()
         if _all_copies(var_copy):
             nchains, which = self._push_chains(0, count=False), _lib.BUF_VALUE
+            if chains is not None:
+                nchains = n
         else:
             self._push(var_copy, 0)
             nchains, which = 1, (_lib.BUF_VALUE_EVID if evidence_chain else _lib.BUF_VALUE)
         m = np.zeros(self.weight.shape[0], np.int64)
-        _lib.check(L.nsk_weight_moments(h, which, 0, nchains, _lib.ptr(m)))
+        _lib.check(L.nsk_weight_moments(h, which, first, nchains, _lib.ptr(m)))
         if counts:
             return m, nchains
         return m.astype(np.float64) * 2.0 ** -32 / np.float64(nchains)
 
     def learn_pcd(self, epochs, stepsize, decay=1.0, reg_param=0.0, sweeps=1, sample_evidence=True, target=None,
-                  normalize=True, weight_copy=0, moments=False):
+                  normalize=True, weight_copy=0, moments=False, clamped=0, clamp=True):
         """Maximum-likelihood learning by persistent contrastive divergence on the device (nsk_pcd_steps).  The rows of
         ``var_value`` are the persistent chains ("fantasy particles"); each of the ``epochs`` steps sweeps all of them
         ``sweeps`` times under the current weights (burn-in sweeps: nothing is tallied), sums their per-weight statistics
@@ -983,17 +994,26 @@ class FactorGraph(object):
         ``learn``, which takes one clipped SGD step per variable visit.
 
         ``target`` (nweight,) are the statistics to match; None means those of the evidence chain,
-        ``weight_moments(evidence_chain=True)``, which is right for FULLY OBSERVED data.  With latent variables the
-        caller supplies the target -- for example the mean of the ``weight_statistics`` column of a clamped
-        ``sample(..., sample_evidence=False)`` run under the current weights; a clamped phase inside the call is out of
-        scope here.  ``sample_evidence=True`` lets the chains sample every variable (the free phase).
+        ``weight_moments(evidence_chain=True)``, which is right for FULLY OBSERVED data.  ``sample_evidence=True`` lets the
+        chains sample every variable (the free phase).
+
+        With LATENT variables the target moves with the weights: it is the mean statistics of chains that sample the
+        latent variables with the evidence held.  ``clamped=K > 0`` (nsk_pcd_latent_steps) makes the first ``K`` rows of
+        ``var_value`` that clamped population and the other rows the free one; ``target`` must then be None.  Every step
+        sweeps the clamped rows ``sweeps`` times with the evidence held, then the free rows ``sweeps`` times under
+        ``sample_evidence``, and moves the weights along ``clamped mean - free mean`` by the same rule
+        (``diagnostics.pcd_latent_step``).  ``clamp=True`` first writes ``initialValue`` into every evidence variable
+        (``isEvidence`` 1, 2 or 3) of the clamped rows; ``clamp=False`` trusts the rows as they are -- each may hold the
+        evidence of another training example.  Both populations persist across steps and calls.
 
         The chains are pushed as ``inference(var_copy="all")`` pushes them, without the tally; afterwards ``var_value``
         holds every chain's state and ``weight_value[weight_copy]`` the learned weights.  ``count`` is untouched.
         Returns a dict: ``grad_max`` -- float64 ``(epochs,)``, the largest ``|target - mean|`` (divided by ``n_w`` with
         ``normalize``) over the weights that are not fixed, at the weights each step swept under; ``target``; ``chains``;
         ``factors_per_weight`` -- int64 ``(nweight,)``; and with ``moments=True`` ``moments`` -- int64 ``(epochs,
-        nweight)``, every step's sums (``diagnostics.pcd_step`` is the update in numpy)."""
+        nweight)``, every step's sums (``diagnostics.pcd_step`` is the update in numpy).  With ``clamped=K``
+        ``target`` is None, the dict gains ``clamped`` and ``moments`` is ``(epochs, 2, nweight)``: the clamped rows' sums, then the
+        free rows'."""
         epochs, sweeps = int(epochs), int(sweeps)
         if epochs < 1 or epochs > 65536:
             raise ValueError("learn_pcd: epochs must lie in [1, 65536]")
@@ -1003,6 +1023,27 @@ class FactorGraph(object):
         if not (np.isfinite(stepsize) and np.isfinite(decay) and np.isfinite(reg_param)) or reg_param < 0:
             raise ValueError("learn_pcd: stepsize, decay and reg_param must be finite, reg_param not negative")
         nw = self.weight.shape[0]
+        clamped = int(clamped)
+        if clamped != 0:
+            if clamped < 1 or clamped > int(self.var_value.shape[0]) - 1:
+                raise ValueError("learn_pcd: clamped must lie in [1, rows of var_value - 1]: a clamped and a free population")
+            if target is not None:
+                raise ValueError("learn_pcd: with clamped rows the target is their statistics; target must be None")
+            if 2 * epochs * sweeps > 2 ** 31 - 1:
+                raise ValueError("learn_pcd: 2 x epochs x sweeps must be at most 2**31 - 1 with clamped rows")
+            L, h = _lib.lib(), self._engine()
+            nchains = self._push_chains(weight_copy, count=False)
+            gmax = np.zeros(epochs, np.float64)
+            rows = np.zeros((epochs, 2, nw), np.int64) if moments else None
+            _lib.check(L.nsk_pcd_latent_steps(h, clamped, int(bool(clamp)), epochs, sweeps, int(bool(sample_evidence)), stepsize,
+                                              decay, reg_param, int(bool(normalize)), _lib.ptr(gmax), _lib.ptr(rows)))
+            self._pull_chains(count=False)
+            self._pull(0, weight_copy, values=False, count=False)
+            out = {"grad_max": gmax, "target": None, "chains": nchains, "clamped": clamped,
+                   "factors_per_weight": np.bincount(self.factor["weightId"].astype(np.int64), minlength=nw).astype(np.int64)}
+            if moments:
+                out["moments"] = rows
+            return out
         if target is not None:
             target = np.ascontiguousarray(target, np.float64)
             if target.shape != (nw,) or not np.isfinite(target).all():
