@@ -535,6 +535,56 @@ int nsk_smc_sweeps(nsk_graph *g, const double *betas /* nsteps */, int64_t nstep
                    int32_t *ancestors /* (nsteps - 1) x chains, may be NULL */,
                    int32_t *resampled /* nsteps - 1, may be NULL */);
 
+/* Parallel tempering (FactorGraph.parallel_tempering): replica exchange between the chains of the handle.  The two calls
+ * above are annealers -- beta changes over time and no chain samples the target along the way.  Here chain r stays at the
+ * inverse temperature betas[r] for the whole call and STATES travel between the chains through Metropolis swaps, so a
+ * chain at beta = 1 keeps sampling the target while the hot chains carry it across the barriers between its modes; its
+ * tallies are marginals.  Temperatures do not move: chain r's tallies always belong to betas[r].
+ * The call acts on ALL chains of the handle (R = nsk_get_chains).  With w_base the device weight table as it stands when
+ * the call begins and s0 the sweep index at entry, for t = 0 .. nsteps - 1, in this order on the handle's stream and
+ * without a host wait between steps:
+ *   1. sweep   for r = 0 .. R - 1: w[s] = betas[r] * w_base[s] for every slot, fixed weights included (one rounded
+ *              float64 product, the scale of nsk_tempered_sweeps), the tables derived from the weights are rebuilt, and
+ *              chain r -- and no other -- runs sweeps_per_step sweeps by the one-chain launches, keyed seed ^ (r << 32),
+ *              at the sweep indices s0 + t * sweeps_per_step + i: every replica of a step uses the same indices.  They
+ *              are burn-in sweeps (nothing tallied), except those of chain tally_chain, which are tallied exactly as a
+ *              one-chain inference call tallies them (tally_chain = -1: none).  No sweep kernel, kernel argument, plan or
+ *              captured sequence differs from those of nsk_gibbs_sweeps;
+ *   2. score   U[r] = the log-potential of chain r's state under w_base, for all chains in one walk, with the very bits
+ *              nsk_log_potential returns; lp[t * R + r] = U[r] -- after the sweep, before the swap;
+ *   3. decide  the pair of the chains r and r + 1 is proposed iff r and t have the same parity and r + 1 < R (the
+ *              deterministic even-odd scheme: the pairs of a step are disjoint).  d = (betas[r] - betas[r + 1]) *
+ *              (U[r + 1] - U[r]): two rounded differences, one rounded product.  The swap is accepted iff d >= 0.0, or
+ *              d >= -745.0 and uniforms[t * (R - 1) + r] < exp(d), exp the library's specified exponential (DESIGN.md
+ *              "nsk_exp", the oracle's orc_exp_det bit for bit); a NaN d rejects.  accepted[t * (R - 1) + r] is 1, 0, or
+ *              -1 for a pair not proposed at step t (numbskull_amd.diagnostics.pt_swap_rule is this rule in numpy and
+ *              returns the device's decisions integer for integer when fed the lp row and that exp);
+ *   4. swap    the value bytes of the two chains of every accepted pair are exchanged in place, device to device.
+ *              Tallies, trace storage and the evidence chain are not exchanged.  The sweep generators are keyed by the
+ *              slot r, so a state goes on under the stream of the slot it moved to.
+ * Then w = w_base again, bit for bit (a copy), the handle is marked so that a following sweep call rebuilds the tables
+ * under the base weights, and the call synchronises ONCE and downloads lp (nsteps x R) and accepted (nsteps x (R - 1),
+ * int32); each may be NULL.  sweeps_done and the sweep index have advanced by nsteps x sweeps_per_step, as after
+ * nsk_tempered_sweeps.  An error after the first scale still restores the base weights.  A tally kept in the value bytes
+ * is first brought back to its array; a pending uint8 position tally is folded into the masters at entry and again
+ * before the call returns, so that only chain tally_chain's tallies have grown.  A swap can carry a value from a slot into
+ * its neighbour, so after a call with R > 1 the handle treats chain 0 and the chains behind it as lying in their domains
+ * only if all of them did, as after nsk_smc_sweeps.  R = 1 is served: it has no pairs and accepted has no columns.
+ * NSK_E_INVALID, before anything is enqueued and with values, weights, counters and the generator untouched: what
+ * nsk_tempered_sweeps refuses (the sequential scan, own_range / NSK_FLAG_PARTITION, a boundary exchange, nsteps outside
+ * [1, 65536], sweeps_per_step < 1 or nsteps * sweeps_per_step > INT32_MAX); a beta that is negative, infinite or NaN;
+ * uniforms == NULL while R > 1; a uniform outside [0, 1) or NaN (all nsteps x (R - 1) are checked); tally_chain outside
+ * [-1, R); a handle that records a sample trace (tear it down first).
+ * Memory: what nsk_log_potential uploads at its first use, stays.  The copy of the base weights, lp, the betas, the
+ * uniforms, the decisions and the partner words live for the call only: nsk_graph_info.device_bytes is afterwards what
+ * it was.  NSK_E_NOMEM names the size of what does not fit.
+ * Cost: a step rebuilds the tables R times, once in front of every replica, where nsk_tempered_sweeps rebuilds them
+ * once (DESIGN.md has the measurements).  nsk_profile_* keeps counting sweep-kernel launches only. */
+int nsk_pt_sweeps(nsk_graph *g, const double *betas /* chains */, int64_t nsteps, int64_t sweeps_per_step,
+                  int sample_evidence, const double *uniforms /* nsteps x (chains - 1), each in [0, 1) */,
+                  int tally_chain /* -1: none */,
+                  double *lp /* nsteps x chains, may be NULL */, int32_t *accepted /* nsteps x (chains - 1), may be NULL */);
+
 /* Effective sample size from the trace, on the device (FactorGraph.mixing): per column of a BIT-PACKED trace, the
  * split-chain estimator of numbskull_amd.diagnostics.effective_sample_size with the lags cut at max_lag, in one
  * streaming pass over the packed rows -- no row is unpacked or leaves the device.  Rows first_row .. first_row +

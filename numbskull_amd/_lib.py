@@ -33,7 +33,7 @@ SYMBOLS = (
     "nsk_log_potential", "nsk_factor_values", "nsk_trace_log_potential", "nsk_trace_download_log_potential",
     "nsk_weight_stats", "nsk_trace_weight_stats", "nsk_trace_download_weight_stats",
     "nsk_conditionals", "nsk_trace_conditionals", "nsk_trace_download_conditionals", "nsk_icm", "nsk_tempered_sweeps",
-    "nsk_smc_sweeps", "nsk_pl_gradient", "nsk_mple_steps", "nsk_weight_moments", "nsk_pcd_steps", "nsk_pcd_latent_steps",
+    "nsk_smc_sweeps", "nsk_pt_sweeps", "nsk_pl_gradient", "nsk_mple_steps", "nsk_weight_moments", "nsk_pcd_steps", "nsk_pcd_latent_steps",
     "nsk_trace_ess", "nsk_trace_autocov_counts", "nsk_trace_pair_counts",
     "nsk_trace_value_autocov_counts", "nsk_trace_value_ess", "nsk_trace_value_pair_counts",
     "nsk_selftest_exp", "nsk_selftest_philox", "nsk_selftest_stream", "nsk_device_count", "nsk_last_error", "nsk_version",
@@ -192,6 +192,7 @@ def lib():
                                            C.c_double, C.c_int, C.c_void_p, C.c_void_p]
         L.nsk_tempered_sweeps.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int] + [C.c_void_p] * 4
         L.nsk_smc_sweeps.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int, C.c_double] + [C.c_void_p] * 6
+        L.nsk_pt_sweeps.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
         L.nsk_trace_ess.argtypes = [C.c_void_p, C.c_int64, C.c_int64, C.c_int64] + [C.c_void_p] * 4
         L.nsk_trace_autocov_counts.argtypes = [C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p]
         L.nsk_trace_pair_counts.argtypes = [C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p]

@@ -429,6 +429,16 @@ static int chains_run(nsk_graph *g, int64_t nsweeps, int sample_evidence, int bu
     return NSK_OK;
 }
 
+// Chain r of the handle alone (nsk_pt.hip: a replica under its own weight table): what chains_run's loop does for one
+// chain -- the one-chain launches through a ChainSwap view, eagerly, from the handle's sweep index on.  The caller sets
+// the sweep index and sweeps_done back between replicas; with burnin == 0 the sweeps are tallied into chain r's arrays and
+// pos_tally_sweeps counts them.
+int nsk_gibbs_chain(nsk_graph *g, int r, int64_t nsweeps, int sample_evidence, int burnin) {
+    if (g->scan != NSK_SCAN_CHROMATIC) return fail(NSK_E_INVALID, "one chain of several: the sequential scan is not served");
+    ChainSwap cs(g, r);
+    return gibbs_eager(g, nsweeps, sample_evidence, burnin);
+}
+
 // (keep_packed: nsk_gibbs_run; only a one-chain handle keeps its tally in the value bytes)
 static int sweeps_run(nsk_graph *g, int64_t nsweeps, int sample_evidence, int burnin, bool keep_packed = false) {
     if (g->nchains > 1) return chains_run(g, nsweeps, sample_evidence, burnin);

@@ -2,8 +2,9 @@
 // the library (nsk_api.hip: C-ABI, state sync; nsk_exchange.hip: the multi-GPU boundary exchange; nsk_gibbs.hip /
 // nsk_learn.hip: the sweep drivers of numbskull/factorgraph.py:141,163,202; nsk_trace.hip, nsk_energy.hip, nsk_wstats.hip,
 // nsk_cond.hip: the diagnostics; nsk_icm.hip: the greedy MAP search; nsk_temper.hip: tempered sweep schedules;
-// nsk_smc.hip: population annealing on top of them; nsk_plgrad.hip: the pseudo-likelihood gradient and MPLE learning;
-// nsk_pcd.hip: the chain-summed moments and persistent contrastive divergence, fully observed and with latent variables).
+// nsk_smc.hip: population annealing on top of them; nsk_pt.hip: parallel tempering; nsk_plgrad.hip: the pseudo-likelihood
+// gradient and MPLE learning; nsk_pcd.hip: the chain-summed moments and persistent contrastive divergence, fully observed
+// and with latent variables).
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -480,6 +481,7 @@ int nsk_p2p_flush(nsk_graph *g);                   // enqueue the pending closin
 void nsk_p2p_fill(nsk_graph *g, nsk::TabP2P &px, const unsigned long long *tag_base, unsigned int tag, bool wait);   // kernel argument of a fused launch
 void nsk_drop_sweep_graph(nsk_graph *g);            // the captured sweep sequence bakes exchange pointers: drop it when they change
 int nsk_gibbs_run(nsk_graph *g, int64_t nsweeps, int sample_evidence, int burnin, bool p2p, bool keep_packed = false);   // nsk_gibbs.hip
+int nsk_gibbs_chain(nsk_graph *g, int r, int64_t nsweeps, int sample_evidence, int burnin);   // chain r alone, eagerly (nsk_gibbs.hip)
 void nsk_refresh_prog_weights(nsk_graph *g, bool force = false);
 void nsk_refresh_ztab(nsk_graph *g, int set = 0, hipStream_t st = nullptr);
 int nsk_fold_position_tally(nsk_graph *g);

@@ -56,6 +56,10 @@ weights restated with the device's roundings, and the estimators of log Z, which
 (nsk_smc_sweeps): the device's resampling decision and ancestor choice restated operation by
 operation, and the estimate of log Z from a resampled population.
 
+``pt_swap_rule``, ``pt_paths`` and ``pt_ladder`` are the host side of ``FactorGraph.parallel_tempering`` (nsk_pt_sweeps;
+DESIGN.md section 4): the device's Metropolis decision on the swaps of a step restated operation by operation, the walk of
+every starting replica over the slots with its round trips, and a geometric ladder of inverse temperatures.
+
 ``pl_gradient_counts`` and ``mple_step`` restate ``FactorGraph.pl_gradient`` / ``learn_mple`` (nsk_pl_gradient,
 nsk_mple_steps): the gradient of the log-pseudo-likelihood as int64 sums of quantised terms -- exact,
 whatever the order -- and the weight update of maximum pseudo-likelihood learning, one rounded operation each.
@@ -783,6 +787,89 @@ def smc_resample(log_weights, u, threshold, exp=np.exp):
     anc = ident.copy()
     anc[n == 0] = np.repeat(ident, np.maximum(n - 1, 0))
     return True, anc, float(S), float(Q)
+
+
+def pt_swap_rule(betas, lp_row, uniforms_row, t, exp=np.exp):
+    """The swap decisions of step ``t`` of parallel tempering as nsk_pt_sweeps takes them (include/numbskull_amd.h, step
+    3): ``betas`` (R,) the chains' inverse temperatures, ``lp_row`` (R,) their log-potentials behind the step's sweeps,
+    ``uniforms_row`` (R - 1,) the step's uniforms in [0, 1).  Returns int32 ``(R - 1,)``: for the pair of the chains r and
+    r + 1, -1 where the pair is not proposed (r and t of different parity), else 1 or 0.  ``d = (betas[r] - betas[r + 1])
+    * (lp_row[r + 1] - lp_row[r])`` -- two rounded differences, one rounded product -- and the swap is accepted iff ``d >=
+    0``, or ``d >= -745`` and ``uniforms_row[r] < exp(d)``; a NaN ``d`` rejects.  Fed the device's ``lp`` row and the
+    oracle's ``exp_det`` as ``exp`` it returns the device's decisions integer for integer; ``np.exp`` may differ in a last
+    place and so, rarely, in a decision."""
+    b = np.ascontiguousarray(betas, np.float64)
+    u = np.ascontiguousarray(lp_row, np.float64)
+    if b.ndim != 1 or b.size < 1 or u.shape != b.shape:
+        raise ValueError("pt_swap_rule: betas and lp_row are 1-d arrays of one entry a chain, got %r and %r" % (b.shape, u.shape))
+    R = b.size
+    x = np.ascontiguousarray(uniforms_row if R > 1 else np.zeros(0), np.float64)
+    if x.shape != (R - 1,):
+        raise ValueError("pt_swap_rule: uniforms_row holds one uniform a pair, (R - 1,), got %r" % (x.shape,))
+    if not ((x >= 0.0) & (x < 1.0)).all():
+        raise ValueError("pt_swap_rule: a uniform lies outside [0, 1)")
+    out = np.full(R - 1, -1, np.int32)
+    with np.errstate(invalid="ignore", over="ignore"):
+        for r in range(int(t) & 1, R - 1, 2):
+            db = b[r] - b[r + 1]
+            du = u[r + 1] - u[r]
+            d = db * du
+            if d >= 0.0:
+                out[r] = 1
+            elif d >= -745.0:
+                out[r] = 1 if x[r] < float(np.asarray(exp(np.array([d], np.float64))).ravel()[0]) else 0
+            else:
+                out[r] = 0              # (a NaN d lands here)
+    return out
+
+
+def pt_paths(accepted):
+    """The walk of the replicas over the slots of a parallel-tempering run: ``accepted`` int ``(T, R - 1)`` as
+    nsk_pt_sweeps returns it (1: the states of the chains r and r + 1 changed places behind step t; 0 and -1: they did
+    not).  Returns ``(paths, round_trips)``: ``paths`` int64 ``(T, R)``, ``paths[t, s]`` the starting slot of the state
+    that sits in slot s behind step t; ``round_trips`` int64 ``(R,)``, per starting slot the number of completed round
+    trips slot 0 -> slot R - 1 -> slot 0 of its state (a state that starts in slot 0 has visited it).  With one chain
+    there is nowhere to go: no round trips."""
+    a = np.asarray(accepted)
+    if a.ndim != 2:
+        raise ValueError("pt_paths: accepted is (T, R - 1), got %r" % (a.shape,))
+    T, R = a.shape[0], a.shape[1] + 1
+    where = np.arange(R, dtype=np.int64)            # slot -> the starting slot of its state
+    paths, trips = np.zeros((T, R), np.int64), np.zeros(R, np.int64)
+    leg = np.zeros(R, np.int64)                     # per state: 0 nothing yet, 1 has been at slot 0, 2 ... and then at R - 1
+    leg[where[0]] = 1
+    for t in range(T):
+        acc = np.nonzero(a[t] == 1)[0]
+        if len(acc) > 1 and (np.diff(acc) < 2).any():
+            raise ValueError("pt_paths: step %d accepts two pairs that share a chain" % t)
+        for r in acc:
+            where[r], where[r + 1] = where[r + 1], where[r]
+        paths[t] = where
+        if R > 1:
+            top, bottom = where[R - 1], where[0]
+            if leg[top] == 1:
+                leg[top] = 2
+            if leg[bottom] == 2:
+                trips[bottom] += 1
+            if leg[bottom] != 1:
+                leg[bottom] = 1
+    return paths, trips
+
+
+def pt_ladder(n, beta_min):
+    """A geometric ladder of ``n`` inverse temperatures from ``beta_min`` up to 1.0: ``beta_min ** (1 - i / (n - 1))``,
+    the last exactly 1.0 (the cold chain, which samples the target); ``n = 1`` is ``[1.0]``.  Neighbouring chains of a
+    geometric ladder have equal ratios, which gives about equal swap rates where the heat capacity is flat."""
+    n, beta_min = int(n), float(beta_min)
+    if n < 1:
+        raise ValueError("pt_ladder: at least one chain")
+    if not 0.0 < beta_min <= 1.0:
+        raise ValueError("pt_ladder: beta_min lies in (0, 1]")
+    if n == 1:
+        return np.ones(1)
+    out = beta_min ** (1.0 - np.arange(n, dtype=np.float64) / (n - 1))
+    out[0], out[-1] = beta_min, 1.0
+    return out
 
 
 def smc_estimate(logw_pre, resampled, log_weights, log_z0):

@@ -1253,6 +1253,51 @@ class FactorGraph(object):
         return {"log_weights": logw, "log_potentials": lp, "logw_pre": pre, "ancestors": anc, "resampled": flag != 0,
                 "offsets": offsets}
 
+    def parallel_tempering(self, betas, steps, sweeps=1, seed=0, sample_evidence=False, weight_copy=0, target=None):
+        """Parallel tempering, driven on the device (nsk_pt_sweeps): replica exchange between the chains.  One chain per
+        row of ``var_value``, pushed and pulled as ``tempered_sweeps`` does; chain r stays at ``betas[r]`` (``len(betas)``
+        must equal the number of rows: ValueError) for all ``steps`` steps.  A step sweeps every chain ``sweeps`` times
+        under its own temperature, takes every chain's log-potential under the unscaled weights and proposes to swap the
+        STATES of neighbouring chains -- pairs (0, 1), (2, 3), ... at even steps, (1, 2), (3, 4), ... at odd ones -- each
+        accepted with probability ``min(1, exp((betas[r] - betas[r + 1]) (U[r + 1] - U[r])))``, decided and exchanged on
+        the device.  Temperatures do not move, so a chain at beta = 1 samples the target throughout while the hot chains
+        carry it between its modes (``diagnostics.pt_ladder`` makes a ladder that ends there).  The uniforms come from
+        ``np.random.RandomState(seed).random_sample((steps, chains - 1))``.  With ``target=r`` the sweeps of chain r are
+        tallied: ``count`` grows by its tally and ``chain_count[r]`` keeps it, as after ``inference(var_copy="all")``;
+        without, nothing is tallied.  The weights come back as they were and ``var_value`` is left holding the final
+        states.  Returns a dict: ``lp`` float64 ``(steps, chains)``, the log-potentials behind every step's sweeps and in
+        front of its swaps; ``accepted`` int32 ``(steps, chains - 1)``, 1, 0, or -1 for a pair not proposed at that step;
+        ``swap_rate`` ``(chains - 1,)``, accepted over proposed per pair (NaN for a pair never proposed); ``paths`` and
+        ``round_trips`` (``diagnostics.pt_paths``); ``uniforms``.  ``diagnostics.pt_swap_rule`` restates the decision."""
+        from .diagnostics import pt_paths
+        b = self._schedule(betas, "parallel_tempering")
+        nchains = int(self.var_value.shape[0])
+        if len(b) != nchains:
+            raise ValueError("parallel_tempering: %d inverse temperatures for %d chains (rows of var_value)" % (len(b), nchains))
+        steps, sweeps = int(steps), int(sweeps)
+        if steps < 1 or sweeps < 1:
+            raise ValueError("parallel_tempering: steps and sweeps must be at least 1")
+        tally = -1 if target is None else int(target)
+        if not -1 <= tally < nchains or (target is not None and tally < 0):
+            raise ValueError("parallel_tempering: target is None or a chain in [0, %d)" % nchains)
+        uniforms = np.ascontiguousarray(np.random.RandomState(seed).random_sample((steps, nchains - 1)), np.float64)
+        L, h = _lib.lib(), self._engine()
+        self._push_chains(weight_copy, count=tally >= 0)
+        before = self.chain_count.copy()
+        lp = np.zeros((steps, nchains), np.float64)
+        acc = np.zeros((steps, nchains - 1), np.int32)
+        _lib.check(L.nsk_pt_sweeps(h, _lib.ptr(b), steps, sweeps, int(bool(sample_evidence)), _lib.ptr(uniforms), tally,
+                                   _lib.ptr(lp), _lib.ptr(acc)))
+        cc = self._pull_chains(count=tally >= 0)
+        if tally >= 0:
+            self.count += (cc - before).sum(axis=0)
+            self.chain_count[:] = cc
+        proposed, taken = (acc >= 0).sum(axis=0), (acc == 1).sum(axis=0)
+        with np.errstate(invalid="ignore", divide="ignore"):
+            rate = np.where(proposed > 0, taken / np.maximum(proposed, 1), np.nan)
+        paths, trips = pt_paths(acc)
+        return {"lp": lp, "accepted": acc, "swap_rate": rate, "paths": paths, "round_trips": trips, "uniforms": uniforms}
+
     def _log_z0(self, sample_evidence):
         """the log of the number of states of the variables a sweep samples"""
         sampled = self.colors() >= 0
