@@ -278,6 +278,78 @@ int nsk_trace_download_conditionals(nsk_graph *g, double *sums /* chains x total
 int nsk_icm(nsk_graph *g, int which, int64_t first_chain, int64_t nchains, int64_t max_sweeps, int sample_evidence,
             int64_t *sweeps /* nchains */, int64_t *changed /* nchains x max_sweeps, may be NULL */);
 
+/* Loopy belief propagation (FactorGraph.belief_propagation): sum-product message passing on the factor graph, flooding
+ * schedule -- deterministic inference beside the sampler.  Exact on forests (after clamping), an approximation that may
+ * not converge on graphs with cycles.  numbskull_amd.diagnostics.bp_layout / bp_iterate / bp_factor_beliefs are the rule
+ * in numpy, bit for bit: every sum and product is taken in the order stated here, the exponential is the library's
+ * specified one, nothing is fused or reassociated.
+ * Scope: ONE state -- chain `chain` of NSK_BUF_VALUE or the evidence chain (NSK_BUF_VALUE_EVID, chain 0) -- under the
+ * current weights.  A variable is CLAMPED at its value in that state when the sweep kernels would not sample it: without
+ * a position (isEvidence == 4), or isEvidence != 0 with sample_evidence == 0; every other variable is FREE.
+ * Structure, per factor f in the caller's order: its member positions are its `arity` edge positions (a function that
+ * reads positions beyond its arity -- EQUAL reads 1, the DP_GEN_* functions 1 to 3 -- has those too; NOOP has none); its
+ * DISTINCT members in order of first occurrence get the local slots 0, 1, ..; the free ones among them, in that order,
+ * are the table's axes j = 0 .. A_f - 1, the first the most significant digit of a table index (C order); T_f = the
+ * product of their cardinalities (1 without a free member, and then no edge).  Directed edges (f, j) are numbered
+ * factor-major; edge e owns card(var(e)) doubles at msg_off[e] in each message array, f2v (factor to variable) and v2f.
+ * Tables: theta_f(a) = weight * eval_factor, ONE rounded product, the factor asked as its first member sees it, the
+ * free members at the digits of a, the clamped ones at their values; psi_f(a) = exp(theta_f(a) - max_a theta_f).
+ * Messages start at 1 / card.  Iteration t:
+ *   factor phase, per edge (f, j): m[k] = the sum over the table indices a with digit j equal to k, ascending, of
+ *     ((psi_f(a) * v2f[(f,0)][a_0]) * ..) over the axes i != j ascending; Z = m[0] + m[1] + .. in k order;
+ *     new[k] = m[k] / Z; with damping d > 0, new[k] = (1 - d) * new[k] + d * old[k] (two products, one sum; 1 - d
+ *     computed once); the edge's residual is the largest |new[k] - old[k]|, a NaN counting as +inf; residual[t] = the
+ *     largest over all edges;
+ *   variable phase, per free variable with the edges e_0 < .. < e_{n-1}: P = all ones; for i ascending: v2f[e_i] = P,
+ *     then P = P * f2v[e_i] entry by entry, then RESCALE(P): while the largest entry is > 0 and < 2^-512, every entry
+ *     times 2^512 (exact).  belief = P / (P[0] + P[1] + ..).  Then S = all ones; for i descending: v2f[e_i] = v2f[e_i] * S,
+ *     RESCALE, divided by its k-ordered sum; S = S * f2v[e_i], RESCALE.  (The product of all others, without a division.)
+ * A clamped variable's belief is the indicator of its value, a free variable in no table has the uniform one.  Two hard
+ * constraints that contradict each other give what IEEE gives (0 / 0 = NaN), as the conditionals do.
+ * Factor beliefs: b_f(a) = (psi_f(a) * v2f[(f,0)][a_0]) * .., divided by their a-ordered sum.
+ *   nsk_bp_setup     builds structure and tables for the state named and resets the messages; *info (may be NULL) = the
+ *                    sizes.  A set-up that was there is replaced.  Refused, naming the lowest offending factor and before
+ *                    anything is allocated: more than NSK_BP_MAX_MEMBERS distinct members, T_f > NSK_BP_MAX_TABLE, UFO
+ *                    (it reads members by value), a factor of function 13, 16 or 17 on a handle without
+ *                    NSK_FLAG_HEAD_BY_VID (the literal head lookup has no single energy), an index outside the arrays.
+ *   nsk_bp_layout    table_off[nfactor + 1], edge_off[nfactor + 1], edge_var[nedges] (the caller's ids), msg_off[nedges + 1];
+ *                    any may be NULL.
+ *   nsk_bp_run       up to max_iters (1 .. 4096) iterations from the resident messages, damping in [0, 1), tol >= 0.
+ *                    Everything is enqueued at once; the kernels of iteration t >= 1 return at once when
+ *                    residual[t - 1] <= tol.  *iters = the iterations run up to and including the first with
+ *                    residual <= tol, or -max_iters when there is none: NOT converged.  residual (may be NULL)
+ *                    [max_iters]: 0 behind the early exit.  May be called again: it continues.
+ *   nsk_bp_beliefs   the "full" layout of the conditionals above: variable i of the selection owns C_i doubles; vids as
+ *                    there (NULL with nvids = 0 = all variables).
+ *   nsk_bp_download  what = NSK_BP_THETA, NSK_BP_FACTOR_BELIEFS (computed by the call; both table_off's layout),
+ *                    NSK_BP_F2V, NSK_BP_V2F (msg_off's layout).
+ *   nsk_bp_clear     frees the set-up (NSK_OK without one).
+ * Run, beliefs, layout and download without a set-up are NSK_E_INVALID.  `which` and the handles refused follow
+ * nsk_log_potential; a tally kept in the value bytes is first brought back to its array, as in nsk_icm.  Nothing of the
+ * handle changes: values, tallies, weights and the generator stay.  The set-up is resident and counted in
+ * nsk_graph_info.device_bytes: 16 bytes a table entry, 16 a message entry + 20 an edge, 8 a member position + 8 a distinct
+ * member, 24 a factor, 17 a variable + 8 a value (16 where a free variable of cardinality above 16 has an edge); NSK_E_NOMEM names the
+ * bytes.  nsk_profile_* keeps counting sweep-kernel launches only.  (Diagnostic, NSK_DIAG=1 NSK_BP_GRID_CAP=blocks,
+ * read at each call: caps every grid of these calls, so that small graphs run the later trips of the lanes' loops.) */
+#define NSK_BP_MAX_MEMBERS 16
+#define NSK_BP_MAX_TABLE 4096
+#define NSK_BP_THETA 0
+#define NSK_BP_FACTOR_BELIEFS 1
+#define NSK_BP_F2V 2
+#define NSK_BP_V2F 3
+typedef struct {
+    int64_t nfactor, nedges, ntable, nmsg;      /* factors, directed edges, table entries, doubles of one message array */
+    int64_t nfree, nisolated, nclamped;         /* free variables; those among them in no table; clamped variables */
+    int64_t nbelief, max_table, device_bytes;   /* doubles of all beliefs; the largest T_f; bytes the set-up holds */
+} nsk_bp_info;
+int nsk_bp_setup(nsk_graph *g, int which, int64_t chain, int sample_evidence, nsk_bp_info *info);
+int nsk_bp_layout(nsk_graph *g, int64_t *table_off, int64_t *edge_off, int64_t *edge_var, int64_t *msg_off);
+int nsk_bp_run(nsk_graph *g, int64_t max_iters, double damping, double tol, int64_t *iters,
+               double *residual /* max_iters, may be NULL */);
+int nsk_bp_beliefs(nsk_graph *g, const int64_t *vids, int64_t nvids, double *out /* total */);
+int nsk_bp_download(nsk_graph *g, int what, double *out);
+int nsk_bp_clear(nsk_graph *g);
+
 /* Pseudo-likelihood gradient and maximum pseudo-likelihood learning (FactorGraph.pl_gradient / learn_mple): the
  * derivative of sum_v log P(x_v | every other variable) over a selection of variables with respect to every weight, and
  * the deterministic, sampling-free learner built on it.  No random number is drawn and no logarithm is taken on the

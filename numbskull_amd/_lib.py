@@ -34,6 +34,7 @@ SYMBOLS = (
     "nsk_weight_stats", "nsk_trace_weight_stats", "nsk_trace_download_weight_stats",
     "nsk_conditionals", "nsk_trace_conditionals", "nsk_trace_download_conditionals", "nsk_icm", "nsk_tempered_sweeps",
     "nsk_smc_sweeps", "nsk_pt_sweeps", "nsk_pl_gradient", "nsk_mple_steps", "nsk_weight_moments", "nsk_pcd_steps", "nsk_pcd_latent_steps",
+    "nsk_bp_setup", "nsk_bp_layout", "nsk_bp_run", "nsk_bp_beliefs", "nsk_bp_download", "nsk_bp_clear",
     "nsk_trace_ess", "nsk_trace_autocov_counts", "nsk_trace_pair_counts",
     "nsk_trace_value_autocov_counts", "nsk_trace_value_ess", "nsk_trace_value_pair_counts",
     "nsk_selftest_exp", "nsk_selftest_philox", "nsk_selftest_stream", "nsk_device_count", "nsk_last_error", "nsk_version",
@@ -65,6 +66,27 @@ class GraphInfo(C.Structure):
                 ("tiles_shape", C.c_int64), ("tiles_shape_padded", C.c_int64), ("tiles_lane", C.c_int64),
                 ("tiles_general", C.c_int64), ("tiles_general_roles", C.c_int64),
                 ("ep_groups", C.c_int64), ("ep_groups_two_pass", C.c_int64)]
+
+
+class BpInfo(C.Structure):
+    _fields_ = [(k, C.c_int64) for k in ("nfactor", "nedges", "ntable", "nmsg", "nfree", "nisolated", "nclamped",
+                                         "nbelief", "max_table", "device_bytes")]
+
+
+# belief propagation (include/numbskull_amd.h): the caps of a factor, what nsk_bp_download hands out, and the grids of its
+# launches (csrc/nsk_bp.hip bp_blocks): one item a lane, blocks of BP_BLOCK lanes (BP_VAR_BLOCK in the variable phase),
+# at most BP_MAX_BLOCKS -- or the diagnostic cap NSK_BP_GRID_CAP; more items loop
+BP_MAX_MEMBERS, BP_MAX_TABLE = 16, 4096
+BP_THETA, BP_FACTOR_BELIEFS, BP_F2V, BP_V2F = range(4)
+BP_BLOCK, BP_VAR_BLOCK, BP_MAX_BLOCKS = 256, 128, 2048
+BP_VAR_REG = 6          # a binary variable of at most this many edges is served from registers (csrc/nsk_kernels_bp.h)
+
+
+def bp_trips(items, cap=0, block=BP_BLOCK):
+    """Trips the lanes of a belief-propagation launch over ``items`` items make."""
+    limit = min(BP_MAX_BLOCKS, int(cap)) if cap > 0 else BP_MAX_BLOCKS
+    blocks = max(1, min((int(items) + block - 1) // block, limit))
+    return (int(items) + blocks * block - 1) // (blocks * block)
 
 
 # the launch of nsk_pl_gradient / nsk_mple_steps (csrc/nsk_kernels_plgrad.h nsk_plgrad_blocks): blocks of PLGRAD_BLOCK lanes
@@ -182,6 +204,12 @@ def lib():
         L.nsk_trace_conditionals.argtypes = [C.c_void_p, C.c_void_p, C.c_int64]
         L.nsk_trace_download_conditionals.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(C.c_int64)]
         L.nsk_icm.argtypes = [C.c_void_p, C.c_int, C.c_int64, C.c_int64, C.c_int64, C.c_int, C.c_void_p, C.c_void_p]
+        L.nsk_bp_setup.argtypes = [C.c_void_p, C.c_int, C.c_int64, C.c_int, C.POINTER(BpInfo)]
+        L.nsk_bp_layout.argtypes = [C.c_void_p] * 5
+        L.nsk_bp_run.argtypes = [C.c_void_p, C.c_int64, C.c_double, C.c_double, C.POINTER(C.c_int64), C.c_void_p]
+        L.nsk_bp_beliefs.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]
+        L.nsk_bp_download.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
+        L.nsk_bp_clear.argtypes = [C.c_void_p]
         L.nsk_pl_gradient.argtypes = [C.c_void_p, C.c_int, C.c_int64, C.c_int64, C.c_void_p, C.c_int64] + [C.c_void_p] * 3
         L.nsk_mple_steps.argtypes = [C.c_void_p, C.c_int, C.c_int64, C.c_int64, C.c_void_p, C.c_int64, C.c_int64,
                                      C.c_double, C.c_double, C.c_double, C.c_void_p, C.c_void_p]

@@ -1,0 +1,381 @@
+// nsk_bp.hip -- loopy belief propagation (nsk_internal.h NskBp, nsk_kernels_bp.h): nsk_bp_setup builds the structure of one
+// state on the host from the compiled records (which variables are clamped, every factor's distinct members, table axes,
+// directed edges, the per-variable edge lists), uploads it and fills the tables; nsk_bp_run enqueues every iteration on
+// the handle's stream without a synchronisation between them -- once the residual is at or below the tolerance the later
+// launches end on the device -- and copies the residuals back once.  The launches are not counted by the profiling bracket.
+#include <hip/hip_runtime.h>
+
+#include <cstring>
+
+#include "nsk_internal.h"
+#include "nsk_kernels_bp.h"
+
+using namespace nsk;
+
+// (diagnostic, NSK_DIAG=1 NSK_BP_GRID_CAP=blocks, read at each call: small grids, later trips)
+static unsigned int bp_blocks(long long items, int block = NSK_BLOCK) {
+    long long limit = NSK_BP_MAX_BLOCKS;
+    if (const char *env = nsk::diag_env("NSK_BP_GRID_CAP")) {
+        const long long cap = atoll(env);
+        if (cap > 0 && cap < limit) limit = cap;
+    }
+    const long long need = (items + block - 1) / block;
+    return (unsigned int)std::max<long long>(1, std::min(need, limit));
+}
+
+static void bp_free(nsk_graph *g) {
+    NskBp &b = g->bp;
+    for (void *p : b.owned) dev_free(g, p);
+    b = NskBp();
+}
+
+static BpArgs bp_args(const nsk_graph *g) {
+    const NskBp &b = g->bp;
+    BpArgs a = {};
+    a.f_rec = (const uint4 *)g->f_rec; a.mrec = (const int2 *)b.mrec; a.pm_off = b.pm_off;
+    a.slot_off = b.slot_off; a.slot_rec = (const int2 *)b.slot_rec;
+    a.tab_off = b.tab_off; a.edge_off = b.edge_off; a.e_fac = b.e_fac; a.msg_off = b.msg_off;
+    a.v_list = b.v_list; a.v_eoff = b.v_eoff; a.v_edges = b.v_edges;
+    a.b_off = b.d_b_off; a.v_state = b.v_state; a.v_card = g->v_card;
+    a.w = g->w; a.logtab = g->logtab;
+    a.theta = b.theta; a.psi = b.psi; a.f2v = b.f2v; a.v2f = b.v2f; a.belief = b.belief; a.wk = b.wk;
+    a.nfactor = (long long)g->c.nfactor; a.ntable = (long long)b.info.ntable; a.nid = (long long)g->c.nid;
+    a.nedge = (int32_t)b.info.nedges; a.nvlist = b.nvlist;
+    return a;
+}
+
+// member positions a function reads whatever its arity says (nsk_energy.hip energy_check_factors)
+static int64_t bp_need(int fn) {
+    switch (fn) {
+    case 3: case 18: case 19: case 20: case 30: return 1;
+    case 21: case 22: case 25: case 26: return 2;
+    case 23: case 24: return 3;
+    default: return 0;
+    }
+}
+
+template <typename T>
+static int bp_upload(nsk_graph *g, T **ptr, const std::vector<T> &h) {
+    int rc = dev_upload(g, ptr, h);
+    if (!rc) g->bp.owned.push_back(*ptr);
+    return rc;
+}
+template <typename T>
+static int bp_alloc(nsk_graph *g, T **ptr, size_t n) {
+    int rc = dev_alloc(g, ptr, n);
+    if (!rc) g->bp.owned.push_back(*ptr);
+    return rc;
+}
+
+static int bp_common(nsk_graph *g, const char *what, bool need_setup) {
+    if (!g) return fail(NSK_E_INVALID, "null graph");
+    int rc = energy_whole_graph(g, what);
+    if (rc) return rc;
+    if (need_setup && !g->bp.ready) return fail(NSK_E_INVALID, std::string(what) + ": no belief propagation is set up (nsk_bp_setup)");
+    return NSK_OK;
+}
+
+extern "C" {
+
+int nsk_bp_setup(nsk_graph *g, int which, int64_t chain, int sample_evidence, nsk_bp_info *info_out) {
+    int rc = bp_common(g, "nsk_bp_setup", false);
+    if (rc) return rc;
+    if (which != NSK_BUF_VALUE && which != NSK_BUF_VALUE_EVID) return fail(NSK_E_INVALID, "nsk_bp_setup: which must be NSK_BUF_VALUE or NSK_BUF_VALUE_EVID");
+    if (chain < 0 || chain >= (which == NSK_BUF_VALUE ? g->nchains : 1))
+        return fail(NSK_E_INVALID, "nsk_bp_setup: chain outside those the handle has (the evidence chain exists once)");
+    const Compiled &c = g->c;
+    const int64_t F = c.nfactor, nedge = c.nedge, nid = c.nid, npos = std::min<int64_t>(c.npos, (int64_t)c.p_info.size());
+    const bool head_by_vid = (c.flags & NSK_FLAG_HEAD_BY_VID) != 0;
+    // 0: no variable, 1: clamped, 2: free -- by internal id
+    std::vector<uint8_t> state((size_t)nid, 0);
+    nsk_bp_info info = {};
+    info.nfactor = F;
+    for (int64_t v = 0; v < c.nvar; v++) {
+        const int64_t id = c.iid[(size_t)v];
+        if (id < 0 || id >= nid) return fail(NSK_E_INVALID, "nsk_bp_setup: a variable without an internal id");
+        const bool clamped = id >= npos || ((c.p_info[(size_t)id] & 0xffu) != 0 && !sample_evidence);
+        state[(size_t)id] = clamped ? 1 : 2;
+    }
+    // ---- the structure, factor by factor; every refusal names the lowest offending factor and precedes any allocation
+    std::vector<long long> pm_off((size_t)F + 1, 0), tab_off((size_t)F + 1, 0), msg_off(1, 0);
+    std::vector<int32_t> slot_off((size_t)F + 1, 0), edge_off((size_t)F + 1, 0), slot_rec, mrec, e_fac, e_var;
+    std::vector<int32_t> deg((size_t)nid, 0);
+    auto refuse = [&](int64_t f, const std::string &why) {
+        return fail(NSK_E_INVALID, "nsk_bp_setup: factor " + std::to_string((long long)f) + " " + why);
+    };
+    for (int64_t f = 0; f < F; f++) {
+        const uint32_t head = c.f_rec[4 * (size_t)f];
+        const int fn = (int)(head & 0xffu) - 1;
+        const int64_t ar = (int64_t)(head >> 8), s = (int32_t)c.f_rec[4 * (size_t)f + 1], wz = (int32_t)c.f_rec[4 * (size_t)f + 2];
+        if (!known_function(fn) || wz < 0 || wz >= c.nweight) return refuse(f, "has an unknown function or a weight outside the table");
+        if (fn == 30) return refuse(f, "is UFO, which reads its members by value: belief propagation has no table for it");
+        if ((fn == 13 || fn == 16 || fn == 17) && !head_by_vid)
+            return refuse(f, "reads its head at the literal edge index (function 13, 16 or 17 without NSK_FLAG_HEAD_BY_VID): it has no single energy");
+        if (fn == 8 && ar >= (int64_t)c.logtab.size()) return refuse(f, "(RATIO) has more members than the logarithm table");
+        const int64_t np = fn == -1 ? 0 : std::max(ar, bp_need(fn));
+        if (s < 0 || s + np > nedge) return refuse(f, "has member positions outside the edge array");
+        int32_t ids[NSK_BP_MAX_MEMBERS];
+        int ns = 0;
+        long long T = 1;
+        for (int64_t l = s; l < s + np; l++) {
+            const int32_t id = c.m_rec[2 * (size_t)l];
+            if (id < 0 || id >= nid || !state[(size_t)id]) return refuse(f, "has a member outside the variables");
+            int k = 0;
+            while (k < ns && ids[k] != id) k++;
+            if (k == ns) {
+                if (ns == NSK_BP_MAX_MEMBERS)
+                    return refuse(f, "has more than NSK_BP_MAX_MEMBERS = " + std::to_string(NSK_BP_MAX_MEMBERS) + " distinct members");
+                ids[ns++] = id;
+            }
+            mrec.push_back(k);
+            mrec.push_back(c.m_rec[2 * (size_t)l + 1]);
+        }
+        for (int k = 0; k < ns; k++) {
+            const bool free = state[(size_t)ids[k]] == 2;
+            const long long card = c.v_card_i[(size_t)ids[k]];
+            if (free) {
+                if (card < 1) return refuse(f, "has a free member of cardinality below 1");
+                T *= card;
+                if (T > NSK_BP_MAX_TABLE)
+                    return refuse(f, "has a table of more than NSK_BP_MAX_TABLE = " + std::to_string(NSK_BP_MAX_TABLE) + " entries over its free members");
+            }
+        }
+        for (int k = 0; k < ns; k++) {
+            const bool free = state[(size_t)ids[k]] == 2;
+            slot_rec.push_back(ids[k]);
+            slot_rec.push_back(free ? 1 : 0);
+            if (free) {
+                e_fac.push_back((int32_t)f);
+                e_var.push_back(ids[k]);
+                msg_off.push_back(msg_off.back() + c.v_card_i[(size_t)ids[k]]);
+                deg[(size_t)ids[k]]++;
+            }
+        }
+        if ((int64_t)e_fac.size() > (int64_t)0x7ffffff0) return refuse(f, "and those before it have more than 2^31 directed edges");
+        pm_off[(size_t)f + 1] = pm_off[(size_t)f] + np;
+        slot_off[(size_t)f + 1] = slot_off[(size_t)f] + ns;
+        edge_off[(size_t)f + 1] = (int32_t)e_fac.size();
+        tab_off[(size_t)f + 1] = tab_off[(size_t)f] + T;
+        info.max_table = std::max<int64_t>(info.max_table, T);
+    }
+    const int64_t E = (int64_t)e_fac.size();
+    // ---- per variable: the beliefs' offsets, the free variables with an edge and their edges, ascending
+    NskBp nb;
+    nb.b_off.assign((size_t)nid + 1, 0);
+    std::vector<int32_t> v_list, v_eoff(1, 0), v_edges((size_t)E), slot_of((size_t)nid, -1);
+    for (int64_t id = 0; id < nid; id++) {
+        const long long card = state[(size_t)id] ? std::max<long long>(c.v_card_i[(size_t)id], 0) : 0;
+        nb.b_off[(size_t)id + 1] = nb.b_off[(size_t)id] + card;
+        if (state[(size_t)id] == 1) info.nclamped++;
+        if (state[(size_t)id] != 2) continue;
+        info.nfree++;
+        if (!deg[(size_t)id]) info.nisolated++;
+        else if (card > NSK_ZLOCAL) nb.big = true;
+    }
+    for (int pass = 0; pass < 2; pass++) {          // the binary variables first (k_bp_var), ascending in each part
+        for (int64_t id = 0; id < nid; id++) {
+            if (state[(size_t)id] != 2 || !deg[(size_t)id] || (c.v_card_i[(size_t)id] == 2) != (pass == 0)) continue;
+            slot_of[(size_t)id] = (int32_t)v_list.size();
+            v_list.push_back((int32_t)id);
+            v_eoff.push_back(v_eoff.back() + deg[(size_t)id]);
+        }
+        if (pass == 0) nb.nvbin = (int32_t)v_list.size();
+    }
+    {
+        std::vector<int32_t> cur(v_eoff.begin(), v_eoff.end() - 1);
+        for (int64_t e = 0; e < E; e++) v_edges[(size_t)cur[(size_t)slot_of[(size_t)e_var[(size_t)e]]]++] = (int32_t)e;
+    }
+    info.nedges = E; info.ntable = tab_off[(size_t)F]; info.nmsg = msg_off[(size_t)E]; info.nbelief = nb.b_off[(size_t)nid];
+    // ---- the handle's side: plain values, the records and weights on the device
+    HIPCHECK(hipSetDevice(g->device));
+    if ((rc = energy_ensure(g, 0, "nsk_bp_setup"))) return rc;
+    if ((rc = nsk_unpack_tally(g))) return rc;
+    HIPCHECK(hipStreamSynchronize(g->stream));
+    bp_free(g);
+    NskBp &b = g->bp;
+    b.big = nb.big; b.b_off.swap(nb.b_off); b.info = info; b.nvlist = (int32_t)v_list.size(); b.nvbin = nb.nvbin;
+    const int64_t before = g->mem.total;
+    const double bytes = 16.0 * (double)info.ntable + 16.0 * (double)info.nmsg + 20.0 * (double)E + 8.0 * (double)(mrec.size() / 2) +
+                         8.0 * (double)(slot_rec.size() / 2) + 24.0 * (double)F + 17.0 * (double)nid + (b.big ? 16.0 : 8.0) * (double)info.nbelief;
+    rc = bp_upload(g, &b.pm_off, pm_off);
+    if (!rc) rc = bp_upload(g, &b.tab_off, tab_off);
+    if (!rc) rc = bp_upload(g, &b.msg_off, msg_off);
+    if (!rc) rc = bp_upload(g, &b.d_b_off, b.b_off);
+    if (!rc) rc = bp_upload(g, &b.slot_off, slot_off);
+    if (!rc) rc = bp_upload(g, &b.edge_off, edge_off);
+    if (!rc) rc = bp_upload(g, &b.e_fac, e_fac);
+    if (!rc) rc = bp_upload(g, &b.e_var, e_var);
+    if (!rc) rc = bp_upload(g, &b.v_list, v_list);
+    if (!rc) rc = bp_upload(g, &b.v_eoff, v_eoff);
+    if (!rc) rc = bp_upload(g, &b.v_edges, v_edges);
+    if (!rc) rc = bp_upload(g, &b.mrec, mrec);
+    if (!rc) rc = bp_upload(g, &b.slot_rec, slot_rec);
+    if (!rc) rc = bp_upload(g, &b.v_state, state);
+    if (!rc) rc = bp_alloc(g, &b.theta, (size_t)info.ntable);
+    if (!rc) rc = bp_alloc(g, &b.psi, (size_t)info.ntable);
+    if (!rc) rc = bp_alloc(g, &b.f2v, (size_t)info.nmsg);
+    if (!rc) rc = bp_alloc(g, &b.v2f, (size_t)info.nmsg);
+    if (!rc) rc = bp_alloc(g, &b.belief, (size_t)info.nbelief);
+    if (!rc && b.big) rc = bp_alloc(g, &b.wk, (size_t)info.nbelief);
+    if (rc) {
+        (void)hipStreamSynchronize(g->stream);
+        bp_free(g);
+        if (rc != NSK_E_NOMEM) return rc;
+        return fail(NSK_E_NOMEM, "nsk_bp_setup: structure, tables, messages and beliefs (" + std::to_string((long long)bytes) +
+                                 " bytes) do not fit on the device");
+    }
+    b.info.device_bytes = g->mem.total - before;
+    const BpArgs a = bp_args(g);
+    const char *val = which == NSK_BUF_VALUE ? (const char *)g->val + (size_t)chain * g->chain_stride : (const char *)g->val_evid;
+    const dim3 block(NSK_BLOCK);
+    if (F > 0) {
+        if (c.vbytes == 4) k_bp_tables<int32_t><<<dim3(bp_blocks(a.ntable)), block, 0, g->stream>>>(a, (const int32_t *)val);
+        else k_bp_tables<int8_t><<<dim3(bp_blocks(a.ntable)), block, 0, g->stream>>>(a, (const int8_t *)val);
+        k_bp_psi<<<dim3(bp_blocks(F)), block, 0, g->stream>>>(a);
+    }
+    if (E > 0) k_bp_reset<<<dim3(bp_blocks(E)), block, 0, g->stream>>>(a);
+    if (nid > 0) {
+        if (c.vbytes == 4) k_bp_belief0<int32_t><<<dim3(bp_blocks(nid)), block, 0, g->stream>>>(a, (const int32_t *)val);
+        else k_bp_belief0<int8_t><<<dim3(bp_blocks(nid)), block, 0, g->stream>>>(a, (const int8_t *)val);
+    }
+    hipError_t e = hipGetLastError();
+    const hipError_t e2 = hipStreamSynchronize(g->stream);      // (the uploads read the vectors of this scope)
+    if (e != hipSuccess || e2 != hipSuccess) {
+        bp_free(g);
+        HIPCHECK(e);
+        HIPCHECK(e2);
+    }
+    b.ready = true;
+    if (info_out) *info_out = b.info;
+    return NSK_OK;
+}
+
+int nsk_bp_layout(nsk_graph *g, int64_t *table_off, int64_t *edge_off, int64_t *edge_var, int64_t *msg_off) {
+    int rc = bp_common(g, "nsk_bp_layout", true);
+    if (rc) return rc;
+    const NskBp &b = g->bp;
+    const size_t F = (size_t)b.info.nfactor, E = (size_t)b.info.nedges;
+    HIPCHECK(hipSetDevice(g->device));
+    HIPCHECK(hipStreamSynchronize(g->stream));
+    static_assert(sizeof(long long) == sizeof(int64_t), "offsets cross as they are");
+    if (table_off) HIPCHECK(hipMemcpy(table_off, b.tab_off, (F + 1) * 8, hipMemcpyDeviceToHost));
+    if (msg_off) HIPCHECK(hipMemcpy(msg_off, b.msg_off, (E + 1) * 8, hipMemcpyDeviceToHost));
+    std::vector<int32_t> tmp;
+    if (edge_off) {
+        tmp.resize(F + 1);
+        HIPCHECK(hipMemcpy(tmp.data(), b.edge_off, (F + 1) * 4, hipMemcpyDeviceToHost));
+        for (size_t i = 0; i <= F; i++) edge_off[i] = tmp[i];
+    }
+    if (edge_var && E) {
+        tmp.resize(E);
+        HIPCHECK(hipMemcpy(tmp.data(), b.e_var, E * 4, hipMemcpyDeviceToHost));
+        for (size_t i = 0; i < E; i++) edge_var[i] = g->c.p_vid[(size_t)tmp[i]];       // (a free variable has a position)
+    }
+    return NSK_OK;
+}
+
+int nsk_bp_run(nsk_graph *g, int64_t max_iters, double damping, double tol, int64_t *iters, double *residual) {
+    int rc = bp_common(g, "nsk_bp_run", true);
+    if (rc) return rc;
+    if (!iters) return fail(NSK_E_INVALID, "null argument");
+    if (max_iters < 1 || max_iters > 4096) return fail(NSK_E_INVALID, "nsk_bp_run: max_iters must lie in [1, 4096]");
+    if (!(damping >= 0.0 && damping < 1.0)) return fail(NSK_E_INVALID, "nsk_bp_run: damping must lie in [0, 1)");
+    if (!(tol >= 0.0)) return fail(NSK_E_INVALID, "nsk_bp_run: tol must be at least 0");
+    HIPCHECK(hipSetDevice(g->device));
+    const size_t S = (size_t)max_iters;
+    unsigned long long *res = nullptr;          // [max_iters] bit patterns, for this call only
+    if ((rc = dev_alloc(g, &res, S))) {
+        if (rc != NSK_E_NOMEM) return rc;
+        return fail(NSK_E_NOMEM, "nsk_bp_run: the residuals (" + std::to_string((long long)(S * 8)) + " bytes) do not fit on the device");
+    }
+    hipError_t e = hipMemsetAsync(res, 0, S * 8, g->stream);
+    const BpArgs a = bp_args(g);
+    const double oml = 1.0 - damping;
+    const int nbin = g->bp.nvbin, nall = a.nvlist;
+    const dim3 block(NSK_BLOCK), gf(bp_blocks(a.nedge)), vblock(NSK_BP_VAR_BLOCK),
+               gb(bp_blocks(nbin, NSK_BP_VAR_BLOCK)), gr(bp_blocks(nall - nbin, NSK_BP_VAR_BLOCK));
+    if (a.nedge > 0)
+        for (size_t t = 0; t < S && e == hipSuccess; t++) {
+            k_bp_factor<<<gf, block, 0, g->stream>>>(a, (int)t, tol, damping, oml, res);
+            if (nbin > 0) k_bp_var<true><<<gb, vblock, 0, g->stream>>>(a, 0, nbin, (int)t, tol, res);
+            if (nall > nbin) k_bp_var<false><<<gr, vblock, 0, g->stream>>>(a, nbin, nall, (int)t, tol, res);
+            e = hipGetLastError();
+        }
+    std::vector<double> host(S);
+    if (e == hipSuccess) e = hipMemcpyAsync(host.data(), res, S * 8, hipMemcpyDeviceToHost, g->stream);
+    const hipError_t e2 = hipStreamSynchronize(g->stream);
+    dev_free(g, res);
+    HIPCHECK(e);
+    HIPCHECK(e2);
+    int64_t ran = -max_iters;
+    for (size_t t = 0; t < S; t++) {
+        if (residual) residual[t] = host[t];
+        if (ran < 0 && host[t] <= tol) ran = (int64_t)t + 1;
+    }
+    *iters = ran;
+    return NSK_OK;
+}
+
+int nsk_bp_beliefs(nsk_graph *g, const int64_t *vids, int64_t nvids, double *out) {
+    int rc = bp_common(g, "nsk_bp_beliefs", true);
+    if (rc) return rc;
+    const Compiled &c = g->c;
+    if (nvids < 0 || (!vids && nvids != 0)) return fail(NSK_E_INVALID, "nsk_bp_beliefs: a null selection with a count, or a negative count");
+    if (vids && nvids == 0) return NSK_OK;
+    const int64_t n = vids ? nvids : c.nvar;
+    for (int64_t i = 0; vids && i < n; i++)
+        if (vids[i] < 0 || vids[i] >= c.nvar) return fail(NSK_E_INDEX, "nsk_bp_beliefs: variable id out of range");
+    const NskBp &b = g->bp;
+    if (b.info.nbelief == 0) return NSK_OK;
+    if (!out) return fail(NSK_E_INVALID, "null argument");
+    HIPCHECK(hipSetDevice(g->device));
+    HIPCHECK(hipStreamSynchronize(g->stream));
+    std::vector<double> all((size_t)b.info.nbelief);
+    HIPCHECK(hipMemcpy(all.data(), b.belief, all.size() * 8, hipMemcpyDeviceToHost));
+    size_t o = 0;
+    for (int64_t i = 0; i < n; i++) {
+        const size_t id = (size_t)c.iid[(size_t)(vids ? vids[i] : i)];
+        for (long long k = b.b_off[id]; k < b.b_off[id + 1]; k++) out[o++] = all[(size_t)k];
+    }
+    return NSK_OK;
+}
+
+int nsk_bp_download(nsk_graph *g, int what, double *out) {
+    int rc = bp_common(g, "nsk_bp_download", true);
+    if (rc) return rc;
+    if (what < NSK_BP_THETA || what > NSK_BP_V2F) return fail(NSK_E_INVALID, "nsk_bp_download: what must be NSK_BP_THETA .. NSK_BP_V2F");
+    const NskBp &b = g->bp;
+    const size_t n = (size_t)(what <= NSK_BP_FACTOR_BELIEFS ? b.info.ntable : b.info.nmsg);
+    if (n == 0) return NSK_OK;
+    if (!out) return fail(NSK_E_INVALID, "null argument");
+    HIPCHECK(hipSetDevice(g->device));
+    if (what != NSK_BP_FACTOR_BELIEFS) {
+        HIPCHECK(hipStreamSynchronize(g->stream));
+        HIPCHECK(hipMemcpy(out, what == NSK_BP_THETA ? b.theta : (what == NSK_BP_F2V ? b.f2v : b.v2f), n * 8, hipMemcpyDeviceToHost));
+        return NSK_OK;
+    }
+    double *fb = nullptr;                       // for this call only
+    if ((rc = dev_alloc(g, &fb, n))) {
+        if (rc != NSK_E_NOMEM) return rc;
+        return fail(NSK_E_NOMEM, "nsk_bp_download: the factor beliefs (" + std::to_string((long long)(n * 8)) + " bytes) do not fit on the device");
+    }
+    k_bp_fbelief<<<dim3(bp_blocks((long long)b.info.nfactor)), dim3(NSK_BLOCK), 0, g->stream>>>(bp_args(g), fb);
+    hipError_t e = hipGetLastError();
+    if (e == hipSuccess) e = hipMemcpyAsync(out, fb, n * 8, hipMemcpyDeviceToHost, g->stream);
+    const hipError_t e2 = hipStreamSynchronize(g->stream);
+    dev_free(g, fb);
+    HIPCHECK(e);
+    HIPCHECK(e2);
+    return NSK_OK;
+}
+
+int nsk_bp_clear(nsk_graph *g) {
+    if (!g) return fail(NSK_E_INVALID, "null graph");
+    if (!g->bp.ready) return NSK_OK;
+    HIPCHECK(hipSetDevice(g->device));
+    HIPCHECK(hipStreamSynchronize(g->stream));
+    bp_free(g);
+    return NSK_OK;
+}
+
+}  // extern "C"

@@ -4,7 +4,7 @@
 // nsk_cond.hip: the diagnostics; nsk_icm.hip: the greedy MAP search; nsk_temper.hip: tempered sweep schedules;
 // nsk_smc.hip: population annealing on top of them; nsk_pt.hip: parallel tempering; nsk_plgrad.hip: the pseudo-likelihood
 // gradient and MPLE learning; nsk_pcd.hip: the chain-summed moments and persistent contrastive divergence, fully observed
-// and with latent variables).
+// and with latent variables; nsk_bp.hip: loopy belief propagation).
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -112,6 +112,24 @@ struct NskEnergy {
     double *result = nullptr;          // chains sums (a query's; a trace writes into its lp column)
 };
 
+// Belief propagation (nsk_bp_setup .. nsk_bp_clear; nsk_bp.hip, nsk_kernels_bp.h): the structure of one state's clamped
+// and free variables, the tables, both message arrays and the beliefs, resident from set-up to clear.  Every device
+// array is on the ledger and listed in `owned`; the host keeps the sizes and the beliefs' offsets by internal id.
+struct NskBp {
+    bool ready = false;
+    nsk_bp_info info = {};
+    bool big = false;                  // a free variable of cardinality above NSK_ZLOCAL has an edge: wk exists
+    std::vector<long long> b_off;      // [nid + 1]
+    std::vector<void *> owned;
+    long long *pm_off = nullptr, *tab_off = nullptr, *msg_off = nullptr, *d_b_off = nullptr;
+    int32_t *slot_off = nullptr, *edge_off = nullptr, *e_fac = nullptr, *e_var = nullptr;
+    int32_t *v_list = nullptr, *v_eoff = nullptr, *v_edges = nullptr;
+    int32_t *mrec = nullptr, *slot_rec = nullptr;
+    uint8_t *v_state = nullptr;
+    double *theta = nullptr, *psi = nullptr, *f2v = nullptr, *v2f = nullptr, *belief = nullptr, *wk = nullptr;
+    int32_t nvlist = 0, nvbin = 0;     // free variables with an edge; the binary ones among them, first in v_list
+};
+
 // Boundary exchange, the collective path (nsk_exchange.hip: nsk_exchange_setup, nsk_comm_init, nsk_*_sweeps_exchange):
 // every rank packs the values its peers read into `send`, an all-gather -- the caller's, or RCCL's through `comm` --
 // fills `recv` with every rank's slot, and the unpack scatters them to the ghost ids.  The handle owns the seven
@@ -187,6 +205,7 @@ struct nsk_graph {
     NskTrace trace;
     NskEnergy energy;
     NskWstats wstats;
+    NskBp bp;
     // The segment launches (nsk_seg_plan.h), kept across calls (the N-rank loops sweep one epoch per call) together with
     // the options they were planned for; a call whose options differ plans again.  Learning: per Compiled::learn_seg entry.
     std::vector<nsk::LearnSegPlan> learn_seg_plans;

@@ -68,6 +68,12 @@ whatever the order -- and the weight update of maximum pseudo-likelihood learnin
 DESIGN.md section 4): the per-weight statistics summed over chains as int64 sums of quantised factor values, and the weight
 update of persistent contrastive divergence, one rounded operation each; ``pcd_latent_step`` is the update of
 ``learn_pcd(clamped=K)`` (nsk_pcd_latent_steps), whose target is the mean of a clamped population of chains.
+
+``bp_layout``, ``bp_psi``, ``bp_iterate`` and ``bp_factor_beliefs`` restate ``FactorGraph.belief_propagation``
+(nsk_bp_setup, nsk_bp_run, nsk_bp_download) operation by operation in plain loops: the structure of
+clamped and free variables, tables, directed edges and message offsets, the sum-product iterations with damping, the
+residual and the rescale rule, and the factor beliefs -- the device's doubles bit for bit when handed the library's exp.
+``bethe_log_z`` is the Bethe estimate of log Z from the beliefs, which needs a ``log`` and lives here.
 """
 
 import collections
@@ -906,3 +912,232 @@ def thermodynamic_integral(betas, lp, log_z0):
     b, u = _schedule(betas, lp, "thermodynamic_integral")
     mean = u.mean(axis=1)
     return float(log_z0) + float(np.sum(np.diff(b) * 0.5 * (mean[1:] + mean[:-1])))
+
+
+# ------------------------------------------------------------------------------------------------- belief propagation
+# member positions a function reads whatever its arity says (EQUAL 1, the DP_GEN_* functions 1 to 3)
+_BP_NEED = {3: 1, 18: 1, 19: 1, 20: 1, 30: 1, 21: 2, 22: 2, 25: 2, 26: 2, 23: 3, 24: 3}
+
+
+def bp_layout(factor, fmap, variable, values, sample_evidence=False):
+    """The structure ``FactorGraph.belief_propagation`` (nsk_bp_setup) builds for the state ``values``: a variable is
+    clamped at its value when ``isEvidence`` is 4, or non-zero without ``sample_evidence``, and free otherwise.  Per
+    factor, in order: ``members[f]`` its distinct members in order of first occurrence (none for NOOP), ``slots[f]`` the
+    local slot of every member position, ``axes[f]`` the free ones among the members, in that order -- the axes of the
+    factor's table, the first the most significant digit (C order) -- and ``shapes[f]`` their cardinalities.
+    ``table_off`` (nfactor + 1) the tables' entries, ``edge_off`` (nfactor + 1) the directed edges (f, j), factor-major,
+    ``edge_var`` their variables, ``msg_off`` (nedges + 1): edge e owns ``cardinality`` doubles at ``msg_off[e]`` in
+    either message array.  ``var_edges[v]`` the edges of a free variable, ascending.  ``offsets`` (nvar + 1) the "full"
+    layout of the beliefs.  A dict; ``clamped``, ``values`` and ``card`` are kept in it."""
+    values = np.asarray(values, np.int64)
+    ev = np.asarray(variable["isEvidence"])
+    card = np.asarray(variable["cardinality"]).astype(np.int64)
+    clamped = (ev == 4) | ((ev != 0) & (not sample_evidence))
+    vid = np.asarray(fmap["vid"]).astype(np.int64)
+    members, slots, axes, shapes = [], [], [], []
+    table_off, edge_off, edge_var, msg_off = [0], [0], [], [0]
+    var_edges = [[] for _ in range(len(card))]
+    for f in range(len(factor)):
+        fn, ar, s = int(factor[f]["factorFunction"]), int(factor[f]["arity"]), int(factor[f]["ftv_offset"])
+        npos = 0 if fn == -1 else max(ar, _BP_NEED.get(fn, 0))
+        mine, slot = [], []
+        for v in vid[s:s + npos]:
+            v = int(v)
+            if v not in mine:
+                mine.append(v)
+            slot.append(mine.index(v))
+        ax = [v for v in mine if not clamped[v]]
+        T = 1
+        for v in ax:
+            var_edges[v].append(len(edge_var))
+            edge_var.append(v)
+            msg_off.append(msg_off[-1] + int(card[v]))
+            T *= int(card[v])
+        members.append(mine)
+        slots.append(slot)
+        axes.append(ax)
+        shapes.append([int(card[v]) for v in ax])
+        table_off.append(table_off[-1] + T)
+        edge_off.append(len(edge_var))
+    i64 = lambda x: np.asarray(x, np.int64)             # noqa: E731
+    return {"members": members, "slots": slots, "axes": axes, "shapes": shapes, "table_off": i64(table_off),
+            "edge_off": i64(edge_off), "edge_var": i64(edge_var), "msg_off": i64(msg_off), "var_edges": var_edges,
+            "offsets": np.concatenate([[0], np.cumsum(card)]).astype(np.int64), "clamped": clamped, "values": values,
+            "card": card}
+
+
+def _bp_digits(a, shape):
+    out = [0] * len(shape)
+    for i in range(len(shape) - 1, -1, -1):
+        out[i] = a % shape[i]
+        a //= shape[i]
+    return out
+
+
+def _bp_rescale(v):
+    """while the largest entry is > 0 and < 2^-512: every entry times 2^512 (exact)"""
+    tiny, big = 2.0 ** -512, 2.0 ** 512
+    while True:
+        mx = v[0]
+        for x in v[1:]:
+            if x > mx:
+                mx = x
+        if not (mx > 0.0 and mx < tiny):
+            return v
+        v = [x * big for x in v]
+
+
+def _bp_sum(v):
+    z = v[0]
+    for x in v[1:]:
+        z = z + x
+    return z
+
+
+def bp_psi(layout, theta, exp=np.exp):
+    """``psi_f(a) = exp(theta_f(a) - max_a theta_f)`` for every table: the maximum by exact comparison (a NaN never
+    wins over the first entry), the subtraction rounded once."""
+    theta = np.asarray(theta, np.float64)
+    psi = np.zeros(len(theta))
+    to = layout["table_off"]
+    for f in range(len(to) - 1):
+        th = [float(x) for x in theta[to[f]:to[f + 1]]]
+        mx = th[0]
+        for x in th[1:]:
+            if x > mx:
+                mx = x
+        psi[to[f]:to[f + 1]] = exp(np.array([x - mx for x in th]))
+    return psi
+
+
+def bp_iterate(layout, theta, iters, damping=0.0, tol=0.0, exp=np.exp, messages=None):
+    """Sum-product belief propagation as nsk_bp_run performs it, in plain loops, operation by operation (the header
+    states the rule): up to ``iters`` iterations of the factor phase -- per edge (f, j) the sums over the table
+    entries of ``psi`` times the other axes' incoming messages, normalised in k order, damped with
+    ``(1 - damping) * new + damping * old``, the residual the largest change of a message entry, NaN counting as inf --
+    and the variable phase -- prefix products stored, the belief from the full product, suffix products multiplied in,
+    each vector rescaled by 2^512 while its largest entry is positive and below 2^-512.  The iterations stop behind the
+    first whose residual is ``<= tol``.  ``messages=(f2v, v2f)`` continues from those; None starts at ``1 / card``.
+    Returns a dict: ``f2v``, ``v2f``, ``beliefs`` (the "full" layout of ``layout["offsets"]``: a clamped variable's
+    indicator, a free variable's uniform law where it is in no table), ``residual`` (``iters`` entries, 0 behind the
+    stop), ``iters`` (the iterations run up to and including the first with residual <= tol; ``-iters`` without one),
+    ``psi`` and ``rescaled`` (how often the rescale rule fired)."""
+    to, eo, mo = layout["table_off"], layout["edge_off"], layout["msg_off"]
+    card, off = layout["card"], layout["offsets"]
+    psi = bp_psi(layout, theta, exp)
+    nmsg = int(mo[-1])
+    if messages is None:
+        f2v, v2f = np.zeros(nmsg), np.zeros(nmsg)
+        for e in range(len(mo) - 1):
+            f2v[mo[e]:mo[e + 1]] = v2f[mo[e]:mo[e + 1]] = 1.0 / float(mo[e + 1] - mo[e])
+    else:
+        f2v, v2f = (np.array(m, np.float64) for m in messages)
+    beliefs = np.zeros(int(off[-1]))
+    for v in range(len(card)):
+        if layout["clamped"][v]:
+            if 0 <= layout["values"][v] < card[v]:
+                beliefs[off[v] + layout["values"][v]] = 1.0
+        else:
+            beliefs[off[v]:off[v + 1]] = 1.0 / float(card[v])
+    lam, oml = float(damping), 1.0 - float(damping)
+    residual = np.zeros(iters)
+    ran, fired = -iters, 0
+    count = [0]
+
+    def rescale(v):
+        w = _bp_rescale(v)
+        if w is not v:
+            count[0] += 1
+        return w
+
+    for t in range(iters):
+        if t > 0 and residual[t - 1] <= tol:
+            break
+        res = 0.0
+        new = f2v.copy()
+        for f in range(len(to) - 1):
+            shape = layout["shapes"][f]
+            e0 = int(eo[f])
+            for j in range(len(shape)):
+                m = [0.0] * shape[j]
+                for a in range(int(to[f + 1] - to[f])):
+                    d = _bp_digits(a, shape)
+                    x = float(psi[to[f] + a])
+                    for i in range(len(shape)):
+                        if i != j:
+                            x = x * float(v2f[mo[e0 + i] + d[i]])
+                    m[d[j]] = m[d[j]] + x
+                z = _bp_sum(m)
+                with np.errstate(all="ignore"):
+                    for k in range(shape[j]):
+                        nw = float(np.float64(m[k]) / np.float64(z))
+                        old = float(f2v[mo[e0 + j] + k])
+                        if lam > 0.0:
+                            nw = oml * nw + lam * old
+                        new[mo[e0 + j] + k] = nw
+                        dd = abs(nw - old)
+                        res = max(res, dd if dd == dd else np.inf)
+        f2v = new
+        residual[t] = res
+        with np.errstate(all="ignore"):
+            for v in range(len(card)):
+                edges = layout["var_edges"][v]
+                if layout["clamped"][v] or not edges:
+                    continue
+                n = int(card[v])
+                P = [1.0] * n
+                for e in edges:
+                    v2f[mo[e]:mo[e + 1]] = P
+                    P = rescale([P[k] * float(f2v[mo[e] + k]) for k in range(n)])
+                z = np.float64(_bp_sum(P))
+                beliefs[off[v]:off[v + 1]] = [np.float64(p) / z for p in P]
+                S = [1.0] * n
+                for e in reversed(edges):
+                    T = rescale([float(v2f[mo[e] + k]) * S[k] for k in range(n)])
+                    zt = np.float64(_bp_sum(T))
+                    v2f[mo[e]:mo[e + 1]] = [np.float64(x) / zt for x in T]
+                    S = rescale([S[k] * float(f2v[mo[e] + k]) for k in range(n)])
+        if ran < 0 and res <= tol:
+            ran = t + 1
+    fired = count[0]
+    return {"f2v": f2v, "v2f": v2f, "beliefs": beliefs, "residual": residual, "iters": ran, "psi": psi, "rescaled": fired}
+
+
+def bp_factor_beliefs(layout, psi, v2f):
+    """``b_f(a) = psi_f(a) * v2f[(f, 0)][a_0] * ..`` over the axes ascending, divided by their a-ordered sum; the
+    layout of ``table_off`` (nsk_bp_download, NSK_BP_FACTOR_BELIEFS)."""
+    to, eo, mo = layout["table_off"], layout["edge_off"], layout["msg_off"]
+    out = np.zeros(int(to[-1]))
+    for f in range(len(to) - 1):
+        shape = layout["shapes"][f]
+        b = []
+        for a in range(int(to[f + 1] - to[f])):
+            d = _bp_digits(a, shape)
+            x = float(psi[to[f] + a])
+            for i in range(len(shape)):
+                x = x * float(v2f[mo[int(eo[f]) + i] + d[i]])
+            b.append(x)
+        with np.errstate(all="ignore"):
+            z = np.float64(_bp_sum(b))
+            out[to[f]:to[f + 1]] = [np.float64(x) / z for x in b]
+    return out
+
+
+def bethe_log_z(layout, theta, factor_beliefs, beliefs):
+    """The Bethe estimate of log Z from the beliefs of a belief-propagation run: the sum over factors and table entries
+    of ``b_f (theta_f - log b_f)``, plus the sum over free variables of ``(d_v - 1) sum_k b_v log b_v`` with ``d_v`` the
+    variable's edges, plus ``log cardinality`` for every free variable without an edge; ``0 log 0 = 0``.  Exact where
+    the free part of the graph is a forest and the run has converged.  Of ``layout`` it reads ``card``, ``clamped`` (per
+    variable) and ``edge_var`` (nsk_bp_layout gives the same); ``beliefs`` is in the "full" layout over all variables."""
+    theta = np.asarray(theta, np.float64)
+    fb = np.asarray(factor_beliefs, np.float64)
+    b = np.asarray(beliefs, np.float64)
+    card, clamped = np.asarray(layout["card"], np.int64), np.asarray(layout["clamped"], bool)
+    deg = np.bincount(np.asarray(layout["edge_var"], np.int64), minlength=len(card))
+    with np.errstate(divide="ignore", invalid="ignore"):
+        total = float(np.sum(np.where(fb > 0, fb * (theta - np.log(fb)), 0.0)))
+        h = np.bincount(np.repeat(np.arange(len(card)), card), weights=np.where(b > 0, b * np.log(b), 0.0), minlength=len(card))
+    walked = ~clamped & (deg > 0)
+    total += float(np.sum((deg[walked] - 1) * h[walked]))
+    total += float(np.sum(np.log(card[~clamped & (deg == 0)].astype(np.float64))))
+    return total

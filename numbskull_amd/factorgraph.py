@@ -1408,6 +1408,57 @@ class FactorGraph(object):
         _lib.check(L.nsk_weight_stats(h, _lib.BUF_VALUE_EVID if evidence_chain else _lib.BUF_VALUE, 0, 1, scaled, _lib.ptr(out)))
         return out
 
+    # ------------------------------------------------------------------ belief propagation
+    def belief_propagation(self, max_iters=100, damping=0.0, tol=1e-9, var_copy=0, weight_copy=0, evidence_chain=False,
+                           sample_evidence=False, factor_beliefs=False):
+        """Loopy belief propagation on the device (nsk_bp_setup / nsk_bp_run): sum-product message passing, every factor
+        and every variable updated once per iteration -- deterministic inference beside the sampler.  The variables with
+        ``isEvidence != 0`` are clamped at their values in ``var_value[var_copy]`` (``var_value_evid[var_copy]`` with
+        ``evidence_chain=True``) unless ``sample_evidence``; state and ``weight_value[weight_copy]`` are pushed as
+        ``log_potential`` pushes them, and nothing of the graph changes.  Exact where the free variables form a forest;
+        on a graph with cycles the beliefs and ``log_z`` (the Bethe estimate) are approximations and the iteration may
+        not converge: raise ``damping`` (in [0, 1)) then, and read ``converged``.  At most ``max_iters`` (1 .. 4096)
+        iterations; they stop behind the first whose largest message change is ``<= tol``.  A factor takes part with
+        at most 16 distinct members and 4096 table entries over its free members; UFO and, without ``head_by_vid``, the
+        IMPLY_MLN-type factors are refused (ValueError naming the factor).  Two hard constraints that contradict each
+        other give NaN, as in ``conditionals``.  ``diagnostics.bp_iterate`` is the rule in numpy.
+        Returns a dict: ``offsets``, ``beliefs`` -- the layout of ``conditionals`` over all variables
+        (``diagnostics.tally_layout`` converts to that of ``count``); ``iters``, ``converged``, ``residual`` (float64
+        ``(max_iters,)``, 0 behind the stop); ``log_z``; with ``factor_beliefs=True`` also ``table_offsets``
+        (nfactor + 1), ``theta`` and ``factor_beliefs``."""
+        from .diagnostics import bethe_log_z
+        max_iters = int(max_iters)
+        if max_iters < 1 or max_iters > 4096:
+            raise ValueError("belief_propagation: max_iters must lie in [1, 4096]")
+        if _all_copies(var_copy):
+            raise ValueError('belief_propagation serves one state: var_copy="all" is for the sampler')
+        L, h = _lib.lib(), self._engine()
+        self._push(var_copy, weight_copy)
+        info = _lib.BpInfo()
+        _lib.check(L.nsk_bp_setup(h, _lib.BUF_VALUE_EVID if evidence_chain else _lib.BUF_VALUE, 0, int(bool(sample_evidence)),
+                                  C.byref(info)))
+        try:
+            iters, residual = C.c_int64(0), np.zeros(max_iters, np.float64)
+            _lib.check(L.nsk_bp_run(h, max_iters, float(damping), float(tol), C.byref(iters), _lib.ptr(residual)))
+            _, offsets = self._cond_selection(None, None, "belief_propagation")
+            beliefs = np.zeros(int(offsets[-1]), np.float64)
+            _lib.check(L.nsk_bp_beliefs(h, None, 0, _lib.ptr(beliefs)))
+            theta, fb = np.zeros(info.ntable, np.float64), np.zeros(info.ntable, np.float64)
+            _lib.check(L.nsk_bp_download(h, _lib.BP_THETA, _lib.ptr(theta)))
+            _lib.check(L.nsk_bp_download(h, _lib.BP_FACTOR_BELIEFS, _lib.ptr(fb)))
+            table_off, edge_var = np.zeros(self.factor.shape[0] + 1, np.int64), np.zeros(info.nedges, np.int64)
+            _lib.check(L.nsk_bp_layout(h, _lib.ptr(table_off), None, _lib.ptr(edge_var), None))
+        finally:
+            L.nsk_bp_clear(h)
+        ev = self.variable["isEvidence"]
+        layout = {"card": self.variable["cardinality"].astype(np.int64), "edge_var": edge_var,
+                  "clamped": (ev == 4) | ((ev != 0) & (not sample_evidence))}
+        out = {"offsets": offsets, "beliefs": beliefs, "iters": abs(int(iters.value)), "converged": bool(iters.value > 0),
+               "residual": residual, "log_z": bethe_log_z(layout, theta, fb, beliefs)}
+        if factor_beliefs:
+            out.update(table_offsets=table_off, theta=theta, factor_beliefs=fb)
+        return out
+
     # ------------------------------------------------------------------ log-potential
     def log_potential(self, var_copy=0, weight_copy=0, evidence_chain=False):
         """The unnormalised log-probability of a state: the sum over all factors of weight x factor value, evaluated
