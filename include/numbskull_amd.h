@@ -327,7 +327,7 @@ int nsk_icm(nsk_graph *g, int which, int64_t first_chain, int64_t nchains, int64
  * Run, beliefs, layout and download without a set-up are NSK_E_INVALID.  `which` and the handles refused follow
  * nsk_log_potential; a tally kept in the value bytes is first brought back to its array, as in nsk_icm.  Nothing of the
  * handle changes: values, tallies, weights and the generator stay.  The set-up is resident and counted in
- * nsk_graph_info.device_bytes: 16 bytes a table entry, 16 a message entry + 20 an edge, 8 a member position + 8 a distinct
+ * nsk_graph_info.device_bytes: 24 bytes a table entry (theta, psi and the feature table below), 16 a message entry + 20 an edge, 8 a member position + 8 a distinct
  * member, 24 a factor, 17 a variable + 8 a value (16 where a free variable of cardinality above 16 has an edge); NSK_E_NOMEM names the
  * bytes.  nsk_profile_* keeps counting sweep-kernel launches only.  (Diagnostic, NSK_DIAG=1 NSK_BP_GRID_CAP=blocks,
  * read at each call: caps every grid of these calls, so that small graphs run the later trips of the lanes' loops.) */
@@ -349,6 +349,56 @@ int nsk_bp_run(nsk_graph *g, int64_t max_iters, double damping, double tol, int6
 int nsk_bp_beliefs(nsk_graph *g, const int64_t *vids, int64_t nvids, double *out /* total */);
 int nsk_bp_download(nsk_graph *g, int what, double *out);
 int nsk_bp_clear(nsk_graph *g);
+
+/* Learning by belief propagation (FactorGraph.bp_weight_moments / learn_bp): maximum-likelihood learning whose model
+ * expectations come from the factor beliefs of the resident set-up above instead of from chains -- exact wherever BP is
+ * exact (the free variables form a forest), the Bethe approximation on graphs with cycles, without sampling noise.
+ * Every call here acts on the resident set-up and is NSK_E_INVALID without one, as nsk_bp_run is.
+ * Feature table: feat_f(a) = eval_factor exactly as the set-up asks it for theta_f(a), without the weight, so that
+ * theta_f(a) = w[weight of f] * feat_f(a) is ONE rounded product and reproduces the set-up's own theta bit for bit.  The
+ * set-up fills it in the launch that fills theta (no further launch), owns it (nsk_bp_clear and a replacing set-up free
+ * it) and counts its 8 bytes a table entry among its bytes above.
+ * nsk_bp_refresh: theta[i] = w[slot] * feat[i] from the device weight table as it stands, then psi as the set-up forms
+ *   it; messages and beliefs stay.  How a caller continues nsk_bp_run after uploading new weights (enqueued; no wait).
+ * nsk_bp_moments: the expected per-weight statistics under the factor beliefs, in the int64 fixed point of
+ *   nsk_weight_moments.  Per factor f, x(a) = (psi_f(a) * v2f[(f,0)][a_0]) * .. and Z_f = their a-ordered sum, exactly as
+ *   the factor beliefs above form them.  A factor whose Z_f is not a finite positive number (two hard constraints that
+ *   contradict each other: NaN) is SKIPPED: it adds nothing and counts one in *skipped (may be NULL).  Otherwise per entry
+ *     b = x(a) / Z_f            the very bits of NSK_BP_FACTOR_BELIEFS
+ *     p = b * feat_f(a)         one rounded product
+ *     q = p * 2^32 rounded to the nearest int64, ties to even (numpy: np.rint(p * 2.0**32).astype(np.int64))
+ *     M[weight of f] += q       int64: the order of execution is free
+ *   M_w * 2^-32 is E_b[S_w] to within 2^-33 per table entry.  A factor without a free member (T_f = 1) contributes
+ *   rint(e * 2^32): where every variable is clamped M equals nsk_weight_moments of that state integer for integer.
+ *   moments[nweight] in the caller's weight ids; a weight without a factor reads 0.  NSK_E_RANGE: the rule of
+ *   nsk_weight_moments with nchains = 1 (|b * feat| <= vmax(f)).  numbskull_amd.diagnostics.bp_moment_counts is the rule
+ *   in numpy.  The sums, the counter and Z_f (8 bytes a factor) live for the call only.
+ * nsk_bp_learn_steps: for t = 0 .. nsteps - 1, on the handle's stream without a host wait:
+ *   1. nsk_bp_refresh; with warm == 0 also every message back to 1 / card;
+ *   2. up to iters_per_step iterations exactly as nsk_bp_run enqueues them, with row t of the residuals: the early exit
+ *      applies inside the row, iteration 0 of every step always runs;
+ *   3. zero M and the skip counter, then the launches of nsk_bp_moments;
+ *   4. nsk_pcd_steps' update launch with one chain (a division by 1.0 is exact): target, n_w, step_t = step * decay^t
+ *      formed on the host in t order, reg_param and normalize as there; numbskull_amd.diagnostics.pcd_step with R = 1.
+ *   After the last step one more refresh, so that the resident tables agree with the device weights and a following
+ *   nsk_bp_run continues under the learned weights; then the call synchronises, once.  gmax[t] and moments[t * nweight
+ *   + w] are what nsk_pcd_steps defines; iters[t] follows nsk_bp_run (negative: the step's iterations did not reach tol);
+ *   residual[t * iters_per_step + i]; skipped[t].  Each output may be NULL.  The weights on the device change (fixed
+ *   weights stay; the next sweep call rebuilds what derives from them); values, tallies, sweeps_done, the generator and
+ *   the trace stay.  NSK_E_INVALID, before anything is allocated or enqueued: no set-up, a null target or a target entry
+ *   that is not finite, nsteps or iters_per_step outside [1, 4096], nsteps x iters_per_step > 65536, damping or tol
+ *   outside what nsk_bp_run accepts, warm or normalize other than 0 or 1, a step, decay or reg_param that is not
+ *   finite, reg_param < 0.  NSK_E_RANGE as nsk_bp_moments.  nweight == 0 is NSK_OK with nothing done.  The sums, the
+ *   target, the factor counts, Z_f and the per-step outputs live for the call only; NSK_E_NOMEM names the bytes.
+ * Latent-variable learning needs the difference of two set-ups (evidence clamped and free) and is not served here:
+ * nsk_pcd_latent_steps does that with chains.  Every launch honours NSK_BP_GRID_CAP. */
+int nsk_bp_refresh(nsk_graph *g);
+int nsk_bp_moments(nsk_graph *g, int64_t *moments /* nweight */, int64_t *skipped /* may be NULL */);
+int nsk_bp_learn_steps(nsk_graph *g, const double *target /* nweight, caller's ids */,
+                       int64_t nsteps, int64_t iters_per_step, double damping, double tol, int warm,
+                       double step, double decay, double reg_param, int normalize,
+                       double *gmax /* nsteps */, int64_t *iters /* nsteps */, double *residual /* nsteps x iters_per_step */,
+                       int64_t *moments /* nsteps x nweight */, int64_t *skipped /* nsteps */);
 
 /* Pseudo-likelihood gradient and maximum pseudo-likelihood learning (FactorGraph.pl_gradient / learn_mple): the
  * derivative of sum_v log P(x_v | every other variable) over a selection of variables with respect to every weight, and

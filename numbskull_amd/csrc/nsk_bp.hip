@@ -3,12 +3,18 @@
 // directed edges, the per-variable edge lists), uploads it and fills the tables; nsk_bp_run enqueues every iteration on
 // the handle's stream without a synchronisation between them -- once the residual is at or below the tolerance the later
 // launches end on the device -- and copies the residuals back once.  The launches are not counted by the profiling bracket.
+// Learning by BP on the resident set-up: nsk_bp_refresh rewrites theta and psi from the device weights through the feature
+// table the set-up keeps, nsk_bp_moments reduces the expected per-weight statistics under the factor beliefs in int64 fixed
+// point, and nsk_bp_learn_steps enqueues (refresh, iterations, moments, nsk_pcd.hip's update with one chain) per step
+// without a host wait, as nsk_pcd_steps does; the sums, the target and the per-step outputs live for the call only.
 #include <hip/hip_runtime.h>
 
+#include <cmath>
 #include <cstring>
 
 #include "nsk_internal.h"
 #include "nsk_kernels_bp.h"
+#include "nsk_kernels_pcd.h"     // k_pcd_update
 
 using namespace nsk;
 
@@ -38,7 +44,7 @@ static BpArgs bp_args(const nsk_graph *g) {
     a.v_list = b.v_list; a.v_eoff = b.v_eoff; a.v_edges = b.v_edges;
     a.b_off = b.d_b_off; a.v_state = b.v_state; a.v_card = g->v_card;
     a.w = g->w; a.logtab = g->logtab;
-    a.theta = b.theta; a.psi = b.psi; a.f2v = b.f2v; a.v2f = b.v2f; a.belief = b.belief; a.wk = b.wk;
+    a.theta = b.theta; a.psi = b.psi; a.f2v = b.f2v; a.v2f = b.v2f; a.belief = b.belief; a.wk = b.wk; a.feat = b.feat;
     a.nfactor = (long long)g->c.nfactor; a.ntable = (long long)b.info.ntable; a.nid = (long long)g->c.nid;
     a.nedge = (int32_t)b.info.nedges; a.nvlist = b.nvlist;
     return a;
@@ -73,6 +79,60 @@ static int bp_common(nsk_graph *g, const char *what, bool need_setup) {
     if (rc) return rc;
     if (need_setup && !g->bp.ready) return fail(NSK_E_INVALID, std::string(what) + ": no belief propagation is set up (nsk_bp_setup)");
     return NSK_OK;
+}
+
+// theta and psi from the device weight table as it stands; messages and beliefs stay
+static void bp_refresh_enqueue(nsk_graph *g, const BpArgs &a) {
+    if (a.nfactor == 0) return;
+    k_bp_refresh<<<dim3(bp_blocks(a.ntable)), dim3(NSK_BLOCK), 0, g->stream>>>(a);
+    k_bp_psi<<<dim3(bp_blocks(a.nfactor)), dim3(NSK_BLOCK), 0, g->stream>>>(a);
+}
+
+// max_iters iterations as nsk_bp_run enqueues them, the residuals at res[0 .. max_iters)
+static hipError_t bp_iterations_enqueue(nsk_graph *g, const BpArgs &a, size_t max_iters, double damping, double tol, unsigned long long *res) {
+    const double oml = 1.0 - damping;
+    const int nbin = g->bp.nvbin, nall = a.nvlist;
+    const dim3 block(NSK_BLOCK), gf(bp_blocks(a.nedge)), vblock(NSK_BP_VAR_BLOCK),
+               gb(bp_blocks(nbin, NSK_BP_VAR_BLOCK)), gr(bp_blocks(nall - nbin, NSK_BP_VAR_BLOCK));
+    hipError_t e = hipSuccess;
+    if (a.nedge > 0)
+        for (size_t t = 0; t < max_iters && e == hipSuccess; t++) {
+            k_bp_factor<<<gf, block, 0, g->stream>>>(a, (int)t, tol, damping, oml, res);
+            if (nbin > 0) k_bp_var<true><<<gb, vblock, 0, g->stream>>>(a, 0, nbin, (int)t, tol, res);
+            if (nall > nbin) k_bp_var<false><<<gr, vblock, 0, g->stream>>>(a, nbin, nall, (int)t, tol, res);
+            e = hipGetLastError();
+        }
+    return e;
+}
+
+// zero the sums and the skip counter, then Z_f of every factor and the moment launch
+static hipError_t bp_moments_enqueue(nsk_graph *g, const BpArgs &a, double *zf, unsigned long long *M, unsigned long long *skipped) {
+    hipError_t e = hipMemsetAsync(M, 0, (size_t)std::max<int64_t>(1, g->c.nweight) * sizeof(unsigned long long), g->stream);
+    if (e == hipSuccess) e = hipMemsetAsync(skipped, 0, sizeof(unsigned long long), g->stream);
+    if (e != hipSuccess || a.nfactor == 0) return e;
+    k_bp_fnorm<<<dim3(bp_blocks(a.nfactor)), dim3(NSK_BLOCK), 0, g->stream>>>(a, zf, skipped);
+    k_bp_moments<<<dim3(bp_blocks(a.ntable)), dim3(NSK_BLOCK), 0, g->stream>>>(a, zf, M);
+    return hipGetLastError();
+}
+
+// the device buffers of one call: entered in the ledger, gone when the call returns
+struct BpLearnBufs {
+    nsk_graph *g;
+    unsigned long long *M = nullptr, *skipped = nullptr, *gmax = nullptr, *res = nullptr;
+    double *zf = nullptr, *target = nullptr, *nfac = nullptr;
+    long long *rows = nullptr;
+    explicit BpLearnBufs(nsk_graph *g_) : g(g_) {}
+    ~BpLearnBufs() {
+        dev_free(g, rows); dev_free(g, nfac); dev_free(g, target); dev_free(g, zf);
+        dev_free(g, res); dev_free(g, gmax); dev_free(g, skipped); dev_free(g, M);
+    }
+};
+
+template <typename T>
+static int bp_call_alloc(nsk_graph *g, T **ptr, size_t n, const char *who, const char *what) {
+    const int rc = dev_alloc(g, ptr, n);
+    if (rc != NSK_E_NOMEM) return rc;
+    return fail(NSK_E_NOMEM, std::string(who) + ": " + what + " (" + std::to_string((long long)((n ? n : 1) * sizeof(T))) + " bytes) do not fit on the device");
 }
 
 extern "C" {
@@ -195,7 +255,7 @@ int nsk_bp_setup(nsk_graph *g, int which, int64_t chain, int sample_evidence, ns
     NskBp &b = g->bp;
     b.big = nb.big; b.b_off.swap(nb.b_off); b.info = info; b.nvlist = (int32_t)v_list.size(); b.nvbin = nb.nvbin;
     const int64_t before = g->mem.total;
-    const double bytes = 16.0 * (double)info.ntable + 16.0 * (double)info.nmsg + 20.0 * (double)E + 8.0 * (double)(mrec.size() / 2) +
+    const double bytes = 24.0 * (double)info.ntable + 16.0 * (double)info.nmsg + 20.0 * (double)E + 8.0 * (double)(mrec.size() / 2) +
                          8.0 * (double)(slot_rec.size() / 2) + 24.0 * (double)F + 17.0 * (double)nid + (b.big ? 16.0 : 8.0) * (double)info.nbelief;
     rc = bp_upload(g, &b.pm_off, pm_off);
     if (!rc) rc = bp_upload(g, &b.tab_off, tab_off);
@@ -213,6 +273,7 @@ int nsk_bp_setup(nsk_graph *g, int which, int64_t chain, int sample_evidence, ns
     if (!rc) rc = bp_upload(g, &b.v_state, state);
     if (!rc) rc = bp_alloc(g, &b.theta, (size_t)info.ntable);
     if (!rc) rc = bp_alloc(g, &b.psi, (size_t)info.ntable);
+    if (!rc) rc = bp_alloc(g, &b.feat, (size_t)info.ntable);
     if (!rc) rc = bp_alloc(g, &b.f2v, (size_t)info.nmsg);
     if (!rc) rc = bp_alloc(g, &b.v2f, (size_t)info.nmsg);
     if (!rc) rc = bp_alloc(g, &b.belief, (size_t)info.nbelief);
@@ -289,18 +350,7 @@ int nsk_bp_run(nsk_graph *g, int64_t max_iters, double damping, double tol, int6
         return fail(NSK_E_NOMEM, "nsk_bp_run: the residuals (" + std::to_string((long long)(S * 8)) + " bytes) do not fit on the device");
     }
     hipError_t e = hipMemsetAsync(res, 0, S * 8, g->stream);
-    const BpArgs a = bp_args(g);
-    const double oml = 1.0 - damping;
-    const int nbin = g->bp.nvbin, nall = a.nvlist;
-    const dim3 block(NSK_BLOCK), gf(bp_blocks(a.nedge)), vblock(NSK_BP_VAR_BLOCK),
-               gb(bp_blocks(nbin, NSK_BP_VAR_BLOCK)), gr(bp_blocks(nall - nbin, NSK_BP_VAR_BLOCK));
-    if (a.nedge > 0)
-        for (size_t t = 0; t < S && e == hipSuccess; t++) {
-            k_bp_factor<<<gf, block, 0, g->stream>>>(a, (int)t, tol, damping, oml, res);
-            if (nbin > 0) k_bp_var<true><<<gb, vblock, 0, g->stream>>>(a, 0, nbin, (int)t, tol, res);
-            if (nall > nbin) k_bp_var<false><<<gr, vblock, 0, g->stream>>>(a, nbin, nall, (int)t, tol, res);
-            e = hipGetLastError();
-        }
+    if (e == hipSuccess) e = bp_iterations_enqueue(g, bp_args(g), S, damping, tol, res);
     std::vector<double> host(S);
     if (e == hipSuccess) e = hipMemcpyAsync(host.data(), res, S * 8, hipMemcpyDeviceToHost, g->stream);
     const hipError_t e2 = hipStreamSynchronize(g->stream);
@@ -366,6 +416,138 @@ int nsk_bp_download(nsk_graph *g, int what, double *out) {
     dev_free(g, fb);
     HIPCHECK(e);
     HIPCHECK(e2);
+    return NSK_OK;
+}
+
+int nsk_bp_refresh(nsk_graph *g) {
+    int rc = bp_common(g, "nsk_bp_refresh", true);
+    if (rc) return rc;
+    HIPCHECK(hipSetDevice(g->device));
+    bp_refresh_enqueue(g, bp_args(g));
+    HIPCHECK(hipGetLastError());
+    return NSK_OK;
+}
+
+int nsk_bp_moments(nsk_graph *g, int64_t *moments, int64_t *skipped) {
+    const char *who = "nsk_bp_moments";
+    int rc = bp_common(g, who, true);
+    if (rc) return rc;
+    const Compiled &c = g->c;
+    const size_t nw = (size_t)c.nweight;
+    if (nw == 0) return NSK_OK;
+    if (!moments) return fail(NSK_E_INVALID, "null argument");
+    if ((rc = nsk_moments_range(g, 1, who))) return rc;
+    HIPCHECK(hipSetDevice(g->device));
+    BpLearnBufs b(g);
+    rc = bp_call_alloc(g, &b.M, nw, who, "the int64 sums, 8 bytes a weight");
+    if (!rc) rc = bp_call_alloc(g, &b.skipped, 1, who, "the skip counter");
+    if (!rc) rc = bp_call_alloc(g, &b.zf, (size_t)g->bp.info.nfactor, who, "the factors' normalisers, 8 bytes a factor");
+    if (rc) return rc;
+    std::vector<long long> host(nw);
+    unsigned long long hskip = 0;
+    hipError_t e = bp_moments_enqueue(g, bp_args(g), b.zf, b.M, b.skipped);
+    if (e == hipSuccess) e = hipMemcpyAsync(host.data(), b.M, nw * sizeof(long long), hipMemcpyDeviceToHost, g->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(&hskip, b.skipped, sizeof(hskip), hipMemcpyDeviceToHost, g->stream);
+    const hipError_t e2 = hipStreamSynchronize(g->stream);
+    HIPCHECK(e);
+    HIPCHECK(e2);
+    // slots -> the caller's weight ids, as nsk_weight_moments maps them
+    const int32_t *wmap = c.wmap.empty() ? nullptr : c.wmap.data();
+    for (size_t i = 0; i < nw; i++) moments[i] = (int64_t)host[wmap ? (size_t)wmap[i] : i];
+    if (skipped) *skipped = (int64_t)hskip;
+    return NSK_OK;
+}
+
+int nsk_bp_learn_steps(nsk_graph *g, const double *target, int64_t nsteps, int64_t iters_per_step, double damping, double tol, int warm,
+                       double step, double decay, double reg_param, int normalize, double *gmax, int64_t *iters, double *residual,
+                       int64_t *moments, int64_t *skipped) {
+    const char *who = "nsk_bp_learn_steps";
+    int rc = bp_common(g, who, true);
+    if (rc) return rc;
+    if (!target) return fail(NSK_E_INVALID, "null argument");
+    if (nsteps < 1 || nsteps > 4096) return fail(NSK_E_INVALID, "nsk_bp_learn_steps: nsteps must lie in [1, 4096]");
+    if (iters_per_step < 1 || iters_per_step > 4096) return fail(NSK_E_INVALID, "nsk_bp_learn_steps: iters_per_step must lie in [1, 4096]");
+    if (nsteps * iters_per_step > 65536) return fail(NSK_E_INVALID, "nsk_bp_learn_steps: nsteps x iters_per_step must be at most 65536");
+    if (!(damping >= 0.0 && damping < 1.0)) return fail(NSK_E_INVALID, "nsk_bp_learn_steps: damping must lie in [0, 1)");
+    if (!(tol >= 0.0)) return fail(NSK_E_INVALID, "nsk_bp_learn_steps: tol must be at least 0");
+    if ((warm != 0 && warm != 1) || (normalize != 0 && normalize != 1)) return fail(NSK_E_INVALID, "nsk_bp_learn_steps: warm and normalize must be 0 or 1");
+    if (!std::isfinite(step) || !std::isfinite(decay) || !std::isfinite(reg_param) || reg_param < 0.0)
+        return fail(NSK_E_INVALID, "nsk_bp_learn_steps: step, decay and reg_param must be finite, reg_param not negative");
+    const Compiled &c = g->c;
+    const size_t nw = (size_t)c.nweight, T = (size_t)nsteps, I = (size_t)iters_per_step;
+    for (size_t i = 0; i < nw; i++)
+        if (!std::isfinite(target[i])) return fail(NSK_E_INVALID, "nsk_bp_learn_steps: the target of weight " + std::to_string((long long)i) + " is not finite");
+    if (nw == 0) return NSK_OK;
+    if ((rc = nsk_moments_range(g, 1, who))) return rc;
+    HIPCHECK(hipSetDevice(g->device));
+
+    // the target and the factor counts by slot (w_fixed is by slot too), as nsk_pcd_steps has them
+    const int32_t *wmap = c.wmap.empty() ? nullptr : c.wmap.data();
+    std::vector<double> tgt(nw), nfac(nw, 0.0);
+    for (size_t i = 0; i < nw; i++) tgt[wmap ? (size_t)wmap[i] : i] = target[i];
+    for (size_t f = 0; f < (size_t)c.nfactor; f++) nfac[(size_t)c.f_rec[4 * f + 2]] += 1.0;
+    for (size_t s = 0; s < nw; s++) if (nfac[s] == 0.0) nfac[s] = 1.0;
+    BpLearnBufs b(g);
+    rc = bp_call_alloc(g, &b.M, nw, who, "the int64 sums, 8 bytes a weight");
+    if (!rc) rc = bp_call_alloc(g, &b.skipped, T, who, "the skip counters, 8 bytes a step");
+    if (!rc) rc = bp_call_alloc(g, &b.zf, (size_t)g->bp.info.nfactor, who, "the factors' normalisers, 8 bytes a factor");
+    if (!rc) rc = bp_call_alloc(g, &b.target, nw, who, "the target, 8 bytes a weight");
+    if (!rc) rc = bp_call_alloc(g, &b.nfac, nw, who, "the factor counts, 8 bytes a weight");
+    if (!rc) rc = bp_call_alloc(g, &b.gmax, T, who, "the largest gradients, 8 bytes a step");
+    if (!rc) rc = bp_call_alloc(g, &b.res, T * I, who, "the residuals, nsteps x iters_per_step doubles");
+    if (!rc && moments) rc = bp_call_alloc(g, &b.rows, T * nw, who, "the kept moments, nsteps x nweight int64");
+    if (rc) return rc;
+    hipError_t e = hipMemcpyAsync(b.target, tgt.data(), nw * sizeof(double), hipMemcpyHostToDevice, g->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(b.nfac, nfac.data(), nw * sizeof(double), hipMemcpyHostToDevice, g->stream);
+    if (e == hipSuccess) e = hipMemsetAsync(b.gmax, 0, T * sizeof(unsigned long long), g->stream);
+    if (e == hipSuccess) e = hipMemsetAsync(b.res, 0, T * I * sizeof(unsigned long long), g->stream);
+    if (e != hipSuccess) { (void)hipStreamSynchronize(g->stream); HIPCHECK(e); }
+
+    const BpArgs a = bp_args(g);
+    const unsigned wblocks = (unsigned)((nw + NSK_BLOCK - 1) / NSK_BLOCK);
+    double st = step;           // step_0 = step, step_{t+1} = step_t * decay: the products are formed here, in t order
+    for (size_t t = 0; t < T && e == hipSuccess; t++) {
+        // 1. the tables under the weights as they stand; a cold start resets the messages
+        bp_refresh_enqueue(g, a);
+        if (!warm && a.nedge > 0) k_bp_reset<<<dim3(bp_blocks(a.nedge)), dim3(NSK_BLOCK), 0, g->stream>>>(a);
+        if ((e = hipGetLastError()) != hipSuccess) break;
+        // 2. the iterations, the early exit inside the step's own row of residuals
+        if ((e = bp_iterations_enqueue(g, a, I, damping, tol, b.res + t * I)) != hipSuccess) break;
+        // 3. the Bethe moments
+        if ((e = bp_moments_enqueue(g, a, b.zf, b.M, b.skipped + t)) != hipSuccess) break;
+        // 4. the update: nsk_pcd_steps' with one chain
+        k_pcd_update<<<dim3(wblocks), dim3(NSK_BLOCK), 0, g->stream>>>((const long long *)b.M, b.target, b.nfac, 1.0, (int)nw, g->w, g->w_fixed,
+                                                                      normalize, st, reg_param, b.gmax + t, b.rows ? b.rows + t * nw : nullptr);
+        e = hipGetLastError();
+        g->weights_dirty = true;            // the next sweep call rebuilds what derives from the weights
+        st = st * decay;
+    }
+    // the resident tables agree with the learned weights: a following nsk_bp_run continues under them
+    if (e == hipSuccess) { bp_refresh_enqueue(g, a); e = hipGetLastError(); }
+    std::vector<unsigned long long> hmax(T), hskip(T);
+    std::vector<double> hres(T * I);
+    std::vector<long long> hrows(b.rows ? T * nw : 0);
+    const bool ok = e == hipSuccess;
+    if (ok) e = hipMemcpyAsync(hmax.data(), b.gmax, T * 8, hipMemcpyDeviceToHost, g->stream);
+    if (ok && e == hipSuccess) e = hipMemcpyAsync(hskip.data(), b.skipped, T * 8, hipMemcpyDeviceToHost, g->stream);
+    if (ok && e == hipSuccess) e = hipMemcpyAsync(hres.data(), b.res, T * I * 8, hipMemcpyDeviceToHost, g->stream);
+    if (ok && b.rows && e == hipSuccess) e = hipMemcpyAsync(hrows.data(), b.rows, T * nw * sizeof(long long), hipMemcpyDeviceToHost, g->stream);
+    const hipError_t e2 = hipStreamSynchronize(g->stream);      // (also: the uploads read the host vectors)
+    HIPCHECK(e);
+    HIPCHECK(e2);
+    if (gmax) std::memcpy(gmax, hmax.data(), T * sizeof(double));
+    for (size_t t = 0; t < T; t++) {
+        int64_t ran = -iters_per_step;
+        for (size_t i = 0; i < I; i++) {
+            if (residual) residual[t * I + i] = hres[t * I + i];
+            if (ran < 0 && hres[t * I + i] <= tol) ran = (int64_t)i + 1;
+        }
+        if (iters) iters[t] = ran;
+        if (skipped) skipped[t] = (int64_t)hskip[t];
+    }
+    if (moments)
+        for (size_t t = 0; t < T; t++)
+            for (size_t i = 0; i < nw; i++) moments[t * nw + i] = (int64_t)hrows[t * nw + (wmap ? (size_t)wmap[i] : i)];
     return NSK_OK;
 }
 

@@ -127,6 +127,7 @@ struct NskBp {
     int32_t *mrec = nullptr, *slot_rec = nullptr;
     uint8_t *v_state = nullptr;
     double *theta = nullptr, *psi = nullptr, *f2v = nullptr, *v2f = nullptr, *belief = nullptr, *wk = nullptr;
+    double *feat = nullptr;            // the tables without the weight, filled with theta (nsk_bp_refresh, nsk_bp_moments)
     int32_t nvlist = 0, nvbin = 0;     // free variables with an edge; the binary ones among them, first in v_list
 };
 
@@ -508,6 +509,8 @@ int nsk_unpack_tally(nsk_graph *g);
 int nsk_trace_record(nsk_graph *g);                 // one row of the sample trace behind what the stream holds (nsk_trace.hip)
 void wstats_plan_free(nsk_graph *g, NskWstatsPlan &plan);      // nsk_wstats.hip (the trace's stats column goes with the trace)
 int nsk_wstats_ensure(nsk_graph *g, bool scaled, const char *what);    // ... the by-weight list at the first use (after energy_ensure)
+// the range rule of the int64 moment sums over `nchains` chains: NSK_E_RANGE naming the weight (nsk_pcd.hip; nsk_bp.hip asks with 1)
+int nsk_moments_range(const nsk_graph *g, int64_t nchains, const char *what);
 // the handles the diagnostics serve (whole graph, no exchange); the arrays of the factor walk at the first use (nsk_energy.hip)
 int energy_whole_graph(const nsk_graph *g, const char *what);
 int energy_ensure(nsk_graph *g, int chains, const char *what);

@@ -3,11 +3,16 @@
 // numpy by numbskull_amd.diagnostics.bp_iterate -- device and numpy agree bit for bit, so every sum and product below is
 // taken in the order written there and nothing is reassociated; the library is compiled with -ffp-contract=off).
 //
-//   k_bp_tables   one lane per (factor, table index): theta_f(a) = w * eval_factor, the free members at the digits of a
+//   k_bp_tables   one lane per (factor, table index): feat_f(a) = eval_factor, the free members at the digits of a, and
+//                 theta_f(a) = w * feat_f(a)
 //   k_bp_psi      one lane per factor: psi_f(a) = nsk_exp(theta_f(a) - max_a theta_f)
 //   k_bp_factor   one lane per directed edge (f, j): the message factor -> variable, damping, the residual
 //   k_bp_var      one lane per free variable with an edge: the messages variable -> factor and the belief
 //   k_bp_fbelief  one lane per factor: the factor beliefs, on demand
+//   k_bp_refresh  one lane per table entry: theta = w * feat from the weights as they stand (nsk_bp_refresh)
+//   k_bp_fnorm    one lane per factor: Z_f, the a-ordered sum of k_bp_fbelief (nsk_bp_moments)
+//   k_bp_moments  one lane per table entry: the expected per-weight statistics under the factor beliefs, int64 fixed
+//                 point, one atomic per run of equal weight slot a wave holds
 //
 // A vector over a variable's values (a message, a belief) lives in registers for binary variables, in a lane-private
 // array of NSK_ZLOCAL doubles for cardinalities up to NSK_ZLOCAL (runtime-indexed; the compiler keeps it in registers
@@ -41,6 +46,7 @@ struct BpArgs {
     const int32_t *v_card;
     const double *w, *logtab;
     double *theta, *psi, *f2v, *v2f, *belief, *wk;
+    double *feat;                   // [ntable] eval_factor without the weight: theta = w * feat, one rounded product
     long long nfactor, ntable, nid;
     int32_t nedge, nvlist;
 };
@@ -76,7 +82,9 @@ __global__ __launch_bounds__(NSK_BLOCK) void k_bp_tables(const BpArgs a, const V
         uint4 rec = a.f_rec[f];
         const int2 *mb = a.mrec + a.pm_off[f] - (int)rec.y;        // mb[ftv_offset + i] = the factor's own record i
         g.m_rec = mb;
-        a.theta[idx] = a.w[rec.z] * energy_factor(g, rec, mb, (const int32_t *)lv);
+        const double e = energy_factor(g, rec, mb, (const int32_t *)lv);
+        a.feat[idx] = e;
+        a.theta[idx] = a.w[rec.z] * e;
     }
 }
 
@@ -309,6 +317,127 @@ static __global__ __launch_bounds__(NSK_BLOCK) void k_bp_fbelief(const BpArgs a,
             Z = ai == 0 ? x : Z + x;
         }
         for (int ai = 0; ai < T; ai++) fb[t0 + ai] = fb[t0 + ai] / Z;
+    }
+}
+
+// ---- learning by belief propagation (nsk_bp_refresh, nsk_bp_moments, nsk_bp_learn_steps) ----
+// the factor of a table entry, as k_bp_tables finds it: tab_off[f] <= idx < tab_off[f + 1]; every factor has an entry
+__device__ __forceinline__ long long bp_factor_of(const BpArgs &a, long long idx) {
+    long long lo = 0, hi = a.nfactor;
+    while (hi - lo > 1) {
+        const long long mid = (lo + hi) >> 1;
+        if (a.tab_off[mid] <= idx) lo = mid; else hi = mid;
+    }
+    return lo;
+}
+
+// x(a) of k_bp_fbelief: psi times the incoming messages at the digits of a, the axes ascending
+__device__ __forceinline__ double bp_entry_x(const BpArgs &a, long long t0, int T, int e0, int A, int ai) {
+    double x = a.psi[t0 + ai];
+    int st = T;
+    for (int i = 0; i < A; i++) {
+        const long long mo = a.msg_off[e0 + i];
+        const int ci = (int)(a.msg_off[e0 + i + 1] - mo);
+        st /= ci;
+        x = x * a.v2f[mo + (ai / st) % ci];
+    }
+    return x;
+}
+
+// theta from the device weight table as it stands: one rounded product per entry, the set-up's own (k_bp_psi follows)
+static __global__ __launch_bounds__(NSK_BLOCK) void k_bp_refresh(const BpArgs a) {
+    for (long long idx = (long long)blockIdx.x * NSK_BLOCK + threadIdx.x; idx < a.ntable; idx += (long long)gridDim.x * NSK_BLOCK)
+        a.theta[idx] = a.w[a.f_rec[bp_factor_of(a, idx)].z] * a.feat[idx];
+}
+
+// Z_f, the a-ordered sum of k_bp_fbelief, one lane per factor.  A factor whose Z_f is not a finite positive number takes
+// no part in the moments: it is counted here, a wave's count leaving as one atomic.
+static __global__ __launch_bounds__(NSK_BLOCK) void k_bp_fnorm(const BpArgs a, double *zf, unsigned long long *skipped) {
+    for (long long base = (long long)blockIdx.x * NSK_BLOCK + (threadIdx.x & ~63u); base < a.nfactor; base += (long long)gridDim.x * NSK_BLOCK) {
+        const long long f = base + (threadIdx.x & 63);
+        bool skip = false;
+        if (f < a.nfactor) {
+            const long long t0 = a.tab_off[f];
+            const int T = (int)(a.tab_off[f + 1] - t0);
+            const int e0 = a.edge_off[f], A = a.edge_off[f + 1] - e0;
+            double Z = 0.0;
+            for (int ai = 0; ai < T; ai++) {
+                const double x = bp_entry_x(a, t0, T, e0, A, ai);
+                Z = ai == 0 ? x : Z + x;
+            }
+            zf[f] = Z;
+            skip = !(Z > 0.0 && Z < __longlong_as_double(0x7ff0000000000000LL));
+        }
+        const unsigned long long m = __ballot(skip);
+        if ((threadIdx.x & 63) == 0 && m != 0ull)
+            (void)__hip_atomic_fetch_add(skipped, (unsigned long long)__popcll(m), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+}
+
+__device__ __forceinline__ void bp_moments_add(unsigned long long *M, int slot, long long x) {
+    if (slot >= 0 && x != 0) (void)__hip_atomic_fetch_add(M + slot, (unsigned long long)x, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+
+// The Bethe moments, one lane per table entry: q = rint(((x(a) / Z_f) * feat_f(a)) * 2^32) into M[weight slot of f].  A
+// wave holds 64 consecutive entries a trip; consecutive entries belong to one factor and hence one slot, so the lanes
+// form runs of equal slot.  A segmented prefix sum leaves every run's total in its last lane, which issues the run's one
+// atomic -- but for the run that ends the wave: it is carried in a register (wave-uniform) into the next trip and joins
+// that trip's first run when the slots agree, as k_moments_piece carries its pieces.  What a block's waves carry at the
+// end meets in LDS and equal slots leave as one atomic.  Integers: no order changes a bit.
+static __global__ __launch_bounds__(NSK_BLOCK) void k_bp_moments(const BpArgs a, const double *zf, unsigned long long *M) {
+    __shared__ long long lds_run[NSK_BLOCK / 64];
+    __shared__ int lds_slot[NSK_BLOCK / 64];
+    const int lane = (int)(threadIdx.x & 63), wave = (int)(threadIdx.x >> 6);
+    int cslot = -1;                 // the slot of the carried sum (-1: none)
+    long long carry = 0;
+    for (long long base = (long long)blockIdx.x * NSK_BLOCK + wave * 64; base < a.ntable; base += (long long)gridDim.x * NSK_BLOCK) {
+        const long long idx = base + lane;
+        int slot = -1;
+        long long acc = 0;
+        if (idx < a.ntable) {
+            const long long f = bp_factor_of(a, idx);
+            const long long t0 = a.tab_off[f];
+            const int T = (int)(a.tab_off[f + 1] - t0);
+            const int e0 = a.edge_off[f];
+            slot = (int)a.f_rec[f].z;
+            const double Z = zf[f];
+            if (Z > 0.0 && Z < __longlong_as_double(0x7ff0000000000000LL)) {
+                const double b = bp_entry_x(a, t0, T, e0, a.edge_off[f + 1] - e0, (int)(idx - t0)) / Z;
+                const double p = b * a.feat[idx];
+                acc = __double2ll_rn(p * NSK_GRAD_SCALE);
+            }
+        }
+        const int prev = __shfl_up(slot, 1, 64), next = __shfl_down(slot, 1, 64);
+        const bool head = lane == 0 || prev != slot, tail = lane == 63 || next != slot;
+        const unsigned long long heads = __ballot(head);
+        const int start = 63 - __clzll((long long)(heads & (~0ull >> (63 - lane))));      // the first lane of this lane's run
+#pragma unroll
+        for (int off = 1; off < 64; off <<= 1) {
+            const long long o = __shfl_up(acc, off, 64);
+            if (lane - off >= start) acc += o;
+        }
+        const int first = __shfl(slot, 0, 64);
+        if (first != cslot) {
+            if (lane == 0) bp_moments_add(M, cslot, carry);
+            carry = 0;
+        }
+        if (start == 0) acc += carry;               // (the carry belongs to the first run now, or is 0)
+        if (tail && lane != 63) bp_moments_add(M, slot, acc);
+        cslot = __shfl(slot, 63, 64);
+        carry = __shfl(acc, 63, 64);
+    }
+    if (lane == 0) { lds_slot[wave] = cslot; lds_run[wave] = carry; }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+#pragma unroll
+        for (int k = 0; k < NSK_BLOCK / 64; k++) {
+            const int s = lds_slot[k];
+            if (s < 0) continue;
+            long long x = lds_run[k];
+            for (int j = k + 1; j < NSK_BLOCK / 64; j++)
+                if (lds_slot[j] == s) { x += lds_run[j]; lds_slot[j] = -1; }
+            bp_moments_add(M, s, x);
+        }
     }
 }
 

@@ -147,6 +147,8 @@ int moments_cap() {
 
 }  // namespace
 
+int nsk_moments_range(const nsk_graph *g, int64_t nchains, const char *what) { return moments_range(g, nchains, what); }
+
 extern "C" {
 
 int nsk_weight_moments(nsk_graph *g, int which, int64_t first_chain, int64_t nchains, int64_t *moments) {

@@ -1123,6 +1123,50 @@ def bp_factor_beliefs(layout, psi, v2f):
     return out
 
 
+def bp_moment_counts(layout, feat, psi, v2f, weight_ids, nweight):
+    """The expected per-weight statistics under the factor beliefs as ``FactorGraph.bp_weight_moments(counts=True)`` sums
+    them on the device (nsk_bp_moments): ``feat`` is the table of ``eval_factor`` without the weight (``table_off``'s
+    layout; ``theta = w[weight] * feat``), ``psi`` and ``v2f`` those of a ``bp_iterate`` run, ``weight_ids`` (nfactor,)
+    each factor's weight.  Per factor ``x(a)`` and their a-ordered sum ``Z`` exactly as ``bp_factor_beliefs`` forms them;
+    a factor whose ``Z`` is not a finite positive number (two contradicting hard constraints: NaN) is skipped.
+    Otherwise per entry, one rounded float64 operation each::
+
+        b = x(a) / Z;  p = b * feat(a);  q = np.rint(p * 2.0**32).astype(np.int64);  M[weight] += q
+
+    Integers, so their order does not matter; a factor without a free member adds ``rint(e * 2**32)``, what
+    ``moment_counts`` adds for it.  Returns ``(int64 (nweight,), skipped)``; ``M * 2.0**-32`` are the expectations, each
+    within ``2**-33`` per table entry of the sum of ``b * feat``."""
+    to, eo, mo = layout["table_off"], layout["edge_off"], layout["msg_off"]
+    feat = np.asarray(feat, np.float64)
+    wid = np.asarray(weight_ids).astype(np.int64)
+    nweight = int(nweight)
+    if feat.shape != (int(to[-1]),) or wid.shape != (len(to) - 1,):
+        raise ValueError("bp_moment_counts: feat has the layout of table_off, weight_ids one entry a factor")
+    if wid.size and (wid.min() < 0 or wid.max() >= nweight):
+        raise IndexError("bp_moment_counts: a factor names a weight out of range")
+    counts = np.zeros(nweight, np.int64)
+    skipped = 0
+    psi, v2f = np.asarray(psi, np.float64), np.asarray(v2f, np.float64)
+    for f in range(len(to) - 1):
+        shape = layout["shapes"][f]
+        # x(a) = ((psi(a) * v2f[(f,0)][a_0]) * ..): one elementwise product per axis, ascending -- per entry the same
+        # rounded products in the same order as bp_factor_beliefs takes them one by one
+        x = psi[to[f]:to[f + 1]].reshape(shape if shape else (1,))
+        with np.errstate(invalid="ignore"):         # (0 * inf = NaN is what IEEE gives; it is caught below)
+            for i in range(len(shape)):
+                m = v2f[mo[int(eo[f]) + i]:mo[int(eo[f]) + i + 1]]
+                x = x * m.reshape([-1 if k == i else 1 for k in range(len(shape))])
+        x = x.ravel()
+        z = _bp_sum(x.tolist())                     # the a-ordered sum, one addition after another
+        if not (z > 0.0 and z < np.inf):            # (a NaN fails both: nothing of it reaches a conversion)
+            skipped += 1
+            continue
+        b = x / np.float64(z)
+        p = b * feat[to[f]:to[f + 1]]
+        counts[wid[f]] += np.rint(p * 2.0 ** 32).astype(np.int64).sum(dtype=np.int64)
+    return counts, skipped
+
+
 def bethe_log_z(layout, theta, factor_beliefs, beliefs):
     """The Bethe estimate of log Z from the beliefs of a belief-propagation run: the sum over factors and table entries
     of ``b_f (theta_f - log b_f)``, plus the sum over free variables of ``(d_v - 1) sum_k b_v log b_v`` with ``d_v`` the

@@ -1459,6 +1459,97 @@ class FactorGraph(object):
             out.update(table_offsets=table_off, theta=theta, factor_beliefs=fb)
         return out
 
+    def bp_weight_moments(self, max_iters=100, damping=0.0, tol=1e-9, var_copy=0, weight_copy=0, evidence_chain=False,
+                          sample_evidence=False, counts=False):
+        """The expected per-weight statistics ``E[S_w]`` under belief propagation (nsk_bp_setup / nsk_bp_run /
+        nsk_bp_moments): the sum over every factor of a weight and every entry of its table of factor belief x factor
+        value, reduced on the device in the int64 fixed point of ``weight_moments`` -- exact to within ``2**-33`` per table
+        entry wherever BP is exact (the free variables form a forest), the Bethe approximation on a graph with cycles.
+        State, weights, clamping and the iteration's arguments are those of ``belief_propagation``.  A factor whose
+        beliefs are NaN (two contradicting hard constraints) is left out and counted.  ``diagnostics.bp_moment_counts`` is
+        the rule in numpy.  Returns a dict: ``moments`` -- float64 ``(nweight,)``, the sums ``* 2.0**-32``, or the int64
+        sums with ``counts=True``; ``iters``, ``converged`` as ``belief_propagation`` returns them; ``skipped``.  On a state
+        where every variable is clamped ``moments`` equal ``weight_moments`` of it."""
+        max_iters = int(max_iters)
+        if max_iters < 1 or max_iters > 4096:
+            raise ValueError("bp_weight_moments: max_iters must lie in [1, 4096]")
+        if _all_copies(var_copy):
+            raise ValueError('bp_weight_moments serves one state: var_copy="all" is for the sampler')
+        L, h = _lib.lib(), self._engine()
+        self._push(var_copy, weight_copy)
+        _lib.check(L.nsk_bp_setup(h, _lib.BUF_VALUE_EVID if evidence_chain else _lib.BUF_VALUE, 0, int(bool(sample_evidence)), None))
+        try:
+            iters, skipped = C.c_int64(0), C.c_int64(0)
+            _lib.check(L.nsk_bp_run(h, max_iters, float(damping), float(tol), C.byref(iters), None))
+            m = np.zeros(self.weight.shape[0], np.int64)
+            _lib.check(L.nsk_bp_moments(h, _lib.ptr(m), C.byref(skipped)))
+        finally:
+            L.nsk_bp_clear(h)
+        return {"moments": m if counts else m.astype(np.float64) * 2.0 ** -32, "iters": abs(int(iters.value)),
+                "converged": bool(iters.value > 0), "skipped": int(skipped.value)}
+
+    def learn_bp(self, epochs, stepsize, decay=1.0, reg_param=0.0, iters=20, damping=0.0, tol=1e-9, warm=True,
+                 sample_evidence=True, target=None, normalize=True, var_copy=0, weight_copy=0, moments=False):
+        """Maximum-likelihood learning whose model expectations come from belief propagation instead of chains
+        (nsk_bp_learn_steps): EXACT maximum likelihood where the free variables form a forest -- chains, stars, graphs
+        that the evidence separates --, the Bethe approximation on a graph with cycles; no sampling noise, no chain
+        count, no generator state, reproducible bit for bit.  Each of the ``epochs`` steps rebuilds the tables from the
+        current weights, runs up to ``iters`` BP iterations (from the previous step's messages with ``warm``, from
+        ``1 / cardinality`` without; they stop behind the first whose largest message change is ``<= tol``), takes
+        ``bp_weight_moments`` and moves every weight that is not fixed as ``learn_pcd`` does:
+        ``w += step * ((target - E[S_w]) / n_w - reg_param * w)`` with ``step = stepsize * decay**t``
+        (``normalize=False``: no division by the factor count ``n_w``).  Nothing returns to the host between steps.
+
+        Its signals: ``converged`` says per step whether the iterations reached ``tol`` -- where they do not on a graph
+        with cycles, raise ``damping`` (in [0, 1)) or ``iters``; the gradient of a step that did not converge is that of
+        the messages as they stood.  ``target`` (nweight,) are the statistics to match; None means those of the evidence
+        chain, ``weight_moments(evidence_chain=True)``, which is right for FULLY OBSERVED data, as in ``learn_pcd``.
+        ``sample_evidence=True`` frees every variable with a position (the free phase).  LATENT-variable learning needs
+        the difference of two set-ups, evidence clamped and free, and is not served here: ``learn_pcd(clamped=K)`` does
+        that with chains.
+
+        The state ``var_value[var_copy]`` and ``weight_value[weight_copy]`` are pushed as ``belief_propagation`` pushes
+        them; afterwards ``weight_value[weight_copy]`` holds the learned weights, and the set-up is cleared whatever
+        happens.  Values and ``count`` are untouched.  Returns a dict: ``grad_max`` -- float64 ``(epochs,)``, the largest
+        ``|target - E[S_w]|`` (divided by ``n_w`` with ``normalize``) over the weights that are not fixed, at the weights
+        each step ran under; ``iters`` (epochs,) the iterations each step ran; ``converged`` (epochs,) bool;
+        ``residual`` (epochs, iters); ``skipped`` (epochs,) the factors left out for NaN beliefs; ``target``;
+        ``factors_per_weight``; with ``moments=True`` also ``moments`` -- int64 ``(epochs, nweight)``
+        (``diagnostics.bp_moment_counts``; ``diagnostics.pcd_step`` with ``R=1`` is the update in numpy)."""
+        epochs, iters = int(epochs), int(iters)
+        if epochs < 1 or epochs > 4096 or iters < 1 or iters > 4096 or epochs * iters > 65536:
+            raise ValueError("learn_bp: epochs and iters must lie in [1, 4096], epochs x iters at most 65536")
+        stepsize, decay, reg_param = float(stepsize), float(decay), float(reg_param)
+        if not (np.isfinite(stepsize) and np.isfinite(decay) and np.isfinite(reg_param)) or reg_param < 0:
+            raise ValueError("learn_bp: stepsize, decay and reg_param must be finite, reg_param not negative")
+        if _all_copies(var_copy):
+            raise ValueError('learn_bp serves one state: var_copy="all" is for the sampler')
+        nw = self.weight.shape[0]
+        if target is not None:
+            target = np.ascontiguousarray(target, np.float64)
+            if target.shape != (nw,) or not np.isfinite(target).all():
+                raise ValueError("learn_bp: target is finite float64 (nweight,) = (%d,)" % nw)
+        else:
+            target = self.weight_moments(evidence_chain=True)
+        L, h = _lib.lib(), self._engine()
+        self._push(var_copy, weight_copy)
+        _lib.check(L.nsk_bp_setup(h, _lib.BUF_VALUE, 0, int(bool(sample_evidence)), None))
+        try:
+            gmax, ran, skipped = np.zeros(epochs, np.float64), np.zeros(epochs, np.int64), np.zeros(epochs, np.int64)
+            residual = np.zeros((epochs, iters), np.float64)
+            rows = np.zeros((epochs, nw), np.int64) if moments else None
+            _lib.check(L.nsk_bp_learn_steps(h, _lib.ptr(target), epochs, iters, float(damping), float(tol), int(bool(warm)), stepsize,
+                                            decay, reg_param, int(bool(normalize)), _lib.ptr(gmax), _lib.ptr(ran), _lib.ptr(residual),
+                                            _lib.ptr(rows), _lib.ptr(skipped)))
+            self._pull(var_copy, weight_copy, values=False, count=False)
+        finally:
+            L.nsk_bp_clear(h)
+        out = {"grad_max": gmax, "iters": np.abs(ran), "converged": ran > 0, "residual": residual, "skipped": skipped,
+               "target": target, "factors_per_weight": np.bincount(self.factor["weightId"].astype(np.int64), minlength=nw).astype(np.int64)}
+        if moments:
+            out["moments"] = rows
+        return out
+
     # ------------------------------------------------------------------ log-potential
     def log_potential(self, var_copy=0, weight_copy=0, evidence_chain=False):
         """The unnormalised log-probability of a state: the sum over all factors of weight x factor value, evaluated
