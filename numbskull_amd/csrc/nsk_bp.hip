@@ -115,34 +115,21 @@ static hipError_t bp_moments_enqueue(nsk_graph *g, const BpArgs &a, double *zf, 
     return hipGetLastError();
 }
 
-// the device buffers of one call: entered in the ledger, gone when the call returns
+// the device buffers of one call beside its StepOutputs: entered in the ledger, gone when the call returns
 struct BpLearnBufs {
     nsk_graph *g;
-    unsigned long long *M = nullptr, *skipped = nullptr, *gmax = nullptr, *res = nullptr;
+    unsigned long long *M = nullptr, *skipped = nullptr, *res = nullptr;
     double *zf = nullptr, *target = nullptr, *nfac = nullptr;
-    long long *rows = nullptr;
     explicit BpLearnBufs(nsk_graph *g_) : g(g_) {}
-    ~BpLearnBufs() {
-        dev_free(g, rows); dev_free(g, nfac); dev_free(g, target); dev_free(g, zf);
-        dev_free(g, res); dev_free(g, gmax); dev_free(g, skipped); dev_free(g, M);
-    }
+    ~BpLearnBufs() { dev_free(g, nfac); dev_free(g, target); dev_free(g, zf); dev_free(g, res); dev_free(g, skipped); dev_free(g, M); }
 };
-
-template <typename T>
-static int bp_call_alloc(nsk_graph *g, T **ptr, size_t n, const char *who, const char *what) {
-    const int rc = dev_alloc(g, ptr, n);
-    if (rc != NSK_E_NOMEM) return rc;
-    return fail(NSK_E_NOMEM, std::string(who) + ": " + what + " (" + std::to_string((long long)((n ? n : 1) * sizeof(T))) + " bytes) do not fit on the device");
-}
 
 extern "C" {
 
 int nsk_bp_setup(nsk_graph *g, int which, int64_t chain, int sample_evidence, nsk_bp_info *info_out) {
     int rc = bp_common(g, "nsk_bp_setup", false);
     if (rc) return rc;
-    if (which != NSK_BUF_VALUE && which != NSK_BUF_VALUE_EVID) return fail(NSK_E_INVALID, "nsk_bp_setup: which must be NSK_BUF_VALUE or NSK_BUF_VALUE_EVID");
-    if (chain < 0 || chain >= (which == NSK_BUF_VALUE ? g->nchains : 1))
-        return fail(NSK_E_INVALID, "nsk_bp_setup: chain outside those the handle has (the evidence chain exists once)");
+    if ((rc = chain_select(g, which, chain, 1, "nsk_bp_setup", true))) return rc;
     const Compiled &c = g->c;
     const int64_t F = c.nfactor, nedge = c.nedge, nid = c.nid, npos = std::min<int64_t>(c.npos, (int64_t)c.p_info.size());
     const bool head_by_vid = (c.flags & NSK_FLAG_HEAD_BY_VID) != 0;
@@ -287,7 +274,7 @@ int nsk_bp_setup(nsk_graph *g, int which, int64_t chain, int sample_evidence, ns
     }
     b.info.device_bytes = g->mem.total - before;
     const BpArgs a = bp_args(g);
-    const char *val = which == NSK_BUF_VALUE ? (const char *)g->val + (size_t)chain * g->chain_stride : (const char *)g->val_evid;
+    const char *val = chain_val(g, which, chain);
     const dim3 block(NSK_BLOCK);
     if (F > 0) {
         if (c.vbytes == 4) k_bp_tables<int32_t><<<dim3(bp_blocks(a.ntable)), block, 0, g->stream>>>(a, (const int32_t *)val);
@@ -439,9 +426,9 @@ int nsk_bp_moments(nsk_graph *g, int64_t *moments, int64_t *skipped) {
     if ((rc = nsk_moments_range(g, 1, who))) return rc;
     HIPCHECK(hipSetDevice(g->device));
     BpLearnBufs b(g);
-    rc = bp_call_alloc(g, &b.M, nw, who, "the int64 sums, 8 bytes a weight");
-    if (!rc) rc = bp_call_alloc(g, &b.skipped, 1, who, "the skip counter");
-    if (!rc) rc = bp_call_alloc(g, &b.zf, (size_t)g->bp.info.nfactor, who, "the factors' normalisers, 8 bytes a factor");
+    rc = call_alloc(g, &b.M, nw, who, "the int64 sums, 8 bytes a weight");
+    if (!rc) rc = call_alloc(g, &b.skipped, 1, who, "the skip counter");
+    if (!rc) rc = call_alloc(g, &b.zf, (size_t)g->bp.info.nfactor, who, "the factors' normalisers, 8 bytes a factor");
     if (rc) return rc;
     std::vector<long long> host(nw);
     unsigned long long hskip = 0;
@@ -451,9 +438,7 @@ int nsk_bp_moments(nsk_graph *g, int64_t *moments, int64_t *skipped) {
     const hipError_t e2 = hipStreamSynchronize(g->stream);
     HIPCHECK(e);
     HIPCHECK(e2);
-    // slots -> the caller's weight ids, as nsk_weight_moments maps them
-    const int32_t *wmap = c.wmap.empty() ? nullptr : c.wmap.data();
-    for (size_t i = 0; i < nw; i++) moments[i] = (int64_t)host[wmap ? (size_t)wmap[i] : i];
+    SlotMap(c).from_slots(host.data(), moments);
     if (skipped) *skipped = (int64_t)hskip;
     return NSK_OK;
 }
@@ -465,41 +450,38 @@ int nsk_bp_learn_steps(nsk_graph *g, const double *target, int64_t nsteps, int64
     int rc = bp_common(g, who, true);
     if (rc) return rc;
     if (!target) return fail(NSK_E_INVALID, "null argument");
-    if (nsteps < 1 || nsteps > 4096) return fail(NSK_E_INVALID, "nsk_bp_learn_steps: nsteps must lie in [1, 4096]");
+    if ((rc = refuse(check_nsteps(who, nsteps, 4096)))) return rc;
     if (iters_per_step < 1 || iters_per_step > 4096) return fail(NSK_E_INVALID, "nsk_bp_learn_steps: iters_per_step must lie in [1, 4096]");
     if (nsteps * iters_per_step > 65536) return fail(NSK_E_INVALID, "nsk_bp_learn_steps: nsteps x iters_per_step must be at most 65536");
     if (!(damping >= 0.0 && damping < 1.0)) return fail(NSK_E_INVALID, "nsk_bp_learn_steps: damping must lie in [0, 1)");
     if (!(tol >= 0.0)) return fail(NSK_E_INVALID, "nsk_bp_learn_steps: tol must be at least 0");
     if ((warm != 0 && warm != 1) || (normalize != 0 && normalize != 1)) return fail(NSK_E_INVALID, "nsk_bp_learn_steps: warm and normalize must be 0 or 1");
-    if (!std::isfinite(step) || !std::isfinite(decay) || !std::isfinite(reg_param) || reg_param < 0.0)
-        return fail(NSK_E_INVALID, "nsk_bp_learn_steps: step, decay and reg_param must be finite, reg_param not negative");
+    if ((rc = refuse(check_rates(who, step, decay, reg_param)))) return rc;
     const Compiled &c = g->c;
     const size_t nw = (size_t)c.nweight, T = (size_t)nsteps, I = (size_t)iters_per_step;
-    for (size_t i = 0; i < nw; i++)
-        if (!std::isfinite(target[i])) return fail(NSK_E_INVALID, "nsk_bp_learn_steps: the target of weight " + std::to_string((long long)i) + " is not finite");
+    if ((rc = refuse(check_target(who, target, nw)))) return rc;
     if (nw == 0) return NSK_OK;
     if ((rc = nsk_moments_range(g, 1, who))) return rc;
     HIPCHECK(hipSetDevice(g->device));
 
-    // the target and the factor counts by slot (w_fixed is by slot too), as nsk_pcd_steps has them
-    const int32_t *wmap = c.wmap.empty() ? nullptr : c.wmap.data();
-    std::vector<double> tgt(nw), nfac(nw, 0.0);
-    for (size_t i = 0; i < nw; i++) tgt[wmap ? (size_t)wmap[i] : i] = target[i];
-    for (size_t f = 0; f < (size_t)c.nfactor; f++) nfac[(size_t)c.f_rec[4 * f + 2]] += 1.0;
-    for (size_t s = 0; s < nw; s++) if (nfac[s] == 0.0) nfac[s] = 1.0;
+    // the target and the factor counts by slot
+    std::vector<double> tgt(nw);
+    SlotMap(c).to_slots(target, tgt.data());
+    const std::vector<double> nfac = factors_per_slot(c);
     BpLearnBufs b(g);
-    rc = bp_call_alloc(g, &b.M, nw, who, "the int64 sums, 8 bytes a weight");
-    if (!rc) rc = bp_call_alloc(g, &b.skipped, T, who, "the skip counters, 8 bytes a step");
-    if (!rc) rc = bp_call_alloc(g, &b.zf, (size_t)g->bp.info.nfactor, who, "the factors' normalisers, 8 bytes a factor");
-    if (!rc) rc = bp_call_alloc(g, &b.target, nw, who, "the target, 8 bytes a weight");
-    if (!rc) rc = bp_call_alloc(g, &b.nfac, nw, who, "the factor counts, 8 bytes a weight");
-    if (!rc) rc = bp_call_alloc(g, &b.gmax, T, who, "the largest gradients, 8 bytes a step");
-    if (!rc) rc = bp_call_alloc(g, &b.res, T * I, who, "the residuals, nsteps x iters_per_step doubles");
-    if (!rc && moments) rc = bp_call_alloc(g, &b.rows, T * nw, who, "the kept moments, nsteps x nweight int64");
+    StepOutputs out(g, T, 1);
+    rc = call_alloc(g, &b.M, nw, who, "the int64 sums, 8 bytes a weight");
+    if (!rc) rc = call_alloc(g, &b.skipped, T, who, "the skip counters, 8 bytes a step");
+    if (!rc) rc = call_alloc(g, &b.zf, (size_t)g->bp.info.nfactor, who, "the factors' normalisers, 8 bytes a factor");
+    if (!rc) rc = call_alloc(g, &b.target, nw, who, "the target, 8 bytes a weight");
+    if (!rc) rc = call_alloc(g, &b.nfac, nw, who, "the factor counts, 8 bytes a weight");
+    if (!rc) rc = out.alloc_gmax(who);
+    if (!rc) rc = call_alloc(g, &b.res, T * I, who, "the residuals, nsteps x iters_per_step doubles");
+    if (!rc && moments) rc = out.alloc_rows(who);
     if (rc) return rc;
     hipError_t e = hipMemcpyAsync(b.target, tgt.data(), nw * sizeof(double), hipMemcpyHostToDevice, g->stream);
     if (e == hipSuccess) e = hipMemcpyAsync(b.nfac, nfac.data(), nw * sizeof(double), hipMemcpyHostToDevice, g->stream);
-    if (e == hipSuccess) e = hipMemsetAsync(b.gmax, 0, T * sizeof(unsigned long long), g->stream);
+    if (e == hipSuccess) e = out.zero();
     if (e == hipSuccess) e = hipMemsetAsync(b.res, 0, T * I * sizeof(unsigned long long), g->stream);
     if (e != hipSuccess) { (void)hipStreamSynchronize(g->stream); HIPCHECK(e); }
 
@@ -516,26 +498,23 @@ int nsk_bp_learn_steps(nsk_graph *g, const double *target, int64_t nsteps, int64
         // 3. the Bethe moments
         if ((e = bp_moments_enqueue(g, a, b.zf, b.M, b.skipped + t)) != hipSuccess) break;
         // 4. the update: nsk_pcd_steps' with one chain
-        k_pcd_update<<<dim3(wblocks), dim3(NSK_BLOCK), 0, g->stream>>>((const long long *)b.M, b.target, b.nfac, 1.0, (int)nw, g->w, g->w_fixed,
-                                                                      normalize, st, reg_param, b.gmax + t, b.rows ? b.rows + t * nw : nullptr);
+        k_pcd_update<<<dim3(wblocks), dim3(NSK_BLOCK), 0, g->stream>>>((const long long *)b.M, 1.0, nullptr, 0.0, b.target, b.nfac, (int)nw, g->w, g->w_fixed,
+                                                                      normalize, st, reg_param, out.gmax + t, out.row(t));
         e = hipGetLastError();
         g->weights_dirty = true;            // the next sweep call rebuilds what derives from the weights
         st = st * decay;
     }
     // the resident tables agree with the learned weights: a following nsk_bp_run continues under them
     if (e == hipSuccess) { bp_refresh_enqueue(g, a); e = hipGetLastError(); }
-    std::vector<unsigned long long> hmax(T), hskip(T);
+    std::vector<unsigned long long> hskip(T);
     std::vector<double> hres(T * I);
-    std::vector<long long> hrows(b.rows ? T * nw : 0);
-    const bool ok = e == hipSuccess;
-    if (ok) e = hipMemcpyAsync(hmax.data(), b.gmax, T * 8, hipMemcpyDeviceToHost, g->stream);
-    if (ok && e == hipSuccess) e = hipMemcpyAsync(hskip.data(), b.skipped, T * 8, hipMemcpyDeviceToHost, g->stream);
-    if (ok && e == hipSuccess) e = hipMemcpyAsync(hres.data(), b.res, T * I * 8, hipMemcpyDeviceToHost, g->stream);
-    if (ok && b.rows && e == hipSuccess) e = hipMemcpyAsync(hrows.data(), b.rows, T * nw * sizeof(long long), hipMemcpyDeviceToHost, g->stream);
+    if (e == hipSuccess) e = out.download();
+    if (e == hipSuccess) e = hipMemcpyAsync(hskip.data(), b.skipped, T * 8, hipMemcpyDeviceToHost, g->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(hres.data(), b.res, T * I * 8, hipMemcpyDeviceToHost, g->stream);
     const hipError_t e2 = hipStreamSynchronize(g->stream);      // (also: the uploads read the host vectors)
     HIPCHECK(e);
     HIPCHECK(e2);
-    if (gmax) std::memcpy(gmax, hmax.data(), T * sizeof(double));
+    out.deliver(gmax, moments);
     for (size_t t = 0; t < T; t++) {
         int64_t ran = -iters_per_step;
         for (size_t i = 0; i < I; i++) {
@@ -545,9 +524,6 @@ int nsk_bp_learn_steps(nsk_graph *g, const double *target, int64_t nsteps, int64
         if (iters) iters[t] = ran;
         if (skipped) skipped[t] = (int64_t)hskip[t];
     }
-    if (moments)
-        for (size_t t = 0; t < T; t++)
-            for (size_t i = 0; i < nw; i++) moments[t * nw + i] = (int64_t)hrows[t * nw + (wmap ? (size_t)wmap[i] : i)];
     return NSK_OK;
 }
 

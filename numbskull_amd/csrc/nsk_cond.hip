@@ -134,13 +134,10 @@ extern "C" {
 int nsk_conditionals(nsk_graph *g, int which, int64_t first_chain, int64_t nchains, const int64_t *vids, int64_t nvids,
                      int what, double *out) {
     if (!g) return fail(NSK_E_INVALID, "null graph");
-    if (which != NSK_BUF_VALUE && which != NSK_BUF_VALUE_EVID) return fail(NSK_E_INVALID, "nsk_conditionals: which must be NSK_BUF_VALUE or NSK_BUF_VALUE_EVID");
-    const int64_t R = which == NSK_BUF_VALUE ? g->nchains : 1;
-    if (first_chain < 0 || nchains < 1 || first_chain >= R || nchains > R - first_chain)
-        return fail(NSK_E_INVALID, "nsk_conditionals: chains outside those the handle has (the evidence chain exists once)");
-    if (what != 0 && what != 1) return fail(NSK_E_INVALID, "nsk_conditionals: what must be 0 (potentials) or 1 (probabilities)");
-    int rc = energy_whole_graph(g, "nsk_conditionals");
+    int rc = chain_select(g, which, first_chain, nchains, "nsk_conditionals");
     if (rc) return rc;
+    if (what != 0 && what != 1) return fail(NSK_E_INVALID, "nsk_conditionals: what must be 0 (potentials) or 1 (probabilities)");
+    if ((rc = energy_whole_graph(g, "nsk_conditionals"))) return rc;
     if ((rc = cond_check_vids(g, vids, nvids, "nsk_conditionals"))) return rc;
     NskCondSel s;
     if ((rc = cond_sel_build(g, vids, nvids, s, "nsk_conditionals"))) return rc;
@@ -162,7 +159,7 @@ int nsk_conditionals(nsk_graph *g, int which, int64_t first_chain, int64_t nchai
             if (rc) return rc;
             rb.commit();
         }
-        const char *val = which == NSK_BUF_VALUE ? (const char *)g->val + (size_t)first_chain * g->chain_stride : (const char *)g->val_evid;
+        const char *val = chain_val(g, which, first_chain);
         rc = what == 0 ? cond_launch<COND_POTENTIALS>(g, s, val, (int)nchains, g->packed_sweeps > 0, dev)
                        : cond_launch<COND_PROBABILITIES>(g, s, val, (int)nchains, g->packed_sweeps > 0, dev);
         hipError_t e = hipSuccess;

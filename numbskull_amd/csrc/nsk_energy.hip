@@ -169,15 +169,11 @@ extern "C" {
 int nsk_log_potential(nsk_graph *g, int which, int64_t first_chain, int64_t nchains, double *out) {
     if (!g) return fail(NSK_E_INVALID, "null graph");
     if (!out) return fail(NSK_E_INVALID, "null argument");
-    if (which != NSK_BUF_VALUE && which != NSK_BUF_VALUE_EVID) return fail(NSK_E_INVALID, "nsk_log_potential: which must be NSK_BUF_VALUE or NSK_BUF_VALUE_EVID");
-    const int64_t R = which == NSK_BUF_VALUE ? g->nchains : 1;
-    if (first_chain < 0 || nchains < 1 || first_chain >= R || nchains > R - first_chain)
-        return fail(NSK_E_INVALID, "nsk_log_potential: chains outside those the handle has (the evidence chain exists once)");
-    int rc = energy_whole_graph(g, "nsk_log_potential");
+    int rc = chain_select(g, which, first_chain, nchains, "nsk_log_potential");
+    if (!rc) rc = energy_whole_graph(g, "nsk_log_potential");
     if (rc) return rc;
     if ((rc = energy_ensure(g, (int)nchains, "nsk_log_potential"))) return rc;
-    const char *val = which == NSK_BUF_VALUE ? (const char *)g->val + (size_t)first_chain * g->chain_stride : (const char *)g->val_evid;
-    if ((rc = nsk_energy_enqueue(g, val, (int)nchains, g->packed_sweeps > 0, g->energy.result))) return rc;
+    if ((rc = nsk_energy_enqueue(g, chain_val(g, which, first_chain), (int)nchains, g->packed_sweeps > 0, g->energy.result))) return rc;
     HIPCHECK(hipMemcpyAsync(out, g->energy.result, (size_t)nchains * sizeof(double), hipMemcpyDeviceToHost, g->stream));
     HIPCHECK(hipStreamSynchronize(g->stream));
     return NSK_OK;
@@ -185,10 +181,8 @@ int nsk_log_potential(nsk_graph *g, int which, int64_t first_chain, int64_t ncha
 
 int nsk_factor_values(nsk_graph *g, int which, int64_t chain, double *out) {
     if (!g) return fail(NSK_E_INVALID, "null graph");
-    if (which != NSK_BUF_VALUE && which != NSK_BUF_VALUE_EVID) return fail(NSK_E_INVALID, "nsk_factor_values: which must be NSK_BUF_VALUE or NSK_BUF_VALUE_EVID");
-    if (chain < 0 || chain >= (which == NSK_BUF_VALUE ? g->nchains : 1))
-        return fail(NSK_E_INVALID, "nsk_factor_values: chain outside those the handle has (the evidence chain exists once)");
-    int rc = energy_whole_graph(g, "nsk_factor_values");
+    int rc = chain_select(g, which, chain, 1, "nsk_factor_values", true);
+    if (!rc) rc = energy_whole_graph(g, "nsk_factor_values");
     if (rc) return rc;
     if (g->c.nfactor == 0) return NSK_OK;
     if (!out) return fail(NSK_E_INVALID, "null argument");
@@ -197,8 +191,7 @@ int nsk_factor_values(nsk_graph *g, int which, int64_t chain, double *out) {
     double *dev = nullptr;
     const size_t n = (size_t)g->c.nfactor;
     if ((rc = dev_alloc(g, &dev, n))) return fail(NSK_E_NOMEM, "nsk_factor_values: one double per factor does not fit on the device");
-    const char *val = which == NSK_BUF_VALUE ? (const char *)g->val + (size_t)chain * g->chain_stride : (const char *)g->val_evid;
-    rc = nsk_factor_values_enqueue(g, val, dev);
+    rc = nsk_factor_values_enqueue(g, chain_val(g, which, chain), dev);
     hipError_t e = hipSuccess;
     if (!rc) e = hipMemcpyAsync(out, dev, n * sizeof(double), hipMemcpyDeviceToHost, g->stream);
     if (!rc && e == hipSuccess) e = hipStreamSynchronize(g->stream);

@@ -15,13 +15,10 @@ int nsk_icm(nsk_graph *g, int which, int64_t first_chain, int64_t nchains, int64
             int64_t *sweeps, int64_t *changed) {
     if (!g) return fail(NSK_E_INVALID, "null graph");
     if (!sweeps) return fail(NSK_E_INVALID, "null argument");
-    if (which != NSK_BUF_VALUE && which != NSK_BUF_VALUE_EVID) return fail(NSK_E_INVALID, "nsk_icm: which must be NSK_BUF_VALUE or NSK_BUF_VALUE_EVID");
-    const int64_t R = which == NSK_BUF_VALUE ? g->nchains : 1;
-    if (first_chain < 0 || nchains < 1 || first_chain >= R || nchains > R - first_chain)
-        return fail(NSK_E_INVALID, "nsk_icm: chains outside those the handle has (the evidence chain exists once)");
-    if (max_sweeps < 1 || max_sweeps > 4096) return fail(NSK_E_INVALID, "nsk_icm: max_sweeps must lie in [1, 4096]");
-    int rc = energy_whole_graph(g, "nsk_icm");
+    int rc = chain_select(g, which, first_chain, nchains, "nsk_icm");
     if (rc) return rc;
+    if (max_sweeps < 1 || max_sweeps > 4096) return fail(NSK_E_INVALID, "nsk_icm: max_sweeps must lie in [1, 4096]");
+    if ((rc = energy_whole_graph(g, "nsk_icm"))) return rc;
     HIPCHECK(hipSetDevice(g->device));
     if ((rc = cond_ensure(g, "nsk_icm"))) return rc;
     // a tally kept in bits 1-7 of the value bytes goes back to its array first, as before a state download: the kernel
@@ -43,7 +40,7 @@ int nsk_icm(nsk_graph *g, int which, int64_t first_chain, int64_t nchains, int64
     a.w = g->w; a.logtab = g->logtab;
     a.chain_stride = (long long)g->chain_stride;
     a.head_by_vid = (c.flags & NSK_FLAG_HEAD_BY_VID) ? 1 : 0;
-    char *val = which == NSK_BUF_VALUE ? (char *)g->val + (size_t)first_chain * g->chain_stride : (char *)g->val_evid;
+    char *val = chain_val(g, which, first_chain);
     const size_t ncolors = c.phase_end.size();
     for (size_t s = 0; s < S && e == hipSuccess; s++) {
         const long long *prev = s ? counters + (s - 1) * N : nullptr;

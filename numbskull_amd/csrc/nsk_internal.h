@@ -11,6 +11,7 @@
 
 #include <algorithm>
 #include <cstdlib>
+#include <cstring>
 #include <string>
 #include <vector>
 
@@ -20,6 +21,7 @@
 #include "nsk_device.h"
 #include "nsk_kernels_gibbs.h"
 #include "nsk_seg_plan.h"
+#include "nsk_steps.h"
 
 namespace nsk {
 int fail(int code, const std::string &msg);       // records nsk_last_error, returns code
@@ -363,6 +365,62 @@ static int dev_upload(nsk_graph *g, T **ptr, const std::vector<T> &h) {
     if (rc) return rc;
     if (!h.empty()) HIPCHECK(hipMemcpyAsync(*ptr, h.data(), h.size() * sizeof(T), hipMemcpyHostToDevice, g->stream));
     return NSK_OK;
+}
+// a buffer that lives for one call of `who`: dev_alloc, with the refusal that names it
+template <typename T>
+static int call_alloc(nsk_graph *g, T **ptr, size_t n, const std::string &who, const char *what) {
+    const int rc = dev_alloc(g, ptr, n);
+    if (rc != NSK_E_NOMEM) return rc;
+    return nsk::fail(NSK_E_NOMEM, who + ": " + what + " (" + std::to_string((long long)((n ? n : 1) * sizeof(T))) + " bytes) do not fit on the device");
+}
+// a check of nsk_steps.h as a return code
+static inline int refuse(const std::string &why) { return why.empty() ? NSK_OK : nsk::fail(NSK_E_INVALID, why); }
+
+// The per-step outputs of a learner's call (nsk_pcd_steps, nsk_pcd_latent_steps, nsk_bp_learn_steps): gmax[T], the bit
+// patterns of the steps' largest gradients, and -- where the caller keeps the moments -- rows[T x k x nweight] int64 by
+// slot.  On the ledger from alloc_* to the end of the call.
+struct StepOutputs {
+    nsk_graph *g;
+    size_t T, k, nw;
+    unsigned long long *gmax = nullptr;
+    long long *rows = nullptr;
+    std::vector<unsigned long long> hmax;
+    std::vector<long long> hrows;
+    StepOutputs(nsk_graph *g_, size_t T_, size_t k_) : g(g_), T(T_), k(k_), nw((size_t)g_->c.nweight) {}
+    ~StepOutputs() { dev_free(g, rows); dev_free(g, gmax); }
+    int alloc_gmax(const std::string &who) { return call_alloc(g, &gmax, T, who, "the largest gradients, 8 bytes a step"); }
+    int alloc_rows(const std::string &who) {
+        return call_alloc(g, &rows, T * k * nw, who, k == 1 ? "the kept moments, nsteps x nweight int64" : "the kept moments, nsteps x 2 x nweight int64");
+    }
+    hipError_t zero() { return hipMemsetAsync(gmax, 0, T * sizeof(unsigned long long), g->stream); }
+    long long *row(size_t t) const { return rows ? rows + t * k * nw : nullptr; }       // step t's, or null
+    // enqueue the copies to the host (the caller synchronises the stream) ...
+    hipError_t download() {
+        hmax.resize(T);
+        hrows.resize(rows ? T * k * nw : 0);
+        hipError_t e = hipMemcpyAsync(hmax.data(), gmax, T * sizeof(unsigned long long), hipMemcpyDeviceToHost, g->stream);
+        if (rows && e == hipSuccess) e = hipMemcpyAsync(hrows.data(), rows, hrows.size() * sizeof(long long), hipMemcpyDeviceToHost, g->stream);
+        return e;
+    }
+    // ... and hand them over: the rows by the caller's weight ids (either may be null)
+    void deliver(double *gmax_out, int64_t *moments) const {
+        if (gmax_out) std::memcpy(gmax_out, hmax.data(), T * sizeof(double));
+        if (moments) nsk::SlotMap(g->c).from_slots(hrows.data(), moments, T * k);
+    }
+};
+
+// The chains an entry point names: `which` is NSK_BUF_VALUE (chains [first_chain, first_chain + nchains) of the handle's)
+// or NSK_BUF_VALUE_EVID (the evidence chain, which exists once).  one: the entry point takes a single chain.
+static inline int chain_select(const nsk_graph *g, int which, int64_t first_chain, int64_t nchains, const std::string &who, bool one = false) {
+    if (which != NSK_BUF_VALUE && which != NSK_BUF_VALUE_EVID) return nsk::fail(NSK_E_INVALID, who + ": which must be NSK_BUF_VALUE or NSK_BUF_VALUE_EVID");
+    const int64_t R = which == NSK_BUF_VALUE ? g->nchains : 1;
+    if (first_chain < 0 || nchains < 1 || first_chain >= R || nchains > R - first_chain)
+        return nsk::fail(NSK_E_INVALID, who + (one ? ": chain" : ": chains") + " outside those the handle has (the evidence chain exists once)");
+    return NSK_OK;
+}
+// ... and where the first of them lies (const char * to a reader, char * to nsk_icm, which writes)
+static inline char *chain_val(const nsk_graph *g, int which, int64_t first_chain) {
+    return which == NSK_BUF_VALUE ? (char *)g->val + (size_t)first_chain * g->chain_stride : (char *)g->val_evid;
 }
 
 #define NSK_MAX_CHAINS 1024

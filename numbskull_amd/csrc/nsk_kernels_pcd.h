@@ -24,18 +24,20 @@
 // once the items alone fill the device, so that the atomics do not multiply with the chains.
 //
 // k_pcd_update: one lane per weight slot, not for a fixed weight.  Every line is one rounded IEEE operation:
-//   m = ((double)M * 2^-32) / R              one conversion, an exact scaling, one division
-//   g = target - m;  if (normalize) g = g / n_w
-//   a = reg_param * w;  b = g - a;  c = step * b;  w = w + c
-// and gmax = the largest |g| over those weights: |g| is a non-negative finite double, whose bit pattern orders as an
-// unsigned integer -- a block maximum, then one 64-bit integer atomic max.  With `mout` the step's M is kept.
+//   m = ((double)M * 2^-32) / n              one conversion, an exact scaling, one division: the model's mean over n chains
+//   g = pos - m;  if (normalize) g = g / n_w
+//   w = step_weight(w, g, step, reg_param)   the rule of every learner (nsk_kernels_step.h)
+// pos is target[slot], or with the sums Mc of a clamped population (latent variables) ((double)Mc * 2^-32) / nclamped.
+// gmax = the largest |g| over those weights: |g| is a non-negative finite double, whose bit pattern orders as an
+// unsigned integer (step_block_max).  With `mout` the step's sums are kept: M, or Mc then M.
 //
-// Latent variables (nsk_pcd_latent_steps; at the end of the file): k_pcd_clamp writes the initial values of the evidence
-// variables into the clamped chains, k_pcd_latent_update is k_pcd_update with the clamped chains' mean as its target.
+// Latent variables (nsk_pcd_latent_steps): k_pcd_clamp writes the initial values of the evidence variables into the
+// clamped chains.
 #pragma once
 
 #include "nsk_internal.h"          // NSK_WSTATS_SHORT, NSK_WSTATS_PIECE
 #include "nsk_kernels_energy.h"
+#include "nsk_kernels_step.h"
 
 namespace nsk {
 
@@ -137,39 +139,30 @@ __global__ __launch_bounds__(NSK_BLOCK) void k_moments_piece(const MomentsArgs a
     }
 }
 
-// One PCD step's update (see the top of the file): M, target, nfac by slot; gmax this step's output, zeroed by the host;
-// mout (may be null) this step's row of the kept moments
-static __global__ __launch_bounds__(NSK_BLOCK) void k_pcd_update(const long long *M, const double *target, const double *nfac, double nchains,
-                                                                 int nweight, double *w, const uint8_t *w_fixed, int normalize,
-                                                                 double step, double reg_param, unsigned long long *gmax, long long *mout) {
-    __shared__ unsigned long long lds[NSK_BLOCK / 64];
+// One step's update (see the top of the file): M, Mc (null: target is read), target, nfac by slot; gmax this step's
+// output, zeroed by the host; mout (may be null) this step's row(s) of the kept moments
+static __global__ __launch_bounds__(NSK_BLOCK) void k_pcd_update(const long long *M, double nchains, const long long *Mc, double nclamped,
+                                                                 const double *target, const double *nfac, int nweight, double *w,
+                                                                 const uint8_t *w_fixed, int normalize, double step, double reg_param,
+                                                                 unsigned long long *gmax, long long *mout) {
     const int s = (int)(blockIdx.x * NSK_BLOCK + threadIdx.x);
     unsigned long long mag = 0ull;
     if (s < nweight) {
-        const long long S = M[s];
-        if (mout) mout[s] = S;
+        const long long S = M[s], Sc = Mc ? Mc[s] : 0;
+        if (mout) {
+            if (Mc) { mout[s] = Sc; mout[nweight + s] = S; }
+            else mout[s] = S;
+        }
         if (!w_fixed[s]) {
+            const double pos = Mc ? ((double)Sc * (1.0 / NSK_GRAD_SCALE)) / nclamped : target[s];
             const double m = ((double)S * (1.0 / NSK_GRAD_SCALE)) / nchains;
-            double gr = target[s] - m;
+            double gr = pos - m;
             if (normalize) gr = gr / nfac[s];
-            const double x = w[s];
-            const double a = reg_param * x;
-            const double b = gr - a;
-            const double c = step * b;
-            w[s] = x + c;
+            w[s] = step_weight(w[s], gr, step, reg_param);
             mag = (unsigned long long)__double_as_longlong(fabs(gr));
         }
     }
-#pragma unroll
-    for (int off = 1; off < 64; off <<= 1) { const unsigned long long o = __shfl_xor(mag, off, 64); mag = o > mag ? o : mag; }
-    if ((threadIdx.x & 63) == 0) lds[threadIdx.x >> 6] = mag;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        unsigned long long m = lds[0];
-#pragma unroll
-        for (int k = 1; k < NSK_BLOCK / 64; k++) m = lds[k] > m ? lds[k] : m;
-        if (m > 0ull) (void)__hip_atomic_fetch_max(gmax, m, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    }
+    step_block_max<NSK_BLOCK>(mag, gmax);
 }
 
 // ---- latent variables (nsk_pcd_latent_steps): a clamped and a free population of chains ----
@@ -182,46 +175,6 @@ __global__ __launch_bounds__(NSK_BLOCK) void k_pcd_clamp(VT *val, long long chai
         const int2 p = pairs[i];
         for (int r = (int)blockIdx.y; r < nchains; r += (int)gridDim.y)
             ((VT *)((char *)val + (long long)r * chain_stride))[p.x] = (VT)p.y;
-    }
-}
-
-// One step's update with the target taken from the clamped chains: k_pcd_update with target = mc, every line one
-// rounded IEEE operation:
-//   mc = ((double)Mc * 2^-32) / K;  mf = ((double)Mf * 2^-32) / (R - K);  g = mc - mf;  if (normalize) g = g / n_w
-//   a = reg_param * w;  b = g - a;  c = step * b;  w = w + c
-// gmax as k_pcd_update finds it; mout (may be null): this step's two rows of the kept moments, Mc then Mf.
-static __global__ __launch_bounds__(NSK_BLOCK) void k_pcd_latent_update(const long long *Mc, const long long *Mf, const double *nfac,
-                                                                        double nclamped, double nfree, int nweight, double *w,
-                                                                        const uint8_t *w_fixed, int normalize, double step, double reg_param,
-                                                                        unsigned long long *gmax, long long *mout) {
-    __shared__ unsigned long long lds[NSK_BLOCK / 64];
-    const int s = (int)(blockIdx.x * NSK_BLOCK + threadIdx.x);
-    unsigned long long mag = 0ull;
-    if (s < nweight) {
-        const long long Sc = Mc[s], Sf = Mf[s];
-        if (mout) { mout[s] = Sc; mout[nweight + s] = Sf; }
-        if (!w_fixed[s]) {
-            const double mc = ((double)Sc * (1.0 / NSK_GRAD_SCALE)) / nclamped;
-            const double mf = ((double)Sf * (1.0 / NSK_GRAD_SCALE)) / nfree;
-            double gr = mc - mf;
-            if (normalize) gr = gr / nfac[s];
-            const double x = w[s];
-            const double a = reg_param * x;
-            const double b = gr - a;
-            const double c = step * b;
-            w[s] = x + c;
-            mag = (unsigned long long)__double_as_longlong(fabs(gr));
-        }
-    }
-#pragma unroll
-    for (int off = 1; off < 64; off <<= 1) { const unsigned long long o = __shfl_xor(mag, off, 64); mag = o > mag ? o : mag; }
-    if ((threadIdx.x & 63) == 0) lds[threadIdx.x >> 6] = mag;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        unsigned long long m = lds[0];
-#pragma unroll
-        for (int k = 1; k < NSK_BLOCK / 64; k++) m = lds[k] > m ? lds[k] : m;
-        if (m > 0ull) (void)__hip_atomic_fetch_max(gmax, m, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     }
 }
 

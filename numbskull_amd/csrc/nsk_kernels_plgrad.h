@@ -30,11 +30,12 @@
 //
 // k_mple_update: one lane per weight slot.  S = the int64 sum of G[r][slot] over the call's chains (exact);
 //   gbar = ((double)S * 2^-32) / N           one conversion, an exact scaling, one rounded division
-//   a = reg_param * w;  b = gbar - a;  c = step * b;  w = w + c        one rounded operation each; not for a fixed weight
-// and gmax = the largest |S| over the weights that are not fixed: a block maximum, then one 64-bit integer atomic max.
+//   w = step_weight(w, gbar, step, reg_param)                          the rule of every learner (nsk_kernels_step.h); not for a fixed weight
+// and gmax = the largest |S| over the weights that are not fixed (step_block_max).
 #pragma once
 
 #include "nsk_kernels_cond.h"       // CondArgs, cond_view: what the walk reads of a handle
+#include "nsk_kernels_step.h"
 
 namespace nsk {
 
@@ -170,7 +171,6 @@ __global__ __launch_bounds__(NSK_BLOCK) void k_plgrad(const CondArgs a, const VT
 __global__ __launch_bounds__(NSK_BLOCK) void k_mple_update(const long long *G, int nchains, int nweight, double *w, const uint8_t *w_fixed,
                                                            double n, double step, double reg_param, long long *gmax,
                                                            const unsigned long long *skipped_in, long long *skipped_out) {
-    __shared__ long long lds[NSK_BLOCK / 64];
     const int s = (int)(blockIdx.x * NSK_BLOCK + threadIdx.x);
     long long mag = 0;
     if (s < nweight) {
@@ -178,28 +178,16 @@ __global__ __launch_bounds__(NSK_BLOCK) void k_mple_update(const long long *G, i
         for (int r = 0; r < nchains; r++) S += G[(long long)r * nweight + s];
         if (!w_fixed[s]) {
             const double gbar = ((double)S * (1.0 / NSK_GRAD_SCALE)) / n;
-            const double x = w[s];
-            const double a = reg_param * x;
-            const double b = gbar - a;
-            const double c = step * b;
-            w[s] = x + c;
+            w[s] = step_weight(w[s], gbar, step, reg_param);
             mag = S < 0 ? -S : S;
         }
     }
-#pragma unroll
-    for (int off = 1; off < 64; off <<= 1) { const long long o = __shfl_xor(mag, off, 64); mag = o > mag ? o : mag; }
-    if ((threadIdx.x & 63) == 0) lds[threadIdx.x >> 6] = mag;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        long long m = lds[0];
-#pragma unroll
-        for (int k = 1; k < NSK_BLOCK / 64; k++) m = lds[k] > m ? lds[k] : m;
-        if (m > 0) (void)__hip_atomic_fetch_max(gmax, m, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        if (blockIdx.x == 0) {
-            long long k = 0;
-            for (int r = 0; r < nchains; r++) k += (long long)skipped_in[r];
-            *skipped_out = k;
-        }
+    // (|S| is not negative and gmax starts at 0: the unsigned maximum stores the bits the signed one would)
+    step_block_max<NSK_BLOCK>((unsigned long long)mag, (unsigned long long *)gmax);
+    if (threadIdx.x == 0 && blockIdx.x == 0) {
+        long long k = 0;
+        for (int r = 0; r < nchains; r++) k += (long long)skipped_in[r];
+        *skipped_out = k;
     }
 }
 

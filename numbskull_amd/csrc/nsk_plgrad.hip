@@ -18,11 +18,8 @@ namespace {
 // selected variables that have one, ascending
 int plgrad_selection(const nsk_graph *g, int which, int64_t first_chain, int64_t nchains, const int64_t *vids, int64_t nvids,
                      std::vector<int32_t> &sel, const std::string &what) {
-    if (which != NSK_BUF_VALUE && which != NSK_BUF_VALUE_EVID) return fail(NSK_E_INVALID, what + ": which must be NSK_BUF_VALUE or NSK_BUF_VALUE_EVID");
-    const int64_t R = which == NSK_BUF_VALUE ? g->nchains : 1;
-    if (first_chain < 0 || nchains < 1 || first_chain >= R || nchains > R - first_chain)
-        return fail(NSK_E_INVALID, what + ": chains outside those the handle has (the evidence chain exists once)");
-    int rc = energy_whole_graph(g, what.c_str());
+    int rc = chain_select(g, which, first_chain, nchains, what);
+    if (!rc) rc = energy_whole_graph(g, what.c_str());
     if (rc) return rc;
     if (vids ? nvids < 0 : nvids != 0)
         return fail(NSK_E_INVALID, what + ": a list of variable ids with its length, or NULL with 0 for all variables");
@@ -169,18 +166,17 @@ int nsk_pl_gradient(nsk_graph *g, int which, int64_t first_chain, int64_t nchain
     if ((rc = nsk_unpack_tally(g))) return rc;
     PlgradBufs b(g);
     if ((rc = plgrad_alloc(g, b, sel, R, 0, "nsk_pl_gradient"))) return rc;
-    const char *val = which == NSK_BUF_VALUE ? (const char *)g->val + (size_t)first_chain * g->chain_stride : (const char *)g->val_evid;
     std::vector<long long> host(b.nacc);
-    hipError_t e = plgrad_enqueue(g, plgrad_args(g, b, sel.size()), b, val, (int)nchains);
+    hipError_t e = plgrad_enqueue(g, plgrad_args(g, b, sel.size()), b, chain_val(g, which, first_chain), (int)nchains);
     if (e == hipSuccess) e = hipMemcpyAsync(host.data(), b.acc, b.nacc * sizeof(long long), hipMemcpyDeviceToHost, g->stream);
     const hipError_t e2 = hipStreamSynchronize(g->stream);      // (also: the upload read the selection's vector)
     HIPCHECK(e);
     HIPCHECK(e2);
     // slots -> the caller's weight ids, as nsk_state_download maps the weights
-    const int32_t *wmap = c.wmap.empty() ? nullptr : c.wmap.data();
+    const SlotMap map(c);
     for (size_t r = 0; r < R; r++) {
         for (size_t i = 0; i < nw; i++) {
-            const long long q = host[r * nw + (wmap ? (size_t)wmap[i] : i)];
+            const long long q = host[r * nw + map.slot(i)];
             if (grad_q) grad_q[r * nw + i] = (int64_t)q;
             if (grad) grad[r * nw + i] = (double)q * (1.0 / NSK_GRAD_SCALE);
         }
@@ -195,9 +191,8 @@ int nsk_mple_steps(nsk_graph *g, int which, int64_t first_chain, int64_t nchains
     std::vector<int32_t> sel;
     int rc = plgrad_selection(g, which, first_chain, nchains, vids, nvids, sel, "nsk_mple_steps");
     if (rc) return rc;
-    if (nsteps < 1 || nsteps > 65536) return fail(NSK_E_INVALID, "nsk_mple_steps: nsteps must lie in [1, 65536]");
-    if (!std::isfinite(step) || !std::isfinite(decay) || !std::isfinite(reg_param) || reg_param < 0.0)
-        return fail(NSK_E_INVALID, "nsk_mple_steps: step, decay and reg_param must be finite, reg_param not negative");
+    if ((rc = refuse(check_nsteps("nsk_mple_steps", nsteps, 65536)))) return rc;
+    if ((rc = refuse(check_rates("nsk_mple_steps", step, decay, reg_param)))) return rc;
     const Compiled &c = g->c;
     const size_t R = (size_t)nchains, T = (size_t)nsteps;
     for (size_t t = 0; t < T; t++) { if (gmax) gmax[t] = 0; if (skipped) skipped[t] = 0; }
@@ -208,7 +203,7 @@ int nsk_mple_steps(nsk_graph *g, int which, int64_t first_chain, int64_t nchains
     if ((rc = nsk_unpack_tally(g))) return rc;
     PlgradBufs b(g);
     if ((rc = plgrad_alloc(g, b, sel, R, T, "nsk_mple_steps"))) return rc;
-    const char *val = which == NSK_BUF_VALUE ? (const char *)g->val + (size_t)first_chain * g->chain_stride : (const char *)g->val_evid;
+    const char *val = chain_val(g, which, first_chain);
     const CondArgs a = plgrad_args(g, b, sel.size());
     const int nw = (int)c.nweight;
     const double n = (double)sel.size() * (double)nchains;

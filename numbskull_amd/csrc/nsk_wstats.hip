@@ -111,33 +111,17 @@ static int wstats_plan_build(nsk_graph *g, NskWstatsPlan &plan, const int32_t *s
     const NskWstats &ws = g->wstats;
     NskWstatsPlan p;
     p.ncols = ncols;
-    std::vector<std::vector<uint64_t>> bylen(NSK_WSTATS_SHORT);       // first factor << 32 | column, per length
-    std::vector<uint4> pieces, multi;
-    for (int64_t j = 0; j < ncols; j++) {
-        const size_t s = (size_t)slot[j];
-        const uint32_t off = ws.wf_off[s], len = ws.wf_off[s + 1] - off;
-        if (len == 0) continue;                     // (reads 0: the output is zeroed where it is allocated)
-        if (len <= NSK_WSTATS_SHORT) { bylen[len - 1].push_back((uint64_t)(uint32_t)ws.wf_first[s] << 32 | (uint64_t)j); continue; }
-        const uint32_t npc = (len + NSK_WSTATS_PIECE - 1) / NSK_WSTATS_PIECE;
-        if (npc == 1) { pieces.push_back(make_uint4(off, len, (uint32_t)j, 0u)); continue; }
-        multi.push_back(make_uint4((uint32_t)p.npartial, npc, (uint32_t)j, 0u));
-        for (uint32_t k = 0; k < npc; k++)
-            pieces.push_back(make_uint4(off + k * NSK_WSTATS_PIECE, std::min<uint32_t>(NSK_WSTATS_PIECE, len - k * NSK_WSTATS_PIECE), (uint32_t)(p.npartial + k), 1u));
-        p.npartial += npc;
-    }
-    std::vector<uint2> shorts;
-    for (int k = 0; k < NSK_WSTATS_SHORT; k++) {
-        std::sort(bylen[(size_t)k].begin(), bylen[(size_t)k].end());
-        for (uint64_t key : bylen[(size_t)k]) { const size_t s = (size_t)slot[(size_t)(key & 0xffffffffu)]; shorts.push_back(make_uint2(ws.wf_off[s], (uint32_t)(key & 0xffffffffu))); }
-        p.len_end[k] = (unsigned int)shorts.size();
-        std::vector<uint64_t>().swap(bylen[(size_t)k]);
-    }
-    p.nshort = (int64_t)shorts.size(); p.npiece = (int64_t)pieces.size(); p.nmulti = (int64_t)multi.size();
+    // the cut and its items (nsk_steps.h; a weight without a factor reads 0: the output is zeroed where it is allocated)
+    static_assert(sizeof(WeightCutShort) == sizeof(uint2) && sizeof(WeightItem) == sizeof(uint4), "the items are uploaded as they are");
+    const WeightCut cut = weight_cut(ws.wf_off, ws.wf_first, slot, (size_t)ncols, NSK_WSTATS_SHORT);
+    const WstatsItems it = wstats_items(cut, NSK_WSTATS_PIECE);
+    std::copy(cut.len_end.begin(), cut.len_end.end(), p.len_end);
+    p.nshort = (int64_t)cut.shorts.size(); p.npiece = (int64_t)it.pieces.size(); p.nmulti = (int64_t)it.multi.size(); p.npartial = it.npartial;
     NskRollback rb(g->mem, nsk_free_raw);
     int rc = NSK_OK;
-    if (p.nshort) rc = dev_upload(g, &p.shorts, shorts);
-    if (!rc && p.npiece) rc = dev_upload(g, &p.pieces, pieces);
-    if (!rc && p.nmulti) rc = dev_upload(g, &p.multi, multi);
+    if (p.nshort) rc = dev_upload(g, (WeightCutShort **)&p.shorts, cut.shorts);
+    if (!rc && p.npiece) rc = dev_upload(g, (WeightItem **)&p.pieces, it.pieces);
+    if (!rc && p.nmulti) rc = dev_upload(g, (WeightItem **)&p.multi, it.multi);
     if (!rc && hipStreamSynchronize(g->stream) != hipSuccess) rc = fail(NSK_E_DEVICE, "hipStreamSynchronize failed");
     if (!rc) rc = wstats_partial_ensure(g, p, chains);
     if (rc) {
@@ -163,11 +147,8 @@ extern "C" {
 int nsk_weight_stats(nsk_graph *g, int which, int64_t first_chain, int64_t nchains, int scaled, double *out) {
     if (!g) return fail(NSK_E_INVALID, "null graph");
     if (!out) return fail(NSK_E_INVALID, "null argument");
-    if (which != NSK_BUF_VALUE && which != NSK_BUF_VALUE_EVID) return fail(NSK_E_INVALID, "nsk_weight_stats: which must be NSK_BUF_VALUE or NSK_BUF_VALUE_EVID");
-    const int64_t R = which == NSK_BUF_VALUE ? g->nchains : 1;
-    if (first_chain < 0 || nchains < 1 || first_chain >= R || nchains > R - first_chain)
-        return fail(NSK_E_INVALID, "nsk_weight_stats: chains outside those the handle has (the evidence chain exists once)");
-    int rc = energy_whole_graph(g, "nsk_weight_stats");
+    int rc = chain_select(g, which, first_chain, nchains, "nsk_weight_stats");
+    if (!rc) rc = energy_whole_graph(g, "nsk_weight_stats");
     if (rc) return rc;
     const Compiled &c = g->c;
     if (c.nweight == 0) return NSK_OK;
@@ -191,8 +172,7 @@ int nsk_weight_stats(nsk_graph *g, int which, int64_t first_chain, int64_t nchai
         HIPCHECK(hipMemsetAsync(result, 0, n * sizeof(double), g->stream));     // (weights without a factor are never written)
         ws.result = result; ws.result_chains = (int)nchains;
     }
-    const char *val = which == NSK_BUF_VALUE ? (const char *)g->val + (size_t)first_chain * g->chain_stride : (const char *)g->val_evid;
-    if ((rc = nsk_wstats_enqueue(g, ws.all, val, (int)nchains, g->packed_sweeps > 0, scaled != 0, ws.result, c.nweight))) return rc;
+    if ((rc = nsk_wstats_enqueue(g, ws.all, chain_val(g, which, first_chain),(int)nchains, g->packed_sweeps > 0, scaled != 0, ws.result, c.nweight))) return rc;
     HIPCHECK(hipMemcpyAsync(out, ws.result, (size_t)nchains * (size_t)c.nweight * sizeof(double), hipMemcpyDeviceToHost, g->stream));
     HIPCHECK(hipStreamSynchronize(g->stream));
     return NSK_OK;

@@ -908,6 +908,33 @@ class FactorGraph(object):
             return gq, (skipped if _all_copies(var_copy) else int(skipped[0]))
         return gq.astype(np.float64) * 2.0 ** -32
 
+    # ------------------------------------------------------------------ what the full-batch learners share
+    @staticmethod
+    def _learn_steps(what, epochs, stepsize, decay, reg_param, max_epochs=65536, also=(False, "")):
+        """(epochs, stepsize, decay, reg_param) converted and checked: epochs in [1, max_epochs] (None: the learner's own
+        bound covers them), then ``also`` = (fails, message), a learner's own bound, then the rates"""
+        epochs = int(epochs)
+        if max_epochs is not None and (epochs < 1 or epochs > max_epochs):
+            raise ValueError("%s: epochs must lie in [1, %d]" % (what, max_epochs))
+        if also[0]:
+            raise ValueError(also[1])
+        stepsize, decay, reg_param = float(stepsize), float(decay), float(reg_param)
+        if not (np.isfinite(stepsize) and np.isfinite(decay) and np.isfinite(reg_param)) or reg_param < 0:
+            raise ValueError("%s: stepsize, decay and reg_param must be finite, reg_param not negative" % what)
+        return epochs, stepsize, decay, reg_param
+
+    def _learn_target(self, what, target):
+        """an explicit target checked, None: the statistics of the evidence chain"""
+        if target is None:
+            return self.weight_moments(evidence_chain=True)
+        target = np.ascontiguousarray(target, np.float64)
+        if target.shape != self.weight.shape or not np.isfinite(target).all():
+            raise ValueError("%s: target is finite float64 (nweight,) = (%d,)" % (what, self.weight.shape[0]))
+        return target
+
+    def _factors_per_weight(self):
+        return np.bincount(self.factor["weightId"].astype(np.int64), minlength=self.weight.shape[0]).astype(np.int64)
+
     def learn_mple(self, epochs, stepsize, decay=1.0, reg_param=0.0, var_ids=None, var_copy=0, weight_copy=0,
                    evidence_chain=False):
         """Maximum pseudo-likelihood learning on the device (nsk_mple_steps): ``epochs`` steps of gradient ascent on the
@@ -923,12 +950,7 @@ class FactorGraph(object):
         each step started from (without the penalty); ``skipped`` -- int64 ``(epochs,)``, the variables skipped in each
         step, summed over the examples (see ``pl_gradient``); ``n`` -- selected variables with a position x examples
         (``diagnostics.mple_step`` is the update in numpy)."""
-        epochs = int(epochs)
-        if epochs < 1 or epochs > 65536:
-            raise ValueError("learn_mple: epochs must lie in [1, 65536]")
-        stepsize, decay, reg_param = float(stepsize), float(decay), float(reg_param)
-        if not (np.isfinite(stepsize) and np.isfinite(decay) and np.isfinite(reg_param)) or reg_param < 0:
-            raise ValueError("learn_mple: stepsize, decay and reg_param must be finite, reg_param not negative")
+        epochs, stepsize, decay, reg_param = self._learn_steps("learn_mple", epochs, stepsize, decay, reg_param)
         ids = self._pl_selection(var_ids, var_copy, evidence_chain, "learn_mple")
         L, h = _lib.lib(), self._engine()
         if _all_copies(var_copy):
@@ -1015,13 +1037,8 @@ class FactorGraph(object):
         ``target`` is None, the dict gains ``clamped`` and ``moments`` is ``(epochs, 2, nweight)``: the clamped rows' sums, then the
         free rows'."""
         epochs, sweeps = int(epochs), int(sweeps)
-        if epochs < 1 or epochs > 65536:
-            raise ValueError("learn_pcd: epochs must lie in [1, 65536]")
-        if sweeps < 1 or epochs * sweeps > 2 ** 31 - 1:
-            raise ValueError("learn_pcd: sweeps must be at least 1 and epochs x sweeps at most 2**31 - 1")
-        stepsize, decay, reg_param = float(stepsize), float(decay), float(reg_param)
-        if not (np.isfinite(stepsize) and np.isfinite(decay) and np.isfinite(reg_param)) or reg_param < 0:
-            raise ValueError("learn_pcd: stepsize, decay and reg_param must be finite, reg_param not negative")
+        epochs, stepsize, decay, reg_param = self._learn_steps("learn_pcd", epochs, stepsize, decay, reg_param, also=(
+            sweeps < 1 or epochs * sweeps > 2 ** 31 - 1, "learn_pcd: sweeps must be at least 1 and epochs x sweeps at most 2**31 - 1"))
         nw = self.weight.shape[0]
         clamped = int(clamped)
         if clamped != 0:
@@ -1031,35 +1048,22 @@ class FactorGraph(object):
                 raise ValueError("learn_pcd: with clamped rows the target is their statistics; target must be None")
             if 2 * epochs * sweeps > 2 ** 31 - 1:
                 raise ValueError("learn_pcd: 2 x epochs x sweeps must be at most 2**31 - 1 with clamped rows")
-            L, h = _lib.lib(), self._engine()
-            nchains = self._push_chains(weight_copy, count=False)
-            gmax = np.zeros(epochs, np.float64)
-            rows = np.zeros((epochs, 2, nw), np.int64) if moments else None
-            _lib.check(L.nsk_pcd_latent_steps(h, clamped, int(bool(clamp)), epochs, sweeps, int(bool(sample_evidence)), stepsize,
-                                              decay, reg_param, int(bool(normalize)), _lib.ptr(gmax), _lib.ptr(rows)))
-            self._pull_chains(count=False)
-            self._pull(0, weight_copy, values=False, count=False)
-            out = {"grad_max": gmax, "target": None, "chains": nchains, "clamped": clamped,
-                   "factors_per_weight": np.bincount(self.factor["weightId"].astype(np.int64), minlength=nw).astype(np.int64)}
-            if moments:
-                out["moments"] = rows
-            return out
-        if target is not None:
-            target = np.ascontiguousarray(target, np.float64)
-            if target.shape != (nw,) or not np.isfinite(target).all():
-                raise ValueError("learn_pcd: target is finite float64 (nweight,) = (%d,)" % nw)
         else:
-            target = self.weight_moments(evidence_chain=True)
+            target = self._learn_target("learn_pcd", target)
         L, h = _lib.lib(), self._engine()
         nchains = self._push_chains(weight_copy, count=False)
         gmax = np.zeros(epochs, np.float64)
-        rows = np.zeros((epochs, nw), np.int64) if moments else None
-        _lib.check(L.nsk_pcd_steps(h, _lib.ptr(target), epochs, sweeps, int(bool(sample_evidence)), stepsize, decay, reg_param,
-                                   int(bool(normalize)), _lib.ptr(gmax), _lib.ptr(rows)))
+        rows = np.zeros((epochs, 2, nw) if clamped else (epochs, nw), np.int64) if moments else None
+        tail = (epochs, sweeps, int(bool(sample_evidence)), stepsize, decay, reg_param, int(bool(normalize)), _lib.ptr(gmax), _lib.ptr(rows))
+        if clamped:
+            _lib.check(L.nsk_pcd_latent_steps(h, clamped, int(bool(clamp)), *tail))
+        else:
+            _lib.check(L.nsk_pcd_steps(h, _lib.ptr(target), *tail))
         self._pull_chains(count=False)
         self._pull(0, weight_copy, values=False, count=False)
-        out = {"grad_max": gmax, "target": target, "chains": nchains,
-               "factors_per_weight": np.bincount(self.factor["weightId"].astype(np.int64), minlength=nw).astype(np.int64)}
+        out = {"grad_max": gmax, "target": target, "chains": nchains, "factors_per_weight": self._factors_per_weight()}
+        if clamped:
+            out["clamped"] = clamped
         if moments:
             out["moments"] = rows
         return out
@@ -1517,20 +1521,13 @@ class FactorGraph(object):
         ``factors_per_weight``; with ``moments=True`` also ``moments`` -- int64 ``(epochs, nweight)``
         (``diagnostics.bp_moment_counts``; ``diagnostics.pcd_step`` with ``R=1`` is the update in numpy)."""
         epochs, iters = int(epochs), int(iters)
-        if epochs < 1 or epochs > 4096 or iters < 1 or iters > 4096 or epochs * iters > 65536:
-            raise ValueError("learn_bp: epochs and iters must lie in [1, 4096], epochs x iters at most 65536")
-        stepsize, decay, reg_param = float(stepsize), float(decay), float(reg_param)
-        if not (np.isfinite(stepsize) and np.isfinite(decay) and np.isfinite(reg_param)) or reg_param < 0:
-            raise ValueError("learn_bp: stepsize, decay and reg_param must be finite, reg_param not negative")
+        epochs, stepsize, decay, reg_param = self._learn_steps("learn_bp", epochs, stepsize, decay, reg_param, None, (
+            epochs < 1 or epochs > 4096 or iters < 1 or iters > 4096 or epochs * iters > 65536,
+            "learn_bp: epochs and iters must lie in [1, 4096], epochs x iters at most 65536"))
         if _all_copies(var_copy):
             raise ValueError('learn_bp serves one state: var_copy="all" is for the sampler')
         nw = self.weight.shape[0]
-        if target is not None:
-            target = np.ascontiguousarray(target, np.float64)
-            if target.shape != (nw,) or not np.isfinite(target).all():
-                raise ValueError("learn_bp: target is finite float64 (nweight,) = (%d,)" % nw)
-        else:
-            target = self.weight_moments(evidence_chain=True)
+        target = self._learn_target("learn_bp", target)
         L, h = _lib.lib(), self._engine()
         self._push(var_copy, weight_copy)
         _lib.check(L.nsk_bp_setup(h, _lib.BUF_VALUE, 0, int(bool(sample_evidence)), None))
@@ -1545,7 +1542,7 @@ class FactorGraph(object):
         finally:
             L.nsk_bp_clear(h)
         out = {"grad_max": gmax, "iters": np.abs(ran), "converged": ran > 0, "residual": residual, "skipped": skipped,
-               "target": target, "factors_per_weight": np.bincount(self.factor["weightId"].astype(np.int64), minlength=nw).astype(np.int64)}
+               "target": target, "factors_per_weight": self._factors_per_weight()}
         if moments:
             out["moments"] = rows
         return out

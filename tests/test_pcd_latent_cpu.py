@@ -136,6 +136,21 @@ def test_the_grids_of_the_batched_launches():
         assert np.array_equal(_bits(pl.equal_values(og, x)), _bits(pcd.factor_values(og, x)))
 
 
+def test_the_block_edge_case_is_lively():
+    """tests/test_pcd_latent_gpu.py test_the_update_across_a_block_edge: the mirror alone moves a free weight, its two
+    rows of moments differ, the moments differ between the steps, and weights on both sides of the edge move"""
+    fg, og, color = _host_case(pl.edge_graph(), True)
+    R, K = pl.EDGE_RK
+    vv, _, w0, _ = og.initial_state()
+    free = ~og.weight["isFixed"].astype(bool)
+    assert len(w0) == pl.EDGE_WEIGHTS == 257 and not free[list(pl.EDGE_FIXED)].any() and free.sum() == 257 - len(pl.EDGE_FIXED)
+    x, sweep = pl.disturbed(og, color, pl.SEED, [vv] * R, w0)
+    m = pl.Run(og, color, pl.SEED, x, w0, K, pl.EDGE_STEPS, 1, 1, pcd.stepsize(1), pl.DECAY, 0.01, 1, sweep0=sweep)
+    assert (m.w[free] != w0[free]).any() and (m.moments[:, 0] != m.moments[:, 1]).any() and (m.moments[0] != m.moments[1]).any()
+    assert (m.w[:256] != w0[:256]).any() and m.w[256] != w0[256]
+    assert np.array_equal(_bits(m.w[~free]), _bits(w0[~free]))
+
+
 def test_the_clamp_cases_are_lively():
     """tests/test_pcd_latent_gpu.py test_clamp: 5 chains, 2 clamped, with and without the reset"""
     for clamp in (True, False):

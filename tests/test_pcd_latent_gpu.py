@@ -168,6 +168,25 @@ def test_which_launches_the_parity_graphs_take(name):
         assert one > 0 and two == (one if pl.BATCHED[name] else 2 * one), (name, se, one, two)
 
 
+def test_the_update_across_a_block_edge():
+    """pl.edge_graph(): NSK_BLOCK + 1 = 257 weights, so k_pcd_update's second block holds slot 256 alone; slot 255, the first
+    block's last lane, and two more are fixed.  2 clamped chains + 1 free one, 2 steps: weights, gmax and both rows of
+    moments are the mirror's bit for bit, and weights on both sides of the edge move (tests/test_pcd_latent_cpu.py: the
+    mirror alone says so)."""
+    R, K = pl.EDGE_RK
+    H = Handle(None, R, graph=pl.edge_graph(), hbv=True)
+    try:
+        fixed = list(pl.EDGE_FIXED)
+        assert H.nw == pl.EDGE_WEIGHTS == 257 and not H.free[fixed].any() and H.free[256]
+        assert np.array_equal(H.fg.weight_slots()[fixed], fixed)        # a fixed weight's slot is its id
+        x, sweep = H.disturb()
+        m = _one_call(H, x, H.w0, sweep, K, pl.EDGE_STEPS, 1, 1, 0.01, "block edge")
+        assert (m.moments[0] != m.moments[1]).any(), "the case stands still"
+        assert (m.w[:256] != H.w0[:256]).any() and m.w[256] != H.w0[256]
+    finally:
+        H.close()
+
+
 # ------------------------------------------------------------------------------------------------------- 2. the launches
 @pytest.mark.parametrize("RK", [(4, 2), (3, 1)], ids=lambda rk: "R%d_K%d" % rk)
 def test_both_launch_paths_by_their_launch_counts(RK, monkeypatch):

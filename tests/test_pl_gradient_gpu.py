@@ -401,6 +401,47 @@ def test_mple_steps_equal_the_host_loop_bit_for_bit(golden, name, reg):
     assert np.array_equal(_bits(fg.weight_value[0]), _bits(w))
 
 
+def test_mple_update_across_a_block_edge():
+    """tests/pcd_latent.py edge_graph(): NSK_BLOCK + 1 = 257 weights, so k_mple_update's second block holds slot 256 alone;
+    slot 255, the first block's last lane, and two more are fixed.  Two chains, each an example, all variables, 2 steps:
+    weights, grad_max and skips are the host loop's bit for bit, weights on both sides of the edge move and the sums differ
+    between the steps."""
+    import pcd_latent
+    g = pcd_latent.edge_graph()
+    _, fg = session(g, seed=SEED, head_by_vid=True, chains=2)
+    og = oracle_of(fg, True)
+    # a second example: other values for the variables that are not evidence
+    card, ev = fg.variable["cardinality"], fg.variable["isEvidence"] != 0
+    fg.var_value[1] = np.where(ev, fg.var_value[1], np.random.default_rng(3).integers(0, card))
+    states = fg.var_value.copy()
+    assert (states[0] != states[1]).any()
+    ids = np.arange(len(fg.variable), dtype=np.int64)
+    twin = plgrad.Twin(fg, og, ids)
+    fixed = fg.weight["isFixed"].astype(bool)
+    edge = list(pcd_latent.EDGE_FIXED)
+    assert len(fixed) == pcd_latent.EDGE_WEIGHTS == 257 and fixed[edge].all() and fixed.sum() == len(edge) and not fixed[256]
+    nsteps, step, decay, reg = 2, 0.1, 0.9, 0.01
+    w0 = fg.weight_value[0].astype(np.float64).copy()
+    w, n, st = w0.copy(), 2 * len(twin.ids), step
+    want_gmax, want_skipped, sums = np.zeros(nsteps), np.zeros(nsteps, np.int64), []
+    for t in range(nsteps):
+        parts = [twin.counts(x, w) for x in states]
+        s = parts[0][0] + parts[1][0]
+        want_skipped[t] = parts[0][1] + parts[1][1]
+        want_gmax[t] = float(np.abs(s[~fixed]).max()) * plgrad.Q / n
+        sums.append(s)
+        w = mple_step(w, fixed, s, n, st, reg)
+        st = st * decay
+    res = fg.learn_mple(nsteps, step, decay=decay, reg_param=reg, var_ids=ids, var_copy="all")
+    assert np.array_equal(fg.weight_slots()[edge], edge)                # a fixed weight's slot is its id
+    assert res["n"] == n
+    assert np.array_equal(_bits(fg.weight_value[0]), _bits(w)), np.nonzero(_bits(fg.weight_value[0]) != _bits(w))[0][:8]
+    assert np.array_equal(_bits(res["grad_max"]), _bits(want_gmax)) and np.array_equal(res["skipped"], want_skipped)
+    assert np.array_equal(_bits(w[fixed]), _bits(w0[fixed])) and want_gmax.min() > 0
+    assert (w[:256] != w0[:256]).any() and w[256] != w0[256] and (sums[0] != sums[1]).any(), "the case stands still"
+    fg.close()
+
+
 # ---------------------------------------------------------------------------------------------- G
 def test_mple_learns_the_planted_pairs_from_four_chains():
     """2000 planted pairs as four chains of a 500-pair graph -- four independent draws of it; 400 plain steps from
