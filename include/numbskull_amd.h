@@ -324,6 +324,14 @@ int nsk_icm(nsk_graph *g, int which, int64_t first_chain, int64_t nchains, int64
  *   nsk_bp_download  what = NSK_BP_THETA, NSK_BP_FACTOR_BELIEFS (computed by the call; both table_off's layout),
  *                    NSK_BP_F2V, NSK_BP_V2F (msg_off's layout).
  *   nsk_bp_clear     frees the set-up (NSK_OK without one).
+ *   nsk_bp_select    a handle holds TWO resident set-ups, slots 0 and 1, and one of them is selected: slot 0 on a new
+ *                    handle.  Every nsk_bp_* call above and below -- setup, layout, run, beliefs, download, refresh,
+ *                    moments, learn_steps, clear -- acts on the selected set-up and on nothing else; the other keeps its
+ *                    tables, messages, beliefs and bytes.  A slot outside {0, 1} is NSK_E_INVALID.  The call moves no
+ *                    data and waits for nothing.  nsk_bp_clear frees only the selected set-up, nsk_graph_destroy both;
+ *                    nsk_graph_info.device_bytes counts both, nsk_bp_info.device_bytes each its own.  The two share
+ *                    nothing; only nsk_bp_latent_steps reads both.
+ *   nsk_bp_selected  the selected slot.
  * Run, beliefs, layout and download without a set-up are NSK_E_INVALID.  `which` and the handles refused follow
  * nsk_log_potential; a tally kept in the value bytes is first brought back to its array, as in nsk_icm.  Nothing of the
  * handle changes: values, tallies, weights and the generator stay.  The set-up is resident and counted in
@@ -349,11 +357,13 @@ int nsk_bp_run(nsk_graph *g, int64_t max_iters, double damping, double tol, int6
 int nsk_bp_beliefs(nsk_graph *g, const int64_t *vids, int64_t nvids, double *out /* total */);
 int nsk_bp_download(nsk_graph *g, int what, double *out);
 int nsk_bp_clear(nsk_graph *g);
+int nsk_bp_select(nsk_graph *g, int slot);
+int nsk_bp_selected(nsk_graph *g);
 
 /* Learning by belief propagation (FactorGraph.bp_weight_moments / learn_bp): maximum-likelihood learning whose model
  * expectations come from the factor beliefs of the resident set-up above instead of from chains -- exact wherever BP is
  * exact (the free variables form a forest), the Bethe approximation on graphs with cycles, without sampling noise.
- * Every call here acts on the resident set-up and is NSK_E_INVALID without one, as nsk_bp_run is.
+ * Every call here acts on the selected resident set-up (nsk_bp_select) and is NSK_E_INVALID without one, as nsk_bp_run is.
  * Feature table: feat_f(a) = eval_factor exactly as the set-up asks it for theta_f(a), without the weight, so that
  * theta_f(a) = w[weight of f] * feat_f(a) is ONE rounded product and reproduces the set-up's own theta bit for bit.  The
  * set-up fills it in the launch that fills theta (no further launch), owns it (nsk_bp_clear and a replacing set-up free
@@ -390,8 +400,29 @@ int nsk_bp_clear(nsk_graph *g);
  *   outside what nsk_bp_run accepts, warm or normalize other than 0 or 1, a step, decay or reg_param that is not
  *   finite, reg_param < 0.  NSK_E_RANGE as nsk_bp_moments.  nweight == 0 is NSK_OK with nothing done.  The sums, the
  *   target, the factor counts, Z_f and the per-step outputs live for the call only; NSK_E_NOMEM names the bytes.
- * Latent-variable learning needs the difference of two set-ups (evidence clamped and free) and is not served here:
- * nsk_pcd_latent_steps does that with chains.  Every launch honours NSK_BP_GRID_CAP. */
+ * nsk_bp_latent_steps: learning with LATENT variables, the gradient "statistics with the evidence held - statistics
+ *   with everything free" from two set-ups instead of from two populations of chains (nsk_pcd_latent_steps).  Slot 0 is
+ *   the positive phase, by convention set up with sample_evidence = 0 (evidence held, latent variables free), slot 1 the
+ *   negative phase, set up with sample_evidence = 1; both must be set up, otherwise NSK_E_INVALID.  There is no target.
+ *   For t = 0 .. nsteps - 1, on the handle's stream without a host wait:
+ *   1. both set-ups refreshed from the device weights; with warm == 0 both message sets back to 1 / card;
+ *   2. up to iters_per_step iterations of both, each set-up with its own row of residuals and its own early exit: one
+ *      that has reached tol stops while the other goes on; iteration 0 of every step always runs for both;
+ *   3. the Bethe moments of slot 0 into Mc and of slot 1 into M, the rule of nsk_bp_moments bit for bit, a skip counter
+ *      per set-up;
+ *   4. nsk_pcd_latent_steps' update launch with one chain a side: pos = (Mc * 2^-32) / 1.0, m = (M * 2^-32) / 1.0,
+ *      g = pos - m, then as nsk_pcd_steps; step_t = step * decay^t formed on the host in t order;
+ *      numbskull_amd.diagnostics.pcd_latent_step with K = Rf = 1.
+ *   After the last step both set-ups are refreshed once more, then the call synchronises, once.  The two phases of a
+ *   step share their launches (gridDim.y = 2, the grid what the larger set-up needs): a step costs the launches of one
+ *   nsk_bp_learn_steps step, and each set-up computes what it computes alone, bit for bit.  In every output with an axis
+ *   of 2, index 0 is the clamped set-up and index 1 the free one: iters[nsteps x 2], residual[nsteps x 2 x
+ *   iters_per_step], skipped[nsteps x 2], moments[nsteps x 2 x nweight] (the clamped row first); gmax[nsteps].  Each may be
+ *   NULL.  NSK_E_INVALID, before anything is allocated or enqueued: what nsk_bp_learn_steps refuses, without the target.
+ *   NSK_E_RANGE as nsk_bp_moments.  nweight == 0 is NSK_OK with nothing done.  The sums, the factor counts, Z_f and the
+ *   per-step outputs live for the call only; NSK_E_NOMEM names the bytes.  The weights change as in nsk_bp_learn_steps;
+ *   the selected slot is the same after the call as before.
+ * Every launch honours NSK_BP_GRID_CAP. */
 int nsk_bp_refresh(nsk_graph *g);
 int nsk_bp_moments(nsk_graph *g, int64_t *moments /* nweight */, int64_t *skipped /* may be NULL */);
 int nsk_bp_learn_steps(nsk_graph *g, const double *target /* nweight, caller's ids */,
@@ -399,6 +430,11 @@ int nsk_bp_learn_steps(nsk_graph *g, const double *target /* nweight, caller's i
                        double step, double decay, double reg_param, int normalize,
                        double *gmax /* nsteps */, int64_t *iters /* nsteps */, double *residual /* nsteps x iters_per_step */,
                        int64_t *moments /* nsteps x nweight */, int64_t *skipped /* nsteps */);
+int nsk_bp_latent_steps(nsk_graph *g, int64_t nsteps, int64_t iters_per_step, double damping, double tol, int warm,
+                        double step, double decay, double reg_param, int normalize,
+                        double *gmax /* nsteps */, int64_t *iters /* nsteps x 2 */,
+                        double *residual /* nsteps x 2 x iters_per_step */,
+                        int64_t *moments /* nsteps x 2 x nweight */, int64_t *skipped /* nsteps x 2 */);
 
 /* Pseudo-likelihood gradient and maximum pseudo-likelihood learning (FactorGraph.pl_gradient / learn_mple): the
  * derivative of sum_v log P(x_v | every other variable) over a selection of variables with respect to every weight, and

@@ -35,7 +35,7 @@ SYMBOLS = (
     "nsk_conditionals", "nsk_trace_conditionals", "nsk_trace_download_conditionals", "nsk_icm", "nsk_tempered_sweeps",
     "nsk_smc_sweeps", "nsk_pt_sweeps", "nsk_pl_gradient", "nsk_mple_steps", "nsk_weight_moments", "nsk_pcd_steps", "nsk_pcd_latent_steps",
     "nsk_bp_setup", "nsk_bp_layout", "nsk_bp_run", "nsk_bp_beliefs", "nsk_bp_download", "nsk_bp_clear",
-    "nsk_bp_refresh", "nsk_bp_moments", "nsk_bp_learn_steps",
+    "nsk_bp_refresh", "nsk_bp_moments", "nsk_bp_learn_steps", "nsk_bp_select", "nsk_bp_selected", "nsk_bp_latent_steps",
     "nsk_trace_ess", "nsk_trace_autocov_counts", "nsk_trace_pair_counts",
     "nsk_trace_value_autocov_counts", "nsk_trace_value_ess", "nsk_trace_value_pair_counts",
     "nsk_selftest_exp", "nsk_selftest_philox", "nsk_selftest_stream", "nsk_device_count", "nsk_last_error", "nsk_version",
@@ -215,6 +215,10 @@ def lib():
         L.nsk_bp_moments.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(C.c_int64)]
         L.nsk_bp_learn_steps.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_double, C.c_double, C.c_int, C.c_double,
                                          C.c_double, C.c_double, C.c_int] + [C.c_void_p] * 5
+        L.nsk_bp_select.argtypes = [C.c_void_p, C.c_int]
+        L.nsk_bp_selected.argtypes = [C.c_void_p]
+        L.nsk_bp_latent_steps.argtypes = [C.c_void_p, C.c_int64, C.c_int64, C.c_double, C.c_double, C.c_int, C.c_double,
+                                          C.c_double, C.c_double, C.c_int] + [C.c_void_p] * 5
         L.nsk_pl_gradient.argtypes = [C.c_void_p, C.c_int, C.c_int64, C.c_int64, C.c_void_p, C.c_int64] + [C.c_void_p] * 3
         L.nsk_mple_steps.argtypes = [C.c_void_p, C.c_int, C.c_int64, C.c_int64, C.c_void_p, C.c_int64, C.c_int64,
                                      C.c_double, C.c_double, C.c_double, C.c_void_p, C.c_void_p]

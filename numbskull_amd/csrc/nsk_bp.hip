@@ -7,6 +7,9 @@
 // table the set-up keeps, nsk_bp_moments reduces the expected per-weight statistics under the factor beliefs in int64 fixed
 // point, and nsk_bp_learn_steps enqueues (refresh, iterations, moments, nsk_pcd.hip's update with one chain) per step
 // without a host wait, as nsk_pcd_steps does; the sums, the target and the per-step outputs live for the call only.
+// A handle holds two set-ups (nsk_bp_select swaps the selected one in; everything above acts on it alone), and
+// nsk_bp_latent_steps learns from their difference, evidence clamped and free: the same steps with both set-ups in the
+// same launches (the pair kernels of nsk_kernels_bp.h) and nsk_pcd_latent_steps' update with one chain a side.
 #include <hip/hip_runtime.h>
 
 #include <cmath>
@@ -35,8 +38,7 @@ static void bp_free(nsk_graph *g) {
     b = NskBp();
 }
 
-static BpArgs bp_args(const nsk_graph *g) {
-    const NskBp &b = g->bp;
+static BpArgs bp_args(const nsk_graph *g, const NskBp &b) {
     BpArgs a = {};
     a.f_rec = (const uint4 *)g->f_rec; a.mrec = (const int2 *)b.mrec; a.pm_off = b.pm_off;
     a.slot_off = b.slot_off; a.slot_rec = (const int2 *)b.slot_rec;
@@ -49,6 +51,10 @@ static BpArgs bp_args(const nsk_graph *g) {
     a.nedge = (int32_t)b.info.nedges; a.nvlist = b.nvlist;
     return a;
 }
+static BpArgs bp_args(const nsk_graph *g) { return bp_args(g, g->bp); }       // the selected set-up's
+
+// the set-up of a slot, whichever is selected
+static NskBp &bp_slot(nsk_graph *g, int slot) { return slot == g->bp_slot ? g->bp : g->bp_other; }
 
 // member positions a function reads whatever its arity says (nsk_energy.hip energy_check_factors)
 static int64_t bp_need(int fn) {
@@ -112,6 +118,43 @@ static hipError_t bp_moments_enqueue(nsk_graph *g, const BpArgs &a, double *zf, 
     if (e != hipSuccess || a.nfactor == 0) return e;
     k_bp_fnorm<<<dim3(bp_blocks(a.nfactor)), dim3(NSK_BLOCK), 0, g->stream>>>(a, zf, skipped);
     k_bp_moments<<<dim3(bp_blocks(a.ntable)), dim3(NSK_BLOCK), 0, g->stream>>>(a, zf, M);
+    return hipGetLastError();
+}
+
+// ---- both set-ups in the same launches (nsk_bp_latent_steps): what the three routines above enqueue for one set-up, one
+// launch for the pair where they have one; gridDim.x is what the larger set-up needs, so NSK_BP_GRID_CAP holds here too
+static void bp_refresh_enqueue(nsk_graph *g, const BpPair &p) {
+    if (p.a[0].nfactor == 0) return;                // (the factors are the graph's: both set-ups have them or neither)
+    const dim3 block(NSK_BLOCK);
+    k_bp_refresh2<<<dim3(bp_blocks(std::max(p.a[0].ntable, p.a[1].ntable)), 2), block, 0, g->stream>>>(p);
+    k_bp_psi2<<<dim3(bp_blocks(p.a[0].nfactor), 2), block, 0, g->stream>>>(p);
+}
+
+// p.res: the step's two rows.  A set-up without an edge stays out of every loop; its row stays 0, as alone.
+static hipError_t bp_iterations_enqueue(nsk_graph *g, const BpPair &p, size_t max_iters, double damping, double tol) {
+    const double oml = 1.0 - damping;
+    const int nedge = std::max(p.a[0].nedge, p.a[1].nedge), nbin = std::max(p.nvbin[0], p.nvbin[1]),
+              nrest = std::max(p.a[0].nvlist - p.nvbin[0], p.a[1].nvlist - p.nvbin[1]);
+    const dim3 block(NSK_BLOCK), gf(bp_blocks(nedge), 2), vblock(NSK_BP_VAR_BLOCK), gb(bp_blocks(nbin, NSK_BP_VAR_BLOCK), 2),
+               gr(bp_blocks(nrest, NSK_BP_VAR_BLOCK), 2);
+    hipError_t e = hipSuccess;
+    if (nedge > 0)
+        for (size_t t = 0; t < max_iters && e == hipSuccess; t++) {
+            k_bp_factor2<<<gf, block, 0, g->stream>>>(p, (int)t, tol, damping, oml);
+            if (nbin > 0) k_bp_var2<true><<<gb, vblock, 0, g->stream>>>(p, (int)t, tol);
+            if (nrest > 0) k_bp_var2<false><<<gr, vblock, 0, g->stream>>>(p, (int)t, tol);
+            e = hipGetLastError();
+        }
+    return e;
+}
+
+// p.M[0] and p.M[1] are the halves of one array, p.skipped[0] and [1] neighbours: one memset each
+static hipError_t bp_moments_enqueue(nsk_graph *g, const BpPair &p) {
+    hipError_t e = hipMemsetAsync(p.M[0], 0, 2 * (size_t)std::max<int64_t>(1, g->c.nweight) * sizeof(unsigned long long), g->stream);
+    if (e == hipSuccess) e = hipMemsetAsync(p.skipped[0], 0, 2 * sizeof(unsigned long long), g->stream);
+    if (e != hipSuccess || p.a[0].nfactor == 0) return e;
+    k_bp_fnorm2<<<dim3(bp_blocks(p.a[0].nfactor), 2), dim3(NSK_BLOCK), 0, g->stream>>>(p);
+    k_bp_moments2<<<dim3(bp_blocks(std::max(p.a[0].ntable, p.a[1].ntable)), 2), dim3(NSK_BLOCK), 0, g->stream>>>(p);
     return hipGetLastError();
 }
 
@@ -526,6 +569,105 @@ int nsk_bp_learn_steps(nsk_graph *g, const double *target, int64_t nsteps, int64
     }
     return NSK_OK;
 }
+
+int nsk_bp_latent_steps(nsk_graph *g, int64_t nsteps, int64_t iters_per_step, double damping, double tol, int warm, double step,
+                        double decay, double reg_param, int normalize, double *gmax, int64_t *iters, double *residual, int64_t *moments,
+                        int64_t *skipped) {
+    const char *who = "nsk_bp_latent_steps";
+    int rc = bp_common(g, who, false);
+    if (rc) return rc;
+    NskBp &bc = bp_slot(g, 0), &bf = bp_slot(g, 1);
+    if (!bc.ready || !bf.ready)
+        return fail(NSK_E_INVALID, std::string(who) + ": slot " + (bc.ready ? "1 (the free phase)" : "0 (the clamped phase)") +
+                                   " has no belief propagation set up (nsk_bp_select, nsk_bp_setup)");
+    if ((rc = refuse(check_nsteps(who, nsteps, 4096)))) return rc;
+    if (iters_per_step < 1 || iters_per_step > 4096) return fail(NSK_E_INVALID, "nsk_bp_latent_steps: iters_per_step must lie in [1, 4096]");
+    if (nsteps * iters_per_step > 65536) return fail(NSK_E_INVALID, "nsk_bp_latent_steps: nsteps x iters_per_step must be at most 65536");
+    if (!(damping >= 0.0 && damping < 1.0)) return fail(NSK_E_INVALID, "nsk_bp_latent_steps: damping must lie in [0, 1)");
+    if (!(tol >= 0.0)) return fail(NSK_E_INVALID, "nsk_bp_latent_steps: tol must be at least 0");
+    if ((warm != 0 && warm != 1) || (normalize != 0 && normalize != 1)) return fail(NSK_E_INVALID, "nsk_bp_latent_steps: warm and normalize must be 0 or 1");
+    if ((rc = refuse(check_rates(who, step, decay, reg_param)))) return rc;
+    const Compiled &c = g->c;
+    const size_t nw = (size_t)c.nweight, T = (size_t)nsteps, I = (size_t)iters_per_step, F = (size_t)c.nfactor;
+    if (nw == 0) return NSK_OK;
+    if ((rc = nsk_moments_range(g, 1, who))) return rc;
+    HIPCHECK(hipSetDevice(g->device));
+
+    const std::vector<double> nfac = factors_per_slot(c);
+    BpLearnBufs b(g);
+    StepOutputs out(g, T, 2);
+    rc = call_alloc(g, &b.M, 2 * nw, who, "the int64 sums of both set-ups, 16 bytes a weight");
+    if (!rc) rc = call_alloc(g, &b.skipped, 2 * T, who, "the skip counters, 16 bytes a step");
+    if (!rc) rc = call_alloc(g, &b.zf, 2 * F, who, "the factors' normalisers of both set-ups, 16 bytes a factor");
+    if (!rc) rc = call_alloc(g, &b.nfac, nw, who, "the factor counts, 8 bytes a weight");
+    if (!rc) rc = out.alloc_gmax(who);
+    if (!rc) rc = call_alloc(g, &b.res, 2 * T * I, who, "the residuals, nsteps x 2 x iters_per_step doubles");
+    if (!rc && moments) rc = out.alloc_rows(who);
+    if (rc) return rc;
+    hipError_t e = hipMemcpyAsync(b.nfac, nfac.data(), nw * sizeof(double), hipMemcpyHostToDevice, g->stream);
+    if (e == hipSuccess) e = out.zero();
+    if (e == hipSuccess) e = hipMemsetAsync(b.res, 0, 2 * T * I * sizeof(unsigned long long), g->stream);
+    if (e != hipSuccess) { (void)hipStreamSynchronize(g->stream); HIPCHECK(e); }
+
+    // index 0 of every pair is the clamped set-up (slot 0), index 1 the free one (slot 1); M = {Mc, M}
+    BpPair p = {};
+    p.a[0] = bp_args(g, bc); p.a[1] = bp_args(g, bf);
+    p.nvbin[0] = bc.nvbin; p.nvbin[1] = bf.nvbin;
+    for (size_t s = 0; s < 2; s++) { p.zf[s] = b.zf + s * F; p.M[s] = b.M + s * nw; }
+    const unsigned wblocks = (unsigned)((nw + NSK_BLOCK - 1) / NSK_BLOCK);
+    const int nedge = std::max(p.a[0].nedge, p.a[1].nedge);
+    double st = step;           // step_0 = step, step_{t+1} = step_t * decay: the products are formed here, in t order
+    for (size_t t = 0; t < T && e == hipSuccess; t++) {
+        for (size_t s = 0; s < 2; s++) { p.res[s] = b.res + (2 * t + s) * I; p.skipped[s] = b.skipped + 2 * t + s; }
+        // 1. both tables under the weights as they stand; a cold start resets both message sets
+        bp_refresh_enqueue(g, p);
+        if (!warm && nedge > 0) k_bp_reset2<<<dim3(bp_blocks(nedge), 2), dim3(NSK_BLOCK), 0, g->stream>>>(p);
+        if ((e = hipGetLastError()) != hipSuccess) break;
+        // 2. the iterations of both, each with its own row of residuals and its own early exit
+        if ((e = bp_iterations_enqueue(g, p, I, damping, tol)) != hipSuccess) break;
+        // 3. the Bethe moments of both
+        if ((e = bp_moments_enqueue(g, p)) != hipSuccess) break;
+        // 4. the update: nsk_pcd_latent_steps' with one chain a side
+        k_pcd_update<<<dim3(wblocks), dim3(NSK_BLOCK), 0, g->stream>>>((const long long *)p.M[1], 1.0, (const long long *)p.M[0], 1.0, nullptr, b.nfac, (int)nw,
+                                                                      g->w, g->w_fixed, normalize, st, reg_param, out.gmax + t, out.row(t));
+        e = hipGetLastError();
+        g->weights_dirty = true;            // the next sweep call rebuilds what derives from the weights
+        st = st * decay;
+    }
+    // the resident tables of both agree with the learned weights
+    if (e == hipSuccess) { bp_refresh_enqueue(g, p); e = hipGetLastError(); }
+    std::vector<unsigned long long> hskip(2 * T);
+    std::vector<double> hres(2 * T * I);
+    if (e == hipSuccess) e = out.download();
+    if (e == hipSuccess) e = hipMemcpyAsync(hskip.data(), b.skipped, 2 * T * 8, hipMemcpyDeviceToHost, g->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(hres.data(), b.res, 2 * T * I * 8, hipMemcpyDeviceToHost, g->stream);
+    const hipError_t e2 = hipStreamSynchronize(g->stream);      // (also: the upload reads the host vector)
+    HIPCHECK(e);
+    HIPCHECK(e2);
+    out.deliver(gmax, moments);
+    for (size_t r = 0; r < 2 * T; r++) {            // row r = (step, set-up)
+        int64_t ran = -iters_per_step;
+        for (size_t i = 0; i < I; i++) {
+            if (residual) residual[r * I + i] = hres[r * I + i];
+            if (ran < 0 && hres[r * I + i] <= tol) ran = (int64_t)i + 1;
+        }
+        if (iters) iters[r] = ran;
+        if (skipped) skipped[r] = (int64_t)hskip[r];
+    }
+    return NSK_OK;
+}
+
+int nsk_bp_select(nsk_graph *g, int slot) {
+    if (!g) return fail(NSK_E_INVALID, "null graph");
+    if (slot != 0 && slot != 1) return fail(NSK_E_INVALID, "nsk_bp_select: slot must be 0 or 1");
+    if (slot != g->bp_slot) {                       // host records only: what is enqueued keeps its arrays
+        std::swap(g->bp, g->bp_other);
+        g->bp_slot = slot;
+    }
+    return NSK_OK;
+}
+
+int nsk_bp_selected(nsk_graph *g) { return g ? g->bp_slot : fail(NSK_E_INVALID, "null graph"); }
 
 int nsk_bp_clear(nsk_graph *g) {
     if (!g) return fail(NSK_E_INVALID, "null graph");

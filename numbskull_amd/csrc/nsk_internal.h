@@ -117,6 +117,7 @@ struct NskEnergy {
 // Belief propagation (nsk_bp_setup .. nsk_bp_clear; nsk_bp.hip, nsk_kernels_bp.h): the structure of one state's clamped
 // and free variables, the tables, both message arrays and the beliefs, resident from set-up to clear.  Every device
 // array is on the ledger and listed in `owned`; the host keeps the sizes and the beliefs' offsets by internal id.
+// A handle holds two of them, slots 0 and 1 (nsk_graph::bp is the selected one); they share nothing.
 struct NskBp {
     bool ready = false;
     nsk_bp_info info = {};
@@ -208,7 +209,9 @@ struct nsk_graph {
     NskTrace trace;
     NskEnergy energy;
     NskWstats wstats;
-    NskBp bp;
+    NskBp bp;                          // the SELECTED set-up: every nsk_bp_* call acts on it (nsk_bp_select)
+    NskBp bp_other;                    // ... and the one that is not: nsk_bp_select swaps the two
+    int bp_slot = 0;                   // which of the two slots `bp` is (nsk_bp_latent_steps: 0 clamped, 1 free)
     // The segment launches (nsk_seg_plan.h), kept across calls (the N-rank loops sweep one epoch per call) together with
     // the options they were planned for; a call whose options differ plans again.  Learning: per Compiled::learn_seg entry.
     std::vector<nsk::LearnSegPlan> learn_seg_plans;

@@ -13,6 +13,8 @@
 //   k_bp_fnorm    one lane per factor: Z_f, the a-ordered sum of k_bp_fbelief (nsk_bp_moments)
 //   k_bp_moments  one lane per table entry: the expected per-weight statistics under the factor beliefs, int64 fixed
 //                 point, one atomic per run of equal weight slot a wave holds
+//   k_bp_*2       refresh, psi, reset, factor, var, fnorm and moments for two set-ups in one launch, blockIdx.y naming the
+//                 set-up (nsk_bp_latent_steps): the bodies are shared with the kernels above
 //
 // A vector over a variable's values (a message, a belief) lives in registers for binary variables, in a lane-private
 // array of NSK_ZLOCAL doubles for cardinalities up to NSK_ZLOCAL (runtime-indexed; the compiler keeps it in registers
@@ -88,8 +90,11 @@ __global__ __launch_bounds__(NSK_BLOCK) void k_bp_tables(const BpArgs a, const V
     }
 }
 
-static __global__ __launch_bounds__(NSK_BLOCK) void k_bp_psi(const BpArgs a) {
-    for (long long f = (long long)blockIdx.x * NSK_BLOCK + threadIdx.x; f < a.nfactor; f += (long long)gridDim.x * NSK_BLOCK) {
+// The bodies of the kernels that nsk_bp_latent_steps launches for two set-ups at once take the set-up and the block's
+// index and count: the single kernels pass blockIdx.x and gridDim.x, the pair kernels at the end of the file the same
+// with the set-up blockIdx.y names.
+__device__ __forceinline__ void bp_psi_body(const BpArgs &a, unsigned int bid, unsigned int nblk) {
+    for (long long f = (long long)bid * NSK_BLOCK + threadIdx.x; f < a.nfactor; f += (long long)nblk * NSK_BLOCK) {
         const long long t0 = a.tab_off[f], t1 = a.tab_off[f + 1];
         double mx = a.theta[t0];
         for (long long i = t0 + 1; i < t1; i++) {
@@ -99,15 +104,17 @@ static __global__ __launch_bounds__(NSK_BLOCK) void k_bp_psi(const BpArgs a) {
         for (long long i = t0; i < t1; i++) a.psi[i] = nsk_exp(a.theta[i] - mx);
     }
 }
+static __global__ __launch_bounds__(NSK_BLOCK) void k_bp_psi(const BpArgs a) { bp_psi_body(a, blockIdx.x, gridDim.x); }
 
 // every message entry 1 / card
-static __global__ __launch_bounds__(NSK_BLOCK) void k_bp_reset(const BpArgs a) {
-    for (int e = (int)(blockIdx.x * NSK_BLOCK + threadIdx.x); e < a.nedge; e += (int)(gridDim.x * NSK_BLOCK)) {
+__device__ __forceinline__ void bp_reset_body(const BpArgs &a, unsigned int bid, unsigned int nblk) {
+    for (int e = (int)(bid * NSK_BLOCK + threadIdx.x); e < a.nedge; e += (int)(nblk * NSK_BLOCK)) {
         const long long m0 = a.msg_off[e], m1 = a.msg_off[e + 1];
         const double u = 1.0 / (double)(m1 - m0);
         for (long long i = m0; i < m1; i++) { a.f2v[i] = u; a.v2f[i] = u; }
     }
 }
+static __global__ __launch_bounds__(NSK_BLOCK) void k_bp_reset(const BpArgs a) { bp_reset_body(a, blockIdx.x, gridDim.x); }
 
 // the beliefs the iterations do not write: a clamped variable's indicator, a free variable's uniform law
 template <typename VT>
@@ -151,12 +158,14 @@ __device__ __forceinline__ double bp_store(double *slot, double nw, double lam, 
 }
 
 // iteration t, factor phase.  residual: the bit patterns of non-negative doubles, the order of integer maxima is free.
-static __global__ __launch_bounds__(NSK_BLOCK) void k_bp_factor(const BpArgs a, int t, double tol, double lam, double oml,
-                                                               unsigned long long *residual) {
+// (Every lane of the block comes here and, past the exit, to the barrier: a block without an edge of its own loops no
+// time.  residual is the set-up's own row.)
+__device__ __forceinline__ void bp_factor_body(const BpArgs &a, unsigned int bid, unsigned int nblk, int t, double tol, double lam, double oml,
+                                               unsigned long long *residual) {
     __shared__ double lds[NSK_BLOCK / 64];
     if (t > 0 && __longlong_as_double((long long)residual[t - 1]) <= tol) return;      // block-uniform, before the barrier
     double res = 0.0;
-    for (int e = (int)(blockIdx.x * NSK_BLOCK + threadIdx.x); e < a.nedge; e += (int)(gridDim.x * NSK_BLOCK)) {
+    for (int e = (int)(bid * NSK_BLOCK + threadIdx.x); e < a.nedge; e += (int)(nblk * NSK_BLOCK)) {
         const int f = a.e_fac[e];
         const int e0 = a.edge_off[f], A = a.edge_off[f + 1] - e0, j = e - e0;
         const long long t0 = a.tab_off[f];
@@ -196,6 +205,10 @@ static __global__ __launch_bounds__(NSK_BLOCK) void k_bp_factor(const BpArgs a, 
         for (int k = 1; k < NSK_BLOCK / 64; k++) res = fmax(res, lds[k]);
         if (res > 0.0) atomicMax(residual + t, (unsigned long long)__double_as_longlong(res));
     }
+}
+static __global__ __launch_bounds__(NSK_BLOCK) void k_bp_factor(const BpArgs a, int t, double tol, double lam, double oml,
+                                                               unsigned long long *residual) {
+    bp_factor_body(a, blockIdx.x, gridDim.x, t, tol, lam, oml, residual);
 }
 
 // while the largest entry is > 0 and < 2^-512: every entry times 2^512 (exact)
@@ -283,9 +296,10 @@ __device__ __forceinline__ void bp_var_lane_reg(const BpArgs &a, const int32_t *
 // them from a handful of registers, the other launch the rest (the lane-private vectors of the middle cardinalities cost
 // it its occupancy).
 template <bool BIN>
-__global__ __launch_bounds__(NSK_BP_VAR_BLOCK) void k_bp_var(const BpArgs a, int lo, int hi, int t, double tol, const unsigned long long *residual) {
+__device__ __forceinline__ void bp_var_body(const BpArgs &a, unsigned int bid, unsigned int nblk, int lo, int hi, int t, double tol,
+                                            const unsigned long long *residual) {
     if (t > 0 && __longlong_as_double((long long)residual[t - 1]) <= tol) return;
-    for (int i = lo + (int)(blockIdx.x * NSK_BP_VAR_BLOCK + threadIdx.x); i < hi; i += (int)(gridDim.x * NSK_BP_VAR_BLOCK)) {
+    for (int i = lo + (int)(bid * NSK_BP_VAR_BLOCK + threadIdx.x); i < hi; i += (int)(nblk * NSK_BP_VAR_BLOCK)) {
         const int id = a.v_list[i];
         const int e0 = a.v_eoff[i], d = a.v_eoff[i + 1] - e0;
         const long long b0 = a.b_off[id];
@@ -295,6 +309,10 @@ __global__ __launch_bounds__(NSK_BP_VAR_BLOCK) void k_bp_var(const BpArgs a, int
         else if (n <= NSK_ZLOCAL) bp_var_lane<NSK_ZLOCAL>(a, n, a.v_edges + e0, d, a.belief + b0, nullptr);
         else bp_var_lane<0>(a, n, a.v_edges + e0, d, a.belief + b0, a.wk + b0);
     }
+}
+template <bool BIN>
+__global__ __launch_bounds__(NSK_BP_VAR_BLOCK) void k_bp_var(const BpArgs a, int lo, int hi, int t, double tol, const unsigned long long *residual) {
+    bp_var_body<BIN>(a, blockIdx.x, gridDim.x, lo, hi, t, tol, residual);
 }
 
 // b_f(a) = psi_f(a) * the incoming messages at the digits of a, divided by their a-ordered sum
@@ -345,15 +363,16 @@ __device__ __forceinline__ double bp_entry_x(const BpArgs &a, long long t0, int 
 }
 
 // theta from the device weight table as it stands: one rounded product per entry, the set-up's own (k_bp_psi follows)
-static __global__ __launch_bounds__(NSK_BLOCK) void k_bp_refresh(const BpArgs a) {
-    for (long long idx = (long long)blockIdx.x * NSK_BLOCK + threadIdx.x; idx < a.ntable; idx += (long long)gridDim.x * NSK_BLOCK)
+__device__ __forceinline__ void bp_refresh_body(const BpArgs &a, unsigned int bid, unsigned int nblk) {
+    for (long long idx = (long long)bid * NSK_BLOCK + threadIdx.x; idx < a.ntable; idx += (long long)nblk * NSK_BLOCK)
         a.theta[idx] = a.w[a.f_rec[bp_factor_of(a, idx)].z] * a.feat[idx];
 }
+static __global__ __launch_bounds__(NSK_BLOCK) void k_bp_refresh(const BpArgs a) { bp_refresh_body(a, blockIdx.x, gridDim.x); }
 
 // Z_f, the a-ordered sum of k_bp_fbelief, one lane per factor.  A factor whose Z_f is not a finite positive number takes
 // no part in the moments: it is counted here, a wave's count leaving as one atomic.
-static __global__ __launch_bounds__(NSK_BLOCK) void k_bp_fnorm(const BpArgs a, double *zf, unsigned long long *skipped) {
-    for (long long base = (long long)blockIdx.x * NSK_BLOCK + (threadIdx.x & ~63u); base < a.nfactor; base += (long long)gridDim.x * NSK_BLOCK) {
+__device__ __forceinline__ void bp_fnorm_body(const BpArgs &a, unsigned int bid, unsigned int nblk, double *zf, unsigned long long *skipped) {
+    for (long long base = (long long)bid * NSK_BLOCK + (threadIdx.x & ~63u); base < a.nfactor; base += (long long)nblk * NSK_BLOCK) {
         const long long f = base + (threadIdx.x & 63);
         bool skip = false;
         if (f < a.nfactor) {
@@ -373,6 +392,9 @@ static __global__ __launch_bounds__(NSK_BLOCK) void k_bp_fnorm(const BpArgs a, d
             (void)__hip_atomic_fetch_add(skipped, (unsigned long long)__popcll(m), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     }
 }
+static __global__ __launch_bounds__(NSK_BLOCK) void k_bp_fnorm(const BpArgs a, double *zf, unsigned long long *skipped) {
+    bp_fnorm_body(a, blockIdx.x, gridDim.x, zf, skipped);
+}
 
 __device__ __forceinline__ void bp_moments_add(unsigned long long *M, int slot, long long x) {
     if (slot >= 0 && x != 0) (void)__hip_atomic_fetch_add(M + slot, (unsigned long long)x, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -384,13 +406,14 @@ __device__ __forceinline__ void bp_moments_add(unsigned long long *M, int slot, 
 // atomic -- but for the run that ends the wave: it is carried in a register (wave-uniform) into the next trip and joins
 // that trip's first run when the slots agree, as k_moments_piece carries its pieces.  What a block's waves carry at the
 // end meets in LDS and equal slots leave as one atomic.  Integers: no order changes a bit.
-static __global__ __launch_bounds__(NSK_BLOCK) void k_bp_moments(const BpArgs a, const double *zf, unsigned long long *M) {
+// (Every lane comes to the barrier: a wave without an entry of its own carries nothing, slot -1.)
+__device__ __forceinline__ void bp_moments_body(const BpArgs &a, unsigned int bid, unsigned int nblk, const double *zf, unsigned long long *M) {
     __shared__ long long lds_run[NSK_BLOCK / 64];
     __shared__ int lds_slot[NSK_BLOCK / 64];
     const int lane = (int)(threadIdx.x & 63), wave = (int)(threadIdx.x >> 6);
     int cslot = -1;                 // the slot of the carried sum (-1: none)
     long long carry = 0;
-    for (long long base = (long long)blockIdx.x * NSK_BLOCK + wave * 64; base < a.ntable; base += (long long)gridDim.x * NSK_BLOCK) {
+    for (long long base = (long long)bid * NSK_BLOCK + wave * 64; base < a.ntable; base += (long long)nblk * NSK_BLOCK) {
         const long long idx = base + lane;
         int slot = -1;
         long long acc = 0;
@@ -439,6 +462,42 @@ static __global__ __launch_bounds__(NSK_BLOCK) void k_bp_moments(const BpArgs a,
             bp_moments_add(M, s, x);
         }
     }
+}
+static __global__ __launch_bounds__(NSK_BLOCK) void k_bp_moments(const BpArgs a, const double *zf, unsigned long long *M) {
+    bp_moments_body(a, blockIdx.x, gridDim.x, zf, M);
+}
+
+// ---- two set-ups in the same launches (nsk_bp_latent_steps) ----
+// blockIdx.y names the set-up (0: evidence clamped, 1: free), gridDim.x is what the larger of the two needs; the bodies
+// are those of the single kernels above, so a set-up computes here what it computes alone, bit for bit.  A block whose
+// set-up has fewer items than the grid covers loops no time and still reaches every barrier; each early exit reads its
+// own set-up's row of residuals and is uniform over the block.
+struct BpPair {
+    BpArgs a[2];
+    unsigned long long *res[2];     // the step's row of residuals
+    double *zf[2];                  // [nfactor] each
+    unsigned long long *M[2];       // [nweight] each: the clamped set-up's sums are k_pcd_update's Mc
+    unsigned long long *skipped[2];
+    int nvbin[2];                   // NskBp::nvbin: v_list holds the binary variables first
+};
+
+static __global__ __launch_bounds__(NSK_BLOCK) void k_bp_refresh2(const BpPair p) { bp_refresh_body(p.a[blockIdx.y], blockIdx.x, gridDim.x); }
+static __global__ __launch_bounds__(NSK_BLOCK) void k_bp_psi2(const BpPair p) { bp_psi_body(p.a[blockIdx.y], blockIdx.x, gridDim.x); }
+static __global__ __launch_bounds__(NSK_BLOCK) void k_bp_reset2(const BpPair p) { bp_reset_body(p.a[blockIdx.y], blockIdx.x, gridDim.x); }
+static __global__ __launch_bounds__(NSK_BLOCK) void k_bp_factor2(const BpPair p, int t, double tol, double lam, double oml) {
+    bp_factor_body(p.a[blockIdx.y], blockIdx.x, gridDim.x, t, tol, lam, oml, p.res[blockIdx.y]);
+}
+template <bool BIN>
+__global__ __launch_bounds__(NSK_BP_VAR_BLOCK) void k_bp_var2(const BpPair p, int t, double tol) {
+    const BpArgs &a = p.a[blockIdx.y];
+    const int nbin = p.nvbin[blockIdx.y];
+    bp_var_body<BIN>(a, blockIdx.x, gridDim.x, BIN ? 0 : nbin, BIN ? nbin : a.nvlist, t, tol, p.res[blockIdx.y]);
+}
+static __global__ __launch_bounds__(NSK_BLOCK) void k_bp_fnorm2(const BpPair p) {
+    bp_fnorm_body(p.a[blockIdx.y], blockIdx.x, gridDim.x, p.zf[blockIdx.y], p.skipped[blockIdx.y]);
+}
+static __global__ __launch_bounds__(NSK_BLOCK) void k_bp_moments2(const BpPair p) {
+    bp_moments_body(p.a[blockIdx.y], blockIdx.x, gridDim.x, p.zf[blockIdx.y], p.M[blockIdx.y]);
 }
 
 }  // namespace nsk

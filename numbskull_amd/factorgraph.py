@@ -1493,7 +1493,7 @@ class FactorGraph(object):
                 "converged": bool(iters.value > 0), "skipped": int(skipped.value)}
 
     def learn_bp(self, epochs, stepsize, decay=1.0, reg_param=0.0, iters=20, damping=0.0, tol=1e-9, warm=True,
-                 sample_evidence=True, target=None, normalize=True, var_copy=0, weight_copy=0, moments=False):
+                 sample_evidence=True, target=None, normalize=True, var_copy=0, weight_copy=0, moments=False, latent=False):
         """Maximum-likelihood learning whose model expectations come from belief propagation instead of chains
         (nsk_bp_learn_steps): EXACT maximum likelihood where the free variables form a forest -- chains, stars, graphs
         that the evidence separates --, the Bethe approximation on a graph with cycles; no sampling noise, no chain
@@ -1508,9 +1508,18 @@ class FactorGraph(object):
         with cycles, raise ``damping`` (in [0, 1)) or ``iters``; the gradient of a step that did not converge is that of
         the messages as they stood.  ``target`` (nweight,) are the statistics to match; None means those of the evidence
         chain, ``weight_moments(evidence_chain=True)``, which is right for FULLY OBSERVED data, as in ``learn_pcd``.
-        ``sample_evidence=True`` frees every variable with a position (the free phase).  LATENT-variable learning needs
-        the difference of two set-ups, evidence clamped and free, and is not served here: ``learn_pcd(clamped=K)`` does
-        that with chains.
+        ``sample_evidence=True`` frees every variable with a position (the free phase).
+
+        ``latent=True`` is learning with LATENT variables (nsk_bp_latent_steps), the noise-free counterpart of
+        ``learn_pcd(clamped=K)``: two set-ups of the same state live on the device, one with the evidence held and the
+        other variables free (the positive phase), one with everything free (the negative phase); each step runs both --
+        in the same launches -- and moves the weights along the difference of their Bethe moments,
+        ``w += step * ((E[S_w | evidence] - E[S_w]) / n_w - reg_param * w)``, which ascends the Bethe estimate of the
+        evidence's log-probability (``bp_log_evidence``; exact on forests).  ``target`` must be None then and
+        ``sample_evidence`` is not read.  The dict has no ``target``; ``iters``, ``converged`` and ``skipped`` have the
+        shape ``(epochs, 2)``, ``residual`` ``(epochs, 2, iters)`` and ``moments`` ``(epochs, 2, nweight)``, index 0 of
+        the pair axis the clamped set-up, each set-up stopping at ``tol`` on its own
+        (``diagnostics.pcd_latent_step`` with ``K = Rf = 1`` is the update in numpy).
 
         The state ``var_value[var_copy]`` and ``weight_value[weight_copy]`` are pushed as ``belief_propagation`` pushes
         them; afterwards ``weight_value[weight_copy]`` holds the learned weights, and the set-up is cleared whatever
@@ -1527,6 +1536,11 @@ class FactorGraph(object):
         if _all_copies(var_copy):
             raise ValueError('learn_bp serves one state: var_copy="all" is for the sampler')
         nw = self.weight.shape[0]
+        if latent:
+            if target is not None:
+                raise ValueError("learn_bp: latent=True takes no target (the clamped set-up's moments are the positive phase)")
+            return self._learn_bp_latent(epochs, stepsize, decay, reg_param, iters, damping, tol, warm, normalize, var_copy,
+                                         weight_copy, moments)
         target = self._learn_target("learn_bp", target)
         L, h = _lib.lib(), self._engine()
         self._push(var_copy, weight_copy)
@@ -1546,6 +1560,44 @@ class FactorGraph(object):
         if moments:
             out["moments"] = rows
         return out
+
+    def _learn_bp_latent(self, epochs, stepsize, decay, reg_param, iters, damping, tol, warm, normalize, var_copy, weight_copy, moments):
+        """``learn_bp(latent=True)`` behind its argument checks: slot 0 the clamped set-up, slot 1 the free one"""
+        nw = self.weight.shape[0]
+        L, h = _lib.lib(), self._engine()
+        self._push(var_copy, weight_copy)
+        try:
+            for slot in (0, 1):
+                _lib.check(L.nsk_bp_select(h, slot))
+                _lib.check(L.nsk_bp_setup(h, _lib.BUF_VALUE, 0, slot, None))
+            gmax, ran, skipped = np.zeros(epochs, np.float64), np.zeros((epochs, 2), np.int64), np.zeros((epochs, 2), np.int64)
+            residual = np.zeros((epochs, 2, iters), np.float64)
+            rows = np.zeros((epochs, 2, nw), np.int64) if moments else None
+            _lib.check(L.nsk_bp_latent_steps(h, epochs, iters, float(damping), float(tol), int(bool(warm)), stepsize, decay, reg_param,
+                                             int(bool(normalize)), _lib.ptr(gmax), _lib.ptr(ran), _lib.ptr(residual), _lib.ptr(rows),
+                                             _lib.ptr(skipped)))
+            self._pull(var_copy, weight_copy, values=False, count=False)
+        finally:
+            for slot in (1, 0):                     # (slot 0 stays selected)
+                L.nsk_bp_select(h, slot)
+                L.nsk_bp_clear(h)
+        out = {"grad_max": gmax, "iters": np.abs(ran), "converged": ran > 0, "residual": residual, "skipped": skipped,
+               "factors_per_weight": self._factors_per_weight()}
+        if moments:
+            out["moments"] = rows
+        return out
+
+    def bp_log_evidence(self, max_iters=100, damping=0.0, tol=1e-9, var_copy=0, weight_copy=0):
+        """The Bethe estimate of ``log P(the evidence variables' values)`` under ``weight_value[weight_copy]``:
+        ``log_z`` of ``belief_propagation`` with the evidence held minus ``log_z`` with everything free
+        (``sample_evidence=True``), two runs composed on the host.  It is the objective ``learn_bp(latent=True)``
+        ascends; exact where the graph is a forest and both runs converge, an approximation on a graph with cycles.
+        The arguments are those of ``belief_propagation``.  Returns a dict: ``log_evidence``, ``log_z_clamped``,
+        ``log_z_free``, ``converged`` -- bool ``(2,)`` -- and ``iters`` -- int64 ``(2,)`` --, the clamped run first."""
+        runs = [self.belief_propagation(max_iters, damping, tol, var_copy, weight_copy, sample_evidence=sev) for sev in (False, True)]
+        lz = [float(r["log_z"]) for r in runs]
+        return {"log_evidence": lz[0] - lz[1], "log_z_clamped": lz[0], "log_z_free": lz[1],
+                "converged": np.array([r["converged"] for r in runs], np.bool_), "iters": np.array([r["iters"] for r in runs], np.int64)}
 
     # ------------------------------------------------------------------ log-potential
     def log_potential(self, var_copy=0, weight_copy=0, evidence_chain=False):
