@@ -1,20 +1,23 @@
-// nsk_bp.hip -- loopy belief propagation (nsk_internal.h NskBp, nsk_kernels_bp.h): nsk_bp_setup builds the structure of one
-// state on the host from the compiled records (which variables are clamped, every factor's distinct members, table axes,
-// directed edges, the per-variable edge lists), uploads it and fills the tables; nsk_bp_run enqueues every iteration on
-// the handle's stream without a synchronisation between them -- once the residual is at or below the tolerance the later
-// launches end on the device -- and copies the residuals back once.  The launches are not counted by the profiling bracket.
+// nsk_bp.hip -- loopy belief propagation (nsk_internal.h NskBp, nsk_kernels_bp.h): nsk_bp_setup takes the structure of one
+// state from nsk_bp_plan.h (which variables are clamped, every factor's distinct members, table axes, directed edges, the
+// per-variable edge lists: pure host arithmetic over the compiled records), uploads it and fills the tables; nsk_bp_run
+// enqueues every iteration on the handle's stream without a synchronisation between them -- once the residual is at or
+// below the tolerance the later launches end on the device -- and copies the residuals back once.  The launches are not
+// counted by the profiling bracket.
 // Learning by BP on the resident set-up: nsk_bp_refresh rewrites theta and psi from the device weights through the feature
 // table the set-up keeps, nsk_bp_moments reduces the expected per-weight statistics under the factor beliefs in int64 fixed
 // point, and nsk_bp_learn_steps enqueues (refresh, iterations, moments, nsk_pcd.hip's update with one chain) per step
 // without a host wait, as nsk_pcd_steps does; the sums, the target and the per-step outputs live for the call only.
 // A handle holds two set-ups (nsk_bp_select swaps the selected one in; everything above acts on it alone), and
 // nsk_bp_latent_steps learns from their difference, evidence clamped and free: the same steps with both set-ups in the
-// same launches (the pair kernels of nsk_kernels_bp.h) and nsk_pcd_latent_steps' update with one chain a side.
+// same launches (the pair kernels of nsk_kernels_bp.h) and nsk_pcd_latent_steps' update with one chain a side.  Both
+// learners are bp_steps_run, with n = 1 or 2 set-ups.
 #include <hip/hip_runtime.h>
 
 #include <cmath>
 #include <cstring>
 
+#include "nsk_bp_plan.h"
 #include "nsk_internal.h"
 #include "nsk_kernels_bp.h"
 #include "nsk_kernels_pcd.h"     // k_pcd_update
@@ -55,16 +58,6 @@ static BpArgs bp_args(const nsk_graph *g) { return bp_args(g, g->bp); }       //
 
 // the set-up of a slot, whichever is selected
 static NskBp &bp_slot(nsk_graph *g, int slot) { return slot == g->bp_slot ? g->bp : g->bp_other; }
-
-// member positions a function reads whatever its arity says (nsk_energy.hip energy_check_factors)
-static int64_t bp_need(int fn) {
-    switch (fn) {
-    case 3: case 18: case 19: case 20: case 30: return 1;
-    case 21: case 22: case 25: case 26: return 2;
-    case 23: case 24: return 3;
-    default: return 0;
-    }
-}
 
 template <typename T>
 static int bp_upload(nsk_graph *g, T **ptr, const std::vector<T> &h) {
@@ -167,115 +160,122 @@ struct BpLearnBufs {
     ~BpLearnBufs() { dev_free(g, nfac); dev_free(g, target); dev_free(g, zf); dev_free(g, res); dev_free(g, skipped); dev_free(g, M); }
 };
 
+// the step parameters both learners take, in the order they are refused
+static int bp_steps_check(const std::string &who, int64_t nsteps, int64_t iters_per_step, double damping, double tol, int warm, double step,
+                          double decay, double reg_param, int normalize) {
+    if (int rc = refuse(check_nsteps(who, nsteps, 4096))) return rc;
+    if (iters_per_step < 1 || iters_per_step > 4096) return fail(NSK_E_INVALID, who + ": iters_per_step must lie in [1, 4096]");
+    if (nsteps * iters_per_step > 65536) return fail(NSK_E_INVALID, who + ": nsteps x iters_per_step must be at most 65536");
+    if (!(damping >= 0.0 && damping < 1.0)) return fail(NSK_E_INVALID, who + ": damping must lie in [0, 1)");
+    if (!(tol >= 0.0)) return fail(NSK_E_INVALID, who + ": tol must be at least 0");
+    if ((warm != 0 && warm != 1) || (normalize != 0 && normalize != 1)) return fail(NSK_E_INVALID, who + ": warm and normalize must be 0 or 1");
+    return refuse(check_rates(who, step, decay, reg_param));
+}
+
+// What nsk_bp_learn_steps (n = 1: the selected set-up against `target`, by the caller's weight ids) and nsk_bp_latent_steps
+// (n = 2: slot 0 against slot 1, target null) enqueue, their own arguments checked; per step refresh, (reset), iterations,
+// moments and k_pcd_update, one synchronisation a call.  Every per-set-up buffer is n x the single one, row (step, set-up).
+static int bp_steps_run(nsk_graph *g, const char *who, int n, const double *target, int64_t nsteps, int64_t iters_per_step, double damping,
+                        double tol, int warm, double step, double decay, double reg_param, int normalize, double *gmax, int64_t *iters,
+                        double *residual, int64_t *moments, int64_t *skipped) {
+    const Compiled &c = g->c;
+    const size_t N = (size_t)n, nw = (size_t)c.nweight, T = (size_t)nsteps, I = (size_t)iters_per_step, F = (size_t)c.nfactor;
+    if (nw == 0) return NSK_OK;
+    int rc = nsk_moments_range(g, 1, who);
+    if (rc) return rc;
+    HIPCHECK(hipSetDevice(g->device));
+
+    // the target and the factor counts by slot
+    std::vector<double> tgt(target ? nw : 0);
+    if (target) SlotMap(c).to_slots(target, tgt.data());
+    const std::vector<double> nfac = factors_per_slot(c);
+    BpLearnBufs b(g);
+    StepOutputs out(g, T, N);
+    rc = call_alloc(g, &b.M, N * nw, who, n == 1 ? "the int64 sums, 8 bytes a weight" : "the int64 sums of both set-ups, 16 bytes a weight");
+    if (!rc) rc = call_alloc(g, &b.skipped, N * T, who, n == 1 ? "the skip counters, 8 bytes a step" : "the skip counters, 16 bytes a step");
+    if (!rc) rc = call_alloc(g, &b.zf, N * F, who, n == 1 ? "the factors' normalisers, 8 bytes a factor" : "the factors' normalisers of both set-ups, 16 bytes a factor");
+    if (!rc && target) rc = call_alloc(g, &b.target, nw, who, "the target, 8 bytes a weight");
+    if (!rc) rc = call_alloc(g, &b.nfac, nw, who, "the factor counts, 8 bytes a weight");
+    if (!rc) rc = out.alloc_gmax(who);
+    if (!rc) rc = call_alloc(g, &b.res, N * T * I, who, n == 1 ? "the residuals, nsteps x iters_per_step doubles" : "the residuals, nsteps x 2 x iters_per_step doubles");
+    if (!rc && moments) rc = out.alloc_rows(who);
+    if (rc) return rc;
+    hipError_t e = target ? hipMemcpyAsync(b.target, tgt.data(), nw * sizeof(double), hipMemcpyHostToDevice, g->stream) : hipSuccess;
+    if (e == hipSuccess) e = hipMemcpyAsync(b.nfac, nfac.data(), nw * sizeof(double), hipMemcpyHostToDevice, g->stream);
+    if (e == hipSuccess) e = out.zero();
+    if (e == hipSuccess) e = hipMemsetAsync(b.res, 0, N * T * I * sizeof(unsigned long long), g->stream);
+    if (e != hipSuccess) { (void)hipStreamSynchronize(g->stream); HIPCHECK(e); }
+
+    // n = 1 launches the single kernels on the selected set-up (a; p lends it its first pointers), n = 2 the pair kernels
+    // on p: index 0 of every pair is the clamped set-up (slot 0), index 1 the free one (slot 1)
+    const BpArgs a = bp_args(g);
+    BpPair p = {};
+    for (int s = 0; s < n; s++) {
+        if (n == 2) { p.a[s] = bp_args(g, bp_slot(g, s)); p.nvbin[s] = bp_slot(g, s).nvbin; }
+        p.zf[s] = b.zf + (size_t)s * F; p.M[s] = b.M + (size_t)s * nw;
+    }
+    const int nedge = n == 1 ? a.nedge : std::max(p.a[0].nedge, p.a[1].nedge);
+    auto refresh = [&] { if (n == 1) bp_refresh_enqueue(g, a); else bp_refresh_enqueue(g, p); };
+    const unsigned wblocks = (unsigned)((nw + NSK_BLOCK - 1) / NSK_BLOCK);
+    // the update: nsk_pcd_steps' against the target, or nsk_pcd_latent_steps' (M = {Mc, M}), with one chain a side
+    const long long *Mfree = (const long long *)p.M[n - 1], *Mc = n == 1 ? nullptr : (const long long *)p.M[0];
+    double st = step;           // step_0 = step, step_{t+1} = step_t * decay: the products are formed here, in t order
+    for (size_t t = 0; t < T && e == hipSuccess; t++) {
+        for (size_t s = 0; s < N; s++) { p.res[s] = b.res + (N * t + s) * I; p.skipped[s] = b.skipped + N * t + s; }
+        // 1. the tables under the weights as they stand; a cold start resets the messages
+        refresh();
+        if (!warm && nedge > 0) {
+            if (n == 1) k_bp_reset<<<dim3(bp_blocks(nedge)), dim3(NSK_BLOCK), 0, g->stream>>>(a);
+            else k_bp_reset2<<<dim3(bp_blocks(nedge), 2), dim3(NSK_BLOCK), 0, g->stream>>>(p);
+        }
+        if ((e = hipGetLastError()) != hipSuccess) break;
+        // 2. the iterations, each set-up's early exit inside the step's own row of residuals
+        if ((e = n == 1 ? bp_iterations_enqueue(g, a, I, damping, tol, p.res[0]) : bp_iterations_enqueue(g, p, I, damping, tol)) != hipSuccess) break;
+        // 3. the Bethe moments
+        if ((e = n == 1 ? bp_moments_enqueue(g, a, p.zf[0], p.M[0], p.skipped[0]) : bp_moments_enqueue(g, p)) != hipSuccess) break;
+        // 4. the update
+        k_pcd_update<<<dim3(wblocks), dim3(NSK_BLOCK), 0, g->stream>>>(Mfree, 1.0, Mc, n == 1 ? 0.0 : 1.0, b.target, b.nfac, (int)nw, g->w, g->w_fixed,
+                                                                      normalize, st, reg_param, out.gmax + t, out.row(t));
+        e = hipGetLastError();
+        g->weights_dirty = true;            // the next sweep call rebuilds what derives from the weights
+        st = st * decay;
+    }
+    // the resident tables agree with the learned weights: a following nsk_bp_run continues under them
+    if (e == hipSuccess) { refresh(); e = hipGetLastError(); }
+    std::vector<unsigned long long> hskip(N * T);
+    std::vector<double> hres(N * T * I);
+    if (e == hipSuccess) e = out.download();
+    if (e == hipSuccess) e = hipMemcpyAsync(hskip.data(), b.skipped, N * T * 8, hipMemcpyDeviceToHost, g->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(hres.data(), b.res, N * T * I * 8, hipMemcpyDeviceToHost, g->stream);
+    const hipError_t e2 = hipStreamSynchronize(g->stream);      // (also: the uploads read the host vectors)
+    HIPCHECK(e);
+    HIPCHECK(e2);
+    out.deliver(gmax, moments);
+    for (size_t r = 0; r < N * T; r++) {            // row r = (step, set-up)
+        int64_t ran = -iters_per_step;
+        for (size_t i = 0; i < I; i++) {
+            if (residual) residual[r * I + i] = hres[r * I + i];
+            if (ran < 0 && hres[r * I + i] <= tol) ran = (int64_t)i + 1;
+        }
+        if (iters) iters[r] = ran;
+        if (skipped) skipped[r] = (int64_t)hskip[r];
+    }
+    return NSK_OK;
+}
+
 extern "C" {
 
 int nsk_bp_setup(nsk_graph *g, int which, int64_t chain, int sample_evidence, nsk_bp_info *info_out) {
     int rc = bp_common(g, "nsk_bp_setup", false);
     if (rc) return rc;
     if ((rc = chain_select(g, which, chain, 1, "nsk_bp_setup", true))) return rc;
+    // ---- the structure: every refusal names the lowest offending factor and precedes any allocation
     const Compiled &c = g->c;
-    const int64_t F = c.nfactor, nedge = c.nedge, nid = c.nid, npos = std::min<int64_t>(c.npos, (int64_t)c.p_info.size());
-    const bool head_by_vid = (c.flags & NSK_FLAG_HEAD_BY_VID) != 0;
-    // 0: no variable, 1: clamped, 2: free -- by internal id
-    std::vector<uint8_t> state((size_t)nid, 0);
-    nsk_bp_info info = {};
-    info.nfactor = F;
-    for (int64_t v = 0; v < c.nvar; v++) {
-        const int64_t id = c.iid[(size_t)v];
-        if (id < 0 || id >= nid) return fail(NSK_E_INVALID, "nsk_bp_setup: a variable without an internal id");
-        const bool clamped = id >= npos || ((c.p_info[(size_t)id] & 0xffu) != 0 && !sample_evidence);
-        state[(size_t)id] = clamped ? 1 : 2;
-    }
-    // ---- the structure, factor by factor; every refusal names the lowest offending factor and precedes any allocation
-    std::vector<long long> pm_off((size_t)F + 1, 0), tab_off((size_t)F + 1, 0), msg_off(1, 0);
-    std::vector<int32_t> slot_off((size_t)F + 1, 0), edge_off((size_t)F + 1, 0), slot_rec, mrec, e_fac, e_var;
-    std::vector<int32_t> deg((size_t)nid, 0);
-    auto refuse = [&](int64_t f, const std::string &why) {
-        return fail(NSK_E_INVALID, "nsk_bp_setup: factor " + std::to_string((long long)f) + " " + why);
-    };
-    for (int64_t f = 0; f < F; f++) {
-        const uint32_t head = c.f_rec[4 * (size_t)f];
-        const int fn = (int)(head & 0xffu) - 1;
-        const int64_t ar = (int64_t)(head >> 8), s = (int32_t)c.f_rec[4 * (size_t)f + 1], wz = (int32_t)c.f_rec[4 * (size_t)f + 2];
-        if (!known_function(fn) || wz < 0 || wz >= c.nweight) return refuse(f, "has an unknown function or a weight outside the table");
-        if (fn == 30) return refuse(f, "is UFO, which reads its members by value: belief propagation has no table for it");
-        if ((fn == 13 || fn == 16 || fn == 17) && !head_by_vid)
-            return refuse(f, "reads its head at the literal edge index (function 13, 16 or 17 without NSK_FLAG_HEAD_BY_VID): it has no single energy");
-        if (fn == 8 && ar >= (int64_t)c.logtab.size()) return refuse(f, "(RATIO) has more members than the logarithm table");
-        const int64_t np = fn == -1 ? 0 : std::max(ar, bp_need(fn));
-        if (s < 0 || s + np > nedge) return refuse(f, "has member positions outside the edge array");
-        int32_t ids[NSK_BP_MAX_MEMBERS];
-        int ns = 0;
-        long long T = 1;
-        for (int64_t l = s; l < s + np; l++) {
-            const int32_t id = c.m_rec[2 * (size_t)l];
-            if (id < 0 || id >= nid || !state[(size_t)id]) return refuse(f, "has a member outside the variables");
-            int k = 0;
-            while (k < ns && ids[k] != id) k++;
-            if (k == ns) {
-                if (ns == NSK_BP_MAX_MEMBERS)
-                    return refuse(f, "has more than NSK_BP_MAX_MEMBERS = " + std::to_string(NSK_BP_MAX_MEMBERS) + " distinct members");
-                ids[ns++] = id;
-            }
-            mrec.push_back(k);
-            mrec.push_back(c.m_rec[2 * (size_t)l + 1]);
-        }
-        for (int k = 0; k < ns; k++) {
-            const bool free = state[(size_t)ids[k]] == 2;
-            const long long card = c.v_card_i[(size_t)ids[k]];
-            if (free) {
-                if (card < 1) return refuse(f, "has a free member of cardinality below 1");
-                T *= card;
-                if (T > NSK_BP_MAX_TABLE)
-                    return refuse(f, "has a table of more than NSK_BP_MAX_TABLE = " + std::to_string(NSK_BP_MAX_TABLE) + " entries over its free members");
-            }
-        }
-        for (int k = 0; k < ns; k++) {
-            const bool free = state[(size_t)ids[k]] == 2;
-            slot_rec.push_back(ids[k]);
-            slot_rec.push_back(free ? 1 : 0);
-            if (free) {
-                e_fac.push_back((int32_t)f);
-                e_var.push_back(ids[k]);
-                msg_off.push_back(msg_off.back() + c.v_card_i[(size_t)ids[k]]);
-                deg[(size_t)ids[k]]++;
-            }
-        }
-        if ((int64_t)e_fac.size() > (int64_t)0x7ffffff0) return refuse(f, "and those before it have more than 2^31 directed edges");
-        pm_off[(size_t)f + 1] = pm_off[(size_t)f] + np;
-        slot_off[(size_t)f + 1] = slot_off[(size_t)f] + ns;
-        edge_off[(size_t)f + 1] = (int32_t)e_fac.size();
-        tab_off[(size_t)f + 1] = tab_off[(size_t)f] + T;
-        info.max_table = std::max<int64_t>(info.max_table, T);
-    }
-    const int64_t E = (int64_t)e_fac.size();
-    // ---- per variable: the beliefs' offsets, the free variables with an edge and their edges, ascending
-    NskBp nb;
-    nb.b_off.assign((size_t)nid + 1, 0);
-    std::vector<int32_t> v_list, v_eoff(1, 0), v_edges((size_t)E), slot_of((size_t)nid, -1);
-    for (int64_t id = 0; id < nid; id++) {
-        const long long card = state[(size_t)id] ? std::max<long long>(c.v_card_i[(size_t)id], 0) : 0;
-        nb.b_off[(size_t)id + 1] = nb.b_off[(size_t)id] + card;
-        if (state[(size_t)id] == 1) info.nclamped++;
-        if (state[(size_t)id] != 2) continue;
-        info.nfree++;
-        if (!deg[(size_t)id]) info.nisolated++;
-        else if (card > NSK_ZLOCAL) nb.big = true;
-    }
-    for (int pass = 0; pass < 2; pass++) {          // the binary variables first (k_bp_var), ascending in each part
-        for (int64_t id = 0; id < nid; id++) {
-            if (state[(size_t)id] != 2 || !deg[(size_t)id] || (c.v_card_i[(size_t)id] == 2) != (pass == 0)) continue;
-            slot_of[(size_t)id] = (int32_t)v_list.size();
-            v_list.push_back((int32_t)id);
-            v_eoff.push_back(v_eoff.back() + deg[(size_t)id]);
-        }
-        if (pass == 0) nb.nvbin = (int32_t)v_list.size();
-    }
-    {
-        std::vector<int32_t> cur(v_eoff.begin(), v_eoff.end() - 1);
-        for (int64_t e = 0; e < E; e++) v_edges[(size_t)cur[(size_t)slot_of[(size_t)e_var[(size_t)e]]]++] = (int32_t)e;
-    }
-    info.nedges = E; info.ntable = tab_off[(size_t)F]; info.nmsg = msg_off[(size_t)E]; info.nbelief = nb.b_off[(size_t)nid];
+    BpPlan pl;
+    const std::string why = bp_plan(c, sample_evidence, NSK_BP_MAX_MEMBERS, NSK_BP_MAX_TABLE, NSK_ZLOCAL, pl);
+    if (!why.empty()) return fail(NSK_E_INVALID, why);
+    const nsk_bp_info &info = pl.info;
+    const int64_t F = c.nfactor, nid = c.nid, E = info.nedges;
     // ---- the handle's side: plain values, the records and weights on the device
     HIPCHECK(hipSetDevice(g->device));
     if ((rc = energy_ensure(g, 0, "nsk_bp_setup"))) return rc;
@@ -283,24 +283,24 @@ int nsk_bp_setup(nsk_graph *g, int which, int64_t chain, int sample_evidence, ns
     HIPCHECK(hipStreamSynchronize(g->stream));
     bp_free(g);
     NskBp &b = g->bp;
-    b.big = nb.big; b.b_off.swap(nb.b_off); b.info = info; b.nvlist = (int32_t)v_list.size(); b.nvbin = nb.nvbin;
+    b.big = pl.big; b.b_off.swap(pl.b_off); b.info = info; b.nvlist = (int32_t)pl.v_list.size(); b.nvbin = pl.nvbin;
     const int64_t before = g->mem.total;
-    const double bytes = 24.0 * (double)info.ntable + 16.0 * (double)info.nmsg + 20.0 * (double)E + 8.0 * (double)(mrec.size() / 2) +
-                         8.0 * (double)(slot_rec.size() / 2) + 24.0 * (double)F + 17.0 * (double)nid + (b.big ? 16.0 : 8.0) * (double)info.nbelief;
-    rc = bp_upload(g, &b.pm_off, pm_off);
-    if (!rc) rc = bp_upload(g, &b.tab_off, tab_off);
-    if (!rc) rc = bp_upload(g, &b.msg_off, msg_off);
+    const double bytes = 24.0 * (double)info.ntable + 16.0 * (double)info.nmsg + 20.0 * (double)E + 8.0 * (double)(pl.mrec.size() / 2) +
+                         8.0 * (double)(pl.slot_rec.size() / 2) + 24.0 * (double)F + 17.0 * (double)nid + (b.big ? 16.0 : 8.0) * (double)info.nbelief;
+    rc = bp_upload(g, &b.pm_off, pl.pm_off);
+    if (!rc) rc = bp_upload(g, &b.tab_off, pl.tab_off);
+    if (!rc) rc = bp_upload(g, &b.msg_off, pl.msg_off);
     if (!rc) rc = bp_upload(g, &b.d_b_off, b.b_off);
-    if (!rc) rc = bp_upload(g, &b.slot_off, slot_off);
-    if (!rc) rc = bp_upload(g, &b.edge_off, edge_off);
-    if (!rc) rc = bp_upload(g, &b.e_fac, e_fac);
-    if (!rc) rc = bp_upload(g, &b.e_var, e_var);
-    if (!rc) rc = bp_upload(g, &b.v_list, v_list);
-    if (!rc) rc = bp_upload(g, &b.v_eoff, v_eoff);
-    if (!rc) rc = bp_upload(g, &b.v_edges, v_edges);
-    if (!rc) rc = bp_upload(g, &b.mrec, mrec);
-    if (!rc) rc = bp_upload(g, &b.slot_rec, slot_rec);
-    if (!rc) rc = bp_upload(g, &b.v_state, state);
+    if (!rc) rc = bp_upload(g, &b.slot_off, pl.slot_off);
+    if (!rc) rc = bp_upload(g, &b.edge_off, pl.edge_off);
+    if (!rc) rc = bp_upload(g, &b.e_fac, pl.e_fac);
+    if (!rc) rc = bp_upload(g, &b.e_var, pl.e_var);
+    if (!rc) rc = bp_upload(g, &b.v_list, pl.v_list);
+    if (!rc) rc = bp_upload(g, &b.v_eoff, pl.v_eoff);
+    if (!rc) rc = bp_upload(g, &b.v_edges, pl.v_edges);
+    if (!rc) rc = bp_upload(g, &b.mrec, pl.mrec);
+    if (!rc) rc = bp_upload(g, &b.slot_rec, pl.slot_rec);
+    if (!rc) rc = bp_upload(g, &b.v_state, pl.state);
     if (!rc) rc = bp_alloc(g, &b.theta, (size_t)info.ntable);
     if (!rc) rc = bp_alloc(g, &b.psi, (size_t)info.ntable);
     if (!rc) rc = bp_alloc(g, &b.feat, (size_t)info.ntable);
@@ -493,81 +493,10 @@ int nsk_bp_learn_steps(nsk_graph *g, const double *target, int64_t nsteps, int64
     int rc = bp_common(g, who, true);
     if (rc) return rc;
     if (!target) return fail(NSK_E_INVALID, "null argument");
-    if ((rc = refuse(check_nsteps(who, nsteps, 4096)))) return rc;
-    if (iters_per_step < 1 || iters_per_step > 4096) return fail(NSK_E_INVALID, "nsk_bp_learn_steps: iters_per_step must lie in [1, 4096]");
-    if (nsteps * iters_per_step > 65536) return fail(NSK_E_INVALID, "nsk_bp_learn_steps: nsteps x iters_per_step must be at most 65536");
-    if (!(damping >= 0.0 && damping < 1.0)) return fail(NSK_E_INVALID, "nsk_bp_learn_steps: damping must lie in [0, 1)");
-    if (!(tol >= 0.0)) return fail(NSK_E_INVALID, "nsk_bp_learn_steps: tol must be at least 0");
-    if ((warm != 0 && warm != 1) || (normalize != 0 && normalize != 1)) return fail(NSK_E_INVALID, "nsk_bp_learn_steps: warm and normalize must be 0 or 1");
-    if ((rc = refuse(check_rates(who, step, decay, reg_param)))) return rc;
-    const Compiled &c = g->c;
-    const size_t nw = (size_t)c.nweight, T = (size_t)nsteps, I = (size_t)iters_per_step;
-    if ((rc = refuse(check_target(who, target, nw)))) return rc;
-    if (nw == 0) return NSK_OK;
-    if ((rc = nsk_moments_range(g, 1, who))) return rc;
-    HIPCHECK(hipSetDevice(g->device));
-
-    // the target and the factor counts by slot
-    std::vector<double> tgt(nw);
-    SlotMap(c).to_slots(target, tgt.data());
-    const std::vector<double> nfac = factors_per_slot(c);
-    BpLearnBufs b(g);
-    StepOutputs out(g, T, 1);
-    rc = call_alloc(g, &b.M, nw, who, "the int64 sums, 8 bytes a weight");
-    if (!rc) rc = call_alloc(g, &b.skipped, T, who, "the skip counters, 8 bytes a step");
-    if (!rc) rc = call_alloc(g, &b.zf, (size_t)g->bp.info.nfactor, who, "the factors' normalisers, 8 bytes a factor");
-    if (!rc) rc = call_alloc(g, &b.target, nw, who, "the target, 8 bytes a weight");
-    if (!rc) rc = call_alloc(g, &b.nfac, nw, who, "the factor counts, 8 bytes a weight");
-    if (!rc) rc = out.alloc_gmax(who);
-    if (!rc) rc = call_alloc(g, &b.res, T * I, who, "the residuals, nsteps x iters_per_step doubles");
-    if (!rc && moments) rc = out.alloc_rows(who);
-    if (rc) return rc;
-    hipError_t e = hipMemcpyAsync(b.target, tgt.data(), nw * sizeof(double), hipMemcpyHostToDevice, g->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(b.nfac, nfac.data(), nw * sizeof(double), hipMemcpyHostToDevice, g->stream);
-    if (e == hipSuccess) e = out.zero();
-    if (e == hipSuccess) e = hipMemsetAsync(b.res, 0, T * I * sizeof(unsigned long long), g->stream);
-    if (e != hipSuccess) { (void)hipStreamSynchronize(g->stream); HIPCHECK(e); }
-
-    const BpArgs a = bp_args(g);
-    const unsigned wblocks = (unsigned)((nw + NSK_BLOCK - 1) / NSK_BLOCK);
-    double st = step;           // step_0 = step, step_{t+1} = step_t * decay: the products are formed here, in t order
-    for (size_t t = 0; t < T && e == hipSuccess; t++) {
-        // 1. the tables under the weights as they stand; a cold start resets the messages
-        bp_refresh_enqueue(g, a);
-        if (!warm && a.nedge > 0) k_bp_reset<<<dim3(bp_blocks(a.nedge)), dim3(NSK_BLOCK), 0, g->stream>>>(a);
-        if ((e = hipGetLastError()) != hipSuccess) break;
-        // 2. the iterations, the early exit inside the step's own row of residuals
-        if ((e = bp_iterations_enqueue(g, a, I, damping, tol, b.res + t * I)) != hipSuccess) break;
-        // 3. the Bethe moments
-        if ((e = bp_moments_enqueue(g, a, b.zf, b.M, b.skipped + t)) != hipSuccess) break;
-        // 4. the update: nsk_pcd_steps' with one chain
-        k_pcd_update<<<dim3(wblocks), dim3(NSK_BLOCK), 0, g->stream>>>((const long long *)b.M, 1.0, nullptr, 0.0, b.target, b.nfac, (int)nw, g->w, g->w_fixed,
-                                                                      normalize, st, reg_param, out.gmax + t, out.row(t));
-        e = hipGetLastError();
-        g->weights_dirty = true;            // the next sweep call rebuilds what derives from the weights
-        st = st * decay;
-    }
-    // the resident tables agree with the learned weights: a following nsk_bp_run continues under them
-    if (e == hipSuccess) { bp_refresh_enqueue(g, a); e = hipGetLastError(); }
-    std::vector<unsigned long long> hskip(T);
-    std::vector<double> hres(T * I);
-    if (e == hipSuccess) e = out.download();
-    if (e == hipSuccess) e = hipMemcpyAsync(hskip.data(), b.skipped, T * 8, hipMemcpyDeviceToHost, g->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(hres.data(), b.res, T * I * 8, hipMemcpyDeviceToHost, g->stream);
-    const hipError_t e2 = hipStreamSynchronize(g->stream);      // (also: the uploads read the host vectors)
-    HIPCHECK(e);
-    HIPCHECK(e2);
-    out.deliver(gmax, moments);
-    for (size_t t = 0; t < T; t++) {
-        int64_t ran = -iters_per_step;
-        for (size_t i = 0; i < I; i++) {
-            if (residual) residual[t * I + i] = hres[t * I + i];
-            if (ran < 0 && hres[t * I + i] <= tol) ran = (int64_t)i + 1;
-        }
-        if (iters) iters[t] = ran;
-        if (skipped) skipped[t] = (int64_t)hskip[t];
-    }
-    return NSK_OK;
+    if ((rc = bp_steps_check(who, nsteps, iters_per_step, damping, tol, warm, step, decay, reg_param, normalize))) return rc;
+    if ((rc = refuse(check_target(who, target, (size_t)g->c.nweight)))) return rc;
+    return bp_steps_run(g, who, 1, target, nsteps, iters_per_step, damping, tol, warm, step, decay, reg_param, normalize, gmax, iters, residual,
+                        moments, skipped);
 }
 
 int nsk_bp_latent_steps(nsk_graph *g, int64_t nsteps, int64_t iters_per_step, double damping, double tol, int warm, double step,
@@ -576,85 +505,12 @@ int nsk_bp_latent_steps(nsk_graph *g, int64_t nsteps, int64_t iters_per_step, do
     const char *who = "nsk_bp_latent_steps";
     int rc = bp_common(g, who, false);
     if (rc) return rc;
-    NskBp &bc = bp_slot(g, 0), &bf = bp_slot(g, 1);
-    if (!bc.ready || !bf.ready)
-        return fail(NSK_E_INVALID, std::string(who) + ": slot " + (bc.ready ? "1 (the free phase)" : "0 (the clamped phase)") +
+    if (!bp_slot(g, 0).ready || !bp_slot(g, 1).ready)
+        return fail(NSK_E_INVALID, std::string(who) + ": slot " + (bp_slot(g, 0).ready ? "1 (the free phase)" : "0 (the clamped phase)") +
                                    " has no belief propagation set up (nsk_bp_select, nsk_bp_setup)");
-    if ((rc = refuse(check_nsteps(who, nsteps, 4096)))) return rc;
-    if (iters_per_step < 1 || iters_per_step > 4096) return fail(NSK_E_INVALID, "nsk_bp_latent_steps: iters_per_step must lie in [1, 4096]");
-    if (nsteps * iters_per_step > 65536) return fail(NSK_E_INVALID, "nsk_bp_latent_steps: nsteps x iters_per_step must be at most 65536");
-    if (!(damping >= 0.0 && damping < 1.0)) return fail(NSK_E_INVALID, "nsk_bp_latent_steps: damping must lie in [0, 1)");
-    if (!(tol >= 0.0)) return fail(NSK_E_INVALID, "nsk_bp_latent_steps: tol must be at least 0");
-    if ((warm != 0 && warm != 1) || (normalize != 0 && normalize != 1)) return fail(NSK_E_INVALID, "nsk_bp_latent_steps: warm and normalize must be 0 or 1");
-    if ((rc = refuse(check_rates(who, step, decay, reg_param)))) return rc;
-    const Compiled &c = g->c;
-    const size_t nw = (size_t)c.nweight, T = (size_t)nsteps, I = (size_t)iters_per_step, F = (size_t)c.nfactor;
-    if (nw == 0) return NSK_OK;
-    if ((rc = nsk_moments_range(g, 1, who))) return rc;
-    HIPCHECK(hipSetDevice(g->device));
-
-    const std::vector<double> nfac = factors_per_slot(c);
-    BpLearnBufs b(g);
-    StepOutputs out(g, T, 2);
-    rc = call_alloc(g, &b.M, 2 * nw, who, "the int64 sums of both set-ups, 16 bytes a weight");
-    if (!rc) rc = call_alloc(g, &b.skipped, 2 * T, who, "the skip counters, 16 bytes a step");
-    if (!rc) rc = call_alloc(g, &b.zf, 2 * F, who, "the factors' normalisers of both set-ups, 16 bytes a factor");
-    if (!rc) rc = call_alloc(g, &b.nfac, nw, who, "the factor counts, 8 bytes a weight");
-    if (!rc) rc = out.alloc_gmax(who);
-    if (!rc) rc = call_alloc(g, &b.res, 2 * T * I, who, "the residuals, nsteps x 2 x iters_per_step doubles");
-    if (!rc && moments) rc = out.alloc_rows(who);
-    if (rc) return rc;
-    hipError_t e = hipMemcpyAsync(b.nfac, nfac.data(), nw * sizeof(double), hipMemcpyHostToDevice, g->stream);
-    if (e == hipSuccess) e = out.zero();
-    if (e == hipSuccess) e = hipMemsetAsync(b.res, 0, 2 * T * I * sizeof(unsigned long long), g->stream);
-    if (e != hipSuccess) { (void)hipStreamSynchronize(g->stream); HIPCHECK(e); }
-
-    // index 0 of every pair is the clamped set-up (slot 0), index 1 the free one (slot 1); M = {Mc, M}
-    BpPair p = {};
-    p.a[0] = bp_args(g, bc); p.a[1] = bp_args(g, bf);
-    p.nvbin[0] = bc.nvbin; p.nvbin[1] = bf.nvbin;
-    for (size_t s = 0; s < 2; s++) { p.zf[s] = b.zf + s * F; p.M[s] = b.M + s * nw; }
-    const unsigned wblocks = (unsigned)((nw + NSK_BLOCK - 1) / NSK_BLOCK);
-    const int nedge = std::max(p.a[0].nedge, p.a[1].nedge);
-    double st = step;           // step_0 = step, step_{t+1} = step_t * decay: the products are formed here, in t order
-    for (size_t t = 0; t < T && e == hipSuccess; t++) {
-        for (size_t s = 0; s < 2; s++) { p.res[s] = b.res + (2 * t + s) * I; p.skipped[s] = b.skipped + 2 * t + s; }
-        // 1. both tables under the weights as they stand; a cold start resets both message sets
-        bp_refresh_enqueue(g, p);
-        if (!warm && nedge > 0) k_bp_reset2<<<dim3(bp_blocks(nedge), 2), dim3(NSK_BLOCK), 0, g->stream>>>(p);
-        if ((e = hipGetLastError()) != hipSuccess) break;
-        // 2. the iterations of both, each with its own row of residuals and its own early exit
-        if ((e = bp_iterations_enqueue(g, p, I, damping, tol)) != hipSuccess) break;
-        // 3. the Bethe moments of both
-        if ((e = bp_moments_enqueue(g, p)) != hipSuccess) break;
-        // 4. the update: nsk_pcd_latent_steps' with one chain a side
-        k_pcd_update<<<dim3(wblocks), dim3(NSK_BLOCK), 0, g->stream>>>((const long long *)p.M[1], 1.0, (const long long *)p.M[0], 1.0, nullptr, b.nfac, (int)nw,
-                                                                      g->w, g->w_fixed, normalize, st, reg_param, out.gmax + t, out.row(t));
-        e = hipGetLastError();
-        g->weights_dirty = true;            // the next sweep call rebuilds what derives from the weights
-        st = st * decay;
-    }
-    // the resident tables of both agree with the learned weights
-    if (e == hipSuccess) { bp_refresh_enqueue(g, p); e = hipGetLastError(); }
-    std::vector<unsigned long long> hskip(2 * T);
-    std::vector<double> hres(2 * T * I);
-    if (e == hipSuccess) e = out.download();
-    if (e == hipSuccess) e = hipMemcpyAsync(hskip.data(), b.skipped, 2 * T * 8, hipMemcpyDeviceToHost, g->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(hres.data(), b.res, 2 * T * I * 8, hipMemcpyDeviceToHost, g->stream);
-    const hipError_t e2 = hipStreamSynchronize(g->stream);      // (also: the upload reads the host vector)
-    HIPCHECK(e);
-    HIPCHECK(e2);
-    out.deliver(gmax, moments);
-    for (size_t r = 0; r < 2 * T; r++) {            // row r = (step, set-up)
-        int64_t ran = -iters_per_step;
-        for (size_t i = 0; i < I; i++) {
-            if (residual) residual[r * I + i] = hres[r * I + i];
-            if (ran < 0 && hres[r * I + i] <= tol) ran = (int64_t)i + 1;
-        }
-        if (iters) iters[r] = ran;
-        if (skipped) skipped[r] = (int64_t)hskip[r];
-    }
-    return NSK_OK;
+    if ((rc = bp_steps_check(who, nsteps, iters_per_step, damping, tol, warm, step, decay, reg_param, normalize))) return rc;
+    return bp_steps_run(g, who, 2, nullptr, nsteps, iters_per_step, damping, tol, warm, step, decay, reg_param, normalize, gmax, iters, residual,
+                        moments, skipped);
 }
 
 int nsk_bp_select(nsk_graph *g, int slot) {

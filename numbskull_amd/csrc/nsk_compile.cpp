@@ -13,19 +13,6 @@
 
 namespace nsk {
 
-bool known_function(int fn) {
-    switch (fn) {
-    case -1: case 0: case 1: case 2: case 3: case 4: case 7: case 8: case 9:
-    case 12: case 13: case 14: case 15: case 16: case 17:
-    case 18: case 19: case 20: case 21: case 22: case 23: case 24: case 25: case 26:
-    case 30:
-        return true;
-    default:
-        return false;
-    }
-}
-
-
 // The switches of one call.  The only function of the compiler that reads the environment.
 // Wide quads pay from a few hundred thousand variables per handle on (one MI355X, us per sweep, tile-by-tile kernel /
 // wide-quad kernel, tools/sessions/r6_s25.sh: 256 x 256 grid 6.63 / 6.60, 512 x 512 6.82 / 7.10, 500 x 1000 7.30 / 6.33, 1M grid

@@ -257,6 +257,16 @@ struct RouteCounts { int64_t tiles_shape, tiles_shape_padded, tiles_lane, tiles_
 void compiled_routes(const Compiled &c, int32_t *route, RouteCounts *counts);
 
 // true for function ids of inference.py:74-143
-bool known_function(int fn);
+inline bool known_function(int fn) {
+    switch (fn) {
+    case -1: case 0: case 1: case 2: case 3: case 4: case 7: case 8: case 9:
+    case 12: case 13: case 14: case 15: case 16: case 17:
+    case 18: case 19: case 20: case 21: case 22: case 23: case 24: case 25: case 26:
+    case 30:
+        return true;
+    default:
+        return false;
+    }
+}
 
 }  // namespace nsk

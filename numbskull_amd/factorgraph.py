@@ -1536,53 +1536,33 @@ class FactorGraph(object):
         if _all_copies(var_copy):
             raise ValueError('learn_bp serves one state: var_copy="all" is for the sampler')
         nw = self.weight.shape[0]
-        if latent:
-            if target is not None:
-                raise ValueError("learn_bp: latent=True takes no target (the clamped set-up's moments are the positive phase)")
-            return self._learn_bp_latent(epochs, stepsize, decay, reg_param, iters, damping, tol, warm, normalize, var_copy,
-                                         weight_copy, moments)
-        target = self._learn_target("learn_bp", target)
+        if latent and target is not None:
+            raise ValueError("learn_bp: latent=True takes no target (the clamped set-up's moments are the positive phase)")
+        if not latent:
+            target = self._learn_target("learn_bp", target)
         L, h = _lib.lib(), self._engine()
-        self._push(var_copy, weight_copy)
-        _lib.check(L.nsk_bp_setup(h, _lib.BUF_VALUE, 0, int(bool(sample_evidence)), None))
-        try:
-            gmax, ran, skipped = np.zeros(epochs, np.float64), np.zeros(epochs, np.int64), np.zeros(epochs, np.int64)
-            residual = np.zeros((epochs, iters), np.float64)
-            rows = np.zeros((epochs, nw), np.int64) if moments else None
-            _lib.check(L.nsk_bp_learn_steps(h, _lib.ptr(target), epochs, iters, float(damping), float(tol), int(bool(warm)), stepsize,
-                                            decay, reg_param, int(bool(normalize)), _lib.ptr(gmax), _lib.ptr(ran), _lib.ptr(residual),
-                                            _lib.ptr(rows), _lib.ptr(skipped)))
-            self._pull(var_copy, weight_copy, values=False, count=False)
-        finally:
-            L.nsk_bp_clear(h)
-        out = {"grad_max": gmax, "iters": np.abs(ran), "converged": ran > 0, "residual": residual, "skipped": skipped,
-               "target": target, "factors_per_weight": self._factors_per_weight()}
-        if moments:
-            out["moments"] = rows
-        return out
-
-    def _learn_bp_latent(self, epochs, stepsize, decay, reg_param, iters, damping, tol, warm, normalize, var_copy, weight_copy, moments):
-        """``learn_bp(latent=True)`` behind its argument checks: slot 0 the clamped set-up, slot 1 the free one"""
-        nw = self.weight.shape[0]
-        L, h = _lib.lib(), self._engine()
+        # latent: slot 0 the clamped set-up, slot 1 the free one, and a pair axis in what is kept per set-up; else the selected slot
+        slots, pair = ((0, 1), (2,)) if latent else ((L.nsk_bp_selected(h),), ())
         self._push(var_copy, weight_copy)
         try:
-            for slot in (0, 1):
+            for slot in slots:
                 _lib.check(L.nsk_bp_select(h, slot))
-                _lib.check(L.nsk_bp_setup(h, _lib.BUF_VALUE, 0, slot, None))
-            gmax, ran, skipped = np.zeros(epochs, np.float64), np.zeros((epochs, 2), np.int64), np.zeros((epochs, 2), np.int64)
-            residual = np.zeros((epochs, 2, iters), np.float64)
-            rows = np.zeros((epochs, 2, nw), np.int64) if moments else None
-            _lib.check(L.nsk_bp_latent_steps(h, epochs, iters, float(damping), float(tol), int(bool(warm)), stepsize, decay, reg_param,
-                                             int(bool(normalize)), _lib.ptr(gmax), _lib.ptr(ran), _lib.ptr(residual), _lib.ptr(rows),
-                                             _lib.ptr(skipped)))
+                _lib.check(L.nsk_bp_setup(h, _lib.BUF_VALUE, 0, slot if latent else int(bool(sample_evidence)), None))
+            gmax, ran, skipped = np.zeros(epochs, np.float64), np.zeros((epochs,) + pair, np.int64), np.zeros((epochs,) + pair, np.int64)
+            residual = np.zeros((epochs,) + pair + (iters,), np.float64)
+            rows = np.zeros((epochs,) + pair + (nw,), np.int64) if moments else None
+            args = (epochs, iters, float(damping), float(tol), int(bool(warm)), stepsize, decay, reg_param, int(bool(normalize)),
+                    _lib.ptr(gmax), _lib.ptr(ran), _lib.ptr(residual), _lib.ptr(rows), _lib.ptr(skipped))
+            _lib.check(L.nsk_bp_latent_steps(h, *args) if latent else L.nsk_bp_learn_steps(h, _lib.ptr(target), *args))
             self._pull(var_copy, weight_copy, values=False, count=False)
         finally:
-            for slot in (1, 0):                     # (slot 0 stays selected)
+            for slot in reversed(slots):            # (latent: slot 0 stays selected)
                 L.nsk_bp_select(h, slot)
                 L.nsk_bp_clear(h)
-        out = {"grad_max": gmax, "iters": np.abs(ran), "converged": ran > 0, "residual": residual, "skipped": skipped,
-               "factors_per_weight": self._factors_per_weight()}
+        out = {"grad_max": gmax, "iters": np.abs(ran), "converged": ran > 0, "residual": residual, "skipped": skipped}
+        if not latent:
+            out["target"] = target
+        out["factors_per_weight"] = self._factors_per_weight()
         if moments:
             out["moments"] = rows
         return out
