@@ -360,6 +360,49 @@ int nsk_bp_clear(nsk_graph *g);
 int nsk_bp_select(nsk_graph *g, int slot);
 int nsk_bp_selected(nsk_graph *g);
 
+/* Max-product belief propagation (FactorGraph.map_bp): the resident set-up above run over the (max, +) semiring -- MAP
+ * decoding.  Exact wherever the free variables form a forest (where the MAP assignment is unique); on a graph with
+ * cycles a deterministic start for nsk_icm.  numbskull_amd.diagnostics.ms_iterate / ms_decode are the rule in numpy, bit
+ * for bit.  Every call acts on the selected set-up (nsk_bp_select) and is NSK_E_INVALID without one.
+ * Log domain.  The tables are the set-up's theta (psi is not used); every directed edge owns card doubles at msg_off[e]
+ * in two arrays of their own, F (factor to variable) and V (variable to factor); a cold start sets every entry +0.0.
+ * MAX(a, b) is b where b > a or a is a NaN, else a; folded from its first entry it passes over NaNs as fmax does (an
+ * all-NaN maximum is a NaN of no particular payload; finite weights give no NaN).  Iteration t:
+ *   factor phase, per edge (f, j) and value k: s_j(a) = theta_f(a), then for i = 0 .. A - 1 ascending, i != j:
+ *     s = s + V[(f,i)][a_i]; m[k] = MAX over the table indices a with digit j equal to k; mx = MAX of m[0], m[1], .. in
+ *     k order; new[k] = m[k] - mx; damping and the residual exactly as in nsk_bp_run.  The maximum over a may be taken
+ *     in any order: under this rule a -0.0 meets it only where it runs over a single entry, so the bits do
+ *     not depend on the order;
+ *   variable phase, per free variable with the edges e_0 < .. < e_{d-1}: P_0 = +0.0, P_{i+1} = P_i + F[e_i]; S_{d-1} =
+ *     +0.0, S_{i-1} = S_i + F[e_i]; T = P_i + S_i, V[e_i][k] = T[k] - MAX_k T; the max-marginal b[k] = P_d[k] - MAX_k P_d.
+ * A clamped variable's max-marginal is 0 at its value and -inf elsewhere, a free variable's in no table all 0.
+ *   nsk_bp_map_run        up to max_iters iterations; the ranges, *iters and residual are those of nsk_bp_run; warm
+ *                         (0 or 1) = 0 starts cold, 1 continues from the resident messages.  The first call on a set-up
+ *                         allocates F, V, the max-marginals and the lists of the factors' routes (16 bytes a message
+ *                         entry, 8 a value, at most 4 a directed edge) and starts cold whatever `warm` says; the set-up
+ *                         owns them: nsk_graph_info.device_bytes counts them (nsk_bp_info.device_bytes stays what the
+ *                         set-up reported), nsk_bp_clear, a replacing set-up and nsk_graph_destroy free them;
+ *                         NSK_E_NOMEM names the bytes.  Everything is enqueued at once, one synchronisation.
+ *   nsk_bp_map_marginals  the "full" layout of nsk_bp_beliefs.
+ *   nsk_bp_map_download   what = 0: F, 1: V (msg_off's layout).
+ *   nsk_bp_map_decode     into chain `chain` of `which` (as nsk_icm names a row; a tally kept in the value bytes is first
+ *                         brought back to its array): a free variable with an edge takes argmax_k b[k] -- from best = 0,
+ *                         k ascending, "if b[k] > b[best]: best = k": the smallest k among several maxima, a NaN never
+ *                         wins; clamped variables and free ones in no table keep their values.  *ties (may be NULL) =
+ *                         the free variables with an edge whose largest max-marginal more than one k attains: non-zero
+ *                         means the decode is not unique.
+ *   nsk_bp_map_routes     counts[3] = the factors with an edge that the factor phase serves by one lane a factor (fewer
+ *                         than 64 table entries, cardinalities summing to at most 16), one wave a factor (cardinalities
+ *                         summing to at most 512), one lane a directed edge (the rest).
+ * Marginals, download and decode before the first run on a set-up are NSK_E_INVALID.  The sum-product messages and
+ * beliefs are untouched.  Every launch honours NSK_BP_GRID_CAP. */
+int nsk_bp_map_run(nsk_graph *g, int64_t max_iters, double damping, double tol, int warm, int64_t *iters,
+                   double *residual /* max_iters, may be NULL */);
+int nsk_bp_map_marginals(nsk_graph *g, const int64_t *vids, int64_t nvids, double *out /* total */);
+int nsk_bp_map_download(nsk_graph *g, int what, double *out);
+int nsk_bp_map_decode(nsk_graph *g, int which, int64_t chain, int64_t *ties /* may be NULL */);
+int nsk_bp_map_routes(nsk_graph *g, int64_t *counts /* 3 */);
+
 /* Learning by belief propagation (FactorGraph.bp_weight_moments / learn_bp): maximum-likelihood learning whose model
  * expectations come from the factor beliefs of the resident set-up above instead of from chains -- exact wherever BP is
  * exact (the free variables form a forest), the Bethe approximation on graphs with cycles, without sampling noise.

@@ -36,6 +36,7 @@ SYMBOLS = (
     "nsk_smc_sweeps", "nsk_pt_sweeps", "nsk_pl_gradient", "nsk_mple_steps", "nsk_weight_moments", "nsk_pcd_steps", "nsk_pcd_latent_steps",
     "nsk_bp_setup", "nsk_bp_layout", "nsk_bp_run", "nsk_bp_beliefs", "nsk_bp_download", "nsk_bp_clear",
     "nsk_bp_refresh", "nsk_bp_moments", "nsk_bp_learn_steps", "nsk_bp_select", "nsk_bp_selected", "nsk_bp_latent_steps",
+    "nsk_bp_map_run", "nsk_bp_map_marginals", "nsk_bp_map_download", "nsk_bp_map_decode", "nsk_bp_map_routes",
     "nsk_trace_ess", "nsk_trace_autocov_counts", "nsk_trace_pair_counts",
     "nsk_trace_value_autocov_counts", "nsk_trace_value_ess", "nsk_trace_value_pair_counts",
     "nsk_selftest_exp", "nsk_selftest_philox", "nsk_selftest_stream", "nsk_device_count", "nsk_last_error", "nsk_version",
@@ -80,6 +81,10 @@ class BpInfo(C.Structure):
 BP_MAX_MEMBERS, BP_MAX_TABLE = 16, 4096
 BP_THETA, BP_FACTOR_BELIEFS, BP_F2V, BP_V2F = range(4)
 BP_BLOCK, BP_VAR_BLOCK, BP_MAX_BLOCKS = 256, 128, 2048
+BP_MAP_F, BP_MAP_V = 0, 1           # what nsk_bp_map_download hands out
+# the routes of max-product's factor phase (csrc/nsk_bp_map_plan.h): one lane a factor below BP_MAP_LANE_TABLE entries whose
+# cardinalities sum to at most BP_MAP_LANE_CARDS, one wave a factor up to BP_MAP_LDS, one lane a directed edge beyond
+BP_MAP_LANE_TABLE, BP_MAP_LANE_CARDS, BP_MAP_LDS = 64, 16, 512
 BP_VAR_REG = 6          # a binary variable of at most this many edges is served from registers (csrc/nsk_kernels_bp.h)
 
 
@@ -219,6 +224,11 @@ def lib():
         L.nsk_bp_selected.argtypes = [C.c_void_p]
         L.nsk_bp_latent_steps.argtypes = [C.c_void_p, C.c_int64, C.c_int64, C.c_double, C.c_double, C.c_int, C.c_double,
                                           C.c_double, C.c_double, C.c_int] + [C.c_void_p] * 5
+        L.nsk_bp_map_run.argtypes = [C.c_void_p, C.c_int64, C.c_double, C.c_double, C.c_int, C.POINTER(C.c_int64), C.c_void_p]
+        L.nsk_bp_map_marginals.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]
+        L.nsk_bp_map_download.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
+        L.nsk_bp_map_decode.argtypes = [C.c_void_p, C.c_int, C.c_int64, C.POINTER(C.c_int64)]
+        L.nsk_bp_map_routes.argtypes = [C.c_void_p, C.c_void_p]
         L.nsk_pl_gradient.argtypes = [C.c_void_p, C.c_int, C.c_int64, C.c_int64, C.c_void_p, C.c_int64] + [C.c_void_p] * 3
         L.nsk_mple_steps.argtypes = [C.c_void_p, C.c_int, C.c_int64, C.c_int64, C.c_void_p, C.c_int64, C.c_int64,
                                      C.c_double, C.c_double, C.c_double, C.c_void_p, C.c_void_p]

@@ -25,7 +25,7 @@
 using namespace nsk;
 
 // (diagnostic, NSK_DIAG=1 NSK_BP_GRID_CAP=blocks, read at each call: small grids, later trips)
-static unsigned int bp_blocks(long long items, int block = NSK_BLOCK) {
+unsigned int bp_blocks(long long items, int block) {
     long long limit = NSK_BP_MAX_BLOCKS;
     if (const char *env = nsk::diag_env("NSK_BP_GRID_CAP")) {
         const long long cap = atoll(env);
@@ -35,13 +35,15 @@ static unsigned int bp_blocks(long long items, int block = NSK_BLOCK) {
     return (unsigned int)std::max<long long>(1, std::min(need, limit));
 }
 
+static unsigned int bp_blocks(long long items) { return bp_blocks(items, NSK_BLOCK); }
+
 static void bp_free(nsk_graph *g) {
     NskBp &b = g->bp;
     for (void *p : b.owned) dev_free(g, p);
     b = NskBp();
 }
 
-static BpArgs bp_args(const nsk_graph *g, const NskBp &b) {
+BpArgs bp_args(const nsk_graph *g, const NskBp &b) {
     BpArgs a = {};
     a.f_rec = (const uint4 *)g->f_rec; a.mrec = (const int2 *)b.mrec; a.pm_off = b.pm_off;
     a.slot_off = b.slot_off; a.slot_rec = (const int2 *)b.slot_rec;
@@ -284,6 +286,7 @@ int nsk_bp_setup(nsk_graph *g, int which, int64_t chain, int sample_evidence, ns
     bp_free(g);
     NskBp &b = g->bp;
     b.big = pl.big; b.b_off.swap(pl.b_off); b.info = info; b.nvlist = (int32_t)pl.v_list.size(); b.nvbin = pl.nvbin;
+    bp_map_routes(pl, NSK_ZLOCAL, b.ms_routes);     // (host only: nsk_bp_map_run uploads the lists when it is first called)
     const int64_t before = g->mem.total;
     const double bytes = 24.0 * (double)info.ntable + 16.0 * (double)info.nmsg + 20.0 * (double)E + 8.0 * (double)(pl.mrec.size() / 2) +
                          8.0 * (double)(pl.slot_rec.size() / 2) + 24.0 * (double)F + 17.0 * (double)nid + (b.big ? 16.0 : 8.0) * (double)info.nbelief;

@@ -4,7 +4,8 @@
 // nsk_cond.hip: the diagnostics; nsk_icm.hip: the greedy MAP search; nsk_temper.hip: tempered sweep schedules;
 // nsk_smc.hip: population annealing on top of them; nsk_pt.hip: parallel tempering; nsk_plgrad.hip: the pseudo-likelihood
 // gradient and MPLE learning; nsk_pcd.hip: the chain-summed moments and persistent contrastive divergence, fully observed
-// and with latent variables; nsk_bp.hip: loopy belief propagation).
+// and with latent variables; nsk_bp.hip: loopy belief propagation;
+// nsk_bp_map.hip: max-product on the same set-up).
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -17,6 +18,7 @@
 
 #include "../../include/numbskull_amd.h"
 #include "nsk_alloc.h"
+#include "nsk_bp_map_plan.h"
 #include "nsk_compile.h"
 #include "nsk_device.h"
 #include "nsk_kernels_gibbs.h"
@@ -132,6 +134,12 @@ struct NskBp {
     double *theta = nullptr, *psi = nullptr, *f2v = nullptr, *v2f = nullptr, *belief = nullptr, *wk = nullptr;
     double *feat = nullptr;            // the tables without the weight, filled with theta (nsk_bp_refresh, nsk_bp_moments)
     int32_t nvlist = 0, nvbin = 0;     // free variables with an edge; the binary ones among them, first in v_list
+    // Max-product (nsk_bp_map.hip): the set-up plans the factors' routes (host only); the first nsk_bp_map_run uploads
+    // the lists and allocates both message arrays (nmsg doubles each) and the max-marginals (nbelief) -- all in `owned`.
+    nsk::BpMapRoutes ms_routes;
+    double *ms_f = nullptr, *ms_v = nullptr, *ms_mm = nullptr;
+    int32_t *ms_lane = nullptr, *ms_wave = nullptr, *ms_edge = nullptr;
+    int32_t ms_nlane = 0, ms_nwave = 0, ms_nedge = 0;      // entries of the three lists
 };
 
 // Boundary exchange, the collective path (nsk_exchange.hip: nsk_exchange_setup, nsk_comm_init, nsk_*_sweeps_exchange):
@@ -584,6 +592,11 @@ int nsk_cond_accumulate(nsk_graph *g, const NskCondSel &sel, const void *val, in
 void nsk_cond_sel_free(nsk_graph *g, NskCondSel &sel);      // the device copies of a selection (the trace's goes with the trace)
 namespace nsk { struct EnergyArgs; }
 nsk::EnergyArgs energy_args(const nsk_graph *g);
+// belief propagation's launches (nsk_bp.hip; nsk_bp_map.hip shares them): the persistent grid of `items` items -- where
+// NSK_BP_GRID_CAP applies -- and what the kernels read of a set-up
+namespace nsk { struct BpArgs; }
+unsigned int bp_blocks(long long items, int block);
+nsk::BpArgs bp_args(const nsk_graph *g, const NskBp &b);
 // the log-potential of `nchains` chains from `val` on / every factor's value, enqueued on the handle's stream (nsk_energy.hip)
 int nsk_energy_enqueue(nsk_graph *g, const void *val, int nchains, bool packed_bytes, double *out);
 int nsk_factor_values_enqueue(nsk_graph *g, const void *val, double *out);

@@ -1185,3 +1185,117 @@ def bethe_log_z(layout, theta, factor_beliefs, beliefs):
     total += float(np.sum((deg[walked] - 1) * h[walked]))
     total += float(np.sum(np.log(card[~clamped & (deg == 0)].astype(np.float64))))
     return total
+
+
+# ------------------------------------------------------------------------------------------------- max-product BP
+def _ms_max(a, b):
+    """``b`` where ``b > a`` or ``a`` is a NaN, else ``a``: folded from the first entry it passes over NaNs as fmax does
+    and keeps the first among equal entries"""
+    return b if (b > a or a != a) else a
+
+
+def _ms_fold(v):
+    mx = v[0]
+    for x in v[1:]:
+        mx = _ms_max(mx, x)
+    return mx
+
+
+def ms_iterate(layout, theta, iters, damping=0.0, tol=0.0, messages=None):
+    """Max-product belief propagation in the log domain as nsk_bp_map_run performs it (the header states the rule):
+    ``layout`` and ``theta`` are those of ``bp_iterate``.  Factor phase, per edge (f, j): ``s_j(a) = theta_f(a)`` plus the
+    other axes' incoming ``V`` entries, the axes ascending; ``m[k]`` the maximum over the entries with digit j equal to k
+    (folded ascending here; the device may fold in any order), normalised by ``m[k] - max_k m``, damped as ``bp_iterate``
+    damps, the residual the largest change, NaN counting as inf.  Variable phase: prefix sums ``P``, suffix sums ``S``,
+    ``V[e_i] = (P_i + S_i) - max``, the max-marginal ``P_d - max``.  ``messages=(F, V)`` continues from those; None starts
+    at +0.0.  Returns a dict: ``F``, ``V``, ``max_marginals`` (the "full" layout of ``layout["offsets"]``: a clamped
+    variable has 0 at its value and -inf elsewhere, a free variable in no table all 0), ``residual``, ``iters`` (both as
+    ``bp_iterate`` returns them) and ``negzero_maxima`` -- how many maxima over SEVERAL table entries met a -0.0: the
+    device's order-free maximum equals this fold bit for bit as long as that is 0."""
+    to, eo, mo = layout["table_off"], layout["edge_off"], layout["msg_off"]
+    card, off = layout["card"], layout["offsets"]
+    theta = np.asarray(theta, np.float64)
+    nmsg = int(mo[-1])
+    F, V = (np.zeros(nmsg), np.zeros(nmsg)) if messages is None else (np.array(m, np.float64) for m in messages)
+    mm = np.zeros(int(off[-1]))
+    for v in range(len(card)):
+        if layout["clamped"][v]:
+            mm[off[v]:off[v + 1]] = -np.inf
+            if 0 <= layout["values"][v] < card[v]:
+                mm[off[v] + layout["values"][v]] = 0.0
+    lam, oml = float(damping), 1.0 - float(damping)
+    residual = np.zeros(iters)
+    ran, negzero = -iters, 0
+    for t in range(iters):
+        if t > 0 and residual[t - 1] <= tol:
+            break
+        res = 0.0
+        new = F.copy()
+        with np.errstate(all="ignore"):
+            for f in range(len(to) - 1):
+                shape = layout["shapes"][f]
+                if not shape:
+                    continue
+                e0 = int(eo[f])
+                digits = np.indices(shape).reshape(len(shape), -1)          # digits[i][a], C order
+                for j in range(len(shape)):
+                    s = theta[to[f]:to[f + 1]].copy()
+                    for i in range(len(shape)):
+                        if i != j:
+                            s = s + V[mo[e0 + i] + digits[i]]
+                    m = []
+                    for k in range(shape[j]):
+                        mine = [float(x) for x in s[digits[j] == k]]        # ascending in a
+                        if len(mine) > 1 and any(x == 0.0 and np.signbit(x) for x in mine):
+                            negzero += 1
+                        m.append(_ms_fold(mine))
+                    mx = _ms_fold(m)
+                    for k in range(shape[j]):
+                        nw = float(np.float64(m[k]) - np.float64(mx))
+                        old = float(F[mo[e0 + j] + k])
+                        if lam > 0.0:
+                            nw = oml * nw + lam * old
+                        new[mo[e0 + j] + k] = nw
+                        dd = abs(nw - old)
+                        res = max(res, dd if dd == dd else np.inf)
+        F = new
+        residual[t] = res
+        with np.errstate(all="ignore"):
+            for v in range(len(card)):
+                edges = layout["var_edges"][v]
+                if layout["clamped"][v] or not edges:
+                    continue
+                n = int(card[v])
+                P = np.zeros(n)
+                for e in edges:
+                    V[mo[e]:mo[e + 1]] = P
+                    P = P + F[mo[e]:mo[e + 1]]
+                mm[off[v]:off[v + 1]] = P - np.float64(_ms_fold([float(x) for x in P]))
+                S = np.zeros(n)
+                for e in reversed(edges):
+                    T = V[mo[e]:mo[e + 1]] + S
+                    V[mo[e]:mo[e + 1]] = T - np.float64(_ms_fold([float(x) for x in T]))
+                    S = S + F[mo[e]:mo[e + 1]]
+        if ran < 0 and res <= tol:
+            ran = t + 1
+    return {"F": F, "V": V, "max_marginals": mm, "residual": residual, "iters": ran, "negzero_maxima": negzero}
+
+
+def ms_decode(layout, max_marginals, values):
+    """The assignment nsk_bp_map_decode writes: a free variable with an edge takes ``argmax_k b[k]`` by the comparison
+    of ``icm_choice`` from ``best = 0`` (the smallest k among several maxima, a NaN never wins); every other variable
+    keeps its entry of ``values``.  Returns ``(assignment int64 (nvar,), ties)``: ``ties`` counts the decoded variables
+    whose largest max-marginal more than one k attains."""
+    off = layout["offsets"]
+    b = np.asarray(max_marginals, np.float64)
+    x = np.array(values, np.int64)
+    sel = [v for v in range(len(x)) if not layout["clamped"][v] and layout["var_edges"][v]]
+    ties = 0
+    if sel:
+        sub = np.concatenate([[0], np.cumsum([off[v + 1] - off[v] for v in sel])]).astype(np.int64)
+        p = np.concatenate([b[off[v]:off[v + 1]] for v in sel])
+        x[sel] = icm_choice(sub, p, np.zeros(len(sel), np.int64))
+        for i, v in enumerate(sel):
+            mine = b[off[v]:off[v + 1]]
+            ties += int(np.sum(mine == mine[x[v]]) > 1)
+    return x, ties

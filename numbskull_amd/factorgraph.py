@@ -1463,6 +1463,53 @@ class FactorGraph(object):
             out.update(table_offsets=table_off, theta=theta, factor_beliefs=fb)
         return out
 
+    def map_bp(self, max_iters=100, damping=0.0, tol=1e-9, var_copy=0, weight_copy=0, evidence_chain=False,
+               sample_evidence=False, polish=False, max_sweeps=100):
+        """MAP decoding by max-product belief propagation on the device (nsk_bp_setup / nsk_bp_map_run /
+        nsk_bp_map_decode): the message passing of ``belief_propagation`` over the (max, +) semiring, in the log domain.
+        Exact -- the most probable joint assignment of the free variables given the clamped ones -- wherever the free
+        variables form a forest and that assignment is unique; on a graph with cycles a deterministic starting point
+        that ``polish=True`` hands to ``icm(max_sweeps)``.  State, weights, clamping, the iteration's arguments and the
+        refusals are those of ``belief_propagation``; no random numbers are drawn.  Every free variable in a table takes
+        the value of its largest max-marginal (the smallest among several: ``diagnostics.ms_iterate`` / ``ms_decode``
+        are the rule in numpy); the assignment replaces the row it started from, as ``icm`` leaves its result, and
+        nothing else changes.  Returns a dict: ``values`` (int64, all variables), ``log_potential`` (of ``values``, from
+        ``log_potential()``), ``iters``, ``converged``, ``residual`` as ``belief_propagation`` returns them, ``ties`` --
+        the decoded variables whose largest max-marginal several values attain: non-zero means the decode is not
+        unique --, ``offsets`` and ``max_marginals`` (the layout of ``conditionals``: 0 at a variable's best value,
+        negative elsewhere).  With ``polish`` also ``decoded_log_potential`` (before the sweeps), ``sweeps`` and
+        ``icm_converged``."""
+        max_iters = int(max_iters)
+        if max_iters < 1 or max_iters > 4096:
+            raise ValueError("map_bp: max_iters must lie in [1, 4096]")
+        if _all_copies(var_copy):
+            raise ValueError('map_bp serves one state: var_copy="all" is for the sampler')
+        L, h = _lib.lib(), self._engine()
+        which = _lib.BUF_VALUE_EVID if evidence_chain else _lib.BUF_VALUE
+        self._push(var_copy, weight_copy)
+        _lib.check(L.nsk_bp_setup(h, which, 0, int(bool(sample_evidence)), None))
+        try:
+            iters, ties, residual = C.c_int64(0), C.c_int64(0), np.zeros(max_iters, np.float64)
+            _lib.check(L.nsk_bp_map_run(h, max_iters, float(damping), float(tol), 0, C.byref(iters), _lib.ptr(residual)))
+            _, offsets = self._cond_selection(None, None, "map_bp")
+            mm = np.zeros(int(offsets[-1]), np.float64)
+            _lib.check(L.nsk_bp_map_marginals(h, None, 0, _lib.ptr(mm)))
+            _lib.check(L.nsk_bp_map_decode(h, which, 0, C.byref(ties)))
+        finally:
+            L.nsk_bp_clear(h)
+        self._pull(var_copy, weight_copy, weights=False, count=False)
+        row = (self.var_value_evid if evidence_chain else self.var_value)[var_copy]
+        lp = float(self.log_potential(var_copy, weight_copy, evidence_chain))
+        out = {"values": np.array(row, np.int64), "log_potential": lp, "iters": abs(int(iters.value)),
+               "converged": bool(iters.value > 0), "residual": residual, "ties": int(ties.value), "offsets": offsets,
+               "max_marginals": mm}
+        if polish:
+            pol = self.icm(max_sweeps, var_copy, weight_copy, evidence_chain, sample_evidence)
+            out.update(decoded_log_potential=lp, sweeps=pol["sweeps"], icm_converged=pol["converged"],
+                       values=np.array(row, np.int64),
+                       log_potential=float(self.log_potential(var_copy, weight_copy, evidence_chain)))
+        return out
+
     def bp_weight_moments(self, max_iters=100, damping=0.0, tol=1e-9, var_copy=0, weight_copy=0, evidence_chain=False,
                           sample_evidence=False, counts=False):
         """The expected per-weight statistics ``E[S_w]`` under belief propagation (nsk_bp_setup / nsk_bp_run /
