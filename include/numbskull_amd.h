@@ -403,6 +403,48 @@ int nsk_bp_map_download(nsk_graph *g, int what, double *out);
 int nsk_bp_map_decode(nsk_graph *g, int which, int64_t chain, int64_t *ties /* may be NULL */);
 int nsk_bp_map_routes(nsk_graph *g, int64_t *counts /* 3 */);
 
+/* Sum-product belief propagation under a RESIDUAL schedule (FactorGraph.belief_propagation(schedule="residual")): a round
+ * recomputes only the messages whose inputs moved and commits only those whose pending change is large against the
+ * largest pending one -- the bulk-synchronous form of residual BP.  It acts on the selected resident set-up
+ * (nsk_bp_select; NSK_E_INVALID without one) and SHARES its f2v, v2f and beliefs with nsk_bp_run: beliefs, factor
+ * beliefs, nsk_bp_moments and a following nsk_bp_run work unchanged on what it leaves.  The per-item arithmetic is that of
+ * nsk_bp_run; numbskull_amd.diagnostics.rbp_iterate is the rule in numpy, bit for bit.
+ * State of its own, owned by the set-up: cand, the candidate message of every edge (msg_off's layout), and r[e], a double
+ * per edge: the largest entry of the change a commit of e would make now, |DAMP(cand[k], f2v[k]) - f2v[k]| with
+ * DAMP(c, old) = (1 - d) * c + d * old when the damping d > 0, else c -- bp_store's arithmetic, a NaN counting as +inf.
+ * (Without damping that is |cand[k] - f2v[k]|.  Measuring the DAMPED change is what makes frac = 0 the flooding schedule
+ * bit for bit under any damping.)  Round t:
+ *   1. candidates, over the dirty edges D_t: cand[e] = the factor phase of nsk_bp_run for that edge without damping (the
+ *      sums, Z and the divisions in k order); then r[e] as above.  recomputed[t] = |D_t|.
+ *   2. residual[t] = the largest r[e] over ALL edges (an integer maximum of bit patterns).  The kernels of a round t' > t
+ *      return at once when residual[t] <= tol; round t itself completes, as a flooding iteration does.
+ *   3. select and commit, over all edges: tau = frac * residual[t] (one rounded product) when frac > 0, else +0.0; e is
+ *      selected iff r[e] > 0 and r[e] >= tau.  A selected edge stores new[k] = DAMP(cand[k], f2v[k]); its r[e] becomes the
+ *      largest |DAMP(cand[k], new[k]) - new[k]| (+0.0 without damping); its variable becomes TOUCHED.  updates[t] = the
+ *      edges selected.
+ *   4. variable phase, over the touched variables V_t, each once: exactly the variable phase of nsk_bp_run for that
+ *      variable (every v2f of its edges, its belief).  For each of its edges (g, j) whose v2f vector changed in any bit,
+ *      every other edge (g, i != j) of that factor enters D_{t+1}, each once.
+ * A cold start (warm == 0, and the first call on a set-up whatever `warm` says) resets the messages to 1 / card, takes D_0
+ * = all edges and V_0 = EVERY free variable with an edge; a warm start takes D_0 = all edges (psi may have been refreshed)
+ * and V_0 = the touched variables only.  Hence: with frac == 0, round t leaves the bits of flooding iteration t in f2v,
+ * v2f, the beliefs, residual[t] and *rounds, for any damping and tol; and a warm call of b rounds behind a call of a
+ * rounds (neither meeting tol) leaves what one call of a + b rounds leaves -- only recomputed[0] of the second differs.
+ *   nsk_bp_residual_run  max_rounds in 1 .. 4096, frac in [0, 1], damping and tol as nsk_bp_run, warm 0 or 1; anything else
+ *                        is NSK_E_INVALID before anything is allocated.  *rounds follows *iters of nsk_bp_run: the rounds
+ *                        up to and including the first with residual <= tol, else -max_rounds.  residual, updates and
+ *                        recomputed [max_rounds] may be NULL; behind the early exit they read 0.  The first call on a
+ *                        set-up allocates cand and r, a flag byte an edge and a variable, the two queues and the map
+ *                        from an edge to its variable's place (8 bytes a message entry + 17 an edge + 5 a free variable
+ *                        with an edge; where a variable is not binary or has more than 6 edges another 8 a message
+ *                        entry + 1 an edge for the walks through memory); the set-up owns them as it owns max-product's
+ *                        arrays: counted in nsk_graph_info.device_bytes, freed by nsk_bp_clear, a replacing set-up and
+ *                        nsk_graph_destroy; NSK_E_NOMEM names the bytes.  Everything is enqueued at once, one
+ *                        synchronisation.  Every launch honours NSK_BP_GRID_CAP. */
+int nsk_bp_residual_run(nsk_graph *g, int64_t max_rounds, double frac, double damping, double tol, int warm, int64_t *rounds,
+                        double *residual /* max_rounds, may be NULL */, int64_t *updates /* max_rounds, may be NULL */,
+                        int64_t *recomputed /* max_rounds, may be NULL */);
+
 /* Learning by belief propagation (FactorGraph.bp_weight_moments / learn_bp): maximum-likelihood learning whose model
  * expectations come from the factor beliefs of the resident set-up above instead of from chains -- exact wherever BP is
  * exact (the free variables form a forest), the Bethe approximation on graphs with cycles, without sampling noise.

@@ -287,6 +287,8 @@ int nsk_bp_setup(nsk_graph *g, int which, int64_t chain, int sample_evidence, ns
     NskBp &b = g->bp;
     b.big = pl.big; b.b_off.swap(pl.b_off); b.info = info; b.nvlist = (int32_t)pl.v_list.size(); b.nvbin = pl.nvbin;
     bp_map_routes(pl, NSK_ZLOCAL, b.ms_routes);     // (host only: nsk_bp_map_run uploads the lists when it is first called)
+    b.rs_walk = b.nvlist > b.nvbin;                 // (host only: nsk_bp_residual_run's scratch of the walks through memory)
+    for (int32_t i = 0; i < b.nvbin && !b.rs_walk; i++) b.rs_walk = pl.v_eoff[(size_t)i + 1] - pl.v_eoff[(size_t)i] > NSK_BP_VAR_REG;
     const int64_t before = g->mem.total;
     const double bytes = 24.0 * (double)info.ntable + 16.0 * (double)info.nmsg + 20.0 * (double)E + 8.0 * (double)(pl.mrec.size() / 2) +
                          8.0 * (double)(pl.slot_rec.size() / 2) + 24.0 * (double)F + 17.0 * (double)nid + (b.big ? 16.0 : 8.0) * (double)info.nbelief;

@@ -140,6 +140,13 @@ struct NskBp {
     double *ms_f = nullptr, *ms_v = nullptr, *ms_mm = nullptr;
     int32_t *ms_lane = nullptr, *ms_wave = nullptr, *ms_edge = nullptr;
     int32_t ms_nlane = 0, ms_nwave = 0, ms_nedge = 0;      // entries of the three lists
+    // The residual schedule (nsk_bp_residual.hip): the first nsk_bp_residual_run allocates the candidates and pending
+    // changes, the flags, the queues and the edge -> v_list position map -- all in `owned`.  rs_walk (the set-up's): a
+    // variable takes a walk through memory (not binary, or more than NSK_BP_VAR_REG edges), so rs_pre and rs_chg exist.
+    bool rs_walk = false;
+    double *rs_cand = nullptr, *rs_r = nullptr, *rs_pre = nullptr;
+    uint8_t *rs_chg = nullptr, *rs_dflag = nullptr, *rs_vflag = nullptr;
+    int32_t *rs_dq = nullptr, *rs_vq = nullptr, *rs_vpos = nullptr;
 };
 
 // Boundary exchange, the collective path (nsk_exchange.hip: nsk_exchange_setup, nsk_comm_init, nsk_*_sweeps_exchange):

@@ -223,19 +223,26 @@ __device__ __forceinline__ void bp_rescale(double *v, int n) {
     }
 }
 
+__device__ __forceinline__ bool bp_bits_differ(double x, double y) { return __double_as_longlong(x) != __double_as_longlong(y); }
+
 // one variable's phase.  N == 2: a binary variable, vectors in registers; N == NSK_ZLOCAL: lane-private arrays of n <= N
 // entries; N == 0: the product lives in the variable's belief slot, the running suffix product in its wk slot and the
 // vector under way in the v2f slot itself.
-template <int N>
-__device__ __forceinline__ void bp_var_lane(const BpArgs &a, int n, const int32_t *edges, int d, double *bel, double *wk) {
+// CHG (the residual schedule, nsk_kernels_bpres.h): the prefix products and the vector under way live in `pre` (msg_off's
+// layout) instead of the v2f slot, so the old message is still there when the new one is formed -- the same values, kept
+// elsewhere -- and chg[edge] says whether any bit of it changed.  Without CHG the code is what it was.
+template <int N, bool CHG = false>
+__device__ __forceinline__ void bp_var_lane(const BpArgs &a, int n, const int32_t *edges, int d, double *bel, double *wk, double *pre = nullptr,
+                                            uint8_t *chg = nullptr) {
     double Pl[N ? N : 1], Sl[N ? N : 1], Tl[N ? N : 1];
     double *P = N ? Pl : bel, *S = N ? Sl : wk;
+    double *pf = CHG ? pre : a.v2f;
     if (N == 2) n = 2;
 #define NSK_BP_K for (int k = 0; k < (N == 2 ? 2 : n); k++)
     NSK_BP_K P[k] = 1.0;
     for (int i = 0; i < d; i++) {
         const long long mo = a.msg_off[edges[i]];
-        NSK_BP_K a.v2f[mo + k] = P[k];
+        NSK_BP_K pf[mo + k] = P[k];
         NSK_BP_K P[k] = P[k] * a.f2v[mo + k];
         bp_rescale<N == 2 ? 2 : 0>(P, n);
     }
@@ -245,12 +252,21 @@ __device__ __forceinline__ void bp_var_lane(const BpArgs &a, int n, const int32_
     NSK_BP_K S[k] = 1.0;
     for (int i = d - 1; i >= 0; i--) {
         const long long mo = a.msg_off[edges[i]];
-        double *T = N ? Tl : a.v2f + mo;
-        NSK_BP_K T[k] = a.v2f[mo + k] * S[k];
+        double *T = N ? Tl : pf + mo;
+        NSK_BP_K T[k] = pf[mo + k] * S[k];
         bp_rescale<N == 2 ? 2 : 0>(T, n);
         double Zt = T[0];
         for (int k = 1; k < (N == 2 ? 2 : n); k++) Zt = Zt + T[k];
-        NSK_BP_K a.v2f[mo + k] = T[k] / Zt;
+        if (CHG) {
+            bool c = false;
+            NSK_BP_K {
+                const double nw = T[k] / Zt;
+                c = c || bp_bits_differ(nw, a.v2f[mo + k]);
+                a.v2f[mo + k] = nw;
+            }
+            chg[edges[i]] = c ? 1 : 0;
+        } else
+            NSK_BP_K a.v2f[mo + k] = T[k] / Zt;
         NSK_BP_K S[k] = S[k] * a.f2v[mo + k];
         bp_rescale<N == 2 ? 2 : 0>(S, n);
     }
@@ -260,15 +276,22 @@ __device__ __forceinline__ void bp_var_lane(const BpArgs &a, int n, const int32_
 // The same arithmetic for a binary variable of at most NSK_BP_VAR_REG edges, its incoming messages and prefix products
 // held in registers: every message is read once and written once (the walk above stores the prefixes into v2f and reads
 // them back, and reads f2v in both passes), and the loads of all edges are in flight together.
+// CHG (the residual schedule): the old messages are loaded with the incoming ones, and bit i of the result says whether any
+// bit of edge i's message changed.  Without CHG the code is what it was (the result is 0 and dropped).
 #define NSK_BP_VAR_REG 6
-__device__ __forceinline__ void bp_var_lane_reg(const BpArgs &a, const int32_t *edges, int d, double *bel) {
+template <bool CHG = false>
+__device__ __forceinline__ unsigned int bp_var_lane_reg(const BpArgs &a, const int32_t *edges, int d, double *bel) {
     long long mo[NSK_BP_VAR_REG];
-    double f0[NSK_BP_VAR_REG], f1[NSK_BP_VAR_REG], p0[NSK_BP_VAR_REG], p1[NSK_BP_VAR_REG];
+    double f0[NSK_BP_VAR_REG], f1[NSK_BP_VAR_REG], p0[NSK_BP_VAR_REG], p1[NSK_BP_VAR_REG], o0[NSK_BP_VAR_REG], o1[NSK_BP_VAR_REG];
+    unsigned int changed = 0;
 #pragma unroll
     for (int i = 0; i < NSK_BP_VAR_REG; i++) mo[i] = i < d ? a.msg_off[edges[i]] : 0;
 #pragma unroll
     for (int i = 0; i < NSK_BP_VAR_REG; i++)
-        if (i < d) { f0[i] = a.f2v[mo[i]]; f1[i] = a.f2v[mo[i] + 1]; }
+        if (i < d) {
+            f0[i] = a.f2v[mo[i]]; f1[i] = a.f2v[mo[i] + 1];
+            if (CHG) { o0[i] = a.v2f[mo[i]]; o1[i] = a.v2f[mo[i] + 1]; }
+        }
     double P[2] = {1.0, 1.0};
 #pragma unroll
     for (int i = 0; i < NSK_BP_VAR_REG; i++)
@@ -286,10 +309,17 @@ __device__ __forceinline__ void bp_var_lane_reg(const BpArgs &a, const int32_t *
             double T[2] = {p0[i] * S[0], p1[i] * S[1]};
             bp_rescale<2>(T, 2);
             const double Zt = T[0] + T[1];
-            a.v2f[mo[i]] = T[0] / Zt; a.v2f[mo[i] + 1] = T[1] / Zt;
+            if (CHG) {
+                const double n0 = T[0] / Zt, n1 = T[1] / Zt;
+                if (bp_bits_differ(n0, o0[i]) || bp_bits_differ(n1, o1[i])) changed |= 1u << i;
+                a.v2f[mo[i]] = n0; a.v2f[mo[i] + 1] = n1;
+            } else {
+                a.v2f[mo[i]] = T[0] / Zt; a.v2f[mo[i] + 1] = T[1] / Zt;
+            }
             S[0] = S[0] * f0[i]; S[1] = S[1] * f1[i];
             bp_rescale<2>(S, 2);
         }
+    return changed;
 }
 
 // iteration t, variable phase over the entries [lo, hi) of v_list.  The list holds the binary variables first: BIN serves

@@ -1010,6 +1010,73 @@ def bp_psi(layout, theta, exp=np.exp):
     return psi
 
 
+def _bp_candidate(layout, psi, v2f, f, j):
+    """the factor phase of edge (f, j) without damping: ``m[k] / Z``, the sums over the table entries ascending, Z and the
+    divisions in k order (Python floats)"""
+    to, mo = layout["table_off"], layout["msg_off"]
+    shape, e0 = layout["shapes"][f], int(layout["edge_off"][f])
+    m = [0.0] * shape[j]
+    for a in range(int(to[f + 1] - to[f])):
+        d = _bp_digits(a, shape)
+        x = float(psi[to[f] + a])
+        for i in range(len(shape)):
+            if i != j:
+                x = x * float(v2f[mo[e0 + i] + d[i]])
+        m[d[j]] = m[d[j]] + x
+    z = _bp_sum(m)
+    with np.errstate(all="ignore"):
+        return [float(np.float64(m[k]) / np.float64(z)) for k in range(shape[j])]
+
+
+def _bp_damp(nw, old, lam, oml):
+    return oml * nw + lam * old if lam > 0.0 else nw
+
+
+def _bp_change(nw, old):
+    """``|nw - old|``, a NaN counting as +inf"""
+    dd = abs(nw - old)
+    return dd if dd == dd else np.inf
+
+
+def _bp_var_phase(layout, f2v, v2f, beliefs, v, rescale):
+    """the variable phase of one free variable with an edge, in place: every v2f of its edges and its belief"""
+    mo, off = layout["msg_off"], layout["offsets"]
+    edges, n = layout["var_edges"][v], int(layout["card"][v])
+    with np.errstate(all="ignore"):
+        P = [1.0] * n
+        for e in edges:
+            v2f[mo[e]:mo[e + 1]] = P
+            P = rescale([P[k] * float(f2v[mo[e] + k]) for k in range(n)])
+        z = np.float64(_bp_sum(P))
+        beliefs[off[v]:off[v + 1]] = [np.float64(p) / z for p in P]
+        S = [1.0] * n
+        for e in reversed(edges):
+            T = rescale([float(v2f[mo[e] + k]) * S[k] for k in range(n)])
+            zt = np.float64(_bp_sum(T))
+            v2f[mo[e]:mo[e + 1]] = [np.float64(x) / zt for x in T]
+            S = rescale([S[k] * float(f2v[mo[e] + k]) for k in range(n)])
+
+
+def _bp_start(layout, messages):
+    """the messages (``1 / card`` without ``messages``) and the beliefs no iteration writes: a clamped variable's
+    indicator, a free variable's uniform law"""
+    mo, card, off = layout["msg_off"], layout["card"], layout["offsets"]
+    if messages is None:
+        f2v, v2f = np.zeros(int(mo[-1])), np.zeros(int(mo[-1]))
+        for e in range(len(mo) - 1):
+            f2v[mo[e]:mo[e + 1]] = v2f[mo[e]:mo[e + 1]] = 1.0 / float(mo[e + 1] - mo[e])
+    else:
+        f2v, v2f = (np.array(m, np.float64) for m in messages)
+    beliefs = np.zeros(int(off[-1]))
+    for v in range(len(card)):
+        if layout["clamped"][v]:
+            if 0 <= layout["values"][v] < card[v]:
+                beliefs[off[v] + layout["values"][v]] = 1.0
+        else:
+            beliefs[off[v]:off[v + 1]] = 1.0 / float(card[v])
+    return f2v, v2f, beliefs
+
+
 def bp_iterate(layout, theta, iters, damping=0.0, tol=0.0, exp=np.exp, messages=None):
     """Sum-product belief propagation as nsk_bp_run performs it, in plain loops, operation by operation (the header
     states the rule): up to ``iters`` iterations of the factor phase -- per edge (f, j) the sums over the table
@@ -1023,22 +1090,9 @@ def bp_iterate(layout, theta, iters, damping=0.0, tol=0.0, exp=np.exp, messages=
     stop), ``iters`` (the iterations run up to and including the first with residual <= tol; ``-iters`` without one),
     ``psi`` and ``rescaled`` (how often the rescale rule fired)."""
     to, eo, mo = layout["table_off"], layout["edge_off"], layout["msg_off"]
-    card, off = layout["card"], layout["offsets"]
+    card = layout["card"]
     psi = bp_psi(layout, theta, exp)
-    nmsg = int(mo[-1])
-    if messages is None:
-        f2v, v2f = np.zeros(nmsg), np.zeros(nmsg)
-        for e in range(len(mo) - 1):
-            f2v[mo[e]:mo[e + 1]] = v2f[mo[e]:mo[e + 1]] = 1.0 / float(mo[e + 1] - mo[e])
-    else:
-        f2v, v2f = (np.array(m, np.float64) for m in messages)
-    beliefs = np.zeros(int(off[-1]))
-    for v in range(len(card)):
-        if layout["clamped"][v]:
-            if 0 <= layout["values"][v] < card[v]:
-                beliefs[off[v] + layout["values"][v]] = 1.0
-        else:
-            beliefs[off[v]:off[v + 1]] = 1.0 / float(card[v])
+    f2v, v2f, beliefs = _bp_start(layout, messages)
     lam, oml = float(damping), 1.0 - float(damping)
     residual = np.zeros(iters)
     ran, fired = -iters, 0
@@ -1056,51 +1110,90 @@ def bp_iterate(layout, theta, iters, damping=0.0, tol=0.0, exp=np.exp, messages=
         res = 0.0
         new = f2v.copy()
         for f in range(len(to) - 1):
-            shape = layout["shapes"][f]
             e0 = int(eo[f])
-            for j in range(len(shape)):
-                m = [0.0] * shape[j]
-                for a in range(int(to[f + 1] - to[f])):
-                    d = _bp_digits(a, shape)
-                    x = float(psi[to[f] + a])
-                    for i in range(len(shape)):
-                        if i != j:
-                            x = x * float(v2f[mo[e0 + i] + d[i]])
-                    m[d[j]] = m[d[j]] + x
-                z = _bp_sum(m)
-                with np.errstate(all="ignore"):
-                    for k in range(shape[j]):
-                        nw = float(np.float64(m[k]) / np.float64(z))
-                        old = float(f2v[mo[e0 + j] + k])
-                        if lam > 0.0:
-                            nw = oml * nw + lam * old
-                        new[mo[e0 + j] + k] = nw
-                        dd = abs(nw - old)
-                        res = max(res, dd if dd == dd else np.inf)
+            for j in range(len(layout["shapes"][f])):
+                for k, c in enumerate(_bp_candidate(layout, psi, v2f, f, j)):
+                    old = float(f2v[mo[e0 + j] + k])
+                    nw = _bp_damp(c, old, lam, oml)
+                    new[mo[e0 + j] + k] = nw
+                    res = max(res, _bp_change(nw, old))
         f2v = new
         residual[t] = res
-        with np.errstate(all="ignore"):
-            for v in range(len(card)):
-                edges = layout["var_edges"][v]
-                if layout["clamped"][v] or not edges:
-                    continue
-                n = int(card[v])
-                P = [1.0] * n
-                for e in edges:
-                    v2f[mo[e]:mo[e + 1]] = P
-                    P = rescale([P[k] * float(f2v[mo[e] + k]) for k in range(n)])
-                z = np.float64(_bp_sum(P))
-                beliefs[off[v]:off[v + 1]] = [np.float64(p) / z for p in P]
-                S = [1.0] * n
-                for e in reversed(edges):
-                    T = rescale([float(v2f[mo[e] + k]) * S[k] for k in range(n)])
-                    zt = np.float64(_bp_sum(T))
-                    v2f[mo[e]:mo[e + 1]] = [np.float64(x) / zt for x in T]
-                    S = rescale([S[k] * float(f2v[mo[e] + k]) for k in range(n)])
+        for v in range(len(card)):
+            if not layout["clamped"][v] and layout["var_edges"][v]:
+                _bp_var_phase(layout, f2v, v2f, beliefs, v, rescale)
         if ran < 0 and res <= tol:
             ran = t + 1
     fired = count[0]
     return {"f2v": f2v, "v2f": v2f, "beliefs": beliefs, "residual": residual, "iters": ran, "psi": psi, "rescaled": fired}
+
+
+def rbp_iterate(layout, theta, rounds, frac=0.5, damping=0.0, tol=0.0, exp=np.exp, messages=None):
+    """Sum-product belief propagation under the residual schedule as nsk_bp_residual_run performs it (the header states
+    the rule), from ``bp_iterate``'s pieces.  Round t: the candidates ``cand[e]`` of the dirty edges (all edges in round
+    0) and ``r[e]``, the largest entry of the change a commit of e would make, ``|damp(cand, f2v) - f2v|``;
+    ``residual[t]`` the largest ``r`` over all edges; the edges with ``r > 0`` and ``r >= frac * residual[t]`` (``+0.0``
+    with ``frac == 0``) store their damped candidate, take the ``r`` of the next commit and touch their variable; the
+    touched variables -- in round 0 of a cold start every free variable with an edge -- run ``bp_iterate``'s variable
+    phase, and where a ``v2f`` vector changed in any bit the factor's other edges are dirty in the next round.  The
+    rounds stop behind the first whose residual is ``<= tol``.  ``messages=(f2v, v2f)`` is a warm start from those: the
+    beliefs are what the variable phase last left for them.  Returns a dict: ``f2v``, ``v2f``, ``beliefs``, ``psi`` as
+    ``bp_iterate``; ``residual``, ``updates`` (edges committed), ``recomputed`` (candidates formed) -- ``rounds``
+    entries each, 0 behind the stop --, ``rounds`` (as ``iters`` of ``bp_iterate``), ``cand`` and ``r``."""
+    eo, mo, off, card = layout["edge_off"], layout["msg_off"], layout["offsets"], layout["card"]
+    psi = bp_psi(layout, theta, exp)
+    f2v, v2f, beliefs = _bp_start(layout, messages)
+    walked = [v for v in range(len(card)) if not layout["clamped"][v] and layout["var_edges"][v]]
+    if messages is not None:
+        with np.errstate(all="ignore"):
+            for v in walked:
+                P = [1.0] * int(card[v])
+                for e in layout["var_edges"][v]:
+                    P = _bp_rescale([P[k] * float(f2v[mo[e] + k]) for k in range(len(P))])
+                z = np.float64(_bp_sum(P))
+                beliefs[off[v]:off[v + 1]] = [np.float64(p) / z for p in P]
+    nedge = len(mo) - 1
+    edge_fac = [f for f in range(len(eo) - 1) for _ in range(int(eo[f]), int(eo[f + 1]))]
+    lam, oml = float(damping), 1.0 - float(damping)
+    cand, r = np.zeros(int(mo[-1])), np.zeros(nedge)
+    residual, updates, recomputed = np.zeros(rounds), np.zeros(rounds, np.int64), np.zeros(rounds, np.int64)
+    ran, dirty = -rounds, list(range(nedge))
+
+    def pending(e):
+        return max([0.0] + [_bp_change(_bp_damp(float(cand[k]), float(f2v[k]), lam, oml), float(f2v[k])) for k in range(mo[e], mo[e + 1])])
+
+    for t in range(rounds):
+        if t > 0 and residual[t - 1] <= tol:
+            break
+        for e in dirty:
+            f = edge_fac[e]
+            cand[mo[e]:mo[e + 1]] = _bp_candidate(layout, psi, v2f, f, e - int(eo[f]))
+            r[e] = pending(e)
+        recomputed[t] = len(dirty)
+        res = float(r.max()) if nedge else 0.0
+        residual[t] = res
+        tau = float(frac) * res if frac > 0.0 else 0.0
+        touched = set()
+        for e in range(nedge):
+            if r[e] > 0.0 and r[e] >= tau:
+                for k in range(mo[e], mo[e + 1]):
+                    f2v[k] = _bp_damp(float(cand[k]), float(f2v[k]), lam, oml)
+                r[e] = pending(e)
+                touched.add(int(layout["edge_var"][e]))
+                updates[t] += 1
+        nxt = set()
+        for v in (walked if t == 0 and messages is None else sorted(touched)):
+            edges = layout["var_edges"][v]
+            before = [v2f[mo[e]:mo[e + 1]].copy().view(np.int64) for e in edges]
+            _bp_var_phase(layout, f2v, v2f, beliefs, v, _bp_rescale)
+            for e, old in zip(edges, before):
+                if not np.array_equal(old, v2f[mo[e]:mo[e + 1]].view(np.int64)):
+                    nxt.update(x for x in range(int(eo[edge_fac[e]]), int(eo[edge_fac[e] + 1])) if x != e)
+        dirty = sorted(nxt)
+        if ran < 0 and res <= tol:
+            ran = t + 1
+    return {"f2v": f2v, "v2f": v2f, "beliefs": beliefs, "residual": residual, "updates": updates, "recomputed": recomputed,
+            "rounds": ran, "psi": psi, "cand": cand, "r": r}
 
 
 def bp_factor_beliefs(layout, psi, v2f):

@@ -1413,8 +1413,23 @@ class FactorGraph(object):
         return out
 
     # ------------------------------------------------------------------ belief propagation
+    @staticmethod
+    def _bp_iterations(L, h, who, schedule, frac, max_iters, damping, tol):
+        """The iterations of ``belief_propagation`` on the resident set-up under either schedule: ``(iters, residual,
+        extra)``, ``extra`` the residual schedule's ``updates`` and ``recomputed``."""
+        if schedule not in ("flooding", "residual"):
+            raise ValueError('%s: schedule must be "flooding" or "residual"' % who)
+        iters, residual = C.c_int64(0), np.zeros(max_iters, np.float64)
+        if schedule == "flooding":
+            _lib.check(L.nsk_bp_run(h, max_iters, float(damping), float(tol), C.byref(iters), _lib.ptr(residual)))
+            return iters.value, residual, {}
+        updates, recomputed = np.zeros(max_iters, np.int64), np.zeros(max_iters, np.int64)
+        _lib.check(L.nsk_bp_residual_run(h, max_iters, float(frac), float(damping), float(tol), 0, C.byref(iters), _lib.ptr(residual),
+                                         _lib.ptr(updates), _lib.ptr(recomputed)))
+        return iters.value, residual, {"updates": updates, "recomputed": recomputed}
+
     def belief_propagation(self, max_iters=100, damping=0.0, tol=1e-9, var_copy=0, weight_copy=0, evidence_chain=False,
-                           sample_evidence=False, factor_beliefs=False):
+                           sample_evidence=False, factor_beliefs=False, schedule="flooding", frac=0.5):
         """Loopy belief propagation on the device (nsk_bp_setup / nsk_bp_run): sum-product message passing, every factor
         and every variable updated once per iteration -- deterministic inference beside the sampler.  The variables with
         ``isEvidence != 0`` are clamped at their values in ``var_value[var_copy]`` (``var_value_evid[var_copy]`` with
@@ -1426,6 +1441,12 @@ class FactorGraph(object):
         at most 16 distinct members and 4096 table entries over its free members; UFO and, without ``head_by_vid``, the
         IMPLY_MLN-type factors are refused (ValueError naming the factor).  Two hard constraints that contradict each
         other give NaN, as in ``conditionals``.  ``diagnostics.bp_iterate`` is the rule in numpy.
+        ``schedule="residual"`` (nsk_bp_residual_run; ``diagnostics.rbp_iterate``) replaces the iterations by ROUNDS that
+        recompute only the messages whose inputs moved and commit those whose pending change is at least ``frac`` (in
+        [0, 1]) of the largest pending one: the same fixed points, often with far fewer message updates and on some
+        graphs where flooding does not converge; ``frac=0`` is flooding bit for bit.  ``max_iters`` counts rounds then (a
+        round moves less than an iteration: allow more), and the result gains ``updates`` and ``recomputed``, int64
+        ``(max_iters,)``: the messages committed and the candidates formed per round.
         Returns a dict: ``offsets``, ``beliefs`` -- the layout of ``conditionals`` over all variables
         (``diagnostics.tally_layout`` converts to that of ``count``); ``iters``, ``converged``, ``residual`` (float64
         ``(max_iters,)``, 0 behind the stop); ``log_z``; with ``factor_beliefs=True`` also ``table_offsets``
@@ -1442,8 +1463,7 @@ class FactorGraph(object):
         _lib.check(L.nsk_bp_setup(h, _lib.BUF_VALUE_EVID if evidence_chain else _lib.BUF_VALUE, 0, int(bool(sample_evidence)),
                                   C.byref(info)))
         try:
-            iters, residual = C.c_int64(0), np.zeros(max_iters, np.float64)
-            _lib.check(L.nsk_bp_run(h, max_iters, float(damping), float(tol), C.byref(iters), _lib.ptr(residual)))
+            iters, residual, extra = self._bp_iterations(L, h, "belief_propagation", schedule, frac, max_iters, damping, tol)
             _, offsets = self._cond_selection(None, None, "belief_propagation")
             beliefs = np.zeros(int(offsets[-1]), np.float64)
             _lib.check(L.nsk_bp_beliefs(h, None, 0, _lib.ptr(beliefs)))
@@ -1457,8 +1477,9 @@ class FactorGraph(object):
         ev = self.variable["isEvidence"]
         layout = {"card": self.variable["cardinality"].astype(np.int64), "edge_var": edge_var,
                   "clamped": (ev == 4) | ((ev != 0) & (not sample_evidence))}
-        out = {"offsets": offsets, "beliefs": beliefs, "iters": abs(int(iters.value)), "converged": bool(iters.value > 0),
+        out = {"offsets": offsets, "beliefs": beliefs, "iters": abs(int(iters)), "converged": bool(iters > 0),
                "residual": residual, "log_z": bethe_log_z(layout, theta, fb, beliefs)}
+        out.update(extra)
         if factor_beliefs:
             out.update(table_offsets=table_off, theta=theta, factor_beliefs=fb)
         return out
@@ -1511,12 +1532,13 @@ class FactorGraph(object):
         return out
 
     def bp_weight_moments(self, max_iters=100, damping=0.0, tol=1e-9, var_copy=0, weight_copy=0, evidence_chain=False,
-                          sample_evidence=False, counts=False):
+                          sample_evidence=False, counts=False, schedule="flooding", frac=0.5):
         """The expected per-weight statistics ``E[S_w]`` under belief propagation (nsk_bp_setup / nsk_bp_run /
         nsk_bp_moments): the sum over every factor of a weight and every entry of its table of factor belief x factor
         value, reduced on the device in the int64 fixed point of ``weight_moments`` -- exact to within ``2**-33`` per table
         entry wherever BP is exact (the free variables form a forest), the Bethe approximation on a graph with cycles.
-        State, weights, clamping and the iteration's arguments are those of ``belief_propagation``.  A factor whose
+        State, weights, clamping and the iteration's arguments (``schedule`` and ``frac`` among them) are those of
+        ``belief_propagation``.  A factor whose
         beliefs are NaN (two contradicting hard constraints) is left out and counted.  ``diagnostics.bp_moment_counts`` is
         the rule in numpy.  Returns a dict: ``moments`` -- float64 ``(nweight,)``, the sums ``* 2.0**-32``, or the int64
         sums with ``counts=True``; ``iters``, ``converged`` as ``belief_propagation`` returns them; ``skipped``.  On a state
@@ -1530,14 +1552,14 @@ class FactorGraph(object):
         self._push(var_copy, weight_copy)
         _lib.check(L.nsk_bp_setup(h, _lib.BUF_VALUE_EVID if evidence_chain else _lib.BUF_VALUE, 0, int(bool(sample_evidence)), None))
         try:
-            iters, skipped = C.c_int64(0), C.c_int64(0)
-            _lib.check(L.nsk_bp_run(h, max_iters, float(damping), float(tol), C.byref(iters), None))
+            skipped = C.c_int64(0)
+            iters, _, _ = self._bp_iterations(L, h, "bp_weight_moments", schedule, frac, max_iters, damping, tol)
             m = np.zeros(self.weight.shape[0], np.int64)
             _lib.check(L.nsk_bp_moments(h, _lib.ptr(m), C.byref(skipped)))
         finally:
             L.nsk_bp_clear(h)
-        return {"moments": m if counts else m.astype(np.float64) * 2.0 ** -32, "iters": abs(int(iters.value)),
-                "converged": bool(iters.value > 0), "skipped": int(skipped.value)}
+        return {"moments": m if counts else m.astype(np.float64) * 2.0 ** -32, "iters": abs(int(iters)),
+                "converged": bool(iters > 0), "skipped": int(skipped.value)}
 
     def learn_bp(self, epochs, stepsize, decay=1.0, reg_param=0.0, iters=20, damping=0.0, tol=1e-9, warm=True,
                  sample_evidence=True, target=None, normalize=True, var_copy=0, weight_copy=0, moments=False, latent=False):
