@@ -445,6 +445,86 @@ int nsk_bp_residual_run(nsk_graph *g, int64_t max_rounds, double frac, double da
                         double *residual /* max_rounds, may be NULL */, int64_t *updates /* max_rounds, may be NULL */,
                         int64_t *recomputed /* max_rounds, may be NULL */);
 
+/* Swendsen-Wang cluster updates (FactorGraph.swendsen_wang): a sampler that moves whole clusters of a pairwise binary
+ * model at once, for every chain of the handle in the same launches -- the cure for the slow large-scale fluctuations of
+ * single-site Gibbs near a critical coupling.  numbskull_amd.diagnostics.sw_tables / sw_step are the rule in numpy, bit
+ * for bit and integer for integer.
+ * Model class.  nsk_sw_setup classifies the variables as CLAMPED or FREE exactly as nsk_bp_setup does (`which`, `chain`,
+ * `sample_evidence`, the distinct members and the table axes are those written above it; the clamped values are read
+ * from that one chain).  It is accepted only if every free variable that has a factor is binary and every factor has at
+ * most two distinct free members; otherwise NSK_E_INVALID names the lowest offending factor and nothing is allocated.
+ * A factor nsk_bp_setup refuses (UFO, the literal head lookup, an index outside the arrays, ..) is refused in its words.
+ * A factor with two free members is a BOND, bond ordinal b counting them in ascending factor id; one with a single free
+ * member is a FIELD; one without is ignored.  Any factor function qualifies, with clamped members of any cardinality.
+ * Tables (at set-up, and by nsk_sw_refresh after the weights changed).  theta_f is nsk_bp_setup's, bit for bit.  For a
+ * bond with axes (u, v) and entries t00, t01, t10, t11 in C order:
+ *   J_f = ((t00 + t11) - (t01 + t10)) * 0.25      g_u = ((t10 + t11) - (t00 + t01)) * 0.5
+ *   q_f = exp(-2.0 * |J_f|)                       g_v = ((t01 + t11) - (t00 + t10)) * 0.5
+ * for a field g_u = t1 - t0.  h_v = the sum of the variable's g entries in ascending factor id, from 0.0, plain float64
+ * additions; H_v = h_v * 2^32 rounded to int64, nearest even (as nsk_pl_gradient rounds).  NSK_E_RANGE, the handle as it
+ * was: some J_f or h_v is not finite, or the sum over v of ceil(|h_v|) reaches 2^31 (below it no subset sum of H wraps).
+ * Order.  The free variables that have a factor are numbered by SW ORDINAL, in tiles of at most 1024: a tile grows
+ * breadth-first over the bonds from the lowest caller id not yet placed, neighbours visited in ascending bond ordinal,
+ * and closes at 1024 variables or when its frontier is empty; the next starts at the lowest id not yet placed.  (A
+ * variable with fields only has an ordinal too.)  The order decides which bonds a tile unites in LDS and which counters
+ * the generator reads; nsk_sw_layout hands it out.
+ * One update, sweep index s, chain r keyed seed ^ (r << 32) as everywhere; a uniform from counter (c, stream, s low,
+ * s high ^ tag) is ((x >> 5) << 26 | y >> 6) * 2^-53 from words x and y of the Philox block (streams 4 and 5 are this
+ * sampler's; 0 .. 3 stay with the sweep kernels):
+ *   1. bond b is ACTIVE iff J_f != 0, its ends agree -- x_u == x_v for J_f > 0, x_u != x_v for J_f < 0 -- and
+ *      u(b, 4) >= q_f;
+ *   2. a CLUSTER is a connected component of the ordinals under the active bonds; its label is its smallest ordinal;
+ *   3. Delta_C = the sum over its members of (x_v == 0 ? +H_v : -H_v), exact in int64; |C| likewise;
+ *   4. for the label o: D = (double)Delta_C * 2^-32, e = exp(-D); the cluster flips iff u(o, 5) * (1.0 + e) < 1.0
+ *      (heat bath, probability sigma(D); a NaN does not flip);
+ *   5. every member of a flipping cluster writes 1 - x_v into the chain's values (value_bytes 1 and 4).
+ * Tallies, traces and weights are not touched; a tally kept in the value bytes is first brought back to its array, as in
+ * nsk_icm.  The update consumes ONE sweep index of its own and advances nothing else.
+ *   nsk_sw_plan      no device and no handle: the structure nsk_sw_setup would build for the graph's initial state, with
+ *                    tiles of `tile` ordinals (32 .. 1024).  info, order, bond_factor, bond_ends as below, bond_tile
+ *                    [nbonds] the tile that unites the bond or -1 (the cross list); any may be NULL.
+ *   nsk_sw_setup     *info (may be NULL) = the counts.  The set-up is resident, counted in nsk_graph_info.device_bytes
+ *                    (24 bytes a table entry as nsk_bp_setup's, 16 + 8 a bond or 16 + 16 across tiles, 8 a directed edge,
+ *                    28 a variable with a factor, the structure of the tables) and replaced by a later set-up.  The
+ *                    first nsk_sw_sweeps, and one behind nsk_set_chains, adds parents, accumulators and decisions: 21
+ *                    bytes a variable with a factor and chain.
+ *   nsk_sw_layout    order[nvars] the caller's id of every ordinal, bond_factor[nbonds], bond_ends[nbonds x 2] the
+ *                    ordinals of axes u and v; each may be NULL.
+ *   nsk_sw_download  what = NSK_SW_J, NSK_SW_Q (float64 by bond ordinal), NSK_SW_H (by SW ordinal: the INT64 H_v, stored
+ *                    in the 8-byte slots of out).
+ *   nsk_sw_labels    out[nvars] the labels chain `chain` was given by the last update; NSK_E_INVALID before the first.
+ *   nsk_sw_refresh   the tables from the device weights as they stand; NSK_E_RANGE as above.
+ *   nsk_sw_clear     frees the set-up (NSK_OK without one).
+ *   nsk_sw_sweeps    nsteps steps, each ONE cluster update of every chain followed by gibbs_per_step >= 0 ordinary sweeps,
+ *                    launched, tallied and counted exactly as nsk_gibbs_sweeps(g, gibbs_per_step, the set-up's
+ *                    sample_evidence, burnin) would.  clusters, largest (the size of the largest cluster) and flipped
+ *                    (variables) are nsteps x chains and may be NULL.  Everything is enqueued on the handle's stream
+ *                    without a host wait between steps, one synchronisation at the end.  NSK_E_INVALID before anything
+ *                    is enqueued: no set-up, nsteps outside [1, 65536], gibbs_per_step < 0, nsteps x (1 +
+ *                    gibbs_per_step) above 2^31 - 1, what nsk_tempered_sweeps refuses (the sequential scan, own_range /
+ *                    NSK_FLAG_PARTITION, a boundary exchange), and burnin == 0 with gibbs_per_step > 0 on a handle that
+ *                    records a sample trace.
+ * Nothing here waits on the device for anything: no block waits for another block, every loop of the union-find ends by
+ * parent[x] <= x.  (Diagnostic, NSK_DIAG=1: NSK_SW_TILE=n, 32 .. 1024, read at each set-up, shrinks the
+ * tiles; NSK_SW_GRID_CAP=blocks, read at each nsk_sw_sweeps, caps every grid.) */
+#define NSK_SW_J 0
+#define NSK_SW_Q 1
+#define NSK_SW_H 2
+typedef struct {
+    int64_t nvars, nbonds, ncross;              /* free variables with a factor; bonds; those of them across tiles */
+    int64_t ntiles, nfields, device_bytes;      /* tiles; field factors; bytes the set-up holds */
+} nsk_sw_info;
+int nsk_sw_plan(const nsk_graph_desc *desc, int sample_evidence, int tile, nsk_sw_info *info, int64_t *order, int64_t *bond_factor,
+                int64_t *bond_ends, int64_t *bond_tile);
+int nsk_sw_setup(nsk_graph *g, int which, int64_t chain, int sample_evidence, nsk_sw_info *info);
+int nsk_sw_layout(nsk_graph *g, int64_t *order /* nvars */, int64_t *bond_factor /* nbonds */, int64_t *bond_ends /* nbonds x 2 */);
+int nsk_sw_download(nsk_graph *g, int what, double *out);
+int nsk_sw_labels(nsk_graph *g, int64_t chain, int32_t *out /* nvars */);
+int nsk_sw_refresh(nsk_graph *g);
+int nsk_sw_clear(nsk_graph *g);
+int nsk_sw_sweeps(nsk_graph *g, int64_t nsteps, int64_t gibbs_per_step, int burnin, int64_t *clusters /* nsteps x chains */,
+                  int64_t *largest, int64_t *flipped);
+
 /* Learning by belief propagation (FactorGraph.bp_weight_moments / learn_bp): maximum-likelihood learning whose model
  * expectations come from the factor beliefs of the resident set-up above instead of from chains -- exact wherever BP is
  * exact (the free variables form a forest), the Bethe approximation on graphs with cycles, without sampling noise.

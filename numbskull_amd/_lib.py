@@ -38,6 +38,7 @@ SYMBOLS = (
     "nsk_bp_refresh", "nsk_bp_moments", "nsk_bp_learn_steps", "nsk_bp_select", "nsk_bp_selected", "nsk_bp_latent_steps",
     "nsk_bp_map_run", "nsk_bp_map_marginals", "nsk_bp_map_download", "nsk_bp_map_decode", "nsk_bp_map_routes",
     "nsk_bp_residual_run",
+    "nsk_sw_plan", "nsk_sw_setup", "nsk_sw_layout", "nsk_sw_download", "nsk_sw_labels", "nsk_sw_refresh", "nsk_sw_clear", "nsk_sw_sweeps",
     "nsk_trace_ess", "nsk_trace_autocov_counts", "nsk_trace_pair_counts",
     "nsk_trace_value_autocov_counts", "nsk_trace_value_ess", "nsk_trace_value_pair_counts",
     "nsk_selftest_exp", "nsk_selftest_philox", "nsk_selftest_stream", "nsk_device_count", "nsk_last_error", "nsk_version",
@@ -75,6 +76,13 @@ class BpInfo(C.Structure):
     _fields_ = [(k, C.c_int64) for k in ("nfactor", "nedges", "ntable", "nmsg", "nfree", "nisolated", "nclamped",
                                          "nbelief", "max_table", "device_bytes")]
 
+
+class SwInfo(C.Structure):
+    _fields_ = [(k, C.c_int64) for k in ("nvars", "nbonds", "ncross", "ntiles", "nfields", "device_bytes")]
+
+
+SW_J, SW_Q, SW_H = range(3)         # what nsk_sw_download hands out (SW_H: int64 in the 8-byte slots)
+SW_TILE = 1024                      # ordinals of a Swendsen-Wang tile at most (csrc/nsk_sw_plan.h)
 
 # belief propagation (include/numbskull_amd.h): the caps of a factor, what nsk_bp_download hands out, and the grids of its
 # launches (csrc/nsk_bp.hip bp_blocks): one item a lane, blocks of BP_BLOCK lanes (BP_VAR_BLOCK in the variable phase),
@@ -232,6 +240,14 @@ def lib():
         L.nsk_bp_map_routes.argtypes = [C.c_void_p, C.c_void_p]
         L.nsk_bp_residual_run.argtypes = [C.c_void_p, C.c_int64, C.c_double, C.c_double, C.c_double, C.c_int, C.POINTER(C.c_int64),
                                           C.c_void_p, C.c_void_p, C.c_void_p]
+        L.nsk_sw_plan.argtypes = [C.POINTER(GraphDesc), C.c_int, C.c_int, C.POINTER(SwInfo)] + [C.c_void_p] * 4
+        L.nsk_sw_setup.argtypes = [C.c_void_p, C.c_int, C.c_int64, C.c_int, C.POINTER(SwInfo)]
+        L.nsk_sw_layout.argtypes = [C.c_void_p] * 4
+        L.nsk_sw_download.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
+        L.nsk_sw_labels.argtypes = [C.c_void_p, C.c_int64, C.c_void_p]
+        L.nsk_sw_refresh.argtypes = [C.c_void_p]
+        L.nsk_sw_clear.argtypes = [C.c_void_p]
+        L.nsk_sw_sweeps.argtypes = [C.c_void_p, C.c_int64, C.c_int64, C.c_int] + [C.c_void_p] * 3
         L.nsk_pl_gradient.argtypes = [C.c_void_p, C.c_int, C.c_int64, C.c_int64, C.c_void_p, C.c_int64] + [C.c_void_p] * 3
         L.nsk_mple_steps.argtypes = [C.c_void_p, C.c_int, C.c_int64, C.c_int64, C.c_void_p, C.c_int64, C.c_int64,
                                      C.c_double, C.c_double, C.c_double, C.c_void_p, C.c_void_p]

@@ -5,7 +5,7 @@
 // nsk_smc.hip: population annealing on top of them; nsk_pt.hip: parallel tempering; nsk_plgrad.hip: the pseudo-likelihood
 // gradient and MPLE learning; nsk_pcd.hip: the chain-summed moments and persistent contrastive divergence, fully observed
 // and with latent variables; nsk_bp.hip: loopy belief propagation;
-// nsk_bp_map.hip: max-product on the same set-up).
+// nsk_bp_map.hip: max-product on the same set-up; nsk_sw.hip: Swendsen-Wang cluster updates).
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -149,6 +149,34 @@ struct NskBp {
     int32_t *rs_dq = nullptr, *rs_vq = nullptr, *rs_vpos = nullptr;
 };
 
+// Swendsen-Wang cluster updates (nsk_sw_setup .. nsk_sw_clear; nsk_sw.hip, nsk_kernels_sw.h): the structure of
+// nsk_sw_plan.h, what k_bp_tables reads of bp's, the tables by bond and by ordinal, resident from set-up to clear.  Every
+// device array is on the ledger and listed in `owned`.  The first nsk_sw_sweeps adds the per-chain state of the updates.
+struct NskSw {
+    bool ready = false;
+    nsk_sw_info info = {};
+    int sample_evidence = 0;
+    std::vector<void *> owned;
+    std::vector<int32_t> ord_id, bond_fac, bond_ends;      // host copies for nsk_sw_layout (internal ids, factors, ordinals)
+    // what k_bp_tables / k_bp_refresh read
+    long long *pm_off = nullptr, *tab_off = nullptr;
+    int32_t *slot_off = nullptr, *mrec = nullptr, *slot_rec = nullptr, *edge_off = nullptr;
+    double *theta = nullptr, *feat = nullptr;
+    int64_t ntable = 0, nedge = 0;
+    // the tables
+    int32_t *f_bond = nullptr, *ve_off = nullptr, *ve_edge = nullptr;
+    double *gfield = nullptr, *J = nullptr, *qs = nullptr, *h = nullptr;
+    long long *H = nullptr;
+    // the structure of an update
+    int32_t *d_ord_id = nullptr, *tile_off = nullptr, *tb_off = nullptr, *tb_rec = nullptr, *cross = nullptr;
+    // per chain (sw_state_ensure): parents / labels, the accumulators, the decisions
+    int state_chains = 0;
+    bool have_labels = false;
+    int32_t *parent = nullptr;
+    long long *acc = nullptr;
+    uint8_t *flip = nullptr;
+};
+
 // Boundary exchange, the collective path (nsk_exchange.hip: nsk_exchange_setup, nsk_comm_init, nsk_*_sweeps_exchange):
 // every rank packs the values its peers read into `send`, an all-gather -- the caller's, or RCCL's through `comm` --
 // fills `recv` with every rank's slot, and the unpack scatters them to the ghost ids.  The handle owns the seven
@@ -227,6 +255,7 @@ struct nsk_graph {
     NskBp bp;                          // the SELECTED set-up: every nsk_bp_* call acts on it (nsk_bp_select)
     NskBp bp_other;                    // ... and the one that is not: nsk_bp_select swaps the two
     int bp_slot = 0;                   // which of the two slots `bp` is (nsk_bp_latent_steps: 0 clamped, 1 free)
+    NskSw sw;                          // the Swendsen-Wang set-up (nsk_sw_setup)
     // The segment launches (nsk_seg_plan.h), kept across calls (the N-rank loops sweep one epoch per call) together with
     // the options they were planned for; a call whose options differ plans again.  Learning: per Compiled::learn_seg entry.
     std::vector<nsk::LearnSegPlan> learn_seg_plans;

@@ -1392,3 +1392,72 @@ def ms_decode(layout, max_marginals, values):
             mine = b[off[v]:off[v + 1]]
             ties += int(np.sum(mine == mine[x[v]]) > 1)
     return x, ties
+
+
+# ------------------------------------------------------------------------------------------------- Swendsen-Wang
+def sw_tables(theta, layout, exp=np.exp):
+    """The tables of ``FactorGraph.swendsen_wang`` (nsk_sw_setup) from the theta tables of ``bp_layout``'s structure,
+    bit for bit.  A factor with two free members is a bond, numbered in ascending factor id: with the entries t00, t01,
+    t10, t11 of its table in C order, ``J = ((t00 + t11) - (t01 + t10)) * 0.25``, ``q = exp(-2.0 * |J|)`` and the shares
+    ``((t10 + t11) - (t00 + t01)) * 0.5`` and ``((t01 + t11) - (t00 + t10)) * 0.5`` of its two ends' fields; a factor
+    with one free member gives it ``t1 - t0``.  ``h[v]`` sums a variable's shares in ascending factor id from 0.0 and
+    ``H[v] = rint(h[v] * 2^32)`` as int64 -- both by the CALLER's variable id, 0 for a variable without a factor.
+    Returns a dict: ``J``, ``q``, ``bond_factor``, ``bond_vars`` (nbonds x 2 variable ids, axes u and v), ``h``, ``H``.
+    ValueError for a free member that is not binary or a factor with more than two."""
+    theta = np.asarray(theta, np.float64)
+    J, q, bf, bv = [], [], [], []
+    h = np.zeros(len(layout["card"]), np.float64)
+    for f, ax in enumerate(layout["axes"]):
+        if any(int(layout["card"][v]) != 2 for v in ax) or len(ax) > 2:
+            raise ValueError("sw_tables: factor %d has a free member that is not binary, or more than two" % f)
+        t = theta[int(layout["table_off"][f]):int(layout["table_off"][f + 1])]
+        if len(ax) == 1:
+            h[ax[0]] = h[ax[0]] + (t[1] - t[0])
+        if len(ax) != 2:
+            continue
+        Jf = ((t[0] + t[3]) - (t[1] + t[2])) * 0.25
+        J.append(Jf)
+        q.append(float(np.ravel(exp(np.float64(-2.0 * abs(Jf))))[0]))
+        bf.append(f)
+        bv.append(ax)
+        h[ax[0]] = h[ax[0]] + ((t[2] + t[3]) - (t[0] + t[1])) * 0.5
+        h[ax[1]] = h[ax[1]] + ((t[1] + t[3]) - (t[0] + t[2])) * 0.5
+    return {"J": np.asarray(J, np.float64), "q": np.asarray(q, np.float64), "bond_factor": np.asarray(bf, np.int64),
+            "bond_vars": np.asarray(bv, np.int64).reshape(-1, 2), "h": h, "H": np.rint(h * 4294967296.0).astype(np.int64)}
+
+
+def sw_step(values, order, bond_ends, J, q, H, u_bond, u_cluster, exp=np.exp):
+    """One Swendsen-Wang cluster update (nsk_sw_sweeps), integer for integer.  ``order[o]`` is the variable of SW ordinal
+    o, ``bond_ends`` (nbonds x 2) the ordinals of every bond's ends, ``J``, ``q`` by bond, ``H`` int64 by ORDINAL,
+    ``u_bond[b]`` and ``u_cluster[o]`` the uniforms of streams 4 and 5.  Bond b is active iff ``J[b] != 0``, its ends
+    agree (equal values for J > 0, unequal for J < 0) and ``u_bond[b] >= q[b]``; the clusters are the components under
+    the active bonds, labelled by their smallest ordinal; ``Delta`` sums ``+H`` over a cluster's members at 0 and ``-H``
+    over those at 1; the cluster of label o flips iff ``u_cluster[o] * (1.0 + exp(-(Delta * 2^-32))) < 1.0``.
+    Returns (new values, labels by ordinal, clusters, largest, flipped)."""
+    values = np.array(values, np.int64)
+    order, n = np.asarray(order, np.int64), len(order)
+    x = values[order]
+    parent = list(range(n))
+
+    def find(a):
+        while parent[a] != a:
+            a = parent[a]
+        return a
+
+    for b, (u, v) in enumerate(np.asarray(bond_ends, np.int64).reshape(-1, 2)):
+        agree = (x[u] == x[v]) if J[b] > 0 else (x[u] != x[v])
+        if J[b] != 0 and agree and u_bond[b] >= q[b]:
+            ru, rv = find(int(u)), find(int(v))
+            parent[max(ru, rv)] = min(ru, rv)
+    labels = np.array([find(o) for o in range(n)], np.int64)
+    delta, size = [0] * n, [0] * n
+    for o in range(n):
+        delta[labels[o]] += int(H[o]) if x[o] == 0 else -int(H[o])
+        size[labels[o]] += 1
+    flip = np.zeros(n, bool)
+    for o in np.flatnonzero(labels == np.arange(n)):
+        e = float(np.ravel(exp(np.float64(-(float(delta[o]) * 2.0 ** -32))))[0])
+        flip[o] = u_cluster[o] * (1.0 + e) < 1.0
+    moved = flip[labels] if n else np.zeros(0, bool)
+    values[order[moved]] = 1 - x[moved]
+    return values, labels, int((labels == np.arange(n)).sum()), max(size, default=0), int(moved.sum())

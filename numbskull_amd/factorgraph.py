@@ -1302,6 +1302,54 @@ class FactorGraph(object):
         paths, trips = pt_paths(acc)
         return {"lp": lp, "accepted": acc, "swap_rate": rate, "paths": paths, "round_trips": trips, "uniforms": uniforms}
 
+    def plan_sw(self, sample_evidence=False, tile=_lib.SW_TILE):
+        """Host-only: the structure ``swendsen_wang`` would build (nsk_sw_plan), with tiles of ``tile`` ordinals.  A dict:
+        the counts of nsk_sw_info, ``order`` (the variable of every SW ordinal), ``bond_factor``, ``bond_ends`` (ordinals)
+        and ``bond_tile`` (the tile that unites the bond, -1: the cross list).  ValueError with the library's text for a
+        graph the cluster update does not serve."""
+        desc, keep = self._descriptor()
+        L, info = _lib.lib(), _lib.SwInfo()
+        args = (C.byref(desc), int(bool(sample_evidence)), int(tile), C.byref(info))
+        _lib.check(L.nsk_sw_plan(*(args + (None,) * 4)))
+        out = {"order": np.zeros(info.nvars, np.int64), "bond_factor": np.zeros(info.nbonds, np.int64),
+               "bond_ends": np.zeros((info.nbonds, 2), np.int64), "bond_tile": np.zeros(info.nbonds, np.int64)}
+        _lib.check(L.nsk_sw_plan(*(args + tuple(_lib.ptr(out[k]) for k in ("order", "bond_factor", "bond_ends", "bond_tile")))))
+        out.update({k: getattr(info, k) for k, _ in info._fields_})
+        return out
+
+    def swendsen_wang(self, steps, sweeps=1, burnin=False, sample_evidence=False, var_copy=0, weight_copy=0):
+        """Swendsen-Wang cluster updates on the device (nsk_sw_setup, nsk_sw_sweeps): ``steps`` steps, each one cluster
+        update followed by ``sweeps`` >= 0 ordinary Gibbs sweeps, which are tallied as ``inference`` tallies them unless
+        ``burnin``.  Served where every free variable with a factor is binary and every factor ties at most two free
+        variables -- grids, chains, pairwise DeepDive graphs; ValueError with the library's text otherwise.  State is
+        pushed and pulled as ``inference`` does; ``var_copy="all"`` updates every row of ``var_value`` as a chain of its own
+        in the same launches (the clamped values are read from row 0).  The update itself tallies nothing.  Returns a dict:
+        ``clusters``, ``largest`` (the size of the largest cluster) and ``flipped`` (variables), int64 ``(steps, chains)``,
+        and ``info``, the counts of the set-up.  ``diagnostics.sw_tables`` / ``sw_step`` restate the rule."""
+        steps, sweeps = int(steps), int(sweeps)
+        if steps < 1 or sweeps < 0:
+            raise ValueError("swendsen_wang: steps must be at least 1 and sweeps at least 0")
+        L, h = _lib.lib(), self._engine()
+        chains, tally = _all_copies(var_copy), not burnin and sweeps > 0
+        if chains:
+            nchains = self._push_chains(weight_copy, count=tally)
+            before = self.chain_count.copy()
+        else:
+            nchains = 1
+            self._push(var_copy, weight_copy)
+        info = _lib.SwInfo()
+        _lib.check(L.nsk_sw_setup(h, _lib.BUF_VALUE, 0, int(bool(sample_evidence)), C.byref(info)))
+        out = np.zeros((3, steps, nchains), np.int64)
+        _lib.check(L.nsk_sw_sweeps(h, steps, sweeps, int(bool(burnin)), _lib.ptr(out[0]), _lib.ptr(out[1]), _lib.ptr(out[2])))
+        if chains:
+            cc = self._pull_chains(count=tally)
+            if tally:
+                self.count += (cc - before).sum(axis=0)
+                self.chain_count[:] = cc
+        else:
+            self._pull(var_copy, weight_copy, weights=False, count=tally)
+        return {"clusters": out[0], "largest": out[1], "flipped": out[2], "info": {k: getattr(info, k) for k, _ in info._fields_}}
+
     def _log_z0(self, sample_evidence):
         """the log of the number of states of the variables a sweep samples"""
         sampled = self.colors() >= 0
