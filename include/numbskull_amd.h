@@ -403,6 +403,65 @@ int nsk_bp_map_download(nsk_graph *g, int what, double *out);
 int nsk_bp_map_decode(nsk_graph *g, int which, int64_t chain, int64_t *ties /* may be NULL */);
 int nsk_bp_map_routes(nsk_graph *g, int64_t *counts /* 3 */);
 
+/* Tree-reweighted belief propagation (FactorGraph.reweighted_bp, FactorGraph.log_z_bounds): fractional BP with one
+ * weight rho_f > 0 per factor on the resident set-up above -- the same message passing with every factor counted rho_f
+ * times.  For rho in the spanning-tree polytope of a PAIRWISE graph (diagnostics.edge_appearance) its free energy is
+ * convex and its fixed point an upper bound on log Z; with rho = 1 it is sum-product BP and log_z the Bethe estimate.
+ * Damped, it converges far more readily than BP at strong coupling.  numbskull_amd.diagnostics.trw_iterate / trw_log_z
+ * are the rule in numpy; device and numpy perform the same operations in the same order and differ only in log and exp
+ * (the device's log, the library's specified exponential), so they agree to rounding, not bit for bit.  A run itself is
+ * reproducible: same inputs, same bits, whichever route serves a factor.  Every call acts on the selected set-up
+ * (nsk_bp_select) and is NSK_E_INVALID without one.
+ * State, in msg_off's layout: LF[e][k], the log message factor -> variable, its largest entry 0; LN[e][k], the log
+ * message variable -> factor, normalised the same way; a cold start sets both 0.  MAX is that of max-product above.
+ * Tables: psi_rho_f(a) = exp((theta_f(a) - max_a theta_f) / rho_f), recomputed by every nsk_bp_trw_run.  Iteration t:
+ *   factor phase, per edge (f, j): s[k] = the sum over the table indices a with digit j equal to k, ascending, from 0.0,
+ *     of ((psi_rho_f(a) * exp(LN[(f,0)][a_0])) * ..) over the axes i != j ascending, exp(LN) formed once per message
+ *     entry; new[k] = log s[k] - MAX_k log s[k], the maximum folded in k order; damping in the log domain and the
+ *     residual exactly as in nsk_bp_run (LF = (1 - d) * new + d * LF, a NaN change counting as +inf);
+ *   variable phase, per free variable with the edges e_0 < .. < e_{n-1}: S[k] = the sum over i ascending, from 0.0, of
+ *     rho_{f(e_i)} * LF[e_i][k] (one rounded product, one rounded sum); LN[e_i][k] = (S[k] - LF[e_i][k]) - MAX_k of
+ *     those; belief[k] = exp(S[k] - MAX_k S) divided by the k-ordered sum of those.
+ * A clamped variable's belief is the indicator of its value, a free variable in no table has the uniform one.
+ * Factor beliefs: b_f(a) = (psi_rho_f(a) * exp(LN[(f,0)][a_0])) * .., divided by their a-ordered sum.
+ * Free energy: log_z = sum_f tf[f] + sum_v tv[v] with tf[f] = the a-ordered sum over b_f(a) > 0 of
+ * b_f(a) * (theta_f(a) - rho_f * log b_f(a)); tv[v] = (sum of rho over the edges of v, ascending, - 1) * the k-ordered
+ * sum over b_v[k] > 0 of b_v[k] log b_v[k] for a free variable with an edge, log cardinality for a free variable
+ * without one, 0 for a clamped one.  The caller adds the terms (an exactly rounded sum makes their order irrelevant).
+ *   nsk_bp_trw_run       rho: nfactor doubles in the caller's factor order, every one finite and > 0 (else
+ *                        NSK_E_INVALID naming the entry; a factor without a free member reads its rho nowhere).  The
+ *                        ranges, warm, *iters and residual are those of nsk_bp_map_run.  The first call on a set-up
+ *                        allocates LF, LN, exp(LN), psi_rho, beliefs of its own, rho, the terms and the lists of the
+ *                        factors' routes (24 bytes a message entry, 8 a table entry, 8 a value, 16 a factor, 8 a
+ *                        variable, at most 4 a factor) and starts cold whatever `warm` says; the set-up owns them:
+ *                        nsk_graph_info.device_bytes counts them, nsk_bp_clear, a replacing set-up and nsk_graph_destroy
+ *                        free them; NSK_E_NOMEM names the bytes.  Everything is enqueued at once, one synchronisation.
+ *   nsk_bp_trw_beliefs   the "full" layout of nsk_bp_beliefs.
+ *   nsk_bp_trw_download  what = NSK_BP_TRW_LF, NSK_BP_TRW_LN (msg_off's layout), NSK_BP_TRW_FACTOR_BELIEFS (table_off's,
+ *                        computed by the call), NSK_BP_TRW_TERMS (computed by the call: tf[nfactor] in the caller's
+ *                        factor order, then tv[nvar] in the caller's variable order).
+ *   nsk_bp_trw_routes    counts[2] = the factors with an edge that the factor phase serves by one lane a factor (at most
+ *                        63 table entries, cardinalities summing to at most 16) and by one wave a factor (the rest).
+ *   nsk_bp_trw_plan      host only, no device: the same counts for the set-up nsk_bp_setup would build of `desc`;
+ *                        route[nfactor] (may be NULL) = 0 lane, 1 wave, -1 no edge; *wave_lds (may be NULL) = the doubles
+ *                        of LDS a wave of the wave route takes, the largest T + 2 C among its factors.
+ * Beliefs and download before the first run on a set-up are NSK_E_INVALID.  The sum-product and max-product messages and
+ * beliefs are untouched, and nsk_bp_run, nsk_bp_residual_run, nsk_bp_map_run and the learners do not read these arrays.
+ * Every launch honours NSK_BP_GRID_CAP.  (Diagnostic, NSK_DIAG=1 NSK_TRW_LANE_MAX=n, read by nsk_bp_setup and
+ * nsk_bp_trw_plan: every factor of at most n table entries takes the lane route whatever its cardinalities, every other
+ * the wave route; 0 sends all down the wave route, 4096 all down the lane route.  The bits do not depend on it.) */
+#define NSK_BP_TRW_LF 0
+#define NSK_BP_TRW_LN 1
+#define NSK_BP_TRW_FACTOR_BELIEFS 2
+#define NSK_BP_TRW_TERMS 3
+int nsk_bp_trw_run(nsk_graph *g, const double *rho /* nfactor */, int64_t max_iters, double damping, double tol, int warm,
+                   int64_t *iters, double *residual /* max_iters, may be NULL */);
+int nsk_bp_trw_beliefs(nsk_graph *g, const int64_t *vids, int64_t nvids, double *out /* total */);
+int nsk_bp_trw_download(nsk_graph *g, int what, double *out);
+int nsk_bp_trw_routes(nsk_graph *g, int64_t *counts /* 2 */);
+int nsk_bp_trw_plan(const nsk_graph_desc *desc, int sample_evidence, int64_t *counts /* 2, may be NULL */,
+                    int32_t *route /* nfactor, may be NULL */, int64_t *wave_lds /* may be NULL */);
+
 /* Sum-product belief propagation under a RESIDUAL schedule (FactorGraph.belief_propagation(schedule="residual")): a round
  * recomputes only the messages whose inputs moved and commits only those whose pending change is large against the
  * largest pending one -- the bulk-synchronous form of residual BP.  It acts on the selected resident set-up

@@ -38,6 +38,7 @@ SYMBOLS = (
     "nsk_bp_refresh", "nsk_bp_moments", "nsk_bp_learn_steps", "nsk_bp_select", "nsk_bp_selected", "nsk_bp_latent_steps",
     "nsk_bp_map_run", "nsk_bp_map_marginals", "nsk_bp_map_download", "nsk_bp_map_decode", "nsk_bp_map_routes",
     "nsk_bp_residual_run",
+    "nsk_bp_trw_run", "nsk_bp_trw_beliefs", "nsk_bp_trw_download", "nsk_bp_trw_routes", "nsk_bp_trw_plan",
     "nsk_sw_plan", "nsk_sw_setup", "nsk_sw_layout", "nsk_sw_download", "nsk_sw_labels", "nsk_sw_refresh", "nsk_sw_clear", "nsk_sw_sweeps",
     "nsk_trace_ess", "nsk_trace_autocov_counts", "nsk_trace_pair_counts",
     "nsk_trace_value_autocov_counts", "nsk_trace_value_ess", "nsk_trace_value_pair_counts",
@@ -94,6 +95,10 @@ BP_MAP_F, BP_MAP_V = 0, 1           # what nsk_bp_map_download hands out
 # the routes of max-product's factor phase (csrc/nsk_bp_map_plan.h): one lane a factor below BP_MAP_LANE_TABLE entries whose
 # cardinalities sum to at most BP_MAP_LANE_CARDS, one wave a factor up to BP_MAP_LDS, one lane a directed edge beyond
 BP_MAP_LANE_TABLE, BP_MAP_LANE_CARDS, BP_MAP_LDS = 64, 16, 512
+# tree-reweighted BP: what nsk_bp_trw_download hands out, and the routes of its factor phase (csrc/nsk_bp_trw_plan.h): one
+# lane a factor of at most BP_TRW_LANE_TABLE entries whose cardinalities sum to at most BP_MAP_LANE_CARDS, one wave beyond
+BP_TRW_LF, BP_TRW_LN, BP_TRW_FACTOR_BELIEFS, BP_TRW_TERMS = range(4)
+BP_TRW_LANE_TABLE = 63
 BP_VAR_REG = 6          # a binary variable of at most this many edges is served from registers (csrc/nsk_kernels_bp.h)
 
 
@@ -240,7 +245,12 @@ def lib():
         L.nsk_bp_map_routes.argtypes = [C.c_void_p, C.c_void_p]
         L.nsk_bp_residual_run.argtypes = [C.c_void_p, C.c_int64, C.c_double, C.c_double, C.c_double, C.c_int, C.POINTER(C.c_int64),
                                           C.c_void_p, C.c_void_p, C.c_void_p]
-        L.nsk_sw_plan.argtypes = [C.POINTER(GraphDesc), C.c_int, C.c_int, C.POINTER(SwInfo)] + [C.c_void_p] * 4
+        L.nsk_bp_trw_run.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_double, C.c_double, C.c_int, C.POINTER(C.c_int64), C.c_void_p]
+        L.nsk_bp_trw_beliefs.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]
+        L.nsk_bp_trw_download.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
+        L.nsk_bp_trw_routes.argtypes = [C.c_void_p, C.c_void_p]
+        L.nsk_bp_trw_plan.argtypes = [C.POINTER(GraphDesc), C.c_int, C.c_void_p, C.c_void_p, C.POINTER(C.c_int64)]
+        L.nsk_sw_plan.argtypes =[C.POINTER(GraphDesc), C.c_int, C.c_int, C.POINTER(SwInfo)] + [C.c_void_p] * 4
         L.nsk_sw_setup.argtypes = [C.c_void_p, C.c_int, C.c_int64, C.c_int, C.POINTER(SwInfo)]
         L.nsk_sw_layout.argtypes = [C.c_void_p] * 4
         L.nsk_sw_download.argtypes = [C.c_void_p, C.c_int, C.c_void_p]

@@ -19,6 +19,7 @@
 #include "../../include/numbskull_amd.h"
 #include "nsk_alloc.h"
 #include "nsk_bp_map_plan.h"
+#include "nsk_bp_trw_plan.h"
 #include "nsk_compile.h"
 #include "nsk_device.h"
 #include "nsk_kernels_gibbs.h"
@@ -147,6 +148,14 @@ struct NskBp {
     double *rs_cand = nullptr, *rs_r = nullptr, *rs_pre = nullptr;
     uint8_t *rs_chg = nullptr, *rs_dflag = nullptr, *rs_vflag = nullptr;
     int32_t *rs_dq = nullptr, *rs_vq = nullptr, *rs_vpos = nullptr;
+    // Tree-reweighted BP (nsk_bp_trw.hip): the set-up plans the factors' routes (host only); the first nsk_bp_trw_run
+    // uploads the lists and allocates rho and the factor terms (nfactor doubles each), psi_rho (ntable), LF, LN and
+    // exp(LN) (nmsg each), the beliefs (nbelief) and the variable terms (nid) -- all in `owned`.
+    nsk::BpTrwRoutes tw_routes;
+    double *tw_rho = nullptr, *tw_psi = nullptr, *tw_lf = nullptr, *tw_ln = nullptr, *tw_en = nullptr, *tw_bel = nullptr;
+    double *tw_tf = nullptr, *tw_tv = nullptr;
+    int32_t *tw_lane = nullptr, *tw_wave = nullptr;
+    int32_t tw_nlane = 0, tw_nwave = 0;
 };
 
 // Swendsen-Wang cluster updates (nsk_sw_setup .. nsk_sw_clear; nsk_sw.hip, nsk_kernels_sw.h): the structure of

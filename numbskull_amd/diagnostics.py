@@ -1394,6 +1394,215 @@ def ms_decode(layout, max_marginals, values):
     return x, ties
 
 
+# ------------------------------------------------------------------------------------------------- tree-reweighted BP
+def _trw_rho(layout, rho):
+    nf = len(layout["table_off"]) - 1
+    rho = np.asarray(rho, np.float64)
+    if rho.ndim == 0:
+        rho = np.full(nf, float(rho))
+    if rho.shape != (nf,):
+        raise ValueError("rho must be a scalar or hold one entry per factor (%d)" % nf)
+    if not (np.isfinite(rho) & (rho > 0)).all():
+        raise ValueError("every rho must be finite and greater than 0")
+    return rho
+
+
+def _trw_x(layout, psi, EN, f):
+    """``x(a) = ((psi_rho(a) * EN[(f, 0)][a_0]) * ..)`` over the axes ascending, for every entry of factor f"""
+    to, mo, e0 = layout["table_off"], layout["msg_off"], int(layout["edge_off"][f])
+    shape, out = layout["shapes"][f], []
+    for a in range(int(to[f + 1] - to[f])):
+        d = _bp_digits(a, shape)
+        x = psi[to[f] + a]
+        for i in range(len(shape)):
+            x = x * EN[mo[e0 + i] + d[i]]
+        out.append(x)
+    return out
+
+
+def trw_iterate(layout, theta, rho, iters, damping=0.0, tol=0.0, dtype=np.float64, messages=None):
+    """Tree-reweighted (fractional) belief propagation as nsk_bp_trw_run performs it, in plain loops, operation by
+    operation (the header states the rule); ``layout`` and ``theta`` are those of ``bp_iterate``, ``rho`` a scalar or one
+    weight per factor.  Log messages ``LF`` (factor to variable) and ``LN`` (variable to factor), each vector's largest
+    entry 0, start at 0 (``messages=(LF, LN)`` continues).  Factor phase, per edge (f, j): the sums ``s[k]`` over the
+    table entries, ascending, of ``psi_rho`` times ``exp(LN)`` of the other axes, ``psi_rho = exp((theta - max theta) /
+    rho_f)``; ``new = log s - max log s``, damped in the log domain; the residual is the largest change of an entry, NaN
+    counting as inf.  Variable phase: ``S = sum_i rho_i LF[e_i]``, ``LN[e_i] = (S - LF[e_i]) - max``, the belief
+    ``exp(S - max S)`` normalised in k order.  Every scalar is a ``dtype``: ``np.longdouble`` runs the same code in
+    extended precision, which measures the rule's own rounding noise.  Returns a dict: ``LF``, ``LN``, ``beliefs`` (the
+    "full" layout), ``factor_beliefs``, ``psi``, ``residual`` (float64, 0 behind the stop) and ``iters`` as
+    ``bp_iterate`` counts them."""
+    D = dtype
+    to, eo, mo, card = layout["table_off"], layout["edge_off"], layout["msg_off"], layout["card"]
+    nf = len(to) - 1
+    rho = _trw_rho(layout, rho)
+    efac = np.repeat(np.arange(nf), np.diff(eo))
+    th = np.asarray(theta, np.float64).astype(D)
+    psi = np.zeros(len(th), D)
+    for f in range(nf):
+        mine = th[to[f]:to[f + 1]]
+        psi[to[f]:to[f + 1]] = np.exp((mine - mine.max()) / D(rho[f]))
+    if messages is None:
+        LF, LN = np.zeros(int(mo[-1]), D), np.zeros(int(mo[-1]), D)
+    else:
+        LF, LN = (np.array(m, D) for m in messages)
+    EN = np.exp(LN)
+    beliefs = _bp_start(layout, None)[2].astype(D)
+    lam, oml = D(damping), D(1.0 - float(damping))
+    residual = np.zeros(iters)
+    ran = -iters
+    with np.errstate(all="ignore"):
+        for t in range(iters):
+            if t > 0 and residual[t - 1] <= tol:
+                break
+            res, new = 0.0, LF.copy()
+            for f in range(nf):
+                shape, e0 = layout["shapes"][f], int(eo[f])
+                A = len(shape)
+                s = [[D(0.0)] * c for c in shape]
+                for a in range(int(to[f + 1] - to[f]) if A else 0):
+                    d = _bp_digits(a, shape)
+                    vv = [EN[mo[e0 + i] + d[i]] for i in range(A)]
+                    pre = psi[to[f] + a]
+                    for j in range(A):
+                        x = pre
+                        for h in range(j + 1, A):
+                            x = x * vv[h]
+                        s[j][d[j]] = s[j][d[j]] + x
+                        pre = pre * vv[j]
+                for j in range(A):
+                    lg = [np.log(x) for x in s[j]]
+                    mx = _ms_fold(lg)
+                    for k in range(shape[j]):
+                        old = LF[mo[e0 + j] + k]
+                        nw = lg[k] - mx
+                        if lam > 0:
+                            nw = oml * nw + lam * old
+                        new[mo[e0 + j] + k] = nw
+                        res = max(res, _bp_change(float(abs(nw - old)), 0.0))
+            LF = new
+            residual[t] = res
+            for v in range(len(card)):
+                edges, n = layout["var_edges"][v], int(card[v])
+                if layout["clamped"][v] or not edges:
+                    continue
+                S = [D(0.0)] * n
+                for e in edges:
+                    S = [S[k] + D(rho[efac[e]]) * LF[mo[e] + k] for k in range(n)]
+                for e in edges:
+                    T = [S[k] - LF[mo[e] + k] for k in range(n)]
+                    mt = _ms_fold(T)
+                    LN[mo[e]:mo[e + 1]] = [x - mt for x in T]
+                    EN[mo[e]:mo[e + 1]] = np.exp(LN[mo[e]:mo[e + 1]])
+                mx = _ms_fold(S)
+                B = [np.exp(x - mx) for x in S]
+                z = _bp_sum(B)
+                beliefs[layout["offsets"][v]:layout["offsets"][v + 1]] = [x / z for x in B]
+            if ran < 0 and res <= tol:
+                ran = t + 1
+        fb = np.zeros(len(th), D)
+        for f in range(nf):
+            x = _trw_x(layout, psi, EN, f)
+            z = _bp_sum(x)
+            fb[to[f]:to[f + 1]] = [y / z for y in x]
+    return {"LF": LF, "LN": LN, "beliefs": beliefs, "factor_beliefs": fb, "psi": psi, "residual": residual, "iters": ran}
+
+
+def trw_log_z(layout, theta, rho, factor_beliefs, beliefs, dtype=np.float64, terms=False):
+    """The free energy of tree-reweighted BP at the beliefs of a ``trw_iterate`` run: per factor the a-ordered sum over
+    ``b_f(a) > 0`` of ``b_f (theta_f - rho_f log b_f)``; per free variable with an edge ``(sum of rho over its edges,
+    ascending, - 1)`` times the k-ordered sum over ``b > 0`` of ``b log b``; ``log cardinality`` per free variable without
+    an edge.  An upper bound on log Z at a fixed point where ``rho`` lies in the spanning-tree polytope of a pairwise
+    graph (``edge_appearance``); with ``rho = 1`` it is ``bethe_log_z``.  The terms are added with an exactly rounded sum
+    in float64 (``math.fsum``, as ``FactorGraph.reweighted_bp`` adds the device's) and in ``dtype`` otherwise.
+    ``terms=True`` returns ``(per factor, per variable)`` instead."""
+    import math
+    D = dtype
+    to, eo = layout["table_off"], layout["edge_off"]
+    nf = len(to) - 1
+    rho = _trw_rho(layout, rho)
+    efac = np.repeat(np.arange(nf), np.diff(eo))
+    th, fb, b = np.asarray(theta, np.float64).astype(D), np.asarray(factor_beliefs, D), np.asarray(beliefs, D)
+    tf, tv = np.zeros(nf, D), np.zeros(len(layout["card"]), D)
+    for f in range(nf):
+        term = D(0.0)
+        for a in range(int(to[f]), int(to[f + 1])):
+            if fb[a] > 0:
+                term = term + fb[a] * (th[a] - D(rho[f]) * np.log(fb[a]))
+        tf[f] = term
+    off = layout["offsets"]
+    for v in range(len(layout["card"])):
+        if layout["clamped"][v]:
+            continue
+        edges = layout["var_edges"][v]
+        if not edges:
+            tv[v] = np.log(D(layout["card"][v]))
+            continue
+        R, h = D(0.0), D(0.0)
+        for e in edges:
+            R = R + D(rho[efac[e]])
+        for k in range(int(off[v]), int(off[v + 1])):
+            if b[k] > 0:
+                h = h + b[k] * np.log(b[k])
+        tv[v] = (R - D(1.0)) * h
+    if terms:
+        return tf, tv
+    if D is np.float64:
+        return math.fsum(tf.tolist() + tv.tolist())
+    return tf.sum() + tv.sum()
+
+
+def edge_appearance(layout, trees=64, seed=0):
+    """Edge appearance probabilities for ``trw_iterate`` / ``FactorGraph.reweighted_bp(rho="trees")``: every factor with
+    exactly two free members is an edge between them (a multigraph), ``trees`` random spanning forests are drawn --
+    Kruskal with union-find over a seeded random edge order -- and ``rho_f`` is the share of forests that hold ``f``.  An
+    average of spanning forests lies in the spanning-tree polytope, so the free energy under this rho is an upper bound
+    on log Z.  The edges the first forest left out are put in front of the later forests' orders until each has
+    appeared once, so that no rho is 0 (ValueError when ``trees`` is too small for that).  Factors with fewer than two
+    free members get 1.  A factor with three or more free members is a ValueError: the bound is only claimed for
+    pairwise graphs -- pass rho explicitly to run the algorithm on such a graph all the same."""
+    trees = int(trees)
+    if trees < 1:
+        raise ValueError("edge_appearance: trees must be at least 1")
+    axes = layout["axes"]
+    for f, ax in enumerate(axes):
+        if len(ax) > 2:
+            raise ValueError("edge_appearance: factor %d has %d free members: the tree-reweighted bound is claimed for "
+                             "pairwise graphs only; pass rho explicitly" % (f, len(ax)))
+    fid = np.array([f for f, ax in enumerate(axes) if len(ax) == 2], np.int64)
+    ends = np.array([axes[f] for f in fid], np.int64).reshape(-1, 2)
+    rho = np.ones(len(axes))
+    if not len(fid):
+        return rho
+    rng = np.random.default_rng(seed)
+    count = np.zeros(len(fid), np.int64)
+    unseen = np.zeros(len(fid), bool)
+    nvar = int(ends.max()) + 1
+    for t in range(trees):
+        order = rng.permutation(len(fid))
+        if t > 0:
+            order = np.concatenate([order[unseen[order]], order[~unseen[order]]])
+        parent = list(range(nvar))
+        held = np.zeros(len(fid), bool)
+        for i in order.tolist():
+            u, v = int(ends[i, 0]), int(ends[i, 1])
+            while parent[u] != u:
+                parent[u] = parent[parent[u]]
+                u = parent[u]
+            while parent[v] != v:
+                parent[v] = parent[parent[v]]
+                v = parent[v]
+            if u != v:
+                parent[u] = v
+                held[i] = True
+        count += held
+        unseen = ~held if t == 0 else unseen & ~held
+    if unseen.any():
+        raise ValueError("edge_appearance: %d forests do not cover every edge once; raise trees" % trees)
+    rho[fid] = count / float(trees)
+    return rho
+
+
 # ------------------------------------------------------------------------------------------------- Swendsen-Wang
 def sw_tables(theta, layout, exp=np.exp):
     """The tables of ``FactorGraph.swendsen_wang`` (nsk_sw_setup) from the theta tables of ``bp_layout``'s structure,

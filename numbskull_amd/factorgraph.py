@@ -1579,6 +1579,74 @@ class FactorGraph(object):
                        log_potential=float(self.log_potential(var_copy, weight_copy, evidence_chain)))
         return out
 
+    def reweighted_bp(self, rho="trees", trees=64, seed=0, max_iters=200, damping=0.5, tol=1e-9, var_copy=0, weight_copy=0,
+                      evidence_chain=False, sample_evidence=False, factor_beliefs=False):
+        """Tree-reweighted belief propagation on the device (nsk_bp_setup / nsk_bp_trw_run): the message passing of
+        ``belief_propagation`` with every factor counted ``rho_f`` times, in the log domain.  ``rho`` is one weight per
+        factor (finite, > 0), a scalar for all, or ``"trees"``: the edge appearance probabilities of ``trees`` random
+        spanning forests drawn with ``seed`` (``diagnostics.edge_appearance``).  For such a rho on a PAIRWISE graph the
+        free energy is convex and ``log_z`` at the fixed point is an UPPER BOUND on log Z -- the bound is claimed for
+        pairwise graphs only, and only where ``converged``; ``"trees"`` refuses a factor with three or more free members
+        (ValueError), an explicit rho runs on any graph.  With ``rho=1`` this is sum-product BP and ``log_z`` the Bethe
+        estimate.  Damped iterations converge far more readily than BP at strong coupling.  State, weights, clamping,
+        the caps and the refusals are those of ``belief_propagation``; ``diagnostics.trw_iterate`` / ``trw_log_z`` are the
+        rule in numpy, which the device follows operation by operation but for its own ``log`` and ``exp``.
+        Returns a dict: ``offsets`` and ``beliefs`` (the layout of ``conditionals``), ``iters``, ``converged``,
+        ``residual``, ``log_z``, ``rho`` (float64 per factor); with ``factor_beliefs=True`` also ``table_offsets``,
+        ``theta`` and ``factor_beliefs``."""
+        import math
+        from .diagnostics import bp_layout, edge_appearance
+        max_iters = int(max_iters)
+        if max_iters < 1 or max_iters > 4096:
+            raise ValueError("reweighted_bp: max_iters must lie in [1, 4096]")
+        if _all_copies(var_copy):
+            raise ValueError('reweighted_bp serves one state: var_copy="all" is for the sampler')
+        nf = self.factor.shape[0]
+        if isinstance(rho, str):
+            if rho != "trees":
+                raise ValueError('reweighted_bp: rho must be "trees", a scalar or one entry per factor')
+            row = (self.var_value_evid if evidence_chain else self.var_value)[var_copy]
+            rho = edge_appearance(bp_layout(self.factor, self.fmap, self.variable, row, sample_evidence), trees, seed)
+        rho = np.ascontiguousarray(np.broadcast_to(np.asarray(rho, np.float64), (nf,)) if np.ndim(rho) == 0 else rho, np.float64)
+        if rho.shape != (nf,):
+            raise ValueError("reweighted_bp: rho holds %s entries, the graph has %d factors" % (rho.shape, nf))
+        L, h = _lib.lib(), self._engine()
+        self._push(var_copy, weight_copy)
+        info = _lib.BpInfo()
+        _lib.check(L.nsk_bp_setup(h, _lib.BUF_VALUE_EVID if evidence_chain else _lib.BUF_VALUE, 0, int(bool(sample_evidence)),
+                                  C.byref(info)))
+        try:
+            iters, residual = C.c_int64(0), np.zeros(max_iters, np.float64)
+            _lib.check(L.nsk_bp_trw_run(h, _lib.ptr(rho), max_iters, float(damping), float(tol), 0, C.byref(iters), _lib.ptr(residual)))
+            _, offsets = self._cond_selection(None, None, "reweighted_bp")
+            beliefs = np.zeros(int(offsets[-1]), np.float64)
+            _lib.check(L.nsk_bp_trw_beliefs(h, None, 0, _lib.ptr(beliefs)))
+            terms = np.zeros(nf + self.variable.shape[0], np.float64)
+            _lib.check(L.nsk_bp_trw_download(h, _lib.BP_TRW_TERMS, _lib.ptr(terms)))
+            out = {"offsets": offsets, "beliefs": beliefs, "iters": abs(int(iters.value)), "converged": bool(iters.value > 0),
+                   "residual": residual, "log_z": math.fsum(terms.tolist()), "rho": rho}
+            if factor_beliefs:
+                theta, fb, table_off = np.zeros(info.ntable), np.zeros(info.ntable), np.zeros(nf + 1, np.int64)
+                _lib.check(L.nsk_bp_download(h, _lib.BP_THETA, _lib.ptr(theta)))
+                _lib.check(L.nsk_bp_trw_download(h, _lib.BP_TRW_FACTOR_BELIEFS, _lib.ptr(fb)))
+                _lib.check(L.nsk_bp_layout(h, _lib.ptr(table_off), None, None, None))
+                out.update(table_offsets=table_off, theta=theta, factor_beliefs=fb)
+        finally:
+            L.nsk_bp_clear(h)
+        return out
+
+    def log_z_bounds(self, rho="trees", trees=64, seed=0, max_iters=200, damping=0.5, tol=1e-9, var_copy=0, weight_copy=0,
+                     evidence_chain=False, sample_evidence=False):
+        """The Bethe estimate of ``belief_propagation`` and the tree-reweighted value of ``reweighted_bp`` side by side,
+        both run with the same ``max_iters``, ``damping`` and ``tol``.  On a pairwise graph ``trw`` is an upper bound on
+        log Z where ``trw_converged``; on an attractive binary pairwise model ``bethe`` is a lower bound where
+        ``bethe_converged``, so the two bracket log Z there.  Returns a dict: ``bethe``, ``trw``, ``bethe_converged``,
+        ``trw_converged``."""
+        sel = dict(var_copy=var_copy, weight_copy=weight_copy, evidence_chain=evidence_chain, sample_evidence=sample_evidence)
+        bp = self.belief_propagation(max_iters, damping, tol, **sel)
+        tw = self.reweighted_bp(rho, trees, seed, max_iters, damping, tol, **sel)
+        return {"bethe": bp["log_z"], "trw": tw["log_z"], "bethe_converged": bp["converged"], "trw_converged": tw["converged"]}
+
     def bp_weight_moments(self, max_iters=100, damping=0.0, tol=1e-9, var_copy=0, weight_copy=0, evidence_chain=False,
                           sample_evidence=False, counts=False, schedule="flooding", frac=0.5):
         """The expected per-weight statistics ``E[S_w]`` under belief propagation (nsk_bp_setup / nsk_bp_run /
