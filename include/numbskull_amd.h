@@ -360,6 +360,63 @@ int nsk_bp_clear(nsk_graph *g);
 int nsk_bp_select(nsk_graph *g, int slot);
 int nsk_bp_selected(nsk_graph *g);
 
+/* Belief propagation through WIDE logical factors (FactorGraph.belief_propagation(wide_factors=True)): a factor beyond
+ * the two caps above has no table; its messages are closed forms, O(arity) a factor.  numbskull_amd.diagnostics.
+ * bp_wide_factor is the rule in numpy (to rounding, not bit for bit: the device forms its products by scans).
+ * A factor is WIDE when it has more than NSK_BP_MAX_MEMBERS distinct members or more than NSK_BP_MAX_TABLE table entries,
+ * its function is IMPLY_NATURAL, OR, AND, EQUAL, ISTRUE, LINEAR, LOGICAL or (with NSK_FLAG_HEAD_BY_VID) IMPLY_MLN, every
+ * member is binary, no free variable stands at two of its positions (clamped members may repeat) and it has at most
+ * NSK_BP_WIDE_MAX_MEMBERS positions.  Every other factor takes the table route, with nsk_bp_setup's refusals in
+ * nsk_bp_setup's words; a factor of one of these functions over binary members that is beyond the caps and names a free
+ * member twice, or has more positions, is refused naming it.  A wide factor has T_f = 0 -- no entries in NSK_BP_THETA /
+ * NSK_BP_FACTOR_BELIEFS -- and its directed edges, one per free position, in the factor-major numbering of all edges.
+ * The rule, with nu_l the incoming pair at position l (the indicator of its value for a clamped member), L(s)_j the
+ * product over the positions l != j of a stream s_l, formed as prefix x suffix without a division, and cv =
+ * exp(w * v - max) (the device's deterministic exp) over the two values v the function takes:
+ *   AND, ISTRUE (v = -1, 1), IMPLY_NATURAL (0, 1):  m_j(0) = base, m_j(1) = base + d * L(nu(1))_j, base = c_lo * L(nu(0) + nu(1))_j,
+ *                                                   d = c_hi - c_lo
+ *   OR (-1, 1):       base = c_hi * L(nu(0) + nu(1))_j, d = c_lo - c_hi: m_j(0) = base + d * L(nu(0))_j, m_j(1) = base
+ *   EQUAL (-1, 1):    m_j(0) = base + d * L(nu(0))_j, m_j(1) = base + d * L(nu(1))_j, base and d as AND's
+ *   LOGICAL (0, 1), head h the last position, the streams over the body: base = (c_hi * L(nu(0) + nu(1))_j) * (nu_h(0) + nu_h(1)),
+ *                     d = c_lo - c_hi: m_j(0) = base + d * (nu_h(1) * L(nu(0))_j), m_j(1) = base + d * (nu_h(0) * L(nu(1))_j);
+ *                     to the head, from the body's totals T: m_h(0) = c_hi * T(sum) + d * T(nu(1)), m_h(1) = c_hi * T(sum) + d * T(nu(0))
+ *   IMPLY_MLN (0, 1): as LOGICAL with m_j(0) = base and m_h(1) = c_hi * T(sum)
+ *   LINEAR:           c_l(0) = ge * nu_l(0) + gd * nu_l(1), c_l(1) = gd * nu_l(0) + ge * nu_l(1), (ge, gd) = (1, q) for w >= 0,
+ *                     (q, 1) below, q = exp(-|w|); u_x = nu_h(x) * L(c(x))_j: m_j(0) = u_0 * ge + u_1 * gd,
+ *                     m_j(1) = u_0 * gd + u_1 * ge; m_h(x) = T(c(x))
+ * then Z = m[0] + m[1], new[k] = m[k] / Z, damping and residual as in the factor phase above.  Messages are normalised:
+ * for the pattern functions the stream nu(0) + nu(1) stays near 1, every product is at most about 1 and an underflow to 0
+ * is the correct answer, so nothing is rescaled.  LINEAR's two streams are both below 1 and both products would leave
+ * the range of a double (from about |w| x positions = 700 on): each is kept as a mantissa in [0.5, 1) and an int
+ * exponent, renormalised by exact powers of two after every multiplication, and u_0, u_1 meet at the larger exponent
+ * (in the term, nu_h(x) m_h(x) likewise: the head's pair is multiplied in before the two totals meet).  w is read from
+ * the device weights at every iteration: nsk_bp_refresh has nothing to do for a wide factor.
+ *   nsk_bp_setup_wide  nsk_bp_setup with the wide route on; *winfo (may be NULL) = the wide factors, their positions, the
+ *                      most positions of one, the bytes of LDS a block of the factor phase takes and the bytes the wide
+ *                      arrays hold (8 a position + 20 a wide factor + 4 an edge of the table route; counted in
+ *                      info->device_bytes too).  The wide arrays hang off the selected set-up and go with it
+ *                      (nsk_bp_clear).  Without a wide factor the set-up is nsk_bp_setup's and launches what it launches.
+ *   nsk_bp_wide_terms  factor_ids[nwide] (may be NULL) = the wide factors, ascending; terms[nwide] (may be NULL) = each
+ *                      one's Bethe term sum_a b_f (theta_f - ln b_f) from the resident messages, in its closed form
+ *                      ln Z' + max theta - sum_l sum_x b_l(x) ln nu_l(x), Z' = sum_x nu_j(x) m_j(x) at the last position
+ *                      j, b_l(x) = nu_l(x) m_l(x) / Z', 0 ln 0 = 0 (LINEAR: each position divides by its own
+ *                      sum_x nu_l(x) m_l(x), the same Z' at that position's power of two).
+ *   nsk_bp_wide_plan   host only, no device: the sizes of the set-up nsk_bp_setup_wide would build of `desc`;
+ *                      route[nfactor] (may be NULL) = 0 table, 1 wide.  Both device_bytes are 0: nothing is allocated.
+ * nsk_bp_run, nsk_bp_beliefs, nsk_bp_layout, nsk_bp_download and nsk_bp_clear serve a set-up with wide factors.
+ * nsk_bp_residual_run, nsk_bp_map_run, nsk_bp_trw_run, nsk_bp_moments, nsk_bp_learn_steps and nsk_bp_latent_steps are
+ * NSK_E_INVALID on one.  (Diagnostic, NSK_DIAG=1 NSK_BP_WIDE_MIN=n, read by nsk_bp_setup_wide and nsk_bp_wide_plan:
+ * every eligible factor of at least n distinct members goes wide, so that one graph runs both ways.) */
+#define NSK_BP_WIDE_MAX_MEMBERS 2048
+typedef struct {
+    int64_t nwide, wide_positions, max_positions, lds_bytes, device_bytes;
+} nsk_bp_wide_info;
+int nsk_bp_setup_wide(nsk_graph *g, int which, int64_t chain, int sample_evidence, nsk_bp_info *info /* may be NULL */,
+                      nsk_bp_wide_info *winfo /* may be NULL */);
+int nsk_bp_wide_terms(nsk_graph *g, int64_t *factor_ids /* nwide, may be NULL */, double *terms /* nwide, may be NULL */);
+int nsk_bp_wide_plan(const nsk_graph_desc *desc, int sample_evidence, nsk_bp_info *info /* may be NULL */,
+                     nsk_bp_wide_info *winfo /* may be NULL */, int32_t *route /* nfactor, may be NULL */);
+
 /* Max-product belief propagation (FactorGraph.map_bp): the resident set-up above run over the (max, +) semiring -- MAP
  * decoding.  Exact wherever the free variables form a forest (where the MAP assignment is unique); on a graph with
  * cycles a deterministic start for nsk_icm.  numbskull_amd.diagnostics.ms_iterate / ms_decode are the rule in numpy, bit

@@ -39,6 +39,7 @@ SYMBOLS = (
     "nsk_bp_map_run", "nsk_bp_map_marginals", "nsk_bp_map_download", "nsk_bp_map_decode", "nsk_bp_map_routes",
     "nsk_bp_residual_run",
     "nsk_bp_trw_run", "nsk_bp_trw_beliefs", "nsk_bp_trw_download", "nsk_bp_trw_routes", "nsk_bp_trw_plan",
+    "nsk_bp_setup_wide", "nsk_bp_wide_terms", "nsk_bp_wide_plan",
     "nsk_sw_plan", "nsk_sw_setup", "nsk_sw_layout", "nsk_sw_download", "nsk_sw_labels", "nsk_sw_refresh", "nsk_sw_clear", "nsk_sw_sweeps",
     "nsk_trace_ess", "nsk_trace_autocov_counts", "nsk_trace_pair_counts",
     "nsk_trace_value_autocov_counts", "nsk_trace_value_ess", "nsk_trace_value_pair_counts",
@@ -78,6 +79,10 @@ class BpInfo(C.Structure):
                                          "nbelief", "max_table", "device_bytes")]
 
 
+class BpWideInfo(C.Structure):
+    _fields_ = [(k, C.c_int64) for k in ("nwide", "wide_positions", "max_positions", "lds_bytes", "device_bytes")]
+
+
 class SwInfo(C.Structure):
     _fields_ = [(k, C.c_int64) for k in ("nvars", "nbonds", "ncross", "ntiles", "nfields", "device_bytes")]
 
@@ -89,6 +94,7 @@ SW_TILE = 1024                      # ordinals of a Swendsen-Wang tile at most (
 # launches (csrc/nsk_bp.hip bp_blocks): one item a lane, blocks of BP_BLOCK lanes (BP_VAR_BLOCK in the variable phase),
 # at most BP_MAX_BLOCKS -- or the diagnostic cap NSK_BP_GRID_CAP; more items loop
 BP_MAX_MEMBERS, BP_MAX_TABLE = 16, 4096
+BP_WIDE_MAX_MEMBERS = 2048          # member positions of a wide factor at most (nsk_bp_setup_wide)
 BP_THETA, BP_FACTOR_BELIEFS, BP_F2V, BP_V2F = range(4)
 BP_BLOCK, BP_VAR_BLOCK, BP_MAX_BLOCKS = 256, 128, 2048
 BP_MAP_F, BP_MAP_V = 0, 1           # what nsk_bp_map_download hands out
@@ -250,6 +256,9 @@ def lib():
         L.nsk_bp_trw_download.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
         L.nsk_bp_trw_routes.argtypes = [C.c_void_p, C.c_void_p]
         L.nsk_bp_trw_plan.argtypes = [C.POINTER(GraphDesc), C.c_int, C.c_void_p, C.c_void_p, C.POINTER(C.c_int64)]
+        L.nsk_bp_setup_wide.argtypes = [C.c_void_p, C.c_int, C.c_int64, C.c_int, C.POINTER(BpInfo), C.POINTER(BpWideInfo)]
+        L.nsk_bp_wide_terms.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+        L.nsk_bp_wide_plan.argtypes = [C.POINTER(GraphDesc), C.c_int, C.POINTER(BpInfo), C.POINTER(BpWideInfo), C.c_void_p]
         L.nsk_sw_plan.argtypes =[C.POINTER(GraphDesc), C.c_int, C.c_int, C.POINTER(SwInfo)] + [C.c_void_p] * 4
         L.nsk_sw_setup.argtypes = [C.c_void_p, C.c_int, C.c_int64, C.c_int, C.POINTER(SwInfo)]
         L.nsk_sw_layout.argtypes = [C.c_void_p] * 4

@@ -17,7 +17,7 @@
 #include <cmath>
 #include <cstring>
 
-#include "nsk_bp_plan.h"
+#include "nsk_bp_wide_plan.h"
 #include "nsk_internal.h"
 #include "nsk_kernels_bp.h"
 #include "nsk_kernels_pcd.h"     // k_pcd_update
@@ -98,7 +98,8 @@ static hipError_t bp_iterations_enqueue(nsk_graph *g, const BpArgs &a, size_t ma
     hipError_t e = hipSuccess;
     if (a.nedge > 0)
         for (size_t t = 0; t < max_iters && e == hipSuccess; t++) {
-            k_bp_factor<<<gf, block, 0, g->stream>>>(a, (int)t, tol, damping, oml, res);
+            if (g->bp.winfo.nwide) bp_wide_factor_enqueue(g, a, (int)t, tol, damping, oml, res);      // (both routes' launches)
+            else k_bp_factor<<<gf, block, 0, g->stream>>>(a, (int)t, tol, damping, oml, res);
             if (nbin > 0) k_bp_var<true><<<gb, vblock, 0, g->stream>>>(a, 0, nbin, (int)t, tol, res);
             if (nall > nbin) k_bp_var<false><<<gr, vblock, 0, g->stream>>>(a, nbin, nall, (int)t, tol, res);
             e = hipGetLastError();
@@ -265,29 +266,32 @@ static int bp_steps_run(nsk_graph *g, const char *who, int n, const double *targ
     return NSK_OK;
 }
 
-extern "C" {
-
-int nsk_bp_setup(nsk_graph *g, int which, int64_t chain, int sample_evidence, nsk_bp_info *info_out) {
-    int rc = bp_common(g, "nsk_bp_setup", false);
+int bp_setup(nsk_graph *g, const char *who, int which, int64_t chain, int sample_evidence, int wide_min, nsk_bp_info *info_out) {
+    int rc = bp_common(g, who, false);
     if (rc) return rc;
-    if ((rc = chain_select(g, which, chain, 1, "nsk_bp_setup", true))) return rc;
+    if ((rc = chain_select(g, which, chain, 1, who, true))) return rc;
     // ---- the structure: every refusal names the lowest offending factor and precedes any allocation
     const Compiled &c = g->c;
     BpPlan pl;
-    const std::string why = bp_plan(c, sample_evidence, NSK_BP_MAX_MEMBERS, NSK_BP_MAX_TABLE, NSK_ZLOCAL, pl);
+    BpWidePlan wp;
+    const std::string why = wide_min < 0 ? bp_plan(c, sample_evidence, NSK_BP_MAX_MEMBERS, NSK_BP_MAX_TABLE, NSK_ZLOCAL, pl)
+                                         : bp_plan_wide(c, sample_evidence, NSK_BP_MAX_MEMBERS, NSK_BP_MAX_TABLE, NSK_ZLOCAL, wide_min,
+                                                        NSK_BP_WIDE_MAX_MEMBERS, pl, wp);
     if (!why.empty()) return fail(NSK_E_INVALID, why);
     const nsk_bp_info &info = pl.info;
     const int64_t F = c.nfactor, nid = c.nid, E = info.nedges;
     // ---- the handle's side: plain values, the records and weights on the device
     HIPCHECK(hipSetDevice(g->device));
-    if ((rc = energy_ensure(g, 0, "nsk_bp_setup"))) return rc;
+    if ((rc = energy_ensure(g, 0, who))) return rc;
     if ((rc = nsk_unpack_tally(g))) return rc;
     HIPCHECK(hipStreamSynchronize(g->stream));
     bp_free(g);
     NskBp &b = g->bp;
     b.big = pl.big; b.b_off.swap(pl.b_off); b.info = info; b.nvlist = (int32_t)pl.v_list.size(); b.nvbin = pl.nvbin;
-    bp_map_routes(pl, NSK_ZLOCAL, b.ms_routes);     // (host only: nsk_bp_map_run uploads the lists when it is first called)
-    bp_trw_routes(pl, NSK_ZLOCAL, trw_lane_max(nsk::diag_env("NSK_TRW_LANE_MAX")), b.tw_routes);       // (host only, as above: nsk_bp_trw_run)
+    if (wp.nwide == 0) {            // (the calls that read these routes refuse a set-up with wide factors)
+        bp_map_routes(pl, NSK_ZLOCAL, b.ms_routes);     // (host only: nsk_bp_map_run uploads the lists when it is first called)
+        bp_trw_routes(pl, NSK_ZLOCAL, trw_lane_max(nsk::diag_env("NSK_TRW_LANE_MAX")), b.tw_routes);       // (host only, as above: nsk_bp_trw_run)
+    }
     b.rs_walk = b.nvlist > b.nvbin;                 // (host only: nsk_bp_residual_run's scratch of the walks through memory)
     for (int32_t i = 0; i < b.nvbin && !b.rs_walk; i++) b.rs_walk = pl.v_eoff[(size_t)i + 1] - pl.v_eoff[(size_t)i] > NSK_BP_VAR_REG;
     const int64_t before = g->mem.total;
@@ -307,23 +311,26 @@ int nsk_bp_setup(nsk_graph *g, int which, int64_t chain, int sample_evidence, ns
     if (!rc) rc = bp_upload(g, &b.mrec, pl.mrec);
     if (!rc) rc = bp_upload(g, &b.slot_rec, pl.slot_rec);
     if (!rc) rc = bp_upload(g, &b.v_state, pl.state);
-    if (!rc) rc = bp_alloc(g, &b.theta, (size_t)info.ntable);
-    if (!rc) rc = bp_alloc(g, &b.psi, (size_t)info.ntable);
-    if (!rc) rc = bp_alloc(g, &b.feat, (size_t)info.ntable);
+    // (k_bp_psi reads theta[tab_off[f]] of every factor: with wide factors, which have no entry, one double past the tables)
+    const size_t ntab = (size_t)info.ntable + (wp.nwide ? 1 : 0);
+    if (!rc) rc = bp_alloc(g, &b.theta, ntab);
+    if (!rc) rc = bp_alloc(g, &b.psi, ntab);
+    if (!rc) rc = bp_alloc(g, &b.feat, ntab);
     if (!rc) rc = bp_alloc(g, &b.f2v, (size_t)info.nmsg);
     if (!rc) rc = bp_alloc(g, &b.v2f, (size_t)info.nmsg);
     if (!rc) rc = bp_alloc(g, &b.belief, (size_t)info.nbelief);
     if (!rc && b.big) rc = bp_alloc(g, &b.wk, (size_t)info.nbelief);
+    const char *val = chain_val(g, which, chain);
+    if (!rc && wp.nwide) rc = bp_wide_attach(g, wp, val);
     if (rc) {
         (void)hipStreamSynchronize(g->stream);
         bp_free(g);
         if (rc != NSK_E_NOMEM) return rc;
-        return fail(NSK_E_NOMEM, "nsk_bp_setup: structure, tables, messages and beliefs (" + std::to_string((long long)bytes) +
+        return fail(NSK_E_NOMEM, std::string(who) + ": structure, tables, messages and beliefs (" + std::to_string((long long)bytes) +
                                  " bytes) do not fit on the device");
     }
     b.info.device_bytes = g->mem.total - before;
     const BpArgs a = bp_args(g);
-    const char *val = chain_val(g, which, chain);
     const dim3 block(NSK_BLOCK);
     if (F > 0) {
         if (c.vbytes == 4) k_bp_tables<int32_t><<<dim3(bp_blocks(a.ntable)), block, 0, g->stream>>>(a, (const int32_t *)val);
@@ -345,6 +352,12 @@ int nsk_bp_setup(nsk_graph *g, int which, int64_t chain, int sample_evidence, ns
     b.ready = true;
     if (info_out) *info_out = b.info;
     return NSK_OK;
+}
+
+extern "C" {
+
+int nsk_bp_setup(nsk_graph *g, int which, int64_t chain, int sample_evidence, nsk_bp_info *info_out) {
+    return bp_setup(g, "nsk_bp_setup", which, chain, sample_evidence, -1, info_out);
 }
 
 int nsk_bp_layout(nsk_graph *g, int64_t *table_off, int64_t *edge_off, int64_t *edge_var, int64_t *msg_off) {
@@ -468,6 +481,7 @@ int nsk_bp_moments(nsk_graph *g, int64_t *moments, int64_t *skipped) {
     const char *who = "nsk_bp_moments";
     int rc = bp_common(g, who, true);
     if (rc) return rc;
+    if ((rc = bp_refuse_wide(g->bp, who))) return rc;
     const Compiled &c = g->c;
     const size_t nw = (size_t)c.nweight;
     if (nw == 0) return NSK_OK;
@@ -498,6 +512,7 @@ int nsk_bp_learn_steps(nsk_graph *g, const double *target, int64_t nsteps, int64
     const char *who = "nsk_bp_learn_steps";
     int rc = bp_common(g, who, true);
     if (rc) return rc;
+    if ((rc = bp_refuse_wide(g->bp, who))) return rc;
     if (!target) return fail(NSK_E_INVALID, "null argument");
     if ((rc = bp_steps_check(who, nsteps, iters_per_step, damping, tol, warm, step, decay, reg_param, normalize))) return rc;
     if ((rc = refuse(check_target(who, target, (size_t)g->c.nweight)))) return rc;
@@ -511,6 +526,7 @@ int nsk_bp_latent_steps(nsk_graph *g, int64_t nsteps, int64_t iters_per_step, do
     const char *who = "nsk_bp_latent_steps";
     int rc = bp_common(g, who, false);
     if (rc) return rc;
+    if ((rc = bp_refuse_wide(g->bp, who)) || (rc = bp_refuse_wide(g->bp_other, who))) return rc;
     if (!bp_slot(g, 0).ready || !bp_slot(g, 1).ready)
         return fail(NSK_E_INVALID, std::string(who) + ": slot " + (bp_slot(g, 0).ready ? "1 (the free phase)" : "0 (the clamped phase)") +
                                    " has no belief propagation set up (nsk_bp_select, nsk_bp_setup)");

@@ -74,6 +74,7 @@ extern "C" {
 int nsk_bp_map_run(nsk_graph *g, int64_t max_iters, double damping, double tol, int warm, int64_t *iters, double *residual) {
     int rc = ms_common(g, "nsk_bp_map_run");
     if (rc) return rc;
+    if ((rc = bp_refuse_wide(g->bp, "nsk_bp_map_run"))) return rc;
     if (!iters) return fail(NSK_E_INVALID, "null argument");
     if (max_iters < 1 || max_iters > 4096) return fail(NSK_E_INVALID, "nsk_bp_map_run: max_iters must lie in [1, 4096]");
     if (!(damping >= 0.0 && damping < 1.0)) return fail(NSK_E_INVALID, "nsk_bp_map_run: damping must lie in [0, 1)");

@@ -37,81 +37,109 @@ static inline int64_t bp_need(int fn) {
     }
 }
 
-// Fills `p` for the state whose evidence is clamped (sample_evidence == 0) or free.  max_members, max_table and zlocal
-// are NSK_BP_MAX_MEMBERS, NSK_BP_MAX_TABLE and the device's NSK_ZLOCAL.  Returns the refusal's text, empty where there is
-// none; a refusal names the lowest offending factor.
-static inline std::string bp_plan(const Compiled &c, int sample_evidence, int max_members, long long max_table, int zlocal, BpPlan &p) {
-    const int64_t F = c.nfactor, nedge = c.nedge, nid = c.nid, npos = std::min<int64_t>(c.npos, (int64_t)c.p_info.size());
-    const bool head_by_vid = (c.flags & NSK_FLAG_HEAD_BY_VID) != 0;
+// ---- bp_plan in three parts, so that nsk_bp_wide_plan.h routes single factors elsewhere and shares the rest
+struct BpPlanWork {
+    std::vector<int32_t> deg, ids;                  // [nid] directed edges of a variable; the distinct members of the factor under way
+    int64_t npos = 0;
+    bool head_by_vid = false;
+};
+
+static inline std::string bp_refuse(int64_t f, const std::string &why) { return "nsk_bp_setup: factor " + std::to_string((long long)f) + " " + why; }
+
+// which variables are clamped, the per-factor arrays at their start
+static inline std::string bp_plan_begin(const Compiled &c, int sample_evidence, int max_members, BpPlan &p, BpPlanWork &k) {
+    const int64_t F = c.nfactor, nid = c.nid;
+    k.npos = std::min<int64_t>(c.npos, (int64_t)c.p_info.size());
+    k.head_by_vid = (c.flags & NSK_FLAG_HEAD_BY_VID) != 0;
     p = BpPlan();
     p.state.assign((size_t)nid, 0);
     p.info.nfactor = F;
     for (int64_t v = 0; v < c.nvar; v++) {
         const int64_t id = c.iid[(size_t)v];
         if (id < 0 || id >= nid) return "nsk_bp_setup: a variable without an internal id";
-        const bool clamped = id >= npos || ((c.p_info[(size_t)id] & 0xffu) != 0 && !sample_evidence);
+        const bool clamped = id >= k.npos || ((c.p_info[(size_t)id] & 0xffu) != 0 && !sample_evidence);
         p.state[(size_t)id] = clamped ? 1 : 2;
     }
-    // ---- factor by factor
     p.pm_off.assign((size_t)F + 1, 0); p.tab_off.assign((size_t)F + 1, 0); p.msg_off.assign(1, 0);
     p.slot_off.assign((size_t)F + 1, 0); p.edge_off.assign((size_t)F + 1, 0);
-    std::vector<int32_t> deg((size_t)nid, 0), ids((size_t)std::max(max_members, 1));
-    auto refuse = [](int64_t f, const std::string &why) { return "nsk_bp_setup: factor " + std::to_string((long long)f) + " " + why; };
-    for (int64_t f = 0; f < F; f++) {
-        const uint32_t head = c.f_rec[4 * (size_t)f];
-        const int fn = (int)(head & 0xffu) - 1;
-        const int64_t ar = (int64_t)(head >> 8), s = (int32_t)c.f_rec[4 * (size_t)f + 1], wz = (int32_t)c.f_rec[4 * (size_t)f + 2];
-        if (!known_function(fn) || wz < 0 || wz >= c.nweight) return refuse(f, "has an unknown function or a weight outside the table");
-        if (fn == 30) return refuse(f, "is UFO, which reads its members by value: belief propagation has no table for it");
-        if ((fn == 13 || fn == 16 || fn == 17) && !head_by_vid)
-            return refuse(f, "reads its head at the literal edge index (function 13, 16 or 17 without NSK_FLAG_HEAD_BY_VID): it has no single energy");
-        if (fn == 8 && ar >= (int64_t)c.logtab.size()) return refuse(f, "(RATIO) has more members than the logarithm table");
-        const int64_t np = fn == -1 ? 0 : std::max(ar, bp_need(fn));
-        if (s < 0 || s + np > nedge) return refuse(f, "has member positions outside the edge array");
-        int ns = 0;
-        long long T = 1;
-        for (int64_t l = s; l < s + np; l++) {
-            const int32_t id = c.m_rec[2 * (size_t)l];
-            if (id < 0 || id >= nid || !p.state[(size_t)id]) return refuse(f, "has a member outside the variables");
-            int k = 0;
-            while (k < ns && ids[(size_t)k] != id) k++;
-            if (k == ns) {
-                if (ns == max_members)
-                    return refuse(f, "has more than NSK_BP_MAX_MEMBERS = " + std::to_string(max_members) + " distinct members");
-                ids[(size_t)ns++] = id;
-            }
-            p.mrec.push_back(k);
-            p.mrec.push_back(c.m_rec[2 * (size_t)l + 1]);
+    k.deg.assign((size_t)nid, 0); k.ids.assign((size_t)std::max(max_members, 1), 0);
+    return "";
+}
+
+// what a factor's record says, checked: its function, its first member position and how many it reads
+static inline std::string bp_plan_record(const Compiled &c, const BpPlanWork &k, int64_t f, int &fn, int64_t &s, int64_t &np) {
+    const uint32_t head = c.f_rec[4 * (size_t)f];
+    fn = (int)(head & 0xffu) - 1;
+    const int64_t ar = (int64_t)(head >> 8), wz = (int32_t)c.f_rec[4 * (size_t)f + 2];
+    s = (int32_t)c.f_rec[4 * (size_t)f + 1];
+    if (!known_function(fn) || wz < 0 || wz >= c.nweight) return bp_refuse(f, "has an unknown function or a weight outside the table");
+    if (fn == 30) return bp_refuse(f, "is UFO, which reads its members by value: belief propagation has no table for it");
+    if ((fn == 13 || fn == 16 || fn == 17) && !k.head_by_vid)
+        return bp_refuse(f, "reads its head at the literal edge index (function 13, 16 or 17 without NSK_FLAG_HEAD_BY_VID): it has no single energy");
+    if (fn == 8 && ar >= (int64_t)c.logtab.size()) return bp_refuse(f, "(RATIO) has more members than the logarithm table");
+    np = fn == -1 ? 0 : std::max(ar, bp_need(fn));
+    if (s < 0 || s + np > c.nedge) return bp_refuse(f, "has member positions outside the edge array");
+    return "";
+}
+
+// the per-factor offsets behind factor f, whichever route filled its arrays
+static inline std::string bp_plan_close(BpPlan &p, int64_t f, int64_t np, int ns, long long T) {
+    if ((int64_t)p.e_fac.size() > (int64_t)0x7ffffff0) return bp_refuse(f, "and those before it have more than 2^31 directed edges");
+    p.pm_off[(size_t)f + 1] = p.pm_off[(size_t)f] + np;
+    p.slot_off[(size_t)f + 1] = p.slot_off[(size_t)f] + ns;
+    p.edge_off[(size_t)f + 1] = (int32_t)p.e_fac.size();
+    p.tab_off[(size_t)f + 1] = p.tab_off[(size_t)f] + T;
+    p.info.max_table = std::max<int64_t>(p.info.max_table, T);
+    return "";
+}
+
+// factor f on the table route: its member records, distinct members, table size and directed edges
+static inline std::string bp_plan_factor(const Compiled &c, int max_members, long long max_table, int64_t f, int64_t s, int64_t np, BpPlan &p,
+                                         BpPlanWork &k) {
+    const int64_t nid = c.nid;
+    std::vector<int32_t> &ids = k.ids;
+    int ns = 0;
+    long long T = 1;
+    for (int64_t l = s; l < s + np; l++) {
+        const int32_t id = c.m_rec[2 * (size_t)l];
+        if (id < 0 || id >= nid || !p.state[(size_t)id]) return bp_refuse(f, "has a member outside the variables");
+        int kk = 0;
+        while (kk < ns && ids[(size_t)kk] != id) kk++;
+        if (kk == ns) {
+            if (ns == max_members)
+                return bp_refuse(f, "has more than NSK_BP_MAX_MEMBERS = " + std::to_string(max_members) + " distinct members");
+            ids[(size_t)ns++] = id;
         }
-        for (int k = 0; k < ns; k++) {
-            if (p.state[(size_t)ids[(size_t)k]] != 2) continue;
-            const long long card = c.v_card_i[(size_t)ids[(size_t)k]];
-            if (card < 1) return refuse(f, "has a free member of cardinality below 1");
-            T *= card;
-            if (T > max_table)
-                return refuse(f, "has a table of more than NSK_BP_MAX_TABLE = " + std::to_string(max_table) + " entries over its free members");
-        }
-        for (int k = 0; k < ns; k++) {
-            const int32_t id = ids[(size_t)k];
-            const bool free = p.state[(size_t)id] == 2;
-            p.slot_rec.push_back(id);
-            p.slot_rec.push_back(free ? 1 : 0);
-            if (free) {
-                p.e_fac.push_back((int32_t)f);
-                p.e_var.push_back(id);
-                p.msg_off.push_back(p.msg_off.back() + c.v_card_i[(size_t)id]);
-                deg[(size_t)id]++;
-            }
-        }
-        if ((int64_t)p.e_fac.size() > (int64_t)0x7ffffff0) return refuse(f, "and those before it have more than 2^31 directed edges");
-        p.pm_off[(size_t)f + 1] = p.pm_off[(size_t)f] + np;
-        p.slot_off[(size_t)f + 1] = p.slot_off[(size_t)f] + ns;
-        p.edge_off[(size_t)f + 1] = (int32_t)p.e_fac.size();
-        p.tab_off[(size_t)f + 1] = p.tab_off[(size_t)f] + T;
-        p.info.max_table = std::max<int64_t>(p.info.max_table, T);
+        p.mrec.push_back(kk);
+        p.mrec.push_back(c.m_rec[2 * (size_t)l + 1]);
     }
-    const int64_t E = (int64_t)p.e_fac.size();
-    // ---- per variable: the beliefs' offsets, the free variables with an edge and their edges, ascending
+    for (int kk = 0; kk < ns; kk++) {
+        if (p.state[(size_t)ids[(size_t)kk]] != 2) continue;
+        const long long card = c.v_card_i[(size_t)ids[(size_t)kk]];
+        if (card < 1) return bp_refuse(f, "has a free member of cardinality below 1");
+        T *= card;
+        if (T > max_table)
+            return bp_refuse(f, "has a table of more than NSK_BP_MAX_TABLE = " + std::to_string(max_table) + " entries over its free members");
+    }
+    for (int kk = 0; kk < ns; kk++) {
+        const int32_t id = ids[(size_t)kk];
+        const bool free = p.state[(size_t)id] == 2;
+        p.slot_rec.push_back(id);
+        p.slot_rec.push_back(free ? 1 : 0);
+        if (free) {
+            p.e_fac.push_back((int32_t)f);
+            p.e_var.push_back(id);
+            p.msg_off.push_back(p.msg_off.back() + c.v_card_i[(size_t)id]);
+            k.deg[(size_t)id]++;
+        }
+    }
+    return bp_plan_close(p, f, np, ns, T);
+}
+
+// per variable: the beliefs' offsets, the free variables with an edge and their edges, ascending; the counts
+static inline void bp_plan_finish(const Compiled &c, int zlocal, BpPlan &p, const BpPlanWork &k) {
+    const int64_t F = c.nfactor, nid = c.nid, E = (int64_t)p.e_fac.size();
+    const std::vector<int32_t> &deg = k.deg;
     p.b_off.assign((size_t)nid + 1, 0); p.v_eoff.assign(1, 0); p.v_edges.assign((size_t)E, 0);
     std::vector<int32_t> slot_of((size_t)nid, -1);
     for (int64_t id = 0; id < nid; id++) {
@@ -135,7 +163,22 @@ static inline std::string bp_plan(const Compiled &c, int sample_evidence, int ma
     std::vector<int32_t> cur(p.v_eoff.begin(), p.v_eoff.end() - 1);
     for (int64_t e = 0; e < E; e++) p.v_edges[(size_t)cur[(size_t)slot_of[(size_t)p.e_var[(size_t)e]]]++] = (int32_t)e;
     p.info.nedges = E; p.info.ntable = p.tab_off[(size_t)F]; p.info.nmsg = p.msg_off[(size_t)E]; p.info.nbelief = p.b_off[(size_t)nid];
-    return "";
+}
+
+// Fills `p` for the state whose evidence is clamped (sample_evidence == 0) or free.  max_members, max_table and zlocal
+// are NSK_BP_MAX_MEMBERS, NSK_BP_MAX_TABLE and the device's NSK_ZLOCAL.  Returns the refusal's text, empty where there is
+// none; a refusal names the lowest offending factor.
+static inline std::string bp_plan(const Compiled &c, int sample_evidence, int max_members, long long max_table, int zlocal, BpPlan &p) {
+    BpPlanWork k;
+    std::string why = bp_plan_begin(c, sample_evidence, max_members, p, k);
+    for (int64_t f = 0; f < c.nfactor && why.empty(); f++) {
+        int fn;
+        int64_t s, np;
+        why = bp_plan_record(c, k, f, fn, s, np);
+        if (why.empty()) why = bp_plan_factor(c, max_members, max_table, f, s, np, p, k);
+    }
+    if (why.empty()) bp_plan_finish(c, zlocal, p, k);
+    return why;
 }
 
 }  // namespace nsk

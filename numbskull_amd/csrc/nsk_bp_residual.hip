@@ -59,6 +59,7 @@ int nsk_bp_residual_run(nsk_graph *g, int64_t max_rounds, double frac, double da
     int rc = energy_whole_graph(g, who);
     if (rc) return rc;
     if (!g->bp.ready) return fail(NSK_E_INVALID, std::string(who) + ": no belief propagation is set up (nsk_bp_setup)");
+    if ((rc = bp_refuse_wide(g->bp, who))) return rc;
     if (!rounds) return fail(NSK_E_INVALID, "null argument");
     if (max_rounds < 1 || max_rounds > 4096) return fail(NSK_E_INVALID, std::string(who) + ": max_rounds must lie in [1, 4096]");
     if (!(frac >= 0.0 && frac <= 1.0)) return fail(NSK_E_INVALID, std::string(who) + ": frac must lie in [0, 1]");

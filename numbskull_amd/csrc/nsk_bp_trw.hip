@@ -91,6 +91,7 @@ int nsk_bp_trw_run(nsk_graph *g, const double *rho, int64_t max_iters, double da
                    double *residual) {
     int rc = trw_common(g, "nsk_bp_trw_run");
     if (rc) return rc;
+    if ((rc = bp_refuse_wide(g->bp, "nsk_bp_trw_run"))) return rc;
     if (!iters || !rho) return fail(NSK_E_INVALID, "null argument");
     if (max_iters < 1 || max_iters > 4096) return fail(NSK_E_INVALID, "nsk_bp_trw_run: max_iters must lie in [1, 4096]");
     if (!(damping >= 0.0 && damping < 1.0)) return fail(NSK_E_INVALID, "nsk_bp_trw_run: damping must lie in [0, 1)");

@@ -156,6 +156,12 @@ struct NskBp {
     double *tw_tf = nullptr, *tw_tv = nullptr;
     int32_t *tw_lane = nullptr, *tw_wave = nullptr;
     int32_t tw_nlane = 0, tw_nwave = 0;
+    // Wide logical factors (nsk_bp_setup_wide; nsk_bp_wide.hip, nsk_bp_wide_plan.h): the records, positions and the list
+    // of the table route's directed edges -- all in `owned`.  nwide == 0: a set-up as nsk_bp_setup builds it.
+    nsk_bp_wide_info winfo = {};
+    int32_t *wd_rec = nullptr, *wd_pos_off = nullptr, *wd_pos = nullptr, *wd_narrow = nullptr;
+    std::vector<int32_t> wd_factors;   // the wide factors' ids, ascending
+    int32_t wd_nnarrow = 0;
 };
 
 // Swendsen-Wang cluster updates (nsk_sw_setup .. nsk_sw_clear; nsk_sw.hip, nsk_kernels_sw.h): the structure of
@@ -642,6 +648,18 @@ nsk::EnergyArgs energy_args(const nsk_graph *g);
 namespace nsk { struct BpArgs; }
 unsigned int bp_blocks(long long items, int block);
 nsk::BpArgs bp_args(const nsk_graph *g, const NskBp &b);
+// nsk_bp_setup and nsk_bp_setup_wide (nsk_bp.hip): wide_min < 0 keeps every factor on the table route
+int bp_setup(nsk_graph *g, const char *who, int which, int64_t chain, int sample_evidence, int wide_min, nsk_bp_info *info_out);
+// the wide factors of the selected set-up (nsk_bp_wide.hip): their arrays uploaded in nsk_bp_setup's course, and the factor
+// phase of iteration t of a set-up that has some -- k_bp_factor_narrow and k_bp_wide in k_bp_factor's place
+namespace nsk { struct BpWidePlan; }
+int bp_wide_attach(nsk_graph *g, nsk::BpWidePlan &wp, const char *val);
+void bp_wide_factor_enqueue(nsk_graph *g, const nsk::BpArgs &a, int t, double tol, double damping, double oml, unsigned long long *res);
+// the calls that do not serve wide factors yet
+static inline int bp_refuse_wide(const NskBp &b, const char *who) {
+    if (b.winfo.nwide == 0) return NSK_OK;
+    return nsk::fail(NSK_E_INVALID, std::string(who) + ": the set-up has wide factors (nsk_bp_setup_wide), which this call does not serve");
+}
 // the log-potential of `nchains` chains from `val` on / every factor's value, enqueued on the handle's stream (nsk_energy.hip)
 int nsk_energy_enqueue(nsk_graph *g, const void *val, int nchains, bool packed_bytes, double *out);
 int nsk_factor_values_enqueue(nsk_graph *g, const void *val, double *out);

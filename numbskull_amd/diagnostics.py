@@ -1280,6 +1280,91 @@ def bethe_log_z(layout, theta, factor_beliefs, beliefs):
     return total
 
 
+def _xprod(x):
+    """the product of x as (mantissa in [0.5, 1) or 0, exponent): no partial product leaves the range of its type"""
+    m, e = np.frexp(x)
+    pad = (-len(m)) % 256
+    m = np.concatenate([m, np.full(pad, 0.5, m.dtype)]).reshape(-1, 256)
+    m, e2 = np.frexp(m.prod(1))
+    m, e3 = np.frexp(np.prod(m))
+    return m, int(e.sum()) + pad + int(e2.sum()) + int(e3)
+
+
+def _xjoin(a, ea, b, eb):
+    """(a 2^ea, b 2^eb) at the larger exponent of the two that are not 0, and that exponent"""
+    E = eb if a == 0 else (ea if b == 0 else max(ea, eb))
+    return np.ldexp(a, max(ea - E, -1200)), np.ldexp(b, max(eb - E, -1200)), E
+
+
+def bp_wide_factor(fn, w, nu, clamped, damping=0.0, old=None, dtype=np.float64):
+    """The factor phase of ONE wide logical factor as k_bp_wide performs it (the header states the rule), to rounding:
+    every leave-one-out product is the explicit product of the others, O(n^2), where the device scans.  ``fn`` is the
+    factor function (0 IMPLY_NATURAL, 1 OR, 2 AND, 3 EQUAL, 4 ISTRUE, 7 LINEAR, 9 LOGICAL, 13 IMPLY_MLN), ``w`` its
+    weight, ``nu`` ``(n, 2)`` the incoming messages by member position and ``clamped`` ``(n,)`` a clamped member's value,
+    -1 for a free one (its row of ``nu`` is not read then).  ``old`` ``(n, 2)`` are the messages damped against.  Returns
+    ``(messages, term)``: ``(n, 2)``, the rows of clamped positions 0, and the factor's Bethe term
+    ``sum_a b_f (theta_f - ln b_f)``.  ``dtype=np.longdouble`` is the high-precision reference."""
+    T = dtype
+    clamped = np.asarray(clamped, np.int64)
+    n = len(clamped)
+    nu = np.array(nu, T).reshape(n, 2)
+    for l in np.nonzero(clamped >= 0)[0]:
+        nu[l] = (T(clamped[l] == 0), T(clamped[l] == 1))
+    w = T(w)
+    head = fn in (7, 9, 13)
+    nb = n - 1 if head else n
+    h0, h1 = (nu[n - 1, 0], nu[n - 1, 1]) if head else (T(1), T(1))
+
+    def loo(x, j):          # the product of x over the body without j (j = nb: the total)
+        return np.prod(x[:nb] if j == nb else np.delete(x[:nb], j), dtype=T)
+
+    m = np.zeros((n, 2), T)
+    if fn == 7:
+        q = np.exp(-abs(w))
+        ge, gd = (T(1), q) if w >= 0 else (q, T(1))
+        mx = w * T(nb) if w >= 0 else T(0)
+        c0, c1 = ge * nu[:, 0] + gd * nu[:, 1], gd * nu[:, 0] + ge * nu[:, 1]
+        for j in range(nb + 1):         # products as mantissa and exponent: both streams are below 1 at every position
+            (a, ea), (b, eb) = (_xprod(c0[:nb] if j == nb else np.delete(c0[:nb], j)), _xprod(c1[:nb] if j == nb else np.delete(c1[:nb], j)))
+            if j == nb:                 # the head; for the term its pair is multiplied in BEFORE the two totals meet, so
+                m[j] = _xjoin(a, ea, b, eb)[:2]         # that a head clamped against the larger total keeps the smaller
+                z0, z1, escale = _xjoin(h0 * a, ea, h1 * b, eb)
+            else:
+                u0, u1, _ = _xjoin(h0 * a, ea, h1 * b, eb)
+                m[j] = (u0 * ge + u1 * gd, u0 * gd + u1 * ge)
+    else:
+        lo = -w if fn in (1, 2, 3, 4) else T(0)
+        mx = max(lo, w)
+        clo, chi = np.exp(lo - mx), np.exp(w - mx)
+        cb, cp = (chi, clo) if fn in (1, 9, 13) else (clo, chi)
+        d = cp - cb
+        s = nu[:, 0] + nu[:, 1]
+        for j in range(nb + 1 if head else nb):
+            L0, L1, L2 = loo(nu[:, 0], j), loo(nu[:, 1], j), loo(s, j)
+            if j == nb:                 # the head, from the body's totals
+                base = cb * L2
+                m[j] = (base + d * L1, base + d * L0 if fn == 9 else base)
+                continue
+            base = (cb * L2) * (h0 + h1) if head else cb * L2
+            a0, a1 = (h1 * L0 if fn == 9 else L0), (h0 * L1 if head else L1)
+            m[j] = (base + d * a0 if fn in (1, 3, 9) else base, base + d * a1 if fn != 1 else base)
+    zp = nu[n - 1, 0] * m[n - 1, 0] + nu[n - 1, 1] * m[n - 1, 1]
+    with np.errstate(divide="ignore", invalid="ignore"):
+        if fn == 7:                     # every row at its own scale: its own normaliser, and 2^escale back into ln Z'
+            nm = nu * m
+            nm[n - 1] = (z0, z1)
+            b = nm / nm.sum(1)[:, None]
+            lnz = np.log(z0 + z1) + T(escale) * np.log(T(2))
+        else:
+            b, lnz = (nu * m) / zp, np.log(zp)
+        term = (lnz + mx) - np.sum(np.where(b > 0, b * np.log(nu), T(0)), dtype=T)
+        msg = m / (m[:, 0] + m[:, 1])[:, None]
+    if damping > 0:
+        msg = (T(1) - T(damping)) * msg + T(damping) * np.asarray(old, T)
+    msg[clamped >= 0] = 0
+    return msg, term
+
+
 # ------------------------------------------------------------------------------------------------- max-product BP
 def _ms_max(a, b):
     """``b`` where ``b > a`` or ``a`` is a NaN, else ``a``: folded from the first entry it passes over NaNs as fmax does

@@ -1477,7 +1477,7 @@ class FactorGraph(object):
         return iters.value, residual, {"updates": updates, "recomputed": recomputed}
 
     def belief_propagation(self, max_iters=100, damping=0.0, tol=1e-9, var_copy=0, weight_copy=0, evidence_chain=False,
-                           sample_evidence=False, factor_beliefs=False, schedule="flooding", frac=0.5):
+                           sample_evidence=False, factor_beliefs=False, schedule="flooding", frac=0.5, wide_factors=False):
         """Loopy belief propagation on the device (nsk_bp_setup / nsk_bp_run): sum-product message passing, every factor
         and every variable updated once per iteration -- deterministic inference beside the sampler.  The variables with
         ``isEvidence != 0`` are clamped at their values in ``var_value[var_copy]`` (``var_value_evid[var_copy]`` with
@@ -1495,6 +1495,11 @@ class FactorGraph(object):
         graphs where flooding does not converge; ``frac=0`` is flooding bit for bit.  ``max_iters`` counts rounds then (a
         round moves less than an iteration: allow more), and the result gains ``updates`` and ``recomputed``, int64
         ``(max_iters,)``: the messages committed and the candidates formed per round.
+        ``wide_factors=True`` (nsk_bp_setup_wide; ``diagnostics.bp_wide_factor`` is the rule) also takes the logical factors
+        beyond the two caps -- IMPLY_NATURAL, OR, AND, EQUAL, ISTRUE, LINEAR, LOGICAL and, with ``head_by_vid``, IMPLY_MLN over
+        binary members, up to 2048 positions, no free variable twice -- through closed-form messages, O(arity) a factor;
+        the result gains ``wide_factors`` (their ids) and ``wide_terms`` (their Bethe terms, part of ``log_z``).  The
+        residual schedule does not serve them (ValueError).
         Returns a dict: ``offsets``, ``beliefs`` -- the layout of ``conditionals`` over all variables
         (``diagnostics.tally_layout`` converts to that of ``count``); ``iters``, ``converged``, ``residual`` (float64
         ``(max_iters,)``, 0 behind the stop); ``log_z``; with ``factor_beliefs=True`` also ``table_offsets``
@@ -1505,13 +1510,22 @@ class FactorGraph(object):
             raise ValueError("belief_propagation: max_iters must lie in [1, 4096]")
         if _all_copies(var_copy):
             raise ValueError('belief_propagation serves one state: var_copy="all" is for the sampler')
+        if wide_factors and schedule == "residual":
+            raise ValueError('belief_propagation: schedule="residual" does not serve wide factors')
         L, h = _lib.lib(), self._engine()
         self._push(var_copy, weight_copy)
-        info = _lib.BpInfo()
-        _lib.check(L.nsk_bp_setup(h, _lib.BUF_VALUE_EVID if evidence_chain else _lib.BUF_VALUE, 0, int(bool(sample_evidence)),
-                                  C.byref(info)))
+        info, winfo = _lib.BpInfo(), _lib.BpWideInfo()
+        which = _lib.BUF_VALUE_EVID if evidence_chain else _lib.BUF_VALUE
+        if wide_factors:
+            _lib.check(L.nsk_bp_setup_wide(h, which, 0, int(bool(sample_evidence)), C.byref(info), C.byref(winfo)))
+        else:
+            _lib.check(L.nsk_bp_setup(h, which, 0, int(bool(sample_evidence)), C.byref(info)))
         try:
             iters, residual, extra = self._bp_iterations(L, h, "belief_propagation", schedule, frac, max_iters, damping, tol)
+            if wide_factors:
+                wide_ids, wide_terms = np.zeros(winfo.nwide, np.int64), np.zeros(winfo.nwide, np.float64)
+                _lib.check(L.nsk_bp_wide_terms(h, _lib.ptr(wide_ids), _lib.ptr(wide_terms)))
+                extra.update(wide_factors=wide_ids, wide_terms=wide_terms)
             _, offsets = self._cond_selection(None, None, "belief_propagation")
             beliefs = np.zeros(int(offsets[-1]), np.float64)
             _lib.check(L.nsk_bp_beliefs(h, None, 0, _lib.ptr(beliefs)))
@@ -1528,6 +1542,8 @@ class FactorGraph(object):
         out = {"offsets": offsets, "beliefs": beliefs, "iters": abs(int(iters)), "converged": bool(iters > 0),
                "residual": residual, "log_z": bethe_log_z(layout, theta, fb, beliefs)}
         out.update(extra)
+        if wide_factors:
+            out["log_z"] += float(np.sum(out["wide_terms"]))
         if factor_beliefs:
             out.update(table_offsets=table_off, theta=theta, factor_beliefs=fb)
         return out
@@ -1752,14 +1768,15 @@ class FactorGraph(object):
             out["moments"] = rows
         return out
 
-    def bp_log_evidence(self, max_iters=100, damping=0.0, tol=1e-9, var_copy=0, weight_copy=0):
+    def bp_log_evidence(self, max_iters=100, damping=0.0, tol=1e-9, var_copy=0, weight_copy=0, wide_factors=False):
         """The Bethe estimate of ``log P(the evidence variables' values)`` under ``weight_value[weight_copy]``:
         ``log_z`` of ``belief_propagation`` with the evidence held minus ``log_z`` with everything free
         (``sample_evidence=True``), two runs composed on the host.  It is the objective ``learn_bp(latent=True)``
         ascends; exact where the graph is a forest and both runs converge, an approximation on a graph with cycles.
-        The arguments are those of ``belief_propagation``.  Returns a dict: ``log_evidence``, ``log_z_clamped``,
+        The arguments are those of ``belief_propagation``, ``wide_factors`` included.  Returns a dict: ``log_evidence``, ``log_z_clamped``,
         ``log_z_free``, ``converged`` -- bool ``(2,)`` -- and ``iters`` -- int64 ``(2,)`` --, the clamped run first."""
-        runs = [self.belief_propagation(max_iters, damping, tol, var_copy, weight_copy, sample_evidence=sev) for sev in (False, True)]
+        runs = [self.belief_propagation(max_iters, damping, tol, var_copy, weight_copy, sample_evidence=sev, wide_factors=wide_factors)
+                for sev in (False, True)]
         lz = [float(r["log_z"]) for r in runs]
         return {"log_evidence": lz[0] - lz[1], "log_z_clamped": lz[0], "log_z_free": lz[1],
                 "converged": np.array([r["converged"] for r in runs], np.bool_), "iters": np.array([r["iters"] for r in runs], np.int64)}
