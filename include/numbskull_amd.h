@@ -519,6 +519,70 @@ int nsk_bp_trw_routes(nsk_graph *g, int64_t *counts /* 2 */);
 int nsk_bp_trw_plan(const nsk_graph_desc *desc, int sample_evidence, int64_t *counts /* 2, may be NULL */,
                     int32_t *route /* nfactor, may be NULL */, int64_t *wave_lds /* may be NULL */);
 
+/* Dual MAP bounds (FactorGraph.map_dual): max-sum diffusion in its variable-centred form on the resident set-up above -- a
+ * block-coordinate descent on the dual of the MAP linear relaxation.  It yields an UPPER bound on max_x sum_f theta_f(x)
+ * that no step increases, and a decoded assignment whose log-potential is a lower bound; a gap of zero certifies the
+ * optimum.  numbskull_amd.diagnostics.msd_iterate / msd_terms are the rule in numpy, bit for bit.  Every call acts on the
+ * selected set-up (nsk_bp_select) and is NSK_E_INVALID without one, or on one with wide factors.
+ * State, in msg_off's layout: D[e][k], what factor f(e) has handed to value k of its variable; a cold start sets every
+ * entry +0.0.  MAX is that of max-product above.  The reparametrised table of a factor is
+ *   r_f(a) = theta_f(a), then for every free slot j of f ascending: r = r - D[(f,j)][a_j].
+ * Sweep t visits the colour classes of the compiled layout in ascending order (class k owns the positions
+ * [phase_start[k], phase_end[k]) of nsk_class_layout; no two variables of a class share a factor, which the plan checks
+ * on the set-up's own edges and refuses, naming the lowest factor, where it fails).  For every free variable v of the
+ * class with the edges e_0 < .. < e_{d-1}, all from the D the class step found:
+ *   M[e_i][k]   = (MAX over the table indices a of f(e_i) whose digit for v is k of r_f(a)) + 0.0 -- the maximum in any
+ *                 order: it passes over NaNs, and + 0.0 makes a zero's sign independent of the order;
+ *   B[k]        = +0.0, then B = B + D[e_i][k] for i ascending; tot = B, then tot = tot + M[e_i][k] for i ascending;
+ *   share[k]    = tot[k] / (double)(d + 1);
+ *   D[e_i][k]   = (D[e_i][k] + M[e_i][k]) - share[k] for every i.
+ * residual[t] is the largest |new - old| over the D entries of sweep t, a NaN counting as +inf, taken as nsk_bp_run takes
+ * its residual; the kernels of sweep t >= 1 return when residual[t - 1] <= tol.
+ * Terms: tf[f] = (MAX_a r_f(a)) + 0.0 over the whole table (a factor without free members: its single entry);
+ * tv[v] = MAX_k Bv[k] in k order, Bv[k] = the i-ascending sum from +0.0 of D[e_i][k], for a free variable with an edge,
+ * 0 otherwise.  upper = sum_f tf + sum_v tv >= max_x sum_f theta_f(x) for ANY D; the caller adds the terms (an exactly
+ * rounded sum makes their order irrelevant).
+ *   nsk_bp_dual_run       up to max_sweeps sweeps; the ranges, warm and the sign convention of *sweeps are those of
+ *                         nsk_bp_map_run.  The first call on a set-up allocates D, M, Bv, the terms and the lists of the
+ *                         classes' items (16 bytes a message entry, 8 a value, 8 a factor, 8 a variable, 4 a free
+ *                         variable with an edge) and starts cold whatever `warm` says; the set-up owns them:
+ *                         nsk_graph_info.device_bytes counts them, nsk_bp_clear, a replacing set-up and
+ *                         nsk_graph_destroy free them; NSK_E_NOMEM names the bytes.  One launch per route and non-empty
+ *                         class per sweep, everything enqueued at once, one synchronisation.
+ *   nsk_bp_dual_download  what = NSK_BP_DUAL_D, NSK_BP_DUAL_M (msg_off's layout; M as the last sweep that ran left it),
+ *                         NSK_BP_DUAL_TERMS (computed by the call: tf[nfactor] in the caller's factor order, then tv[nvar]
+ *                         in the caller's variable order), NSK_BP_DUAL_BV (computed by the call: Bv in the "full" layout
+ *                         of nsk_bp_beliefs, 0 for a clamped variable and a free one without an edge).
+ *   nsk_bp_dual_decode    into chain `chain` of `which`, as nsk_bp_map_decode writes: a free variable with an edge takes
+ *                         the smallest k among the maxima of Bv, by that call's scan; *ties (may be NULL) = the variables
+ *                         with several maxima.
+ *   nsk_bp_dual_routes    counts[2] = the free variables with an edge served by one lane a variable (cardinality at most
+ *                         16, every incident table of at most 63 entries, at most 32 edges) and by one wave (the rest).
+ *   nsk_bp_dual_classes   cls[nvar], the caller's order: the colour class of a free variable with an edge, -1 otherwise.
+ *   nsk_bp_dual_plan      host only, no device: the same counts and classes for the set-up nsk_bp_setup would build of
+ *                         `desc`; route[nvar] (may be NULL) = 0 lane, 1 wave, -1 no item; *wave_lds (may be NULL) = the
+ *                         doubles of LDS a wave of the wave route takes, the largest 2 n + C among its variables (n the
+ *                         cardinality, C the largest sum of an incident factor's free cardinalities).
+ * Download and decode before the first run on a set-up are NSK_E_INVALID.  The other BP calls neither read nor write
+ * these arrays.  Every launch honours NSK_BP_GRID_CAP.  The classes and routes of a set-up are planned on
+ * the host when a dual call first asks for them; a set-up that is never asked pays nothing.  (Diagnostic, NSK_DIAG=1
+ * NSK_DUAL_LANE_MAX=n, read by the first dual call on a set-up and by nsk_bp_dual_plan: a variable of cardinality at most 16 takes the lane route where every incident table has at most
+ * n entries, however many edges it has, every other the wave route; 0 sends all down the wave route.  The bits do not
+ * depend on it.) */
+#define NSK_BP_DUAL_D 0
+#define NSK_BP_DUAL_M 1
+#define NSK_BP_DUAL_TERMS 2
+#define NSK_BP_DUAL_BV 3
+int nsk_bp_dual_run(nsk_graph *g, int64_t max_sweeps, double tol, int warm, int64_t *sweeps,
+                    double *residual /* max_sweeps, may be NULL */);
+int nsk_bp_dual_download(nsk_graph *g, int what, double *out);
+int nsk_bp_dual_decode(nsk_graph *g, int which, int64_t chain, int64_t *ties /* may be NULL */);
+int nsk_bp_dual_routes(nsk_graph *g, int64_t *counts /* 2 */);
+int nsk_bp_dual_classes(nsk_graph *g, int32_t *cls /* nvar */);
+int nsk_bp_dual_plan(const nsk_graph_desc *desc, int sample_evidence, int64_t *counts /* 2, may be NULL */,
+                     int32_t *route /* nvar, may be NULL */, int32_t *cls /* nvar, may be NULL */,
+                     int64_t *wave_lds /* may be NULL */);
+
 /* Sum-product belief propagation under a RESIDUAL schedule (FactorGraph.belief_propagation(schedule="residual")): a round
  * recomputes only the messages whose inputs moved and commits only those whose pending change is large against the
  * largest pending one -- the bulk-synchronous form of residual BP.  It acts on the selected resident set-up

@@ -39,6 +39,7 @@ SYMBOLS = (
     "nsk_bp_map_run", "nsk_bp_map_marginals", "nsk_bp_map_download", "nsk_bp_map_decode", "nsk_bp_map_routes",
     "nsk_bp_residual_run",
     "nsk_bp_trw_run", "nsk_bp_trw_beliefs", "nsk_bp_trw_download", "nsk_bp_trw_routes", "nsk_bp_trw_plan",
+    "nsk_bp_dual_run", "nsk_bp_dual_download", "nsk_bp_dual_decode", "nsk_bp_dual_routes", "nsk_bp_dual_classes", "nsk_bp_dual_plan",
     "nsk_bp_setup_wide", "nsk_bp_wide_terms", "nsk_bp_wide_plan",
     "nsk_sw_plan", "nsk_sw_setup", "nsk_sw_layout", "nsk_sw_download", "nsk_sw_labels", "nsk_sw_refresh", "nsk_sw_clear", "nsk_sw_sweeps",
     "nsk_trace_ess", "nsk_trace_autocov_counts", "nsk_trace_pair_counts",
@@ -105,6 +106,11 @@ BP_MAP_LANE_TABLE, BP_MAP_LANE_CARDS, BP_MAP_LDS = 64, 16, 512
 # lane a factor of at most BP_TRW_LANE_TABLE entries whose cardinalities sum to at most BP_MAP_LANE_CARDS, one wave beyond
 BP_TRW_LF, BP_TRW_LN, BP_TRW_FACTOR_BELIEFS, BP_TRW_TERMS = range(4)
 BP_TRW_LANE_TABLE = 63
+# dual MAP bounds: what nsk_bp_dual_download hands out, and the lane route's bounds (csrc/nsk_bp_dual_plan.h): one lane a
+# variable of cardinality at most BP_MAP_LANE_CARDS whose tables have at most BP_DUAL_LANE_TABLE entries and which has at
+# most BP_DUAL_LANE_EDGES edges, one wave beyond
+BP_DUAL_D, BP_DUAL_M, BP_DUAL_TERMS, BP_DUAL_BV = range(4)
+BP_DUAL_LANE_TABLE, BP_DUAL_LANE_EDGES = 63, 32
 BP_VAR_REG = 6          # a binary variable of at most this many edges is served from registers (csrc/nsk_kernels_bp.h)
 
 
@@ -256,6 +262,12 @@ def lib():
         L.nsk_bp_trw_download.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
         L.nsk_bp_trw_routes.argtypes = [C.c_void_p, C.c_void_p]
         L.nsk_bp_trw_plan.argtypes = [C.POINTER(GraphDesc), C.c_int, C.c_void_p, C.c_void_p, C.POINTER(C.c_int64)]
+        L.nsk_bp_dual_run.argtypes = [C.c_void_p, C.c_int64, C.c_double, C.c_int, C.POINTER(C.c_int64), C.c_void_p]
+        L.nsk_bp_dual_download.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
+        L.nsk_bp_dual_decode.argtypes = [C.c_void_p, C.c_int, C.c_int64, C.POINTER(C.c_int64)]
+        L.nsk_bp_dual_routes.argtypes = [C.c_void_p, C.c_void_p]
+        L.nsk_bp_dual_classes.argtypes = [C.c_void_p, C.c_void_p]
+        L.nsk_bp_dual_plan.argtypes = [C.POINTER(GraphDesc), C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_int64)]
         L.nsk_bp_setup_wide.argtypes = [C.c_void_p, C.c_int, C.c_int64, C.c_int, C.POINTER(BpInfo), C.POINTER(BpWideInfo)]
         L.nsk_bp_wide_terms.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
         L.nsk_bp_wide_plan.argtypes = [C.POINTER(GraphDesc), C.c_int, C.POINTER(BpInfo), C.POINTER(BpWideInfo), C.c_void_p]

@@ -292,6 +292,7 @@ int bp_setup(nsk_graph *g, const char *who, int which, int64_t chain, int sample
         bp_map_routes(pl, NSK_ZLOCAL, b.ms_routes);     // (host only: nsk_bp_map_run uploads the lists when it is first called)
         bp_trw_routes(pl, NSK_ZLOCAL, trw_lane_max(nsk::diag_env("NSK_TRW_LANE_MAX")), b.tw_routes);       // (host only, as above: nsk_bp_trw_run)
     }
+    b.du_sev = sample_evidence;                     // (nsk_bp_dual.hip plans its classes from it when a dual call first asks)
     b.rs_walk = b.nvlist > b.nvbin;                 // (host only: nsk_bp_residual_run's scratch of the walks through memory)
     for (int32_t i = 0; i < b.nvbin && !b.rs_walk; i++) b.rs_walk = pl.v_eoff[(size_t)i + 1] - pl.v_eoff[(size_t)i] > NSK_BP_VAR_REG;
     const int64_t before = g->mem.total;

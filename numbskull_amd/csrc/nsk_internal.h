@@ -5,7 +5,7 @@
 // nsk_smc.hip: population annealing on top of them; nsk_pt.hip: parallel tempering; nsk_plgrad.hip: the pseudo-likelihood
 // gradient and MPLE learning; nsk_pcd.hip: the chain-summed moments and persistent contrastive divergence, fully observed
 // and with latent variables; nsk_bp.hip: loopy belief propagation;
-// nsk_bp_map.hip: max-product on the same set-up; nsk_sw.hip: Swendsen-Wang cluster updates).
+// nsk_bp_map.hip: max-product on the same set-up; nsk_bp_dual.hip: dual MAP bounds on it; nsk_sw.hip: Swendsen-Wang cluster updates).
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -18,6 +18,7 @@
 
 #include "../../include/numbskull_amd.h"
 #include "nsk_alloc.h"
+#include "nsk_bp_dual_plan.h"
 #include "nsk_bp_map_plan.h"
 #include "nsk_bp_trw_plan.h"
 #include "nsk_compile.h"
@@ -156,6 +157,16 @@ struct NskBp {
     double *tw_tf = nullptr, *tw_tv = nullptr;
     int32_t *tw_lane = nullptr, *tw_wave = nullptr;
     int32_t tw_nlane = 0, tw_nwave = 0;
+    // Dual MAP bounds (nsk_bp_dual.hip): the set-up notes the state it was built for (du_sev); the first dual call plans
+    // the colour classes' items and their routes from it (host only; du_why is the plan's refusal, returned every time);
+    // the first nsk_bp_dual_run uploads the two lists and allocates D and M (nmsg doubles each), Bv (nbelief) and the
+    // terms (nfactor, nid) -- all in `owned`.  du_reset: D and M have been set to their cold start once.
+    nsk::BpDualPlan du_plan;
+    std::string du_why;
+    int du_sev = 0;
+    bool du_planned = false, du_reset = false;
+    double *du_d = nullptr, *du_m = nullptr, *du_bv = nullptr, *du_tf = nullptr, *du_tv = nullptr;
+    int32_t *du_lane = nullptr, *du_wave = nullptr;
     // Wide logical factors (nsk_bp_setup_wide; nsk_bp_wide.hip, nsk_bp_wide_plan.h): the records, positions and the list
     // of the table route's directed edges -- all in `owned`.  nwide == 0: a set-up as nsk_bp_setup builds it.
     nsk_bp_wide_info winfo = {};

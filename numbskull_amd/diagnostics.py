@@ -1479,6 +1479,97 @@ def ms_decode(layout, max_marginals, values):
     return x, ties
 
 
+# ------------------------------------------------------------------------------------------------- dual MAP bounds
+def _msd_table(layout, theta, D, f):
+    """``r_f`` and the digits of its entries: theta minus the D entries of the factor's free slots, ascending"""
+    to, eo, mo = layout["table_off"], layout["edge_off"], layout["msg_off"]
+    shape = layout["shapes"][f]
+    r = np.array(theta[to[f]:to[f + 1]], np.float64)
+    digits = np.indices(shape).reshape(len(shape), -1) if shape else None
+    for j in range(len(shape)):
+        r = r - D[mo[eo[f] + j] + digits[j]]
+    return r, digits
+
+
+def msd_terms(layout, theta, D):
+    """The terms of the dual bound as nsk_bp_dual_download hands them out: ``(tf, tv, Bv)`` -- per factor the largest
+    entry of its reparametrised table plus 0.0, per variable the largest entry, folded in k order, of ``Bv``, the
+    edge-ordered sum of its D vectors (0 for a clamped variable and a free one without an edge), and ``Bv`` itself in the
+    "full" layout of ``layout["offsets"]``.  ``math.fsum`` of ``tf`` and ``tv`` bounds the best summed theta from above,
+    whatever ``D`` holds."""
+    mo, off = layout["msg_off"], layout["offsets"]
+    D = np.asarray(D, np.float64)
+    nf, nv = len(layout["table_off"]) - 1, len(layout["card"])
+    tf, tv, Bv = np.zeros(nf), np.zeros(nv), np.zeros(int(off[-1]))
+    with np.errstate(all="ignore"):
+        for f in range(nf):
+            tf[f] = np.fmax.reduce(_msd_table(layout, theta, D, f)[0]) + 0.0
+        for v in range(nv):
+            edges = layout["var_edges"][v]
+            if layout["clamped"][v] or not edges:
+                continue
+            B = np.zeros(int(layout["card"][v]))
+            for e in edges:
+                B = B + D[mo[e]:mo[e + 1]]
+            Bv[off[v]:off[v + 1]] = B
+            tv[v] = _ms_fold([float(x) for x in B])
+    return tf, tv, Bv
+
+
+def msd_iterate(layout, theta, classes, sweeps, tol=0.0, bounds=True):
+    """Max-sum diffusion, variable-centred and chromatic, as nsk_bp_dual_run performs it (the header states the rule):
+    ``layout`` and ``theta`` are those of ``bp_iterate``; ``classes`` (nvar,) the colour class of every free variable
+    with an edge, -1 otherwise (nsk_bp_dual_classes / nsk_bp_dual_plan).  A sweep visits the classes ascending; the
+    variables of a class all read the ``D`` the class step found.  The maxima over table entries are taken with
+    ``np.fmax`` (any order; + 0.0 follows), every sum in the rule's order.  Returns a dict: ``D``, ``M``, ``residual``
+    and ``sweeps`` (as ``ms_iterate`` returns its residual and iters) and, with ``bounds``, ``bounds``: the exactly
+    rounded sum of ``msd_terms`` after every class step, the steps of all sweeps in a row."""
+    import math
+    eo, mo = layout["edge_off"], layout["msg_off"]
+    classes = np.asarray(classes, np.int64)
+    theta = np.asarray(theta, np.float64)
+    D, M = np.zeros(int(mo[-1])), np.zeros(int(mo[-1]))
+    residual = np.zeros(sweeps)
+    ran, trail = -sweeps, []
+    for t in range(sweeps):
+        if t > 0 and residual[t - 1] <= tol:
+            break
+        res = 0.0
+        for c in sorted(set(classes[classes >= 0].tolist())):
+            new = D.copy()
+            with np.errstate(all="ignore"):
+                for v in np.flatnonzero(classes == c):
+                    edges = layout["var_edges"][v]
+                    n = int(layout["card"][v])
+                    for e in edges:
+                        f = int(np.searchsorted(eo, e, side="right")) - 1
+                        r, digits = _msd_table(layout, theta, D, f)
+                        own = digits[e - eo[f]]
+                        M[mo[e]:mo[e + 1]] = [np.fmax.reduce(r[own == k]) + 0.0 for k in range(n)]
+                    tot = np.zeros(n)
+                    for e in edges:
+                        tot = tot + D[mo[e]:mo[e + 1]]
+                    for e in edges:
+                        tot = tot + M[mo[e]:mo[e + 1]]
+                    share = tot / float(len(edges) + 1)
+                    for e in edges:
+                        new[mo[e]:mo[e + 1]] = (D[mo[e]:mo[e + 1]] + M[mo[e]:mo[e + 1]]) - share
+                dd = np.abs(new - D)
+            if len(dd):
+                res = max(res, np.inf if np.isnan(dd).any() else float(dd.max()))
+            D = new
+            if bounds:
+                tf, tv, _ = msd_terms(layout, theta, D)
+                trail.append(math.fsum(tf.tolist() + tv.tolist()))
+        residual[t] = res
+        if ran < 0 and res <= tol:
+            ran = t + 1
+    out = {"D": D, "M": M, "residual": residual, "sweeps": ran}
+    if bounds:
+        out["bounds"] = np.array(trail)
+    return out
+
+
 # ------------------------------------------------------------------------------------------------- tree-reweighted BP
 def _trw_rho(layout, rho):
     nf = len(layout["table_off"]) - 1

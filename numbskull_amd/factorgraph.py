@@ -1595,6 +1595,57 @@ class FactorGraph(object):
                        log_potential=float(self.log_potential(var_copy, weight_copy, evidence_chain)))
         return out
 
+    def map_dual(self, max_sweeps=200, tol=1e-9, var_copy=0, weight_copy=0, evidence_chain=False, sample_evidence=False,
+                 polish=True, icm_sweeps=100):
+        """Dual MAP bounds on the device (nsk_bp_setup / nsk_bp_dual_run / nsk_bp_dual_decode): max-sum diffusion, a
+        block-coordinate descent on the dual of the MAP linear relaxation, one launch per colour class.  ``upper`` bounds
+        the log-potential of EVERY assignment of the free variables (given the clamped ones) from above and never goes up
+        from sweep to sweep -- nothing to damp, nothing that may fail to converge; ``lower`` is the log-potential of the
+        assignment decoded from the reparametrised unaries.  ``gap = upper - lower``; a gap of zero (to rounding)
+        certifies that ``values`` is a MAP assignment, and whatever ``icm``, ``anneal``, ``map_estimate`` or ``map_bp``
+        found can be held against ``upper``.  On a forest the bound is tight; on a graph with cycles it is the value of
+        the linear relaxation at best.  State, weights, clamping and the refusals are those of ``map_bp``; the decode
+        takes the smallest among several best values, which can be inconsistent across variables where reparametrised
+        values tie (``ties`` counts such variables), so ``polish=True`` hands it to ``icm(icm_sweeps)`` -- the lower bound
+        is valid either way.  The assignment replaces the row it started from, as ``map_bp`` leaves its result.
+        ``diagnostics.msd_iterate`` / ``msd_terms`` are the rule in numpy.  Returns a dict: ``upper``, ``lower``, ``gap``,
+        ``values`` (int64, all variables), ``sweeps``, ``converged``, ``residual`` (float64 ``(max_sweeps,)``, 0 behind
+        the stop), ``ties``, ``offsets`` and ``reparametrised`` (the layout of ``conditionals``: the summed duals of a
+        free variable in a table, 0 elsewhere).  With ``polish`` also ``decoded_log_potential`` (before the sweeps),
+        ``icm_sweeps_run`` and ``icm_converged``."""
+        import math
+        max_sweeps = int(max_sweeps)
+        if max_sweeps < 1 or max_sweeps > 4096:
+            raise ValueError("map_dual: max_sweeps must lie in [1, 4096]")
+        if _all_copies(var_copy):
+            raise ValueError('map_dual serves one state: var_copy="all" is for the sampler')
+        L, h = _lib.lib(), self._engine()
+        which = _lib.BUF_VALUE_EVID if evidence_chain else _lib.BUF_VALUE
+        self._push(var_copy, weight_copy)
+        _lib.check(L.nsk_bp_setup(h, which, 0, int(bool(sample_evidence)), None))
+        try:
+            sweeps, ties, residual = C.c_int64(0), C.c_int64(0), np.zeros(max_sweeps, np.float64)
+            _lib.check(L.nsk_bp_dual_run(h, max_sweeps, float(tol), 0, C.byref(sweeps), _lib.ptr(residual)))
+            _, offsets = self._cond_selection(None, None, "map_dual")
+            terms = np.zeros(self.factor.shape[0] + self.variable.shape[0], np.float64)
+            bv = np.zeros(int(offsets[-1]), np.float64)
+            _lib.check(L.nsk_bp_dual_download(h, _lib.BP_DUAL_TERMS, _lib.ptr(terms)))
+            _lib.check(L.nsk_bp_dual_download(h, _lib.BP_DUAL_BV, _lib.ptr(bv)))
+            _lib.check(L.nsk_bp_dual_decode(h, which, 0, C.byref(ties)))
+        finally:
+            L.nsk_bp_clear(h)
+        self._pull(var_copy, weight_copy, weights=False, count=False)
+        row = (self.var_value_evid if evidence_chain else self.var_value)[var_copy]
+        lp = float(self.log_potential(var_copy, weight_copy, evidence_chain))
+        out = {"upper": math.fsum(terms.tolist()), "sweeps": abs(int(sweeps.value)), "converged": bool(sweeps.value > 0),
+               "residual": residual, "ties": int(ties.value), "offsets": offsets, "reparametrised": bv}
+        if polish:
+            pol = self.icm(icm_sweeps, var_copy, weight_copy, evidence_chain, sample_evidence)
+            out.update(decoded_log_potential=lp, icm_sweeps_run=pol["sweeps"], icm_converged=pol["converged"])
+            lp = float(self.log_potential(var_copy, weight_copy, evidence_chain))
+        out.update(lower=lp, gap=out["upper"] - lp, values=np.array(row, np.int64))
+        return out
+
     def reweighted_bp(self, rho="trees", trees=64, seed=0, max_iters=200, damping=0.5, tol=1e-9, var_copy=0, weight_copy=0,
                       evidence_chain=False, sample_evidence=False, factor_beliefs=False):
         """Tree-reweighted belief propagation on the device (nsk_bp_setup / nsk_bp_trw_run): the message passing of
